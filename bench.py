@@ -9,7 +9,10 @@ N > 1 from a plain shell: the script starts its own N ranks (python -m torch.dis
 One "step" = one pass of the hot path over one batch: Testbed::train (occupancy update when due, ray generation +
 march, network forward on the un-compacted samples, loss + compaction, forward/backward on 2^18 compacted samples,
 Adam+EMA). Inputs are resident in HBM before the timed region. Prints ONE JSON line (rank 0).
-On several GPUs the line carries BOTH scaling modes: `value` / `scaling` for the mode asked for (weak by default: 2^18
+A plain run sets up, burns in, warms up and times the K steps; every other leg of the record (the rest of the 1000-2000 window,
+per-kernel table, late regime, fixed cost, other precision, other scaling mode, live HBM counters, CPU baseline) runs with --full.
+--dump-outputs DIR writes what the last timed step computed as .npy files, for comparing two builds on the same inputs.
+With --full on several GPUs the line carries BOTH scaling modes: `value` / `scaling` for the mode asked for (weak by default: 2^18
 compacted samples per rank and step; --strong: the single-GPU step divided over the ranks) and the other mode's value in
 `strong_scaling` / `weak_scaling`, measured in the same job.
 """
@@ -68,6 +71,11 @@ LIMITER_NOTES = {
 }
 
 
+# the fields of the last timed step's rnb_step_stats written by --dump-outputs (its two host timings are left out: they differ from run to run)
+DUMP_STATS = ("training_step", "rays_per_batch", "next_rays_per_batch", "measured_batch_size", "measured_batch_size_before_compaction", "n_rays_kept",
+              "density_grid_updated", "loss", "ek_loss", "mask_loss")
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -110,7 +118,18 @@ def parse(argv=None):
     ap.add_argument("--no-live-pmc", action="store_true", help="do not collect the HBM counters of `roofline.traffic` in this run (child processes under rocprofv3 --pmc); the record "
                     "then carries the committed summary's value and says so")
     ap.add_argument("--live-pmc-steps", type=int, default=10, help="steps each of those counter passes averages over")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run every leg of the record beyond the K timed steps: the rest of the window (--window-end), the per-kernel "
+                    "pass (--profile-steps), the late regime, the other scaling mode, the fixed cost, the parity and deterministic modes, the live HBM counters and the CPU "
+                    "baseline. Without it those options are ignored and the run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what their last step computed (rank 0) as DIR/<name>.npy: "
+                    "params_fp32 (the trained weights, float32), density_grid (the occupancy grid, float32) and step_stats (float64: %s)" % ", ".join(DUMP_STATS))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.window_end = args.late_step = args.profile_steps = args.other_leg_steps = args.fixed_cost_steps = args.parity_mode_steps = 0
+        args.no_cpu_baseline = args.no_live_pmc = True
+    return args
 
 
 # kernels of a bench kernel group (substring of the kernel name as rocprofv3 prints it, mangled or not)
@@ -351,6 +370,16 @@ def main(argv=None, engine=None):
     for _ in range(args.warmup):
         trainer.step()
     elapsed, rays, samples, samples_before, timed_ms, last = timed_run(trainer, args.steps)
+    if args.dump_outputs:
+        if hasattr(trainer, "sync_parameters"):
+            trainer.sync_parameters(names=("PARAMS_FP32",))  # sharded optimizer: every rank's chunk of the masters (a collective: all ranks call it)
+        engine.sync()
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            outputs = {"params_fp32": ctx.get("PARAMS_FP32"), "density_grid": ctx.get("DENSITY_GRID"),
+                       "step_stats": np.array([getattr(last, k) for k in DUMP_STATS], dtype=np.float64)}
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu_state = state_of(ctx, last) if want_cpu and args.cpu_baseline_steps > 0 else None  # the regime `value` was measured in
 
@@ -490,7 +519,7 @@ def main(argv=None, engine=None):
         ms_per_step = 1e3 * elapsed / args.steps
         value = rays / elapsed
         # the HBM counters of the record's rooflines, collected now and in the regime of the per-kernel pass above (child processes; this process's contexts are idle)
-        live, live_note = (None, "--no-live-pmc") if (args.no_live_pmc or world != 1 or engine.name != "hip" or not prof) else live_pmc(args, prof_first_step)
+        live, live_note = (None, "--no-live-pmc" if args.full else "not collected: a run without --full") if (args.no_live_pmc or world != 1 or engine.name != "hip" or not prof) else live_pmc(args, prof_first_step)
 
         def pmc_file(name):
             p = os.path.join(ROOT, "profiles", name)

@@ -10,8 +10,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--views", "4", "--res", "48", "--focal", "84", "--batch-log2", "12", "--burn-in", "2", "--warmup", "1", "--steps", "2", "--other-leg-steps", "1",
-         "--window-end", "0", "--late-step", "0", "--profile-steps", "0", "--no-cpu-baseline", "--burn-in-mode", "deterministic"]
+WORKLOAD = ["--views", "4", "--res", "48", "--focal", "84", "--batch-log2", "12", "--burn-in", "2", "--warmup", "1", "--steps", "2"]
+SMALL = WORKLOAD + ["--other-leg-steps", "1", "--window-end", "0", "--late-step", "0", "--profile-steps", "0", "--no-cpu-baseline", "--burn-in-mode", "deterministic", "--full"]
 
 
 def _run(extra, tail=()):
@@ -51,3 +51,32 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_only_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full one rank runs set-up, burn-in, warm-up and the K timed steps only (the window to step 2000 that --full would add is thousands of
+    CPU steps here), and --dump-outputs writes what the last timed step computed."""
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_gloo_entry.py"), "--gpus", "1"] + WORKLOAD + ["--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=550, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and len(rec["timed_steps_ms"]) == 2
+    for k in ("window_1000_2000", "late_regime", "fixed_cost", "parity_mode", "deterministic_mode", "roofline"):
+        assert rec[k] is None, k
+    assert "cpu_baseline" not in rec and rec["kernels_ms_per_step"] == {}
+    import numpy as np
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert sorted(files) == ["density_grid.npy", "params_fp32.npy", "step_stats.npy"]
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    assert files["params_fp32.npy"].dtype == np.float32 and files["density_grid.npy"].dtype == np.float32 and files["step_stats.npy"].dtype == np.float64
+    assert np.isfinite(files["params_fp32.npy"]).all() and files["params_fp32.npy"].any()
+    stats = files["step_stats.npy"]
+    assert stats[0] == rec["config"]["first_timed_step"] + rec["steps"]  # training_step: the last timed step's
+    assert abs(stats[7] - rec["config"]["loss"]) <= 1e-6  # its loss, as the record reports it

@@ -4,7 +4,7 @@ tag=$1; shift
 mkdir -p gpurun_out/$tag
 for env in "$@"; do
   for rep in 1 2; do
-    out=$(env $env timeout 120 python bench.py --albedo --steps 200 --no-cpu-baseline --profile-steps 0 --late-step 0 2>/dev/null | grep "^{")
+    out=$(env $env timeout 120 python bench.py --full --albedo --steps 200 --no-cpu-baseline --profile-steps 0 --late-step 0 2>/dev/null | grep "^{")
     python - "$env" "$out" <<'PY' >> gpurun_out/$tag/ab_albedo.txt
 import json, sys
 d = json.loads(sys.argv[2])

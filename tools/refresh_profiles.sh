@@ -5,9 +5,9 @@ R=${1:-r05}
 O=gpurun_out/${R}p
 mkdir -p $O $O/pmc
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-python bench.py 2>$O/bench_default.err | grep "^{" > $O/bench_default.json                        # the defaults: steps 1000-2000 timed, + late regime
-python bench.py --steps 20 2>/dev/null | grep "^{" > $O/bench_steps20.json                        # the driver's command line
-python bench.py --albedo --no-cpu-baseline --late-step 0 --parity-mode-steps 0 2>/dev/null | grep "^{" > $O/bench_albedo.json
+python bench.py --full 2>$O/bench_default.err | grep "^{" > $O/bench_default.json                        # the defaults: steps 1000-2000 timed, + late regime
+python bench.py --full --steps 20 2>/dev/null | grep "^{" > $O/bench_steps20.json                        # the short timed window
+python bench.py --full --albedo --no-cpu-baseline --late-step 0 --parity-mode-steps 0 2>/dev/null | grep "^{" > $O/bench_albedo.json
 for regime in 980 1980; do
 for mode in serial overlapped; do
   rm -rf /tmp/kt_$mode

@@ -3,7 +3,7 @@
 #   BURN=980 bash tools/serial_kernels.sh "ENV" "ENV" ...
 burn=${BURN:-980}
 for env in "$@"; do
-  out=$(env $env python bench.py --burn-in $burn --steps 20 --warmup 20 --no-cpu-baseline --profile-steps 100 --window-end 0 --late-step 0 --fixed-cost-steps 0 --parity-mode-steps 0 --no-live-pmc $BENCH_ARGS 2>/dev/null | grep "^{")
+  out=$(env $env python bench.py --full --burn-in $burn --steps 20 --warmup 20 --no-cpu-baseline --profile-steps 100 --window-end 0 --late-step 0 --fixed-cost-steps 0 --parity-mode-steps 0 --no-live-pmc $BENCH_ARGS 2>/dev/null | grep "^{")
   python - "$env" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])
