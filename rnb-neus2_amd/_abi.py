@@ -178,14 +178,52 @@ PROTOTYPES = {
 }
 
 
+# ---- include/rnb_render.h: the inference tracer, a header of its own with its own version (the HIP library only; the CPU checker has no tracer) ----
+RENDER_ABI_VERSION = 1
+RENDER_CHANNELS = 9  # normal 3, albedo 3, opacity, depth, samples
+
+
+class RenderOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("min_transmittance", C.c_float),
+        ("near_distance", C.c_float),
+        ("use_inference_params", C.c_uint32),
+        ("use_occupancy", C.c_uint32),
+        ("max_rays_in_flight", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class RenderStats(C.Structure):
+    _fields_ = [
+        ("n_rays", C.c_uint32),
+        ("n_hit", C.c_uint32),
+        ("rounds", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_samples", C.c_uint64),
+        ("ms", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+RENDER_PROTOTYPES = {
+    "render_abi_version": (_u32, []),
+    "render_default_options": (_i, [C.POINTER(RenderOptions)]),
+    "render": (_i, [_ctx, _stream, C.POINTER(View), C.POINTER(RenderOptions), C.c_void_p, C.POINTER(RenderStats)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
-    def __init__(self, lib, prefix):
+    def __init__(self, lib, prefix, tables=(PROTOTYPES,)):
         self.lib = lib
         self.prefix = prefix
         missing = []
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in [kv for t in tables for kv in t.items()]:
             try:
                 fn = getattr(lib, prefix + name)
             except AttributeError:
@@ -198,5 +236,6 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_"):
-    return Functions(lib, prefix)
+def declare(lib, prefix="rnb_", render=False):
+    """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), which only the HIP library exports."""
+    return Functions(lib, prefix, (PROTOTYPES, RENDER_PROTOTYPES) if render else (PROTOTYPES,))

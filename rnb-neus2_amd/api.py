@@ -13,7 +13,9 @@ from . import _abi
 from ._abi import Config, View, StepStats, BUF, BUF_DTYPE
 
 __all__ = ["Context", "Config", "View", "StepStats", "load_library", "default_config", "library_path",
-           "load_sdf_init_weights", "RnbError", "BUF"]
+           "load_sdf_init_weights", "RnbError", "BUF", "scaled_view", "RENDER_CHANNELS"]
+
+RENDER_CHANNELS = _abi.RENDER_CHANNELS
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _REPO_ROOT = os.path.dirname(_PKG_DIR)
@@ -43,9 +45,11 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_")
+        _FUNCS = _abi.declare(lib, "rnb_", render=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
+            raise RuntimeError("render ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -77,6 +81,31 @@ def _stream_handle(stream):
     if isinstance(stream, int):
         return C.c_void_p(stream)
     return C.c_void_p(getattr(stream, "cuda_stream"))  # torch.cuda.Stream
+
+
+def _view_struct(v):
+    """A view dict (width, height, focal_length, principal_point, xform 3x4 camera-to-world) -> rnb_view."""
+    out = View()
+    out.width = int(v["width"])
+    out.height = int(v["height"])
+    out.focal_length[:] = [float(x) for x in v["focal_length"]]
+    out.principal_point[:] = [float(x) for x in v["principal_point"]]
+    out.xform[:] = [float(x) for x in np.asarray(v["xform"], dtype=np.float32).reshape(12)]
+    return out
+
+
+def scaled_view(view, factor):
+    """The same camera at another resolution: width, height and the focal lengths (pixels) scaled by `factor`, the principal point (normalised to [0, 1])
+    kept. factor 0.25 = a quarter of the resolution; the width and height are rounded and at least 1."""
+    f = float(factor)
+    if not f > 0:
+        raise ValueError("scale factor must be positive")
+    w, h = max(1, int(round(int(view["width"]) * f))), max(1, int(round(int(view["height"]) * f)))
+    fx, fy = (float(x) for x in view["focal_length"])
+    out = dict(view)
+    out.update(width=w, height=h, focal_length=(fx * w / int(view["width"]), fy * h / int(view["height"])), principal_point=tuple(float(x) for x in view["principal_point"]),
+               xform=np.asarray(view["xform"], dtype=np.float32).reshape(3, 4).copy())
+    return out
 
 
 class Context:
@@ -374,6 +403,42 @@ class Context:
         self.put("COORDS", coords)
         self._check(self.f.forward_infer(self._h, None, C.c_void_p(cptr), n, C.c_void_p(optr), int(bool(inference))))
         return self.get("MLP_OUT", n * 16).reshape(n, 16)
+
+    # -- rendering (include/rnb_render.h; Testbed::render_nerf / NerfTracer::trace, src/testbed_nerf.cu:2499-2770) ----------------------
+    def _render_options(self, min_transmittance, inference, occupancy, max_rays_in_flight, near_distance):
+        opt = _abi.RenderOptions()
+        self._check(self.f.render_default_options(C.byref(opt)))
+        opt.min_transmittance = float(min_transmittance)
+        opt.use_inference_params = int(bool(inference))
+        opt.use_occupancy = int(bool(occupancy))
+        opt.max_rays_in_flight = int(max_rays_in_flight)
+        if near_distance is not None:
+            opt.near_distance = float(near_distance)
+        return opt
+
+    def render_into(self, view, out_ptr, min_transmittance=0.01, inference=True, occupancy=True, max_rays_in_flight=0, near_distance=None, stream=None):
+        """rnb_render into device memory: out_ptr receives view height x width x RENDER_CHANNELS float32 (see include/rnb_render.h for the channels).
+        Returns the rnb_render_stats as a dict. Leaves the training state as it was."""
+        st = _abi.RenderStats()
+        opt = self._render_options(min_transmittance, inference, occupancy, max_rays_in_flight, near_distance)
+        self._check(self.f.render(self._h, _stream_handle(stream), C.byref(_view_struct(view)), C.byref(opt), C.c_void_p(out_ptr), C.byref(st)))
+        return st.as_dict()
+
+    def render(self, view, min_transmittance=0.01, inference=True, occupancy=True, max_rays_in_flight=0, near_distance=None, stream=None):
+        """The maps the model predicts for one camera (a view dict as set_dataset takes): normal [H,W,3] (unit, world frame, 0 where nothing is hit),
+        albedo [H,W,3], opacity, depth (camera-forward, of the max-weight sample; 0 where opacity <= 0.2) and n_samples [H,W], plus `stats`; numpy arrays on the host.
+        inference: EMA weights (what a snapshot holds); occupancy: skip the cells the occupancy bitfield marks empty; min_transmittance: 0 composites every ray to the
+        box exit; max_rays_in_flight (0 = 2^19) bounds the workspace and does not change the image."""
+        h, w = int(view["height"]), int(view["width"])
+        n = h * w * RENDER_CHANNELS
+        ptr = self.device_malloc(max(n, 1) * 4)
+        try:
+            stats = self.render_into(view, ptr, min_transmittance, inference, occupancy, max_rays_in_flight, near_distance, stream)
+            img = self.download(ptr, n, np.float32).reshape(h, w, RENDER_CHANNELS)
+        finally:
+            self.device_free(ptr)
+        return dict(normal=img[..., 0:3].copy(), albedo=img[..., 3:6].copy(), opacity=img[..., 6].copy(), depth=img[..., 7].copy(),
+                    n_samples=img[..., 8].astype(np.uint32), stats=stats)
 
     # -- mesh extraction (src/testbed_nerf.cu:4218-4269, src/marching_cubes.cu:794-822) ----------------------
     def device_malloc(self, n_bytes):

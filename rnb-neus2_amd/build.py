@@ -6,9 +6,9 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG_DIR, "csrc", "rnb_neus2_hip.hip")
 OUT = os.path.join(PKG_DIR, "librnb_neus2_hip.so")
-DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "kernels_mesh.cuh")] + [
+DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "kernels_mesh.cuh", "kernels_render.cuh")] + [
     os.path.join(PKG_DIR, "host", f) for f in ("mesh.hpp", "mc_table.hpp")] + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", "rnb_neus2.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", f) for f in ("rnb_neus2.h", "rnb_render.h")]
 
 # -ffp-contract=off: the index/ray arithmetic must match the CPU checker bit for bit (no FMA contraction).
 # -packed-fp32-ops (device target feature): no v_pk_{mul,add,fma}_f32. Measured on MI355X / ROCm 7.2 with tools/march_determinism.py: the
@@ -54,7 +54,7 @@ def build(force=False, verbose=False):
 ROOT = os.path.dirname(PKG_DIR)
 TESTBED_SRC = os.path.join(PKG_DIR, "host", "testbed_main.cpp")
 TESTBED_OUT = os.path.join(ROOT, "build", "testbed")
-TESTBED_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("testbed_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "mesh.hpp", "mc_table.hpp", "dist_transport.hpp")] + [
+TESTBED_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("testbed_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "mesh.hpp", "mc_table.hpp", "dist_transport.hpp", "snapshot.hpp")] + [
     os.path.join(ROOT, "include", "rnb_neus2.h")]
 
 
@@ -84,6 +84,27 @@ def build_testbed(force=False, verbose=False):
     return TESTBED_OUT
 
 
+RENDER_SRC = os.path.join(PKG_DIR, "host", "render_main.cpp")
+RENDER_OUT = os.path.join(ROOT, "build", "render")
+RENDER_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("render_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "snapshot.hpp")] + [
+    os.path.join(ROOT, "include", f) for f in ("rnb_neus2.h", "rnb_render.h")]
+
+
+def build_render(force=False, verbose=False):
+    """`build/render`: the normal / albedo / depth maps of a trained snapshot for the cameras of a scene (include/rnb_render.h); plain g++, links the HIP library + zlib."""
+    if not force and os.path.exists(RENDER_OUT):
+        t = os.path.getmtime(RENDER_OUT)
+        if not any(os.path.getmtime(d) > t for d in RENDER_DEPS):
+            return RENDER_OUT
+    os.makedirs(os.path.dirname(RENDER_OUT), exist_ok=True)
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), RENDER_SRC, "-o", RENDER_OUT,
+           "-L" + PKG_DIR, "-lrnb_neus2_hip", "-lz", "-Wl,-rpath,$ORIGIN/../rnb-neus2_amd"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return RENDER_OUT
+
+
 HOSTLIB_SRC = os.path.join(PKG_DIR, "host", "hostlib.cpp")
 HOSTLIB_OUT = os.path.join(PKG_DIR, "librnb_host.so")
 HOSTLIB_DEPS = [HOSTLIB_SRC, os.path.join(PKG_DIR, "host", "png16.hpp"), os.path.join(ROOT, "include", "rnb_host.h")]
@@ -106,3 +127,4 @@ if __name__ == "__main__":
     print(build_hostlib(force=True, verbose=True))
     print(build(force=True, verbose=True))
     print(build_testbed(force=True, verbose=True))
+    print(build_render(force=True, verbose=True))

@@ -4,6 +4,7 @@
 #include "kernels_net.cuh"
 #include "kernels_ray.cuh"
 #include "kernels_mesh.cuh"
+#include "kernels_render.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>
@@ -277,6 +278,14 @@ struct rnb_ctx {
 	} knobs;
 	DevBuf<RayLoss> ray_loss;
 	DevBuf<McTable> mc_table; // marching-cubes case table, uploaded on first use
+	// rnb_render's workspace (kernels_render.cuh), sized for render_cap rays in flight and grown on demand: two ray arrays (compaction goes from one to the other),
+	// the alive flags / their prefix sums and the scan's block sums, the tile's results, the round's network inputs and outputs (RENDER_MAX_N samples per ray),
+	// and the counters {records to evaluate, hit pixels, samples (64 bits)}
+	uint32_t render_cap = 0;
+	DevBuf<RenderRay> render_rays[2];
+	DevBuf<uint32_t> render_keep, render_scan, render_counts;
+	DevBuf<float> render_res, render_coords;
+	DevBuf<half_t> render_out;
 	// training scratch
 	DevBuf<half_t> fm;       // feature-major operand arrays
 	DevBuf<uint32_t> g12;
@@ -1495,6 +1504,7 @@ int rnb_destroy(rnb_ctx* c) try {
 	c->loss.free(); c->mlp_out.free(); c->chain_rec.free(); c->ray_grad.free(); c->ray_of.free(); c->slot_of.free(); c->wg_partial.free(); c->dloss_dout.free();
 	c->wimg_fwd.free(); c->wimg_fbs.free(); c->wimg_train.free(); c->wimg_rgb.free(); c->cin_eval.free(); c->dcin.free(); c->rgb_out_scratch.free(); c->src_slot.free(); c->ray_const.free(); c->ray_base1.free(); c->scan_words.free(); c->idx1.free(); c->idx2.free(); c->fwd_counts.free(); c->unfinished.free();
 	c->ray_setup.free(); c->ray_t.free(); c->ray_dunnorm.free(); c->ray_steps.free(); c->ray_base.free(); c->ray_slot.free(); c->ncomp.free(); c->cbase.free(); c->scan_tiles.free(); c->loss_partial.free(); c->ray_loss.free();
+	c->render_rays[0].free(); c->render_rays[1].free(); c->render_keep.free(); c->render_scan.free(); c->render_counts.free(); c->render_res.free(); c->render_coords.free(); c->render_out.free();
 	c->mc_table.free(); c->fm.free(); c->g12.free(); c->srec.free(); c->var_partial.free(); c->dw_partial.free();
 	c->prof.destroy();
 	if (c->s_march) { (void)hipStreamSynchronize(c->s_march); (void)hipStreamDestroy(c->s_march); }
@@ -2568,6 +2578,118 @@ int rnb_gradient_part_wait(rnb_ctx* c, uint32_t part, void* stream) try {
 	}
 	HIP_TRY(hipStreamWaitEvent(as_stream(stream), early ? c->ev_sc[0] : mid ? c->ev_sc[1] : c->ev_all, 0));
 	if (early && c->sc.dp) HIP_TRY(hipStreamWaitEvent(as_stream(stream), c->ev_dw, 0)); // block 0 holds the MLPs' gradients (side stream)
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- inference tracer (include/rnb_render.h; Testbed::NerfTracer, src/testbed_nerf.cu:2499-2770) ----
+uint32_t rnb_render_abi_version(void) { return RNB_RENDER_ABI_VERSION; }
+
+int rnb_render_default_options(rnb_render_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_RENDER_ABI_VERSION;
+	opt->min_transmittance = 0.01f; // testbed.h:723
+	opt->near_distance = 0.2f;      // testbed_nerf.cu:48
+	opt->use_inference_params = 1;
+	opt->use_occupancy = 1;
+	opt->max_rays_in_flight = 0;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_render(rnb_ctx* c, void* stream, const rnb_view* view, const rnb_render_options* opt, float* out, rnb_render_stats* stats) try {
+	if (!c || !view || !opt) return fail(RNB_ERR_INVALID, "rnb_render: null argument");
+	if (opt->abi_version != RNB_RENDER_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_render: options abi_version mismatch (expected RNB_RENDER_ABI_VERSION)");
+	if (!out) return fail(RNB_ERR_INVALID, "rnb_render: out_dev is null");
+	if (view->width == 0 || view->height == 0) return fail(RNB_ERR_INVALID, "rnb_render: empty view");
+	const uint64_t n_pix = (uint64_t)view->width * view->height;
+	if (n_pix > (1ull << 31)) return fail(RNB_ERR_INVALID, "rnb_render: more than 2^31 pixels");
+	if (!(opt->min_transmittance >= 0.f && opt->min_transmittance < 1.f)) return fail(RNB_ERR_INVALID, "rnb_render: min_transmittance must be in [0, 1)");
+	if (!(opt->near_distance >= 0.f) || !std::isfinite(opt->near_distance)) return fail(RNB_ERR_INVALID, "rnb_render: near_distance must be finite and >= 0");
+	if (!(view->focal_length[0] > 0.f && view->focal_length[1] > 0.f)) return fail(RNB_ERR_INVALID, "rnb_render: focal lengths must be positive");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
+
+	// tile size: a multiple of 64 (the write kernel's 16-byte stores start on a 4-pixel boundary), no larger than the image needs
+	uint32_t R = opt->max_rays_in_flight ? opt->max_rays_in_flight : (1u << 19);
+	R = std::max<uint32_t>(64u, R / 64u * 64u);
+	R = (uint32_t)std::min<uint64_t>(R, (n_pix + 63) / 64 * 64);
+	if (R > c->render_cap) {
+		c->render_rays[0].free(); c->render_rays[1].free(); c->render_keep.free(); c->render_scan.free(); c->render_res.free(); c->render_coords.free(); c->render_out.free();
+		c->render_cap = 0;
+		if (c->render_rays[0].alloc(R) != hipSuccess || c->render_rays[1].alloc(R) != hipSuccess || c->render_keep.alloc(R) != hipSuccess ||
+		    c->render_scan.alloc(scan_scratch_elems(R)) != hipSuccess || c->render_res.alloc((size_t)R * RENDER_RES_FLOATS) != hipSuccess ||
+		    c->render_coords.alloc((size_t)R * RENDER_MAX_N * 7) != hipSuccess || c->render_out.alloc((size_t)R * RENDER_MAX_N * 16) != hipSuccess) {
+			c->render_rays[0].free(); c->render_rays[1].free(); c->render_keep.free(); c->render_scan.free(); c->render_res.free(); c->render_coords.free(); c->render_out.free();
+			return fail(RNB_ERR_NOMEM, "rnb_render: hipMalloc failed for the render workspace (lower max_rays_in_flight)");
+		}
+		c->render_cap = R;
+	}
+	if (!c->render_counts.p && c->render_counts.alloc(4) != hipSuccess) return fail(RNB_ERR_NOMEM, "rnb_render: hipMalloc failed for the counters");
+	uint32_t* n_eval = c->render_counts.p;
+	uint32_t* n_hit = c->render_counts.p + 1;
+	unsigned long long* n_samples = reinterpret_cast<unsigned long long*>(c->render_counts.p + 2);
+	HIP_TRY(hipMemsetAsync(c->render_counts.p, 0, 16, s));
+
+	RenderArgs a;
+	std::memset(&a, 0, sizeof(a));
+	a.view.width = view->width; a.view.height = view->height;
+	a.view.focal[0] = view->focal_length[0]; a.view.focal[1] = view->focal_length[1];
+	a.view.principal[0] = view->principal_point[0]; a.view.principal[1] = view->principal_point[1];
+	for (int k = 0; k < 12; ++k) a.view.xform[k] = view->xform[k];
+	a.view.normal = nullptr; a.view.albedo = nullptr;
+	a.A = c->aabb;
+	a.bitfield = opt->use_occupancy ? c->bitfield.p : nullptr;
+	a.near_distance = opt->near_distance;
+	a.min_transmittance = opt->min_transmittance;
+	a.apply_no_albedo = c->cfg.apply_no_albedo;
+	a.fwd[0] = view->xform[2]; a.fwd[1] = view->xform[6]; a.fwd[2] = view->xform[10];
+	const bool inference = opt->use_inference_params != 0;
+	const bool vec = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+	uint32_t rounds = 0;
+	for (uint64_t p0 = 0; p0 < n_pix; p0 += R) {
+		const uint32_t nt = (uint32_t)std::min<uint64_t>(R, n_pix - p0);
+		a.p0 = (uint32_t)p0; a.nt = nt;
+		hipLaunchKernelGGL(k_render_init, dim3((nt + 255) / 256), dim3(256), 0, s, a, c->render_rays[0].p, c->render_keep.p, c->render_res.p);
+		HIP_TRY(hipGetLastError());
+		uint32_t cur = 0, n_cur = nt;
+		while (true) {
+			uint32_t n_alive = 0;
+			int rc = scan_exclusive(c->render_keep.p, n_cur, s, &n_alive, c->render_scan.p); // the round's one read (and synchronisation)
+			if (rc != RNB_OK) return rc;
+			if (n_alive == 0) break;
+			hipLaunchKernelGGL(k_render_compact, dim3((n_cur + 255) / 256), dim3(256), 0, s, n_cur, c->render_rays[cur].p, c->render_keep.p, n_alive, c->render_rays[cur ^ 1].p);
+			cur ^= 1;
+			// Samples per ray this round. The reference takes clamp(n_initialised / n_alive, 1, 8) (testbed_nerf.cu:2731): one sample per ray in the first round, and
+			// ~20 rounds for an 800 x 800 frame of a trained scene, each paying a read-back and seven launches. Here the round's budget is what the workspace holds,
+			// RENDER_MAX_N samples per ray of the tile, spread over the rays still alive (at most RENDER_ROUND_MAX each). The image does not depend on it.
+			const uint32_t n = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((uint64_t)RENDER_MAX_N * nt / n_alive, 1), RENDER_ROUND_MAX);
+			HIP_TRY(hipMemsetAsync(n_eval, 0, 4, s));
+			hipLaunchKernelGGL(k_render_march, dim3((n_alive + 255) / 256), dim3(256), 0, s, a, n_alive, n, c->render_rays[cur].p, c->render_coords.p, n_eval, n_samples);
+			HIP_TRY(hipGetLastError());
+			rc = launch_forward(c, s, c->render_coords.p, n_eval, n * n_alive, c->render_out.p, inference);
+			if (rc != RNB_OK) return rc;
+			hipLaunchKernelGGL(k_render_composite, dim3((n_alive + 255) / 256), dim3(256), 0, s, a, n_alive, c->render_rays[cur].p, c->render_coords.p, c->render_out.p,
+			                   c->render_keep.p, c->render_res.p, n_hit);
+			HIP_TRY(hipGetLastError());
+			n_cur = n_alive;
+			++rounds;
+		}
+		if (vec) hipLaunchKernelGGL(k_render_write<true>, dim3((nt / 4 + 1 + 255) / 256), dim3(256), 0, s, (uint32_t)p0, nt, c->render_res.p, out);
+		else hipLaunchKernelGGL(k_render_write<false>, dim3((nt + 255) / 256), dim3(256), 0, s, (uint32_t)p0, nt, c->render_res.p, out);
+		HIP_TRY(hipGetLastError());
+	}
+	uint32_t counts[4] = {0, 0, 0, 0};
+	HIP_TRY(hipMemcpyAsync(counts, c->render_counts.p, 16, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if (stats) {
+		stats->n_rays = (uint32_t)n_pix;
+		stats->n_hit = counts[1];
+		stats->rounds = rounds;
+		stats->reserved = 0;
+		stats->n_samples = (uint64_t)counts[2] | ((uint64_t)counts[3] << 32);
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
 	return RNB_OK;
 } RNB_GUARD
 

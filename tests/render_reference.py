@@ -1,0 +1,293 @@
+"""An independent numpy statement of the inference tracer (include/rnb_render.h; the reference's NerfTracer, src/testbed_nerf.cu:822-1118, 2248-2432).
+
+It shares no code with rnb-neus2_amd/csrc/kernels_render.cuh. The ray and march arithmetic is float32 in the kernels' operation order (the library is compiled
+with -ffp-contract=off, so every product and sum rounds on its own, as numpy's do): Eigen's three-term sums x0 + (x1 + x2), frexp for the cascades, floor and
+truncation toward zero for the cells. The march therefore finds the same samples, bit for bit. The composite follows composite_kernel_nerf (NeuS alpha,
+Normals / Depth modes) and shade_kernel_nerf; its transcendental functions differ from the device's in the last bits.
+
+Each ray is marched to the box exit in one go (the per-ray result does not depend on the rounds the library splits it into), the network is a callback
+net(coords float32 [n, 7]) -> float16 [n, 16] -- an analytic SDF (analytic_net) or the CPU checker's forward_infer on the same parameters.
+"""
+import numpy as np
+
+f32 = np.float32
+GRIDSIZE = 128
+CASCADES = 8
+MAX_STEPS = 1024
+SQRT3 = f32(1.73205080757)
+MIN_STEP = f32(SQRT3 / f32(1024))
+MAX_STEP = f32(MIN_STEP * f32(1024))
+WARP_MAX = f32(MIN_STEP * f32(1 << (CASCADES - 1)))
+CHANNELS = 9
+
+
+def esum3(a, b, c):
+    return a + (b + c)
+
+
+def camera_rays(view):
+    """Origins and unit directions of every pixel, row-major, as float32 [H*W, 3]: pixel (x, y) at ((x + 0.5) / W, (y + 0.5) / H)."""
+    w, h = int(view["width"]), int(view["height"])
+    m = np.asarray(view["xform"], np.float32).reshape(12)
+    fx, fy = (f32(v) for v in view["focal_length"])
+    cx, cy = (f32(v) for v in view["principal_point"])
+    ys, xs = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
+    u = ((xs.ravel() + f32(0.5)) / f32(w)).astype(np.float32)
+    v = ((ys.ravel() + f32(0.5)) / f32(h)).astype(np.float32)
+    dx = (u - cx) * f32(w) / fx
+    dy = (v - cy) * f32(h) / fy
+    dz = np.ones_like(dx)
+    du = np.stack([esum3(m[0] * dx, m[1] * dy, m[2] * dz), esum3(m[4] * dx, m[5] * dy, m[6] * dz), esum3(m[8] * dx, m[9] * dy, m[10] * dz)], axis=1)
+    n = np.sqrt(esum3(du[:, 0] * du[:, 0], du[:, 1] * du[:, 1], du[:, 2] * du[:, 2]))
+    d = (du / n[:, None]).astype(np.float32)
+    o = np.broadcast_to(np.array([m[3], m[7], m[11]], np.float32), d.shape).copy()
+    return o, d
+
+
+def ray_box(o, d, mn, mx):
+    """bounding_box.cuh:163-206, float32; misses get +max float."""
+    FMAX = f32(3.402823466e38)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t0 = (f32(mn) - o[:, 0]) / d[:, 0]
+        t1 = (f32(mx) - o[:, 0]) / d[:, 0]
+        tmin = np.where(t0 > t1, t1, t0)
+        tmax = np.where(t0 > t1, t0, t1)
+        miss = np.zeros(len(o), bool)
+        for k in (1, 2):
+            a = (f32(mn) - o[:, k]) / d[:, k]
+            b = (f32(mx) - o[:, k]) / d[:, k]
+            lo, hi = np.where(a > b, b, a), np.where(a > b, a, b)
+            miss |= (tmin > hi) | (lo > tmax)
+            tmin = np.where(lo > tmin, lo, tmin)
+            tmax = np.where(hi < tmax, hi, tmax)
+    tmin = np.where(miss, FMAX, tmin).astype(np.float32)
+    return tmin
+
+
+def contains(p, mn, mx):
+    return np.all((p >= f32(mn)) & (p <= f32(mx)), axis=1)
+
+
+def _exponent(x):
+    return np.frexp(x.astype(np.float32))[1]
+
+
+def mip_from_dt(dt, pos):
+    maxval = np.fmax(np.fmax(np.abs(pos[:, 0] - f32(0.5)), np.abs(pos[:, 1] - f32(0.5))), np.abs(pos[:, 2] - f32(0.5)))
+    mip = np.minimum(CASCADES - 1, np.maximum(0, _exponent(maxval) + 1))
+    d = dt * f32(2 * GRIDSIZE)
+    big = d >= f32(1)
+    return np.where(big, np.minimum(CASCADES - 1, np.maximum(_exponent(np.where(big, d, f32(1))), mip)), mip)
+
+
+def _expand(v):
+    v = v.astype(np.uint32)
+    v = (v * np.uint32(0x00010001)) & np.uint32(0xFF0000FF)
+    v = (v * np.uint32(0x00000101)) & np.uint32(0x0F00F00F)
+    v = (v * np.uint32(0x00000011)) & np.uint32(0xC30C30C3)
+    v = (v * np.uint32(0x00000005)) & np.uint32(0x49249249)
+    return v
+
+
+def morton3d(x, y, z):
+    return _expand(x) | (_expand(y) << np.uint32(1)) | (_expand(z) << np.uint32(2))
+
+
+def occupied(pos, bitfield, mip):
+    scale = np.ldexp(np.ones(len(pos), np.float32), -mip).astype(np.float32)
+    p = ((pos - f32(0.5)) * scale[:, None] + f32(0.5)).astype(np.float32)
+    # (int)(p * 128): truncation toward zero, then the clamp to the grid
+    idx3 = np.clip(np.trunc(p * f32(GRIDSIZE)).astype(np.int64), 0, GRIDSIZE - 1)
+    idx = morton3d(idx3[:, 0], idx3[:, 1], idx3[:, 2]).astype(np.int64)
+    byte = bitfield[idx // 8 + (GRIDSIZE ** 3 * mip.astype(np.int64)) // 8]
+    return (byte >> (idx % 8).astype(np.uint8)) & 1 != 0
+
+
+def advance_to_next_voxel(t, pos, d, idir, res):
+    resf = res.astype(np.float32)
+    p = resf[:, None] * pos
+    sgn = np.where(np.signbit(d), f32(-1), f32(1)).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        tt = (np.floor(p + f32(0.5) + f32(0.5) * sgn) - p) * idir
+    tm = np.fmin(np.fmin(tt[:, 0], tt[:, 1]), tt[:, 2])  # fminf / fmaxf: a NaN operand (an axis-parallel direction) loses
+    dist = np.fmax(tm / resf, f32(0))
+    target = t + dist
+    t = t + MIN_STEP  # calc_dt with cone angle 0 (aabb_scale 1)
+    go = t < target
+    while go.any():
+        t = np.where(go, t + MIN_STEP, t)
+        go = go & (t < target)
+    return t.astype(np.float32)
+
+
+def march(o, d, bitfield, near=0.2, mn=0.0, mx=1.0):
+    """Every ray to the box exit (at most MAX_STEPS samples). Returns (ray index [S], coords float32 [S, 7]) in ray order, samples of a ray in march order,
+    and n_samples per ray. bitfield None = every cell occupied. Single cascade, cone angle 0 (aabb_scale 1, the scenes this project trains)."""
+    n = len(o)
+    mn, mx = f32(mn), f32(mx)
+    diag = f32(mx - mn)
+    tmin = ray_box(o, d, mn, mx)
+    t = (np.fmax(tmin, f32(near)) + f32(1e-6)).astype(np.float32)
+    with np.errstate(divide="ignore"):
+        idir = (f32(1) / d).astype(np.float32)
+    wd = ((d + f32(1)) * f32(0.5)).astype(np.float32)
+    cnt = np.zeros(n, np.int64)
+    alive = contains(o + t[:, None] * d, mn, mx)
+    ray_ids, coords = [], []
+    while alive.any():
+        a = np.nonzero(alive)[0]
+        ta = t[a]
+        pos = (o[a] + ta[:, None] * d[a]).astype(np.float32)
+        inside = contains(pos, mn, mx)
+        alive[a[~inside]] = False
+        a, ta, pos = a[inside], ta[inside], pos[inside]
+        dt = np.full(len(a), MIN_STEP, np.float32)
+        mip = mip_from_dt(dt, pos)
+        occ = np.ones(len(a), bool) if bitfield is None else occupied(pos, bitfield, mip)
+        e = a[occ]
+        if len(e):
+            wp = ((pos[occ] - mn) / diag).astype(np.float32)
+            c = np.empty((len(e), 7), np.float32)
+            c[:, 0:3] = wp
+            c[:, 3] = (dt[occ] - MIN_STEP) / (WARP_MAX - MIN_STEP)
+            c[:, 4:7] = wd[e]
+            ray_ids.append(e)
+            coords.append(c)
+            t[e] = ta[occ] + dt[occ]
+            cnt[e] += 1
+            alive[e[cnt[e] >= MAX_STEPS]] = False
+        s = a[~occ]
+        if len(s):
+            t[s] = advance_to_next_voxel(ta[~occ], pos[~occ], d[s], idir[s], (GRIDSIZE >> mip[~occ]).astype(np.int64))
+    if ray_ids:
+        rid = np.concatenate(ray_ids)
+        co = np.concatenate(coords)
+        order = np.argsort(rid, kind="stable")  # samples of a ray stay in march order
+        return rid[order], co[order], cnt
+    return np.zeros(0, np.int64), np.zeros((0, 7), np.float32), cnt
+
+
+def _logistic(x):
+    return (1.0 / (1.0 + np.exp(-x.astype(np.float64)))).astype(np.float32)
+
+
+def composite(view, o, rid, coords, out, n_rays, min_transmittance=0.01, no_albedo=False, mn=0.0, mx=1.0):
+    """composite_kernel_nerf (testbed_nerf.cu:881-1118) in Normals + Depth modes and shade_kernel_nerf: float32 [n_rays, 9] in the channel order of rnb_render.h."""
+    out = out.astype(np.float32)
+    counts = np.bincount(rid, minlength=n_rays)
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    jmax = int(counts.max()) if n_rays and len(rid) else 0
+    m = np.asarray(view["xform"], np.float32).reshape(3, 4)
+    fwd = m[:, 2]
+    diag = f32(mx) - f32(mn)
+    W = np.zeros(n_rays, np.float32)
+    N = np.zeros((n_rays, 3), np.float32)
+    A = np.zeros((n_rays, 3), np.float32)
+    wmax = np.zeros(n_rays, np.float32)
+    depth = np.zeros(n_rays, np.float32)
+    nsamp = np.zeros(n_rays, np.int64)
+    live = counts > 0
+    stopped = np.zeros(n_rays, bool)
+    for j in range(jmax):
+        r = np.nonzero(live & (counts > j))[0]
+        if not len(r):
+            break
+        s = first[r] + j
+        ob, c = out[s], coords[s]
+        dt = c[:, 3] * (WARP_MAX - MIN_STEP) + MIN_STEP
+        dv = ob[:, 8:11] * f32(2) - f32(1)
+        dv = dv / np.sqrt(esum3(dv[:, 0] * dv[:, 0], dv[:, 1] * dv[:, 1], dv[:, 2] * dv[:, 2]))[:, None]
+        inv_s = np.exp((np.float16(10) * out[s, 7].astype(np.float16)).astype(np.float32))
+        g = ob[:, 4:7]
+        true_cos = dv[:, 0] * g[:, 0] + dv[:, 1] * g[:, 1] + dv[:, 2] * g[:, 2]
+        iter_cos = -np.maximum(f32(0), -true_cos)  # cos_anneal_ratio 1: the relu(-cos / 2 + 1 / 2) term carries weight 0
+        half_step = (iter_cos * dt).astype(np.float64) * 0.5
+        sdf = ob[:, 3].astype(np.float64)
+        est_next = (sdf + half_step).astype(np.float32)
+        est_prev = (sdf - half_step).astype(np.float32)
+        nc, pc = _logistic(est_next * inv_s), _logistic(est_prev * inv_s)
+        alpha = np.clip(((pc - nc) + f32(1e-5)) / (pc + f32(1e-5)), 0, 1).astype(np.float32)
+        weight = alpha * (f32(1) - W[r])
+        gn = np.sqrt(esum3(g[:, 0] * g[:, 0], g[:, 1] * g[:, 1], g[:, 2] * g[:, 2]))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            nrm = np.where(gn[:, None] > 0, g / gn[:, None], f32(0)).astype(np.float32)
+        alb = np.ones((len(r), 3), np.float32) if no_albedo else _logistic(ob[:, 0:3])
+        N[r] += weight[:, None] * nrm
+        A[r] += weight[:, None] * alb
+        W[r] += weight
+        nsamp[r] += 1
+        better = weight > wmax[r]
+        pos = c[:, 0:3] * diag + f32(mn)
+        dep = esum3(fwd[0] * (pos[:, 0] - o[r, 0]), fwd[1] * (pos[:, 1] - o[r, 1]), fwd[2] * (pos[:, 2] - o[r, 2]))
+        wmax[r] = np.where(better, weight, wmax[r])
+        depth[r] = np.where(better, dep, depth[r])
+        if min_transmittance > 0:
+            stop = W[r] > f32(1) - f32(min_transmittance)
+            stopped[r[stop]] = True
+            live[r[stop]] = False
+    res = np.zeros((n_rays, CHANNELS), np.float32)
+    hit = W > 0
+    nn = np.sqrt(esum3(N[:, 0] * N[:, 0], N[:, 1] * N[:, 1], N[:, 2] * N[:, 2]))
+    ok = hit & (nn > 0)
+    res[ok, 0:3] = N[ok] / nn[ok, None]
+    res[hit, 3:6] = A[hit] / W[hit, None]
+    opacity = np.where(stopped, f32(1), W)
+    res[:, 6] = opacity
+    res[:, 7] = np.where(opacity > f32(0.2), depth, f32(0))
+    res[:, 8] = nsamp
+    return res
+
+
+def render(view, net, bitfield=None, min_transmittance=0.01, near=0.2, no_albedo=False, chunk=1 << 16):
+    """The whole tracer: float32 [H, W, 9] (the layout of rnb_render) and the number of network samples."""
+    o, d = camera_rays(view)
+    rid, coords, cnt = march(o, d, bitfield, near)
+    out = np.zeros((len(coords), 16), np.float16)
+    for k in range(0, len(coords), chunk):
+        out[k:k + chunk] = net(coords[k:k + chunk])
+    res = composite(view, o, rid, coords, out, len(o), min_transmittance, no_albedo)
+    return res.reshape(int(view["height"]), int(view["width"]), CHANNELS), len(coords)
+
+
+def analytic_net(sdf_and_grad, variance=0.8, albedo_logit=(0.0, 1.0, -1.0)):
+    """A network stand-in from an SDF on world positions: outputs 0..2 albedo logits, 3 the SDF, 4..6 its gradient, 7 the variance (inv_s = exp(10 variance)),
+    8..10 the warped direction echoed (the network's BENT_DIR outputs). Box [0, 1]^3, so the warped position is the position."""
+    def net(coords):
+        sdf, grad = sdf_and_grad(coords[:, 0:3].astype(np.float64))
+        o = np.zeros((len(coords), 16), np.float32)
+        o[:, 0:3] = albedo_logit
+        o[:, 3] = sdf
+        o[:, 4:7] = grad
+        o[:, 7] = variance
+        o[:, 8:11] = coords[:, 4:7]
+        return o.astype(np.float16)
+    return net
+
+
+def sphere_sdf(center=(0.5, 0.5, 0.5), radius=0.25):
+    c = np.asarray(center, np.float64)
+
+    def f(p):
+        v = p - c
+        n = np.linalg.norm(v, axis=1)
+        return n - radius, v / np.maximum(n, 1e-12)[:, None]
+    return f
+
+
+def bitfield_from_sdf(sdf_and_grad, band=2.5 / GRIDSIZE):
+    """An occupancy bitfield (uint8 [128^3 / 8 * 8]) whose cascade-0 cells are occupied where |sdf(cell centre)| < band; the coarser cascades are empty."""
+    i = np.arange(GRIDSIZE ** 3, dtype=np.uint32)
+    # morton3D_invert of the index: the cell's x, y, z
+    def inv(x):
+        x = x & np.uint32(0x49249249)
+        x = (x | (x >> np.uint32(2))) & np.uint32(0xC30C30C3)
+        x = (x | (x >> np.uint32(4))) & np.uint32(0x0F00F00F)
+        x = (x | (x >> np.uint32(8))) & np.uint32(0xFF0000FF)
+        x = (x | (x >> np.uint32(16))) & np.uint32(0x0000FFFF)
+        return x
+    xyz = np.stack([inv(i), inv(i >> np.uint32(1)), inv(i >> np.uint32(2))], axis=1).astype(np.float64)
+    sdf, _ = sdf_and_grad((xyz + 0.5) / GRIDSIZE)
+    occ = np.abs(sdf) < band
+    bits = np.zeros(GRIDSIZE ** 3 // 8 * CASCADES, np.uint8)
+    bits[: GRIDSIZE ** 3 // 8] = np.packbits(occ.reshape(-1, 8)[:, ::-1], axis=1).ravel()
+    return bits
