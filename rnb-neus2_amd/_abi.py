@@ -216,6 +216,67 @@ RENDER_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh.h: the sparse mesh extractor, a header of its own with its own version (the HIP library only) ----
+MESH_ABI_VERSION = 1
+MESH_CULL_NONE, MESH_CULL_OCCUPANCY = 0, 1
+MESH_ATTR_COLORS, MESH_ATTR_NORMALS = 1, 2
+MESH_MAX_RES = 4096
+
+
+class MeshOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("res", C.c_uint32 * 3),
+        ("lattice_min", C.c_float),
+        ("lattice_max", C.c_float),
+        ("aabb_min", C.c_float * 3),
+        ("aabb_max", C.c_float * 3),
+        ("thresh", C.c_float),
+        ("use_inference_params", C.c_uint32),
+        ("cull", C.c_uint32),
+        ("brick", C.c_uint32),
+        ("attributes", C.c_uint32),
+        ("max_points_in_flight", C.c_uint32),
+        ("max_active_points", C.c_uint64),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class Mesh(C.Structure):
+    _fields_ = [
+        ("verts", C.c_void_p),
+        ("indices", C.c_void_p),
+        ("colors", C.c_void_p),
+        ("normals", C.c_void_p),
+        ("n_verts", C.c_uint32),
+        ("n_indices", C.c_uint32),
+    ]
+
+
+class MeshStats(C.Structure):
+    _fields_ = [
+        ("n_bricks", C.c_uint64),
+        ("n_kept", C.c_uint64),
+        ("n_evaluated", C.c_uint64),
+        ("n_sign_change", C.c_uint64),
+        ("n_points_evaluated", C.c_uint64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+MESH_PROTOTYPES = {
+    "mesh_abi_version": (_u32, []),
+    "mesh_default_options": (_i, [C.POINTER(MeshOptions)]),
+    "extract_mesh": (_i, [_ctx, _stream, C.POINTER(MeshOptions), C.POINTER(Mesh), C.POINTER(MeshStats)]),
+    "mesh_free": (_i, [_ctx, C.POINTER(Mesh)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -236,6 +297,6 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_", render=False):
-    """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), which only the HIP library exports."""
-    return Functions(lib, prefix, (PROTOTYPES, RENDER_PROTOTYPES) if render else (PROTOTYPES,))
+def declare(lib, prefix="rnb_", render=False, mesh=False):
+    """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h); only the HIP library exports those."""
+    return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()))

@@ -45,11 +45,13 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_", render=True)
+        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
             raise RuntimeError("render ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_abi_version() != _abi.MESH_ABI_VERSION:
+            raise RuntimeError("mesh ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -472,6 +474,40 @@ class Context:
         self.device_free(pv.value)
         self.device_free(pi.value)
         return verts, idx
+
+    def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
+                     cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None):
+        """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
+        marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
+        Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
+        The device mesh is released before returning. Leaves the training state as it was."""
+        opt = _abi.MeshOptions()
+        self._check(self.f.mesh_default_options(C.byref(opt)))
+        opt.res[:] = [int(res)] * 3 if np.isscalar(res) else [int(x) for x in res]
+        opt.lattice_min, opt.lattice_max = float(lattice_min), float(lattice_max)
+        opt.aabb_min[:] = [float(x) for x in aabb_min]
+        opt.aabb_max[:] = [float(x) for x in aabb_max]
+        opt.thresh = float(thresh)
+        opt.use_inference_params = int(bool(inference))
+        if cull not in ("none", "occupancy", _abi.MESH_CULL_NONE, _abi.MESH_CULL_OCCUPANCY):
+            raise ValueError("cull must be 'none' or 'occupancy'")
+        opt.cull = {"none": _abi.MESH_CULL_NONE, "occupancy": _abi.MESH_CULL_OCCUPANCY}.get(cull, cull)
+        opt.brick = int(brick)
+        opt.attributes = (_abi.MESH_ATTR_COLORS if colors else 0) | (_abi.MESH_ATTR_NORMALS if normals else 0)
+        opt.max_points_in_flight = int(max_points_in_flight)
+        opt.max_active_points = int(max_active_points)
+        m, st = _abi.Mesh(), _abi.MeshStats()
+        self._check(self.f.extract_mesh(self._h, _stream_handle(stream), C.byref(opt), C.byref(m), C.byref(st)))
+        try:
+            out = dict(verts=self.download(m.verts, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32),
+                       indices=self.download(m.indices, m.n_indices, np.uint32) if m.n_indices else np.empty(0, np.uint32))
+            for key, ptr in (("colors", m.colors), ("normals", m.normals)):
+                if ptr:
+                    out[key] = self.download(ptr, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32)
+            out["stats"] = st.as_dict()
+        finally:
+            self.f.mesh_free(self._h, C.byref(m))
+        return out
 
     def upload(self, array):
         """numpy array -> library-side buffer (device_malloc + copy); release with device_free."""

@@ -6,9 +6,9 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG_DIR, "csrc", "rnb_neus2_hip.hip")
 OUT = os.path.join(PKG_DIR, "librnb_neus2_hip.so")
-DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "kernels_mesh.cuh", "kernels_render.cuh")] + [
+DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "kernels_mesh.cuh", "kernels_render.cuh", "kernels_mesh_sparse.cuh")] + [
     os.path.join(PKG_DIR, "host", f) for f in ("mesh.hpp", "mc_table.hpp")] + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", f) for f in ("rnb_neus2.h", "rnb_render.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", f) for f in ("rnb_neus2.h", "rnb_render.h", "rnb_mesh.h")]
 
 # -ffp-contract=off: the index/ray arithmetic must match the CPU checker bit for bit (no FMA contraction).
 # -packed-fp32-ops (device target feature): no v_pk_{mul,add,fma}_f32. Measured on MI355X / ROCm 7.2 with tools/march_determinism.py: the
@@ -105,6 +105,27 @@ def build_render(force=False, verbose=False):
     return RENDER_OUT
 
 
+MESH_SRC = os.path.join(PKG_DIR, "host", "mesh_main.cpp")
+MESH_OUT = os.path.join(ROOT, "build", "mesh")
+MESH_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("mesh_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "snapshot.hpp", "mesh.hpp", "mc_table.hpp")] + [
+    os.path.join(ROOT, "include", f) for f in ("rnb_neus2.h", "rnb_mesh.h")]
+
+
+def build_mesh(force=False, verbose=False):
+    """`build/mesh`: the coloured mesh of a trained snapshot through the sparse extractor (include/rnb_mesh.h); plain g++, links the HIP library + zlib."""
+    if not force and os.path.exists(MESH_OUT):
+        t = os.path.getmtime(MESH_OUT)
+        if not any(os.path.getmtime(d) > t for d in MESH_DEPS):
+            return MESH_OUT
+    os.makedirs(os.path.dirname(MESH_OUT), exist_ok=True)
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), MESH_SRC, "-o", MESH_OUT,
+           "-L" + PKG_DIR, "-lrnb_neus2_hip", "-lz", "-Wl,-rpath,$ORIGIN/../rnb-neus2_amd"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return MESH_OUT
+
+
 HOSTLIB_SRC = os.path.join(PKG_DIR, "host", "hostlib.cpp")
 HOSTLIB_OUT = os.path.join(PKG_DIR, "librnb_host.so")
 HOSTLIB_DEPS = [HOSTLIB_SRC, os.path.join(PKG_DIR, "host", "png16.hpp"), os.path.join(ROOT, "include", "rnb_host.h")]
@@ -128,3 +149,4 @@ if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_testbed(force=True, verbose=True))
     print(build_render(force=True, verbose=True))
+    print(build_mesh(force=True, verbose=True))

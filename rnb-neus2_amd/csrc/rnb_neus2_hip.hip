@@ -5,6 +5,7 @@
 #include "kernels_ray.cuh"
 #include "kernels_mesh.cuh"
 #include "kernels_render.cuh"
+#include "kernels_mesh_sparse.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>
@@ -2069,6 +2070,22 @@ int scan_exclusive(uint32_t* data, uint64_t n, hipStream_t s, uint32_t* total_ou
 }
 } // namespace
 
+// the marching-cubes case table of host/mesh.hpp on the device, uploaded on first use
+static int ensure_mc_table(rnb_ctx* c) {
+	if (c->mc_table.p) return RNB_OK;
+	static const mesh::Tables T;
+	std::vector<McTable> h(1);
+	for (int m = 0; m < 256; ++m) {
+		int k = 0;
+		for (; T.tri[m][k] >= 0; ++k) h[0].tri[m][k] = T.tri[m][k];
+		h[0].n[m] = (uint8_t)k;
+		for (; k < 40; ++k) h[0].tri[m][k] = -1;
+	}
+	if (c->mc_table.alloc(1) != hipSuccess) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the case table");
+	HIP_TRY(hipMemcpy(c->mc_table.p, h.data(), sizeof(McTable), hipMemcpyHostToDevice));
+	return RNB_OK;
+}
+
 int rnb_marching_cubes(rnb_ctx* c, void* stream, const float* density, const uint32_t res[3], const float aabb_min[3], const float aabb_max[3], float thresh,
                        float** verts_out, uint32_t** indices_out, uint32_t* n_verts, uint32_t* n_indices) try {
 	if (!c || !density || !res || !aabb_min || !aabb_max || !verts_out || !indices_out || !n_verts || !n_indices) return fail(RNB_ERR_INVALID, "null argument");
@@ -2076,18 +2093,7 @@ int rnb_marching_cubes(rnb_ctx* c, void* stream, const float* density, const uin
 	const uint64_t res3 = (uint64_t)res[0] * res[1] * res[2];
 	if (res3 == 0 || res3 >= (1ull << 32)) return fail(RNB_ERR_INVALID, "lattice must hold 1 .. 2^32-1 points");
 	hipStream_t s = as_stream(stream);
-	if (!c->mc_table.p) { // the case table of host/mesh.hpp, once
-		static const mesh::Tables T;
-		std::vector<McTable> h(1);
-		for (int m = 0; m < 256; ++m) {
-			int k = 0;
-			for (; T.tri[m][k] >= 0; ++k) h[0].tri[m][k] = T.tri[m][k];
-			h[0].n[m] = (uint8_t)k;
-			for (; k < 40; ++k) h[0].tri[m][k] = -1;
-		}
-		if (c->mc_table.alloc(1) != hipSuccess) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the case table");
-		HIP_TRY(hipMemcpy(c->mc_table.p, h.data(), sizeof(McTable), hipMemcpyHostToDevice));
-	}
+	if (int rc = ensure_mc_table(c); rc != RNB_OK) return rc;
 	McArgs a;
 	a.density = density; a.rx = res[0]; a.ry = res[1]; a.rz = res[2]; a.thresh = thresh;
 	for (int d = 0; d < 3; ++d) { a.sc[d] = (aabb_max[d] - aabb_min[d]) / (float)res[d]; a.mn[d] = aabb_min[d]; }
@@ -2688,6 +2694,217 @@ int rnb_render(rnb_ctx* c, void* stream, const rnb_view* view, const rnb_render_
 		stats->rounds = rounds;
 		stats->reserved = 0;
 		stats->n_samples = (uint64_t)counts[2] | ((uint64_t)counts[3] << 32);
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- sparse mesh extraction (include/rnb_mesh.h) ----
+uint32_t rnb_mesh_abi_version(void) { return RNB_MESH_ABI_VERSION; }
+
+int rnb_mesh_default_options(rnb_mesh_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_ABI_VERSION;
+	for (int k = 0; k < 3; ++k) { opt->res[k] = 256; opt->aabb_min[k] = 0.f; opt->aabb_max[k] = 1.f; }
+	opt->lattice_min = 0.f; opt->lattice_max = 1.f;
+	opt->thresh = 0.f;
+	opt->use_inference_params = 1;
+	opt->cull = RNB_MESH_CULL_OCCUPANCY;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_free(rnb_ctx* c, rnb_mesh* m) try {
+	if (!c || !m) return fail(RNB_ERR_INVALID, "null argument");
+	if (m->verts) (void)hipFree(m->verts);
+	if (m->indices) (void)hipFree(m->indices);
+	if (m->colors) (void)hipFree(m->colors);
+	if (m->normals) (void)hipFree(m->normals);
+	std::memset(m, 0, sizeof(*m));
+	return RNB_OK;
+} RNB_GUARD
+
+extern "C++" {
+namespace {
+constexpr uint32_t MESH_DEFAULT_BRICK = 16; // measured against 32 (tools/bench_mesh.py, profiles/mesh_sparse.md): fewer points evaluated around the surface
+// The device memory of one rnb_extract_mesh call: what is still held when the object goes out of scope is released; bytes held now and at the peak.
+struct MeshWorkspace {
+	std::vector<std::pair<void*, size_t>> held;
+	size_t cur = 0, peak = 0;
+	template <typename T>
+	bool alloc(T** p, size_t count) {
+		*p = nullptr;
+		const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+		if (hipMalloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+		held.emplace_back((void*)*p, bytes);
+		cur += bytes; peak = std::max(peak, cur);
+		return true;
+	}
+	template <typename T>
+	void release(T*& p) { // free now
+		for (auto& h : held) if (h.first == (void*)p && p) { (void)hipFree(h.first); cur -= h.second; h.first = nullptr; }
+		p = nullptr;
+	}
+	void* keep(void* p) { // the caller owns it from here on (it still counts as held)
+		for (auto& h : held) if (h.first == p) h.first = nullptr;
+		return p;
+	}
+	~MeshWorkspace() { for (auto& h : held) if (h.first) (void)hipFree(h.first); }
+};
+} // namespace
+} // extern "C++"
+
+int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_mesh* out, rnb_mesh_stats* stats) try {
+	if (!c || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: null argument");
+	std::memset(out, 0, sizeof(*out));
+	if (opt->abi_version != RNB_MESH_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: options abi_version mismatch (expected RNB_MESH_ABI_VERSION)");
+	for (int k = 0; k < 3; ++k) if (opt->res[k] == 0 || opt->res[k] > RNB_MESH_MAX_RES) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: res must be 1 .. 4096 per axis");
+	if (opt->cull != RNB_MESH_CULL_NONE && opt->cull != RNB_MESH_CULL_OCCUPANCY) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: unknown cull mode");
+	if (opt->attributes & ~(RNB_MESH_ATTR_COLORS | RNB_MESH_ATTR_NORMALS)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: unknown attribute bits");
+	const uint32_t B = opt->brick ? opt->brick : MESH_DEFAULT_BRICK;
+	if (B < 8 || B > 64 || (B & (B - 1))) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: brick must be a power of two, 8 .. 64 (0 = default)");
+	if (!std::isfinite(opt->lattice_min) || !std::isfinite(opt->lattice_max) || !std::isfinite(opt->thresh)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: lattice bounds and thresh must be finite");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
+	if (int rc = ensure_mc_table(c); rc != RNB_OK) return rc;
+
+	MeshWorkspace ws;
+	MsArgs a;
+	std::memset(&a, 0, sizeof(a));
+	a.lb = ilog2(B);
+	uint64_t n_bricks64 = 1;
+	for (int k = 0; k < 3; ++k) {
+		a.r[k] = opt->res[k]; a.nb[k] = (opt->res[k] + B - 1) / B; n_bricks64 *= a.nb[k];
+		a.sc[k] = (opt->aabb_max[k] - opt->aabb_min[k]) / (float)opt->res[k]; a.mn[k] = opt->aabb_min[k];
+	}
+	a.thresh = opt->thresh;
+	a.n_bricks = (uint32_t)n_bricks64; // at most (4096 / 8)^3 = 2^27
+	const uint32_t lb3 = 3 * a.lb;
+	const uint64_t brick_points = 1ull << lb3;
+	const bool inference = opt->use_inference_params != 0;
+
+	// 1. which bricks are kept, which are evaluated, and their slots
+	const uint32_t n_bwg = (a.n_bricks + MC_WG - 1) / MC_WG;
+	uint32_t *bwg = nullptr, *bscan = nullptr, *list = nullptr;
+	if (!ws.alloc(&a.word, a.n_bricks) || !ws.alloc(&bwg, n_bwg) || !ws.alloc(&bscan, scan_scratch_elems(n_bwg))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick words");
+	hipLaunchKernelGGL(k_ms_classify, dim3((a.n_bricks + 3) / 4), dim3(256), 0, s, a, (double)opt->lattice_min, (double)opt->lattice_max - (double)opt->lattice_min,
+	                   opt->cull == RNB_MESH_CULL_OCCUPANCY ? (const uint8_t*)c->bitfield.p : (const uint8_t*)nullptr);
+	hipLaunchKernelGGL(k_ms_mark<false>, dim3(n_bwg), dim3(MC_WG), 0, s, a, bwg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+	HIP_TRY(hipGetLastError());
+	uint32_t n_eval = 0;
+	int rc = scan_exclusive(bwg, n_bwg, s, &n_eval, bscan);
+	if (rc != RNB_OK) return rc;
+	if (!ws.alloc(&list, n_eval)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick list");
+	a.list = list;
+	hipLaunchKernelGGL(k_ms_mark<true>, dim3(n_bwg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, bwg, list);
+	HIP_TRY(hipGetLastError());
+	uint64_t n_kept = 0;
+	{ // the kept count, for the statistics: the evaluated count is the scan's total
+		std::vector<uint32_t> h(a.n_bricks);
+		HIP_TRY(hipMemcpyAsync(h.data(), a.word, (size_t)a.n_bricks * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		for (uint32_t w : h) n_kept += w & 1u;
+	}
+	ws.release(bwg); ws.release(bscan);
+	const uint64_t n_active_points = (uint64_t)n_eval * brick_points;
+	if (opt->max_active_points && n_active_points > opt->max_active_points)
+		return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: " + std::to_string(n_active_points) + " lattice points would be held at once (" + std::to_string(n_eval) + " bricks of " +
+		            std::to_string(B) + "^3), max_active_points is " + std::to_string(opt->max_active_points));
+	if (n_eval >= (1u << 30)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: more than 2^30 bricks to evaluate");
+
+	uint32_t n_act = 0, nv = 0, ni = 0;
+	float* verts = nullptr;
+	uint32_t* indices = nullptr;
+	if (n_eval) {
+		// 2. the lattice values of the evaluated bricks, through the point-query kernel of rnb_sdf_lattice
+		half_t* vals = nullptr;
+		float* pos = nullptr;
+		uint64_t per_launch = opt->max_points_in_flight ? opt->max_points_in_flight : (1u << 22);
+		const uint32_t slots_per_launch = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per_launch >> lb3, 1), n_eval);
+		if (!ws.alloc(&vals, n_active_points) || !ws.alloc(&pos, (size_t)slots_per_launch * brick_points * 3))
+			return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for " + std::to_string(n_active_points) + " lattice values (set max_active_points to fail before allocating, or cull)");
+		a.vals = vals;
+		const float diag = c->aabb.mx - c->aabb.mn;
+		for (uint32_t s0 = 0; s0 < n_eval; s0 += slots_per_launch) {
+			const uint32_t np = (uint32_t)(std::min<uint32_t>(slots_per_launch, n_eval - s0) * brick_points); // at most 2^22 or one brick (2^18)
+			hipLaunchKernelGGL(k_ms_positions, dim3((np + 255) / 256), dim3(256), 0, s, a, s0, np, opt->lattice_min, opt->lattice_max - opt->lattice_min, c->aabb.mn, diag, pos);
+			HIP_TRY(hipGetLastError());
+			rc = launch_point_query(c, s, pos, np, vals + (size_t)s0 * brick_points, nullptr, nullptr, 0, inference);
+			if (rc != RNB_OK) return rc;
+		}
+		// 3. which of them see both sides of the threshold; only those keep an edge table
+		uint32_t *act = nullptr, *aoff = nullptr, *ascan = nullptr, *alist = nullptr;
+		if (!ws.alloc(&act, n_eval) || !ws.alloc(&aoff, n_eval) || !ws.alloc(&ascan, scan_scratch_elems(n_eval))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick flags");
+		hipLaunchKernelGGL(k_ms_sign, dim3(n_eval), dim3(256), 0, s, a, act);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(aoff, act, (size_t)n_eval * 4, hipMemcpyDeviceToDevice, s));
+		rc = scan_exclusive(aoff, n_eval, s, &n_act, ascan);
+		if (rc != RNB_OK) return rc;
+		ws.release(pos); ws.release(ascan);
+		a.act = act; a.aoff = aoff;
+		if (n_act) {
+			if ((uint64_t)n_act << (lb3 - 8) >= (1ull << 31)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: too many bricks with a sign change for one launch");
+			const uint32_t n_wg = n_act << (lb3 - 8);
+			uint32_t *wg = nullptr, *wscan = nullptr, *vidx = nullptr;
+			if (!ws.alloc(&alist, n_act) || !ws.alloc(&wg, n_wg) || !ws.alloc(&wscan, scan_scratch_elems(n_wg)) || !ws.alloc(&vidx, (size_t)n_act * 3 * brick_points))
+				return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the edge tables of " + std::to_string(n_act) + " bricks");
+			a.alist = alist;
+			hipLaunchKernelGGL(k_ms_list, dim3((n_eval + 255) / 256), dim3(256), 0, s, n_eval, act, aoff, alist);
+			// 4. vertices, then triangles: count, scan, write (the dense path's scheme over the bricks' workgroups)
+			hipLaunchKernelGGL(k_ms_verts<false>, dim3(n_wg), dim3(MC_WG), 0, s, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr);
+			HIP_TRY(hipGetLastError());
+			rc = scan_exclusive(wg, n_wg, s, &nv, wscan);
+			if (rc != RNB_OK) return rc;
+			if (!ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
+			hipLaunchKernelGGL(k_ms_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
+			hipLaunchKernelGGL(k_ms_faces<false>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr);
+			HIP_TRY(hipGetLastError());
+			rc = scan_exclusive(wg, n_wg, s, &ni, wscan);
+			if (rc != RNB_OK) return rc;
+			if (!ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
+			hipLaunchKernelGGL(k_ms_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			ws.release(wg); ws.release(wscan); ws.release(vidx); ws.release(alist);
+		}
+		ws.release(vals); ws.release(act); ws.release(aoff);
+	}
+	ws.release(a.word); ws.release(list);
+	if (!verts && !ws.alloc(&verts, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
+	if (!indices && !ws.alloc(&indices, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
+
+	// 5. attributes: the full network at the vertices, in batches
+	float *colors = nullptr, *normals = nullptr;
+	if (opt->attributes) {
+		if ((opt->attributes & RNB_MESH_ATTR_COLORS) && !ws.alloc(&colors, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the colours");
+		if ((opt->attributes & RNB_MESH_ATTR_NORMALS) && !ws.alloc(&normals, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the normals");
+		const uint32_t batch = std::min<uint32_t>(1u << 20, std::max(nv, 1u));
+		float* coords = nullptr;
+		half_t* net = nullptr;
+		if (!ws.alloc(&coords, (size_t)batch * 7) || !ws.alloc(&net, (size_t)batch * 16)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the attribute batch");
+		const float diag = c->aabb.mx - c->aabb.mn;
+		for (uint32_t v0 = 0; v0 < nv; v0 += batch) {
+			const uint32_t nb = std::min(batch, nv - v0);
+			hipLaunchKernelGGL(k_ms_vertex_coords, dim3((nb + 255) / 256), dim3(256), 0, s, verts + (size_t)v0 * 3, nb, c->aabb.mn, diag, coords);
+			HIP_TRY(hipGetLastError());
+			rc = launch_forward(c, s, coords, nullptr, nb, net, inference);
+			if (rc != RNB_OK) return rc;
+			hipLaunchKernelGGL(k_ms_vertex_attr, dim3((nb + 255) / 256), dim3(256), 0, s, net, nb, colors ? colors + (size_t)v0 * 3 : nullptr, normals ? normals + (size_t)v0 * 3 : nullptr);
+			HIP_TRY(hipGetLastError());
+		}
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(coords); ws.release(net);
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	out->verts = (float*)ws.keep(verts); out->indices = (uint32_t*)ws.keep(indices);
+	out->colors = (float*)ws.keep(colors); out->normals = (float*)ws.keep(normals);
+	out->n_verts = nv; out->n_indices = ni;
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_bricks = a.n_bricks; stats->n_kept = n_kept; stats->n_evaluated = n_eval; stats->n_sign_change = n_act;
+		stats->n_points_evaluated = n_active_points;
+		stats->peak_workspace = ws.peak;
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}
 	return RNB_OK;

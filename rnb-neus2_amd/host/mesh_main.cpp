@@ -1,0 +1,179 @@
+// mesh_main.cpp — `./build/mesh`: the coloured mesh of a trained snapshot through the sparse extractor of include/rnb_mesh.h (the counterpart of the testbed's
+// --save-mesh, which uses the dense path). The scene is read by the testbed's loader (dataset.hpp: scale, offset and the normalisation of the OBJ) and the
+// snapshot by snapshot.hpp (its EMA weights, occupancy grid and network configuration).
+//
+//   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
+//
+// The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
+// ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
+// Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
+#include "../../include/rnb_neus2.h"
+#include "../../include/rnb_mesh.h"
+#include "dataset.hpp"
+#include "json_min.hpp"
+#include "mesh.hpp"
+#include "msgpack_min.hpp"
+#include "png16.hpp"
+#include "snapshot.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <map>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace {
+
+using namespace hostio;
+
+struct Flag { const char* name; const char* meta; const char* help; };
+const Flag FLAGS[] = {
+	{"snapshot", "PATH", "Trained snapshot (.msgpack) written by testbed --save-snapshot."},
+	{"scene", "DIR", "The scene the snapshot was trained on: its bounding box and the normalisation of the mesh."},
+	{"out", "FILE", "Output mesh (.obj)."},
+	{"resolution", "R", "Lattice points per axis, rounded up to a multiple of 16 (default 256; at most 4096)."},
+	{"cull", "MODE", "occupancy (default): skip the bricks the occupancy grid marks empty; none: evaluate the whole lattice."},
+	{"brick", "N", "Lattice points per brick edge: 8, 16, 32 or 64 (default: the library's)."},
+	{"normals", "MODE", "ring (default): area-weighted face normals, as the testbed; gradient: the SDF gradient at the vertex, from the device."},
+};
+struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
+
+void print_help(std::ostream& os, const char* prog) {
+	os << "  " << prog << " {OPTIONS}\n\n    coloured mesh of a trained snapshot, extracted brick by brick\n\n  OPTIONS:\n\n      -h, --help\n                                        Display this help menu.\n";
+	for (const auto& f : FLAGS) os << "      --" << f.name << "=[" << f.meta << "]\n                                        " << f.help << "\n";
+}
+
+std::map<std::string, std::string> parse_cli(int argc, char** argv, bool& help) {
+	std::map<std::string, std::string> a;
+	help = false;
+	for (int i = 1; i < argc; ++i) {
+		std::string tok = argv[i];
+		if (tok == "-h" || tok == "--help") { help = true; continue; }
+		if (tok.rfind("--", 0) != 0) throw ParseError("Passed in argument, but no positional arguments were ready to receive it: " + tok);
+		std::string name = tok.substr(2), value;
+		const size_t eq = name.find('=');
+		bool inline_value = eq != std::string::npos;
+		if (inline_value) { value = name.substr(eq + 1); name = name.substr(0, eq); }
+		bool known = false;
+		for (const auto& f : FLAGS) known = known || name == f.name;
+		if (!known) throw ParseError("Flag could not be matched: " + name);
+		if (!inline_value) {
+			if (i + 1 >= argc) throw ParseError("Flag '" + name + "' requires an argument but received none");
+			value = argv[++i];
+		}
+		a[name] = value;
+	}
+	return a;
+}
+
+uint32_t parse_u32(const std::string& k, const std::string& s) {
+	char* e = nullptr;
+	const unsigned long long v = std::strtoull(s.c_str(), &e, 10);
+	if (s.empty() || *e || s[0] == '-' || v > 0xffffffffull) throw ParseError("Argument '" + k + "' received invalid value type '" + s + "'");
+	return (uint32_t)v;
+}
+
+#define RNB_CHECK(expr)                                                                          \
+	do {                                                                                         \
+		int rc_ = (expr);                                                                        \
+		if (rc_ != RNB_OK) throw std::runtime_error(std::string(#expr) + ": " + rnb_last_error()); \
+	} while (0)
+
+} // namespace
+
+int main(int argc, char** argv) {
+	std::map<std::string, std::string> a;
+	uint32_t resolution = 256, brick = 0, cull = RNB_MESH_CULL_OCCUPANCY;
+	bool gradient = false;
+	try {
+		bool help = false;
+		a = parse_cli(argc, argv, help);
+		if (help) { print_help(std::cout, argv[0]); return 0; }
+		if (!a.count("snapshot") || !a.count("scene") || !a.count("out")) throw ParseError("--snapshot, --scene and --out are required");
+		if (a.count("resolution")) resolution = parse_u32("resolution", a["resolution"]);
+		if (resolution == 0 || resolution > RNB_MESH_MAX_RES) throw ParseError("Argument 'resolution' must be 1 .. 4096");
+		if (a.count("brick")) brick = parse_u32("brick", a["brick"]);
+		if (brick != 0 && brick != 8 && brick != 16 && brick != 32 && brick != 64) throw ParseError("Argument 'brick' must be 8, 16, 32 or 64");
+		if (a.count("cull")) {
+			if (a["cull"] == "none") cull = RNB_MESH_CULL_NONE;
+			else if (a["cull"] != "occupancy") throw ParseError("Argument 'cull' must be none or occupancy");
+		}
+		if (a.count("normals")) {
+			if (a["normals"] == "gradient") gradient = true;
+			else if (a["normals"] != "ring") throw ParseError("Argument 'normals' must be ring or gradient");
+		}
+	} catch (const ParseError& e) {
+		std::cerr << e.what() << std::endl;
+		print_help(std::cerr, argv[0]);
+		return 255;
+	}
+	const std::string scene = a["scene"], snap_path = a["snapshot"];
+	if (!path_exists(snap_path)) { std::fprintf(stderr, "Snapshot path %s does not exist.\n", snap_path.c_str()); return 1; }
+	if (!is_dir(scene)) { std::fprintf(stderr, "Scene path %s does not exist.\n", scene.c_str()); return 1; }
+
+	rnb_ctx* ctx = nullptr;
+	rnb_mesh dm;
+	std::memset(&dm, 0, sizeof(dm));
+	try {
+		const Dataset ds = load_dataset(scene);
+		const snapshot::Data sd = snapshot::read(snap_path);
+		rnb_config cfg;
+		RNB_CHECK(rnb_default_config(&cfg));
+		snapshot::apply_network_config(sd.network_config, (float)ds.aabb_scale, cfg);
+		const jsonmin::Value& hp = sd.network_config["hyperparams"];
+		if (hp.contains("accumulate")) cfg.accumulate = hp["accumulate"].as_string() == "half" ? RNB_ACCUM_HALF : RNB_ACCUM_FP32;
+		if (sd.has_aabb_scale) cfg.aabb_scale = sd.aabb_scale;
+		RNB_CHECK(rnb_create(&cfg, &ctx));
+		const uint64_t n = rnb_n_params(ctx);
+		if (sd.params.size() != n) throw std::runtime_error("Can't set params because CPU buffer has the wrong size.");
+		RNB_CHECK(rnb_set_params(ctx, sd.params.data())); // master = float(EMA half) and the EMA weights with it, as a resumed testbed run
+		RNB_CHECK(rnb_set_training_step(ctx, sd.training_step)); // the hash-grid levels in use (grid.h:1430-1437)
+		void* gp; uint64_t gnb;
+		RNB_CHECK(rnb_buffer(ctx, RNB_BUF_DENSITY_GRID, &gp, &gnb));
+		if (sd.grid.size() != gnb / 4) throw std::runtime_error("Incompatible number of grid cascades.");
+		RNB_CHECK(rnb_memcpy(ctx, gp, sd.grid.data(), gnb, RNB_H2D));
+		RNB_CHECK(rnb_update_density_bitfield(ctx, nullptr));
+
+		// the testbed's lattice (compute_and_save_marching_cubes_mesh): next_multiple(res, 16) over the scene's box, threshold 0, EMA weights
+		const uint32_t res = (resolution + 15u) / 16u * 16u;
+		const float amin = 0.5f - 0.5f * (float)cfg.aabb_scale, amax = 0.5f + 0.5f * (float)cfg.aabb_scale;
+		rnb_mesh_options mo;
+		RNB_CHECK(rnb_mesh_default_options(&mo));
+		for (int k = 0; k < 3; ++k) { mo.res[k] = res; mo.aabb_min[k] = amin; mo.aabb_max[k] = amax; }
+		mo.lattice_min = amin; mo.lattice_max = amax;
+		mo.thresh = 0.0f;
+		mo.cull = cull;
+		mo.brick = brick;
+		mo.attributes = RNB_MESH_ATTR_COLORS | (gradient ? RNB_MESH_ATTR_NORMALS : 0u);
+		rnb_mesh_stats st;
+		RNB_CHECK(rnb_extract_mesh(ctx, nullptr, &mo, &dm, &st));
+		mesh::Mesh m;
+		m.verts.resize(dm.n_verts); m.colors.resize(dm.n_verts); m.indices.resize(dm.n_indices);
+		if (dm.n_verts) {
+			RNB_CHECK(rnb_memcpy(ctx, m.verts.data(), dm.verts, (uint64_t)dm.n_verts * 12, RNB_D2H));
+			RNB_CHECK(rnb_memcpy(ctx, m.colors.data(), dm.colors, (uint64_t)dm.n_verts * 12, RNB_D2H));
+		}
+		if (dm.n_indices) RNB_CHECK(rnb_memcpy(ctx, m.indices.data(), dm.indices, (uint64_t)dm.n_indices * 4, RNB_D2H));
+		if (gradient) {
+			m.normals.resize(dm.n_verts);
+			if (dm.n_verts) RNB_CHECK(rnb_memcpy(ctx, m.normals.data(), dm.normals, (uint64_t)dm.n_verts * 12, RNB_D2H));
+		} else mesh::compute_normals(m);
+		RNB_CHECK(rnb_mesh_free(ctx, &dm));
+		std::printf("%u^3: %llu of %llu bricks kept, %llu evaluated (%.1f %% of the lattice), %llu with a sign change, peak workspace %.1f MB, %.1f ms\n", res,
+		            (unsigned long long)st.n_kept, (unsigned long long)st.n_bricks, (unsigned long long)st.n_evaluated,
+		            100.0 * (double)st.n_points_evaluated / ((double)res * res * res), (unsigned long long)st.n_sign_change, (double)st.peak_workspace / 1e6, st.ms);
+		std::printf("#vertices=%zu #triangles=%zu\n", m.verts.size(), m.indices.size() / 3);
+		mesh::save_obj(a["out"], m, ds.scale, ds.offset, ds.n2w_s, ds.n2w_t, ds.from_na);
+		rnb_destroy(ctx);
+	} catch (const std::exception& e) {
+		std::fprintf(stderr, "Uncaught exception: %s\n", e.what());
+		if (ctx) { rnb_mesh_free(ctx, &dm); rnb_destroy(ctx); }
+		return 1;
+	}
+	return 0;
+}
