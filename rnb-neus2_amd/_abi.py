@@ -277,6 +277,69 @@ MESH_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_clean.h: components / keep-largest / outward orientation of a device mesh, a header of its own with its own version (the HIP library only) ----
+MESH_CLEAN_ABI_VERSION = 1
+MESH_KEEP_ALL, MESH_KEEP_LARGEST = 0, 1
+MESH_ORIENT_NONE, MESH_ORIENT_OUTWARD = 0, 1
+MESH_Q_SHIFT, MESH_Q_TERM_LOG2 = 44, 18
+MESH_NO_LABEL = 0xFFFFFFFF
+
+
+class MeshCleanOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("keep", C.c_uint32),
+        ("orient", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshComponent(C.Structure):
+    _fields_ = [
+        ("label", C.c_uint32),
+        ("n_vertices", C.c_uint32),
+        ("n_triangles", C.c_uint32),
+        ("kept", C.c_uint32),
+        ("area_q", C.c_int64),
+        ("volume_q", C.c_int64),
+    ]
+
+
+# the same record as a numpy dtype (Context.clean_mesh returns the table as a structured array)
+MESH_COMPONENT_DTYPE = [("label", "<u4"), ("n_vertices", "<u4"), ("n_triangles", "<u4"), ("kept", "<u4"), ("area_q", "<i8"), ("volume_q", "<i8")]
+
+
+class MeshCleanStats(C.Structure):
+    _fields_ = [
+        ("n_components", C.c_uint32),
+        ("n_kept", C.c_uint32),
+        ("n_verts_in", C.c_uint32),
+        ("n_verts_out", C.c_uint32),
+        ("n_tris_in", C.c_uint32),
+        ("n_tris_out", C.c_uint32),
+        ("largest_label", C.c_uint32),
+        ("hook_passes", C.c_uint32),
+        ("flatten_passes", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("area_q_in", C.c_int64),
+        ("area_q_out", C.c_int64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved2", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_CLEAN_PROTOTYPES = {
+    "mesh_clean_abi_version": (_u32, []),
+    "mesh_clean_default_options": (_i, [C.POINTER(MeshCleanOptions)]),
+    "mesh_clean": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshCleanOptions), C.POINTER(Mesh), C.POINTER(C.c_void_p), C.POINTER(MeshCleanStats)]),
+    "mesh_clean_table_free": (_i, [_ctx, C.c_void_p]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -297,6 +360,7 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_", render=False, mesh=False):
-    """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h); only the HIP library exports those."""
-    return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()))
+def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False):
+    """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
+    (include/rnb_mesh_clean.h); only the HIP library exports those."""
+    return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ()))

@@ -45,13 +45,15 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True)
+        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
             raise RuntimeError("render ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_abi_version() != _abi.MESH_ABI_VERSION:
             raise RuntimeError("mesh ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_clean_abi_version() != _abi.MESH_CLEAN_ABI_VERSION:
+            raise RuntimeError("mesh-clean ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -476,11 +478,15 @@ class Context:
         return verts, idx
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
-                     cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None):
+                     cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
-        The device mesh is released before returning. Leaves the training state as it was."""
+        The device mesh is released before returning. Leaves the training state as it was.
+        keep ("all" / "largest") and / or orient ("none" / "outward"): the device mesh goes through rnb_mesh_clean (see clean_mesh) before it is downloaded, and the
+        dict gains `clean_stats`. The one not given leaves its part alone (keep="all", orient="none"), as build/mesh --keep / --orient do. With both None (the
+        default) nothing of that runs."""
+        copt = None if keep is None and orient is None else self._clean_options("all" if keep is None else keep, "none" if orient is None else orient)
         opt = _abi.MeshOptions()
         self._check(self.f.mesh_default_options(C.byref(opt)))
         opt.res[:] = [int(res)] * 3 if np.isscalar(res) else [int(x) for x in res]
@@ -498,15 +504,74 @@ class Context:
         opt.max_active_points = int(max_active_points)
         m, st = _abi.Mesh(), _abi.MeshStats()
         self._check(self.f.extract_mesh(self._h, _stream_handle(stream), C.byref(opt), C.byref(m), C.byref(st)))
+        cleaned, cst = _abi.Mesh(), _abi.MeshCleanStats()
         try:
-            out = dict(verts=self.download(m.verts, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32),
-                       indices=self.download(m.indices, m.n_indices, np.uint32) if m.n_indices else np.empty(0, np.uint32))
-            for key, ptr in (("colors", m.colors), ("normals", m.normals)):
-                if ptr:
-                    out[key] = self.download(ptr, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32)
+            if copt is not None:  # device to device: the extracted mesh never visits the host
+                self._check(self.f.mesh_clean(self._h, _stream_handle(stream), C.byref(m), C.byref(copt), C.byref(cleaned), None, C.byref(cst)))
+            out = self._download_mesh(m if copt is None else cleaned)
             out["stats"] = st.as_dict()
+            if copt is not None:
+                out["clean_stats"] = cst.as_dict()
         finally:
             self.f.mesh_free(self._h, C.byref(m))
+            self.f.mesh_free(self._h, C.byref(cleaned))
+        return out
+
+    def _download_mesh(self, m):
+        out = dict(verts=self.download(m.verts, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32),
+                   indices=self.download(m.indices, m.n_indices, np.uint32) if m.n_indices else np.empty(0, np.uint32))
+        for key, ptr in (("colors", m.colors), ("normals", m.normals)):
+            if ptr:
+                out[key] = self.download(ptr, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32)
+        return out
+
+    def _clean_options(self, keep, orient):
+        keeps = {"all": _abi.MESH_KEEP_ALL, "largest": _abi.MESH_KEEP_LARGEST}
+        orients = {"none": _abi.MESH_ORIENT_NONE, "outward": _abi.MESH_ORIENT_OUTWARD}
+        if keep not in keeps:
+            raise ValueError("keep must be 'all' or 'largest'")
+        if orient not in orients:
+            raise ValueError("orient must be 'none' or 'outward'")
+        opt = _abi.MeshCleanOptions()
+        self._check(self.f.mesh_clean_default_options(C.byref(opt)))
+        opt.keep, opt.orient = keeps[keep], orients[orient]
+        return opt
+
+    def clean_mesh(self, verts, indices, colors=None, normals=None, keep="largest", orient="outward", table=False, stream=None):
+        """rnb_mesh_clean (include/rnb_mesh_clean.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals. The
+        connected components (vertices joined by triangles), keep="largest" (greatest area; "all": only unused vertices go), orient="outward" (the triangles of a
+        component of negative signed volume get their second and third index swapped; "none": as they come). Returns a dict of numpy arrays (verts, indices, colors /
+        normals when given) in the input's order, `stats`, and with table=True `table`: one record per component (label, n_vertices, n_triangles, kept, area_q,
+        volume_q), ascending label. For a dict m that extract_mesh returned: clean_mesh(m["verts"], m["indices"], m.get("colors"), m.get("normals")). Leaves the training state as it was."""
+        copt = self._clean_options(keep, orient)
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+        attrs = {}
+        for key, a in (("colors", colors), ("normals", normals)):
+            if a is not None:
+                attrs[key] = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+                if attrs[key].shape != v.shape:
+                    raise ValueError("%s must have one row per vertex" % key)
+        m, cleaned, cst, tab = _abi.Mesh(), _abi.Mesh(), _abi.MeshCleanStats(), C.c_void_p()
+        ptrs = []
+        try:
+            for key, a in (("verts", v), ("indices", idx), ("colors", attrs.get("colors")), ("normals", attrs.get("normals"))):
+                if a is not None:
+                    ptrs.append(self.upload(a) if a.size else self.device_malloc(4))
+                    setattr(m, key, ptrs[-1])
+            m.n_verts, m.n_indices = v.shape[0], idx.size
+            self._check(self.f.mesh_clean(self._h, _stream_handle(stream), C.byref(m), C.byref(copt), C.byref(cleaned), C.byref(tab) if table else None, C.byref(cst)))
+            out = self._download_mesh(cleaned)
+            out["stats"] = cst.as_dict()
+            if table:
+                dt = np.dtype(_abi.MESH_COMPONENT_DTYPE)
+                out["table"] = self.download(tab.value, cst.n_components, dt) if cst.n_components else np.empty(0, dt)
+        finally:
+            for p in ptrs:
+                self.device_free(p)
+            self.f.mesh_free(self._h, C.byref(cleaned))
+            if tab.value:
+                self.f.mesh_clean_table_free(self._h, tab)
         return out
 
     def upload(self, array):

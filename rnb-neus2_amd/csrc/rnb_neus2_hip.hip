@@ -6,6 +6,7 @@
 #include "kernels_mesh.cuh"
 #include "kernels_render.cuh"
 #include "kernels_mesh_sparse.cuh"
+#include "kernels_mesh_clean.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>
@@ -2904,6 +2905,127 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 		std::memset(stats, 0, sizeof(*stats));
 		stats->n_bricks = a.n_bricks; stats->n_kept = n_kept; stats->n_evaluated = n_eval; stats->n_sign_change = n_act;
 		stats->n_points_evaluated = n_active_points;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh cleaning (include/rnb_mesh_clean.h) ----
+uint32_t rnb_mesh_clean_abi_version(void) { return RNB_MESH_CLEAN_ABI_VERSION; }
+
+int rnb_mesh_clean_default_options(rnb_mesh_clean_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_CLEAN_ABI_VERSION;
+	opt->keep = RNB_MESH_KEEP_LARGEST;
+	opt->orient = RNB_MESH_ORIENT_OUTWARD;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_clean_table_free(rnb_ctx* c, rnb_mesh_component* table) try {
+	if (!c) return fail(RNB_ERR_INVALID, "null argument");
+	if (table) (void)hipFree(table);
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_clean_options* opt, rnb_mesh* out, rnb_mesh_component** table_dev, rnb_mesh_clean_stats* stats) try {
+	if (table_dev) *table_dev = nullptr;
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: null argument");
+	if (in == out) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: in and out must be different objects");
+	const rnb_mesh m = *in;
+	std::memset(out, 0, sizeof(*out));
+	if (opt->abi_version != RNB_MESH_CLEAN_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: options abi_version mismatch (expected RNB_MESH_CLEAN_ABI_VERSION)");
+	if (opt->keep != RNB_MESH_KEEP_ALL && opt->keep != RNB_MESH_KEEP_LARGEST) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown keep mode");
+	if (opt->orient != RNB_MESH_ORIENT_NONE && opt->orient != RNB_MESH_ORIENT_OUTWARD) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown orient mode");
+	if (m.n_indices % 3u) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: n_indices is not a multiple of 3");
+	if ((m.n_verts && !m.verts) || (m.n_indices && !m.indices)) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: null vertex or index buffer");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	MeshWorkspace ws;
+	ClResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	hres.best = CL_NONE;
+	uint32_t n_comp = 0, nvo = 0, nto = 0;
+	rnb_mesh_component* table = nullptr;
+	float *overts = nullptr, *ocolors = nullptr, *onormals = nullptr;
+	uint32_t* oidx = nullptr;
+	if (nt) {
+		const uint32_t g_v = (nv + CL_WG - 1) / CL_WG, g_t = (nt + CL_WG - 1) / CL_WG; // nv >= 1 is checked right below (every index would be out of range)
+		if (nv == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: an index is out of range (the mesh has no vertices)");
+		uint32_t *parent = nullptr, *used = nullptr, *cid = nullptr, *scan = nullptr, *twg = nullptr, *cflags = nullptr;
+		ClResult* dres = nullptr;
+		if (!ws.alloc(&parent, nv) || !ws.alloc(&used, nv) || !ws.alloc(&cid, nv) || !ws.alloc(&twg, g_t) || !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) || !ws.alloc(&dres, 1))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		// 1. every index is range-checked before any is used as an address
+		hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
+		hipLaunchKernelGGL(k_cl_validate, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & CL_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: an index is out of range (>= n_verts)");
+		// 2. labels: one hooking launch, one flattening launch; roots -> component ids in ascending label order
+		hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, parent);
+		hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
+		hipLaunchKernelGGL(k_cl_roots, dim3(g_v), dim3(CL_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, cid, nv);
+		HIP_TRY(hipGetLastError());
+		int rc = scan_exclusive(cid, nv, s, &n_comp, scan);
+		if (rc != RNB_OK) return rc;
+		if (!ws.alloc(&table, n_comp) || !ws.alloc(&cflags, n_comp)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the table of " + std::to_string(n_comp) + " components");
+		HIP_TRY(hipMemsetAsync(table, 0, std::max<size_t>(n_comp, 1) * sizeof(rnb_mesh_component), s));
+		hipLaunchKernelGGL(k_cl_relabel, dim3(g_v), dim3(CL_WG), 0, s, parent, (const uint32_t*)used, (const uint32_t*)cid, table, nv);
+		const uint32_t* comp = parent;
+		// 3. per-component sums, the selection
+		hipLaunchKernelGGL(k_cl_sums<true>, dim3(g_t), dim3(CL_WG), 0, s, (const float*)m.verts, (const uint32_t*)m.indices, nt, comp, table, dres);
+		hipLaunchKernelGGL(k_cl_sums<false>, dim3(g_v), dim3(CL_WG), 0, s, (const float*)nullptr, (const uint32_t*)nullptr, nv, comp, table, dres);
+		hipLaunchKernelGGL(k_cl_select, dim3(1), dim3(1024), 0, s, table, n_comp, opt->keep, opt->orient, cflags, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & CL_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: the area or volume term of a triangle is not finite or not below 2^18");
+		ws.release(used);
+		// 4. compaction: the new vertex numbering (cid's memory is reused), the kept triangles per workgroup
+		uint32_t* vmap = cid;
+		hipLaunchKernelGGL(k_cl_vflag, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, vmap, nv);
+		HIP_TRY(hipGetLastError());
+		rc = scan_exclusive(vmap, nv, s, &nvo, scan);
+		if (rc != RNB_OK) return rc;
+		hipLaunchKernelGGL(k_cl_tris<false>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+		HIP_TRY(hipGetLastError());
+		rc = scan_exclusive(twg, g_t, s, &nto, scan);
+		if (rc != RNB_OK) return rc;
+		if (!ws.alloc(&overts, (size_t)nvo * 3) || !ws.alloc(&oidx, (size_t)nto * 3) || (m.colors && !ws.alloc(&ocolors, (size_t)nvo * 3)) || (m.normals && !ws.alloc(&onormals, (size_t)nvo * 3)))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
+		hipLaunchKernelGGL(k_cl_verts, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, overts, ocolors, onormals);
+		hipLaunchKernelGGL(k_cl_tris<true>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, oidx);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		if (n_comp && hres.best < n_comp) { // the label of the selected component, for the statistics
+			uint32_t label = CL_NONE;
+			HIP_TRY(hipMemcpy(&label, &table[hres.best].label, 4, hipMemcpyDeviceToHost));
+			hres.best = label;
+		} else hres.best = CL_NONE;
+		ws.release(parent); ws.release(cid); ws.release(scan); ws.release(twg); ws.release(cflags); ws.release(dres);
+	} else {
+		if (!ws.alloc(&overts, 1) || !ws.alloc(&oidx, 1) || (m.colors && !ws.alloc(&ocolors, 1)) || (m.normals && !ws.alloc(&onormals, 1)) || (table_dev && !ws.alloc(&table, 1)))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
+	}
+	out->verts = (float*)ws.keep(overts); out->indices = (uint32_t*)ws.keep(oidx);
+	out->colors = (float*)ws.keep(ocolors); out->normals = (float*)ws.keep(onormals);
+	out->n_verts = nvo; out->n_indices = nto * 3u;
+	if (table_dev) *table_dev = (rnb_mesh_component*)ws.keep(table);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_components = n_comp; stats->n_kept = hres.n_kept;
+		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
+		stats->largest_label = hres.best;
+		stats->hook_passes = nt ? 1u : 0u; stats->flatten_passes = nt ? 1u : 0u;
+		stats->area_q_in = hres.area_in; stats->area_q_out = hres.area_out;
 		stats->peak_workspace = ws.peak;
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}

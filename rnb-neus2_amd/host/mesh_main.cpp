@@ -3,12 +3,17 @@
 // snapshot by snapshot.hpp (its EMA weights, occupancy grid and network configuration).
 //
 //   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
+//        [--keep all|largest] [--orient none|outward]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
+// With --keep and / or --orient the device mesh goes through rnb_mesh_clean (include/rnb_mesh_clean.h) before it is downloaded: connected components, the largest one
+// kept, triangles turned outward -- the pipeline's post-processing without the round trip through an OBJ. Without them nothing of that is called; with only one of
+// them the other part is left alone (--keep alone does not turn anything, --orient alone keeps every component), as Context.extract_mesh(keep=, orient=) does.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
+#include "../../include/rnb_mesh_clean.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -40,6 +45,8 @@ const Flag FLAGS[] = {
 	{"cull", "MODE", "occupancy (default): skip the bricks the occupancy grid marks empty; none: evaluate the whole lattice."},
 	{"brick", "N", "Lattice points per brick edge: 8, 16, 32 or 64 (default: the library's)."},
 	{"normals", "MODE", "ring (default): area-weighted face normals, as the testbed; gradient: the SDF gradient at the vertex, from the device."},
+	{"keep", "MODE", "Clean the mesh on the device. largest: only the connected component of the greatest area; all: every component."},
+	{"orient", "MODE", "Clean the mesh on the device. outward: components of negative signed volume are turned inside out; none: triangles as extracted."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -89,7 +96,8 @@ uint32_t parse_u32(const std::string& k, const std::string& s) {
 int main(int argc, char** argv) {
 	std::map<std::string, std::string> a;
 	uint32_t resolution = 256, brick = 0, cull = RNB_MESH_CULL_OCCUPANCY;
-	bool gradient = false;
+	bool gradient = false, clean = false;
+	uint32_t keep = RNB_MESH_KEEP_ALL, orient = RNB_MESH_ORIENT_NONE; // with one of the two flags given, the other one leaves its part alone
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -107,6 +115,16 @@ int main(int argc, char** argv) {
 			if (a["normals"] == "gradient") gradient = true;
 			else if (a["normals"] != "ring") throw ParseError("Argument 'normals' must be ring or gradient");
 		}
+		if (a.count("keep")) {
+			clean = true;
+			if (a["keep"] == "largest") keep = RNB_MESH_KEEP_LARGEST;
+			else if (a["keep"] != "all") throw ParseError("Argument 'keep' must be all or largest");
+		}
+		if (a.count("orient")) {
+			clean = true;
+			if (a["orient"] == "outward") orient = RNB_MESH_ORIENT_OUTWARD;
+			else if (a["orient"] != "none") throw ParseError("Argument 'orient' must be none or outward");
+		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
 		print_help(std::cerr, argv[0]);
@@ -117,8 +135,9 @@ int main(int argc, char** argv) {
 	if (!is_dir(scene)) { std::fprintf(stderr, "Scene path %s does not exist.\n", scene.c_str()); return 1; }
 
 	rnb_ctx* ctx = nullptr;
-	rnb_mesh dm;
+	rnb_mesh dm, cm;
 	std::memset(&dm, 0, sizeof(dm));
+	std::memset(&cm, 0, sizeof(cm));
 	try {
 		const Dataset ds = load_dataset(scene);
 		const snapshot::Data sd = snapshot::read(snap_path);
@@ -152,6 +171,16 @@ int main(int argc, char** argv) {
 		mo.attributes = RNB_MESH_ATTR_COLORS | (gradient ? RNB_MESH_ATTR_NORMALS : 0u);
 		rnb_mesh_stats st;
 		RNB_CHECK(rnb_extract_mesh(ctx, nullptr, &mo, &dm, &st));
+		rnb_mesh_clean_stats cs;
+		if (clean) { // device to device; the ring normals below are then those of the cleaned mesh
+			rnb_mesh_clean_options co;
+			RNB_CHECK(rnb_mesh_clean_default_options(&co));
+			co.keep = keep; co.orient = orient;
+			RNB_CHECK(rnb_mesh_clean(ctx, nullptr, &dm, &co, &cm, nullptr, &cs));
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+		}
 		mesh::Mesh m;
 		m.verts.resize(dm.n_verts); m.colors.resize(dm.n_verts); m.indices.resize(dm.n_indices);
 		if (dm.n_verts) {
@@ -167,12 +196,17 @@ int main(int argc, char** argv) {
 		std::printf("%u^3: %llu of %llu bricks kept, %llu evaluated (%.1f %% of the lattice), %llu with a sign change, peak workspace %.1f MB, %.1f ms\n", res,
 		            (unsigned long long)st.n_kept, (unsigned long long)st.n_bricks, (unsigned long long)st.n_evaluated,
 		            100.0 * (double)st.n_points_evaluated / ((double)res * res * res), (unsigned long long)st.n_sign_change, (double)st.peak_workspace / 1e6, st.ms);
+		if (clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
+		                       cs.n_verts_in, cs.n_verts_out, cs.ms);
 		std::printf("#vertices=%zu #triangles=%zu\n", m.verts.size(), m.indices.size() / 3);
-		mesh::save_obj(a["out"], m, ds.scale, ds.offset, ds.n2w_s, ds.n2w_t, ds.from_na);
+		// --orient outward speaks of the file: the device turned every kept component counter-clockwise seen from outside, and the faces are written as they are
+		// (without it, the scene's from_na flag decides whether save_obj reverses them, as in the testbed). save_obj maps positions by a uniform scale and a shift,
+		// which keeps the winding as long as the scales are positive (scale > 0 and n2w_s > 0, as every scene the loader accepts has them).
+		mesh::save_obj(a["out"], m, ds.scale, ds.offset, ds.n2w_s, ds.n2w_t, (clean && orient == RNB_MESH_ORIENT_OUTWARD) ? true : ds.from_na);
 		rnb_destroy(ctx);
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "Uncaught exception: %s\n", e.what());
-		if (ctx) { rnb_mesh_free(ctx, &dm); rnb_destroy(ctx); }
+		if (ctx) { rnb_mesh_free(ctx, &dm); rnb_mesh_free(ctx, &cm); rnb_destroy(ctx); }
 		return 1;
 	}
 	return 0;

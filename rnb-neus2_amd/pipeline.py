@@ -168,11 +168,47 @@ def postprocess_mesh(data_dir, output_mesh_path, logger=None):
     shutil.rmtree(os.path.join(data_dir, "output"), ignore_errors=True)
 
 
+def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe):
+    """The last stage on the device: one `build/mesh` process that extracts the mesh of the stage-2 snapshot (plan_two_stage passes --save-snapshot) at `resolution`,
+    keeps the largest connected component and turns it outward (include/rnb_mesh_clean.h), and writes `output_mesh_path`. Pure; the snapshot named here is the first
+    of snapshot_candidates, run_device_postprocess replaces it by the one that exists."""
+    return [str(mesh_exe), "--snapshot", snapshot_candidates(data_dir, max_steps)[0], "--scene", str(data_dir), "--out", str(output_mesh_path),
+            "--resolution", str(resolution), "--keep", "largest", "--orient", "outward"]
+
+
+def default_mesh_exe(testbed_path):
+    """build/mesh beside build/testbed."""
+    return os.path.join(os.path.dirname(os.path.abspath(testbed_path)), "mesh")
+
+
+def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None):
+    """postprocess_mesh's job without the OBJ round trip: runs plan_device_postprocess' command, then drops the training output directory as postprocess_mesh does."""
+    logger = logger or SimpleLogger()
+    cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe)
+    found = [p for p in snapshot_candidates(data_dir, max_steps) if os.path.exists(p)]
+    if not found:
+        raise RuntimeError("Snapshot not found after {} iterations".format(max_steps))
+    cmd[cmd.index("--snapshot") + 1] = found[0]
+    os.makedirs(os.path.dirname(output_mesh_path) or ".", exist_ok=True)
+    logger.info("Post-processing on the device: {}".format(" ".join(cmd)))
+    result = subprocess.run(cmd, capture_output=True, text=True)
+    if result.stdout:
+        for line in result.stdout.strip().split("\n"):
+            logger.info(line)
+    if result.returncode != 0:
+        if result.stderr:
+            logger.error(result.stderr)
+        raise RuntimeError("Device post-processing failed with code {}".format(result.returncode))
+    logger.info("Mesh exported to: {}".format(output_mesh_path))
+    shutil.rmtree(os.path.join(data_dir, "output"), ignore_errors=True)
+
+
 def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mesh_resolution=1024, scaling_mode="auto", sphere_scale=1.0, margin_px=20,
                       warmup_ratio=0.1, mask_weight=1.0, super_normal=False, use_l1=False, use_rgb_plus=True, has_albedo=False,
-                      albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None):
+                      albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None, device_postprocess=False, mesh_exe=None):
     """load -> prepare (<output_dir>/prepared_data) -> train (two-stage, or warm-up + albedo scaling + two-stage when
-    `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)"""
+    `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
+    device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh."""
     logger = logger or SimpleLogger()
     from .dataloaders import load_data
     from .prepare import prepare_testbed_data
@@ -188,6 +224,9 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     else:
         run_two_stage(testbed_path, data_dir, max_steps, flags, resolution=mesh_resolution, no_albedo=True, logger=logger)
     output_mesh = os.path.join(output_dir, "mesh.obj")
-    postprocess_mesh(data_dir, output_mesh, logger)
+    if device_postprocess:
+        run_device_postprocess(data_dir, max_steps, mesh_resolution, output_mesh, mesh_exe or default_mesh_exe(testbed_path), logger)
+    else:
+        postprocess_mesh(data_dir, output_mesh, logger)
     logger.info("=== Pipeline complete ===")
     return output_mesh

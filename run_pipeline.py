@@ -34,6 +34,8 @@ _SPEC = """
 --no-rgbplus        | flag  |        | switch the RGB+ channel off
 --n-samples         | int   | 2000   | pixels per view used to estimate the albedo gains
 --seed              | int   | 0      | seed of numpy's generator
+--device-postprocess | flag |        | clean the final mesh on the GPU (build/mesh --keep largest --orient outward on the stage-2 snapshot) instead of in Python
+--mesh-exe          | str   |        | --device-postprocess only: the mesh executable (default: build/mesh beside the testbed)
 """
 
 
@@ -62,13 +64,19 @@ def pipeline_kwargs(ns):
     """argparse namespace -> keywords of rnb_neus2_amd.pipeline.run_full_pipeline."""
     renamed = {"input": "input_path", "testbed": "testbed_path", "output": "output_dir", "supernormal": "super_normal", "l1": "use_l1",
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
-    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus")}
+    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
+    if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
+        kw["device_postprocess"] = True
+        kw["mesh_exe"] = ns.mesh_exe or None
     return kw
 
 
 def main(argv=None):
-    ns = build_parser().parse_args(argv)
+    parser = build_parser()
+    ns = parser.parse_args(argv)
+    if ns.mesh_exe and not ns.device_postprocess:
+        parser.error("--mesh-exe is only used with --device-postprocess")
     np.random.seed(ns.seed)
     return run_full_pipeline(**pipeline_kwargs(ns))
 
