@@ -340,6 +340,50 @@ MESH_CLEAN_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_simplify.h: vertex clustering with quadric placement of a device mesh, a header of its own with its own version (the HIP library only) ----
+MESH_SIMPLIFY_ABI_VERSION = 1
+MESH_PLACE_QUADRIC, MESH_PLACE_MEAN = 0, 1
+MESH_SIMPLIFY_MAX_DIM, MESH_SIMPLIFY_MAX_CELLS = 4096, 1 << 30
+MESH_SIMPLIFY_Q_SHIFT, MESH_SIMPLIFY_Q_TERM_LOG2 = 40, 22
+
+
+class MeshSimplifyOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("origin", C.c_float * 3),
+        ("cell", C.c_float),
+        ("dims", C.c_uint32 * 3),
+        ("placement", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshSimplifyStats(C.Structure):
+    _fields_ = [
+        ("n_verts_in", C.c_uint32),
+        ("n_tris_in", C.c_uint32),
+        ("n_clusters", C.c_uint32),
+        ("n_verts_out", C.c_uint32),
+        ("n_tris_out", C.c_uint32),
+        ("n_tris_collapsed", C.c_uint32),
+        ("n_clamped", C.c_uint32),
+        ("n_fallback", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_SIMPLIFY_PROTOTYPES = {
+    "mesh_simplify_abi_version": (_u32, []),
+    "mesh_simplify_default_options": (_i, [C.POINTER(MeshSimplifyOptions)]),
+    "mesh_simplify": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshSimplifyOptions), C.POINTER(Mesh), C.POINTER(MeshSimplifyStats)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -360,7 +404,8 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False):
+def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
-    (include/rnb_mesh_clean.h); only the HIP library exports those."""
-    return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ()))
+    (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h); only the HIP library exports those."""
+    return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
+                     + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()))

@@ -45,7 +45,7 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True)
+        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -54,6 +54,8 @@ def load_library():
             raise RuntimeError("mesh ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_clean_abi_version() != _abi.MESH_CLEAN_ABI_VERSION:
             raise RuntimeError("mesh-clean ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_simplify_abi_version() != _abi.MESH_SIMPLIFY_ABI_VERSION:
+            raise RuntimeError("mesh-simplify ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -478,14 +480,18 @@ class Context:
         return verts, idx
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
-                     cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None):
+                     cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
+                     simplify=None, placement="quadric"):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
         The device mesh is released before returning. Leaves the training state as it was.
         keep ("all" / "largest") and / or orient ("none" / "outward"): the device mesh goes through rnb_mesh_clean (see clean_mesh) before it is downloaded, and the
         dict gains `clean_stats`. The one not given leaves its part alone (keep="all", orient="none"), as build/mesh --keep / --orient do. With both None (the
-        default) nothing of that runs."""
+        default) nothing of that runs.
+        simplify = N: after that, still on the device, the mesh goes through rnb_mesh_simplify (see simplify_mesh) on the grid simplify_grid(aabb_min, aabb_max, N) --
+        N^3 cubic cells from aabb_min, N along the longest edge of the box, the grid of build/mesh --simplify N -- with `placement`, and the dict gains `simplify_stats`. With None (the default) nothing of that runs."""
+        sopt = None if simplify is None else self._simplify_options(*self.simplify_grid(aabb_min, aabb_max, simplify), placement)
         copt = None if keep is None and orient is None else self._clean_options("all" if keep is None else keep, "none" if orient is None else orient)
         opt = _abi.MeshOptions()
         self._check(self.f.mesh_default_options(C.byref(opt)))
@@ -505,16 +511,25 @@ class Context:
         m, st = _abi.Mesh(), _abi.MeshStats()
         self._check(self.f.extract_mesh(self._h, _stream_handle(stream), C.byref(opt), C.byref(m), C.byref(st)))
         cleaned, cst = _abi.Mesh(), _abi.MeshCleanStats()
+        simplified, sst = _abi.Mesh(), _abi.MeshSimplifyStats()
         try:
+            last = m
             if copt is not None:  # device to device: the extracted mesh never visits the host
                 self._check(self.f.mesh_clean(self._h, _stream_handle(stream), C.byref(m), C.byref(copt), C.byref(cleaned), None, C.byref(cst)))
-            out = self._download_mesh(m if copt is None else cleaned)
+                last = cleaned
+            if sopt is not None:
+                self._check(self.f.mesh_simplify(self._h, _stream_handle(stream), C.byref(last), C.byref(sopt), C.byref(simplified), C.byref(sst)))
+                last = simplified
+            out = self._download_mesh(last)
             out["stats"] = st.as_dict()
             if copt is not None:
                 out["clean_stats"] = cst.as_dict()
+            if sopt is not None:
+                out["simplify_stats"] = sst.as_dict()
         finally:
             self.f.mesh_free(self._h, C.byref(m))
             self.f.mesh_free(self._h, C.byref(cleaned))
+            self.f.mesh_free(self._h, C.byref(simplified))
         return out
 
     def _download_mesh(self, m):
@@ -572,6 +587,65 @@ class Context:
             self.f.mesh_free(self._h, C.byref(cleaned))
             if tab.value:
                 self.f.mesh_clean_table_free(self._h, tab)
+        return out
+
+    @staticmethod
+    def simplify_grid(aabb_min, aabb_max, n):
+        """The cell grid `simplify=N` and build/mesh --simplify N lay over a box: (origin, cell, dims) with origin = aabb_min, cell = the longest edge / N (computed in
+        double precision, rounded to float32) and dims = N on every axis, N = 1 .. 1024 (N^3 cells is the call's cap). build/mesh's box is the scene's cube; on a box
+        that is not a cube the cells stay cubes, so the grid reaches past the box on its shorter axes (cells that stay empty cost one bit each)."""
+        n = int(n)
+        if not 1 <= n or n ** 3 > _abi.MESH_SIMPLIFY_MAX_CELLS:
+            raise ValueError("simplify must be 1 .. 1024")
+        lo = np.asarray(aabb_min, np.float32).astype(np.float64)
+        hi = np.asarray(aabb_max, np.float32).astype(np.float64)
+        cell = np.float32((hi - lo).max() / n)
+        if not (np.isfinite(cell) and cell > 0):
+            raise ValueError("the box must have a positive, finite extent")
+        return tuple(float(x) for x in lo), float(cell), (n, n, n)
+
+    def _simplify_options(self, origin, cell, dims, placement):
+        placements = {"quadric": _abi.MESH_PLACE_QUADRIC, "mean": _abi.MESH_PLACE_MEAN}
+        if placement not in placements:
+            raise ValueError("placement must be 'quadric' or 'mean'")
+        opt = _abi.MeshSimplifyOptions()
+        self._check(self.f.mesh_simplify_default_options(C.byref(opt)))
+        opt.origin[:] = [float(x) for x in origin]
+        opt.cell = float(cell)
+        opt.dims[:] = [int(dims)] * 3 if np.isscalar(dims) else [int(x) for x in dims]
+        opt.placement = placements[placement]
+        return opt
+
+    def simplify_mesh(self, verts, indices, colors=None, normals=None, origin=(0.0, 0.0, 0.0), cell=1.0 / 256.0, dims=256, placement="quadric", stream=None):
+        """rnb_mesh_simplify (include/rnb_mesh_simplify.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals.
+        Vertex clustering on the grid of dims (int or 3 ints) cells of edge `cell` from `origin`: the used vertices of a cell become one vertex, placed by
+        placement="quadric" (the regularised minimiser of the squared distances to the planes of the triangles that touch the cell, kept inside the cell) or "mean";
+        colours are averaged, normals summed and normalised; triangles that lose a corner are dropped, the others keep order and winding. Bit-reproducible. Returns a
+        dict of numpy arrays like clean_mesh, with `stats` = `simplify_stats` (counts, n_clamped, n_fallback, peak_workspace, ms). Leaves the training state as it was."""
+        sopt = self._simplify_options(origin, cell, dims, placement)
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+        attrs = {}
+        for key, a in (("colors", colors), ("normals", normals)):
+            if a is not None:
+                attrs[key] = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+                if attrs[key].shape != v.shape:
+                    raise ValueError("%s must have one row per vertex" % key)
+        m, simplified, sst = _abi.Mesh(), _abi.Mesh(), _abi.MeshSimplifyStats()
+        ptrs = []
+        try:
+            for key, a in (("verts", v), ("indices", idx), ("colors", attrs.get("colors")), ("normals", attrs.get("normals"))):
+                if a is not None:
+                    ptrs.append(self.upload(a) if a.size else self.device_malloc(4))
+                    setattr(m, key, ptrs[-1])
+            m.n_verts, m.n_indices = v.shape[0], idx.size
+            self._check(self.f.mesh_simplify(self._h, _stream_handle(stream), C.byref(m), C.byref(sopt), C.byref(simplified), C.byref(sst)))
+            out = self._download_mesh(simplified)
+            out["stats"] = out["simplify_stats"] = sst.as_dict()
+        finally:
+            for p in ptrs:
+                self.device_free(p)
+            self.f.mesh_free(self._h, C.byref(simplified))
         return out
 
     def upload(self, array):

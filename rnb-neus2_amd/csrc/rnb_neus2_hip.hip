@@ -7,6 +7,7 @@
 #include "kernels_render.cuh"
 #include "kernels_mesh_sparse.cuh"
 #include "kernels_mesh_clean.cuh"
+#include "kernels_mesh_simplify.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>
@@ -3026,6 +3027,119 @@ int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_
 		stats->largest_label = hres.best;
 		stats->hook_passes = nt ? 1u : 0u; stats->flatten_passes = nt ? 1u : 0u;
 		stats->area_q_in = hres.area_in; stats->area_q_out = hres.area_out;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh simplification (include/rnb_mesh_simplify.h) ----
+uint32_t rnb_mesh_simplify_abi_version(void) { return RNB_MESH_SIMPLIFY_ABI_VERSION; }
+
+int rnb_mesh_simplify_default_options(rnb_mesh_simplify_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_SIMPLIFY_ABI_VERSION;
+	opt->cell = 1.0f / 256.0f;
+	opt->dims[0] = opt->dims[1] = opt->dims[2] = 256u;
+	opt->placement = RNB_MESH_PLACE_QUADRIC;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_simplify_options* opt, rnb_mesh* out, rnb_mesh_simplify_stats* stats) try {
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: null argument");
+	if (in == out) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: in and out must be different objects");
+	const rnb_mesh m = *in;
+	std::memset(out, 0, sizeof(*out));
+	if (opt->abi_version != RNB_MESH_SIMPLIFY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: options abi_version mismatch (expected RNB_MESH_SIMPLIFY_ABI_VERSION)");
+	if (opt->placement != RNB_MESH_PLACE_QUADRIC && opt->placement != RNB_MESH_PLACE_MEAN) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: unknown placement");
+	if (!(opt->cell > 0.0f) || !std::isfinite(opt->cell)) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: cell must be finite and > 0");
+	uint64_t n_cells = 1;
+	for (int k = 0; k < 3; ++k) {
+		if (!std::isfinite(opt->origin[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: origin must be finite");
+		if (opt->dims[k] == 0 || opt->dims[k] > RNB_MESH_SIMPLIFY_MAX_DIM) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims must be 1 .. 4096 per axis");
+		n_cells *= opt->dims[k];
+	}
+	if (n_cells > RNB_MESH_SIMPLIFY_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims hold " + std::to_string(n_cells) + " cells, more than RNB_MESH_SIMPLIFY_MAX_CELLS (2^30)");
+	if (m.n_indices % 3u) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: n_indices is not a multiple of 3");
+	if ((m.n_verts && !m.verts) || (m.n_indices && !m.indices)) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: null vertex or index buffer");
+	if (m.n_indices && m.n_verts == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: an index is out of range (the mesh has no vertices)");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	MeshWorkspace ws;
+	SpResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	uint32_t n_cl = 0, nvo = 0, nto = 0;
+	float *overts = nullptr, *ocolors = nullptr, *onormals = nullptr;
+	uint32_t* oidx = nullptr;
+	if (nt) {
+		SpGrid g;
+		for (int k = 0; k < 3; ++k) { g.origin[k] = (double)opt->origin[k]; g.dims[k] = opt->dims[k]; }
+		g.cell = (double)opt->cell;
+		const uint32_t n_words = (uint32_t)((n_cells + 31u) / 32u);
+		const uint32_t g_v = (nv + SP_WG - 1) / SP_WG, g_t = (nt + SP_WG - 1) / SP_WG, g_w = (n_words + SP_WG - 1) / SP_WG;
+		uint32_t *used = nullptr, *vcl = nullptr, *bits = nullptr, *rank = nullptr, *scan = nullptr, *twg = nullptr, *ckey = nullptr, *cused = nullptr, *cmap = nullptr;
+		long long* sums = nullptr;
+		SpResult* dres = nullptr;
+		if (!ws.alloc(&used, nv) || !ws.alloc(&vcl, nv) || !ws.alloc(&bits, n_words) || !ws.alloc(&rank, n_words) || !ws.alloc(&twg, g_t) ||
+		    !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(std::max<uint64_t>(nv, n_words), g_t))) || !ws.alloc(&dres, 1))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(n_cells) + " cells");
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemsetAsync(bits, 0, (size_t)n_words * 4, s));
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		// 1. every index is range-checked before any is used as an address; the occupied cells; cluster ids = ranks of the occupied keys
+		hipLaunchKernelGGL(k_sp_validate, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, dres);
+		hipLaunchKernelGGL(k_sp_cells, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)used, vcl, bits, dres);
+		hipLaunchKernelGGL(k_sp_popc, dim3(g_w), dim3(SP_WG), 0, s, (const uint32_t*)bits, rank, n_words);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		int rc = scan_exclusive(rank, n_words, s, &n_cl, scan); // (synchronises: hres has arrived)
+		if (rc != RNB_OK) return rc;
+		if (hres.flags & SP_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: an index is out of range (>= n_verts)");
+		if (hres.flags & SP_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a coordinate or attribute of a used vertex is not finite");
+		ws.release(used);
+		// 2. the sums of every cluster
+		if (!ws.alloc(&sums, (size_t)n_cl * SP_NSUM) || !ws.alloc(&ckey, n_cl) || !ws.alloc(&cused, n_cl) || !ws.alloc(&cmap, n_cl))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the records of " + std::to_string(n_cl) + " clusters");
+		HIP_TRY(hipMemsetAsync(sums, 0, std::max<size_t>(n_cl, 1) * SP_NSUM * sizeof(long long), s));
+		HIP_TRY(hipMemsetAsync(cused, 0, std::max<size_t>(n_cl, 1) * 4, s));
+		hipLaunchKernelGGL(k_sp_members, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)bits, (const uint32_t*)rank, vcl, ckey, sums, dres);
+		hipLaunchKernelGGL(k_sp_quadric, dim3(g_t), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, sums, dres);
+		// 3. the surviving triangles and the clusters they use, numbered by prefix sums
+		hipLaunchKernelGGL(k_sp_tris<false>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, cused, (const uint32_t*)nullptr, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(cmap, cused, std::max<size_t>(n_cl, 1) * 4, hipMemcpyDeviceToDevice, s));
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		rc = scan_exclusive(cmap, n_cl, s, &nvo, scan);
+		if (rc != RNB_OK) return rc;
+		if (hres.flags & SP_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a term is not finite or not below 2^22 (a vertex or triangle too far from its cell, in cell units)");
+		rc = scan_exclusive(twg, g_t, s, &nto, scan);
+		if (rc != RNB_OK) return rc;
+		ws.release(bits); ws.release(rank);
+		// 4. the output: one solve per cluster, the triangles in input order
+		if (!ws.alloc(&overts, (size_t)nvo * 3) || !ws.alloc(&oidx, (size_t)nto * 3) || (m.colors && !ws.alloc(&ocolors, (size_t)nvo * 3)) || (m.normals && !ws.alloc(&onormals, (size_t)nvo * 3)))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
+		hipLaunchKernelGGL(k_sp_solve, dim3((n_cl + SP_WG - 1) / SP_WG), dim3(SP_WG), 0, s, g, opt->placement, n_cl, (const long long*)sums, (const uint32_t*)ckey, (const uint32_t*)cused, (const uint32_t*)cmap,
+		                   overts, ocolors, onormals, dres);
+		hipLaunchKernelGGL(k_sp_tris<true>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, (uint32_t*)nullptr, (const uint32_t*)cmap, (uint32_t*)nullptr, (const uint32_t*)twg, oidx);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(vcl); ws.release(scan); ws.release(twg); ws.release(sums); ws.release(ckey); ws.release(cused); ws.release(cmap); ws.release(dres);
+	} else {
+		if (!ws.alloc(&overts, 1) || !ws.alloc(&oidx, 1) || (m.colors && !ws.alloc(&ocolors, 1)) || (m.normals && !ws.alloc(&onormals, 1)))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
+	}
+	out->verts = (float*)ws.keep(overts); out->indices = (uint32_t*)ws.keep(oidx);
+	out->colors = (float*)ws.keep(ocolors); out->normals = (float*)ws.keep(onormals);
+	out->n_verts = nvo; out->n_indices = nto * 3u;
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_verts_in = nv; stats->n_tris_in = nt; stats->n_clusters = n_cl; stats->n_verts_out = nvo; stats->n_tris_out = nto; stats->n_tris_collapsed = nt - nto;
+		stats->n_clamped = hres.n_clamped; stats->n_fallback = hres.n_fallback;
 		stats->peak_workspace = ws.peak;
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}

@@ -3,17 +3,20 @@
 // snapshot by snapshot.hpp (its EMA weights, occupancy grid and network configuration).
 //
 //   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
-//        [--keep all|largest] [--orient none|outward]
+//        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
 // With --keep and / or --orient the device mesh goes through rnb_mesh_clean (include/rnb_mesh_clean.h) before it is downloaded: connected components, the largest one
 // kept, triangles turned outward -- the pipeline's post-processing without the round trip through an OBJ. Without them nothing of that is called; with only one of
 // them the other part is left alone (--keep alone does not turn anything, --orient alone keeps every component), as Context.extract_mesh(keep=, orient=) does.
+// With --simplify N the (cleaned) device mesh then goes through rnb_mesh_simplify (include/rnb_mesh_simplify.h): vertex clustering on N^3 cells over the scene's box
+// (origin aabb_min, cell = (aabb_max - aabb_min) / N), the representative of a cell placed by --placement (quadric by default). Ring normals are those of the simplified mesh.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
 #include "../../include/rnb_mesh_clean.h"
+#include "../../include/rnb_mesh_simplify.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -47,6 +50,8 @@ const Flag FLAGS[] = {
 	{"normals", "MODE", "ring (default): area-weighted face normals, as the testbed; gradient: the SDF gradient at the vertex, from the device."},
 	{"keep", "MODE", "Clean the mesh on the device. largest: only the connected component of the greatest area; all: every component."},
 	{"orient", "MODE", "Clean the mesh on the device. outward: components of negative signed volume are turned inside out; none: triangles as extracted."},
+	{"simplify", "N", "Simplify the mesh on the device: vertex clustering on N^3 cells over the scene's box (1 .. 1024), after the cleaning."},
+	{"placement", "MODE", "--simplify only. quadric (default): the vertex of a cell minimises the quadric error of its triangles; mean: the mean of its vertices."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -98,6 +103,7 @@ int main(int argc, char** argv) {
 	uint32_t resolution = 256, brick = 0, cull = RNB_MESH_CULL_OCCUPANCY;
 	bool gradient = false, clean = false;
 	uint32_t keep = RNB_MESH_KEEP_ALL, orient = RNB_MESH_ORIENT_NONE; // with one of the two flags given, the other one leaves its part alone
+	uint32_t simplify = 0, placement = RNB_MESH_PLACE_QUADRIC;           // 0: no simplification
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -124,6 +130,15 @@ int main(int argc, char** argv) {
 			clean = true;
 			if (a["orient"] == "outward") orient = RNB_MESH_ORIENT_OUTWARD;
 			else if (a["orient"] != "none") throw ParseError("Argument 'orient' must be none or outward");
+		}
+		if (a.count("simplify")) {
+			simplify = parse_u32("simplify", a["simplify"]);
+			if (simplify == 0 || (uint64_t)simplify * simplify * simplify > RNB_MESH_SIMPLIFY_MAX_CELLS) throw ParseError("Argument 'simplify' must be 1 .. 1024");
+		}
+		if (a.count("placement")) {
+			if (!simplify) throw ParseError("Argument 'placement' is only used with --simplify");
+			if (a["placement"] == "mean") placement = RNB_MESH_PLACE_MEAN;
+			else if (a["placement"] != "quadric") throw ParseError("Argument 'placement' must be quadric or mean");
 		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
@@ -181,6 +196,18 @@ int main(int argc, char** argv) {
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		}
+		rnb_mesh_simplify_stats ss;
+		if (simplify) { // device to device, after the cleaning
+			rnb_mesh_simplify_options so;
+			RNB_CHECK(rnb_mesh_simplify_default_options(&so));
+			for (int k = 0; k < 3; ++k) { so.origin[k] = amin; so.dims[k] = simplify; }
+			so.cell = (float)(((double)amax - (double)amin) / (double)simplify);
+			so.placement = placement;
+			RNB_CHECK(rnb_mesh_simplify(ctx, nullptr, &dm, &so, &cm, &ss));
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+		}
 		mesh::Mesh m;
 		m.verts.resize(dm.n_verts); m.colors.resize(dm.n_verts); m.indices.resize(dm.n_indices);
 		if (dm.n_verts) {
@@ -198,6 +225,8 @@ int main(int argc, char** argv) {
 		            100.0 * (double)st.n_points_evaluated / ((double)res * res * res), (unsigned long long)st.n_sign_change, (double)st.peak_workspace / 1e6, st.ms);
 		if (clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
 		                       cs.n_verts_in, cs.n_verts_out, cs.ms);
+		if (simplify) std::printf("simplify: %u clusters, %u -> %u triangles (%u collapsed), %u -> %u vertices, %u clamped, %u at the mean, %.1f ms\n", ss.n_clusters, ss.n_tris_in,
+		                          ss.n_tris_out, ss.n_tris_collapsed, ss.n_verts_in, ss.n_verts_out, ss.n_clamped, ss.n_fallback, ss.ms);
 		std::printf("#vertices=%zu #triangles=%zu\n", m.verts.size(), m.indices.size() / 3);
 		// --orient outward speaks of the file: the device turned every kept component counter-clockwise seen from outside, and the faces are written as they are
 		// (without it, the scene's from_na flag decides whether save_obj reverses them, as in the testbed). save_obj maps positions by a uniform scale and a shift,
