@@ -4,6 +4,7 @@ The reference drives this path through ``Testbed`` (src/testbed.cu:2776-2872, sr
 ``Context`` keeps the same verbs (reset_network/init params, load dataset, train step, per-stage calls) and hands
 everything to ``librnb_neus2_hip.so``. There is no CPU fallback: if the HIP library is missing, loading fails.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -552,6 +553,27 @@ class Context:
         opt.keep, opt.orient = keeps[keep], orients[orient]
         return opt
 
+    @contextlib.contextmanager
+    def _device_mesh(self, verts, indices, colors, normals):
+        """A host mesh (verts float32[n,3], indices uint32[m] or [m/3,3], optional per-vertex colors / normals) as an _abi.Mesh on the device; the uploads are freed on exit."""
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        arrays = dict(verts=v, indices=np.ascontiguousarray(indices, dtype=np.uint32).ravel())
+        for key, a in (("colors", colors), ("normals", normals)):
+            if a is not None:
+                arrays[key] = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+                if arrays[key].shape != v.shape:
+                    raise ValueError("%s must have one row per vertex" % key)
+        m, ptrs = _abi.Mesh(), []
+        try:
+            for key, a in arrays.items():
+                ptrs.append(self.upload(a) if a.size else self.device_malloc(4))
+                setattr(m, key, ptrs[-1])
+            m.n_verts, m.n_indices = v.shape[0], arrays["indices"].size
+            yield m
+        finally:
+            for p in ptrs:
+                self.device_free(p)
+
     def clean_mesh(self, verts, indices, colors=None, normals=None, keep="largest", orient="outward", table=False, stream=None):
         """rnb_mesh_clean (include/rnb_mesh_clean.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals. The
         connected components (vertices joined by triangles), keep="largest" (greatest area; "all": only unused vertices go), orient="outward" (the triangles of a
@@ -559,31 +581,16 @@ class Context:
         normals when given) in the input's order, `stats`, and with table=True `table`: one record per component (label, n_vertices, n_triangles, kept, area_q,
         volume_q), ascending label. For a dict m that extract_mesh returned: clean_mesh(m["verts"], m["indices"], m.get("colors"), m.get("normals")). Leaves the training state as it was."""
         copt = self._clean_options(keep, orient)
-        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        idx = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
-        attrs = {}
-        for key, a in (("colors", colors), ("normals", normals)):
-            if a is not None:
-                attrs[key] = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
-                if attrs[key].shape != v.shape:
-                    raise ValueError("%s must have one row per vertex" % key)
-        m, cleaned, cst, tab = _abi.Mesh(), _abi.Mesh(), _abi.MeshCleanStats(), C.c_void_p()
-        ptrs = []
+        cleaned, cst, tab = _abi.Mesh(), _abi.MeshCleanStats(), C.c_void_p()
         try:
-            for key, a in (("verts", v), ("indices", idx), ("colors", attrs.get("colors")), ("normals", attrs.get("normals"))):
-                if a is not None:
-                    ptrs.append(self.upload(a) if a.size else self.device_malloc(4))
-                    setattr(m, key, ptrs[-1])
-            m.n_verts, m.n_indices = v.shape[0], idx.size
-            self._check(self.f.mesh_clean(self._h, _stream_handle(stream), C.byref(m), C.byref(copt), C.byref(cleaned), C.byref(tab) if table else None, C.byref(cst)))
+            with self._device_mesh(verts, indices, colors, normals) as m:
+                self._check(self.f.mesh_clean(self._h, _stream_handle(stream), C.byref(m), C.byref(copt), C.byref(cleaned), C.byref(tab) if table else None, C.byref(cst)))
             out = self._download_mesh(cleaned)
             out["stats"] = cst.as_dict()
             if table:
                 dt = np.dtype(_abi.MESH_COMPONENT_DTYPE)
                 out["table"] = self.download(tab.value, cst.n_components, dt) if cst.n_components else np.empty(0, dt)
         finally:
-            for p in ptrs:
-                self.device_free(p)
             self.f.mesh_free(self._h, C.byref(cleaned))
             if tab.value:
                 self.f.mesh_clean_table_free(self._h, tab)
@@ -623,28 +630,13 @@ class Context:
         colours are averaged, normals summed and normalised; triangles that lose a corner are dropped, the others keep order and winding. Bit-reproducible. Returns a
         dict of numpy arrays like clean_mesh, with `stats` = `simplify_stats` (counts, n_clamped, n_fallback, peak_workspace, ms). Leaves the training state as it was."""
         sopt = self._simplify_options(origin, cell, dims, placement)
-        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
-        idx = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
-        attrs = {}
-        for key, a in (("colors", colors), ("normals", normals)):
-            if a is not None:
-                attrs[key] = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
-                if attrs[key].shape != v.shape:
-                    raise ValueError("%s must have one row per vertex" % key)
-        m, simplified, sst = _abi.Mesh(), _abi.Mesh(), _abi.MeshSimplifyStats()
-        ptrs = []
+        simplified, sst = _abi.Mesh(), _abi.MeshSimplifyStats()
         try:
-            for key, a in (("verts", v), ("indices", idx), ("colors", attrs.get("colors")), ("normals", attrs.get("normals"))):
-                if a is not None:
-                    ptrs.append(self.upload(a) if a.size else self.device_malloc(4))
-                    setattr(m, key, ptrs[-1])
-            m.n_verts, m.n_indices = v.shape[0], idx.size
-            self._check(self.f.mesh_simplify(self._h, _stream_handle(stream), C.byref(m), C.byref(sopt), C.byref(simplified), C.byref(sst)))
+            with self._device_mesh(verts, indices, colors, normals) as m:
+                self._check(self.f.mesh_simplify(self._h, _stream_handle(stream), C.byref(m), C.byref(sopt), C.byref(simplified), C.byref(sst)))
             out = self._download_mesh(simplified)
             out["stats"] = out["simplify_stats"] = sst.as_dict()
         finally:
-            for p in ptrs:
-                self.device_free(p)
             self.f.mesh_free(self._h, C.byref(simplified))
         return out
 

@@ -6,7 +6,7 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG_DIR, "csrc", "rnb_neus2_hip.hip")
 OUT = os.path.join(PKG_DIR, "librnb_neus2_hip.so")
-DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "kernels_mesh.cuh", "kernels_render.cuh", "kernels_mesh_sparse.cuh", "kernels_mesh_clean.cuh", "kernels_mesh_simplify.cuh")] + [
+DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "mesh_common.cuh", "kernels_mesh.cuh", "kernels_render.cuh", "kernels_mesh_sparse.cuh", "kernels_mesh_clean.cuh", "kernels_mesh_simplify.cuh")] + [
     os.path.join(PKG_DIR, "host", f) for f in ("mesh.hpp", "mc_table.hpp")] + [
     os.path.join(os.path.dirname(PKG_DIR), "include", f) for f in ("rnb_neus2.h", "rnb_render.h", "rnb_mesh.h", "rnb_mesh_clean.h", "rnb_mesh_simplify.h")]
 

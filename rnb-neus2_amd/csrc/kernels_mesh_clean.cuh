@@ -1,6 +1,6 @@
 // kernels_mesh_clean.cuh — the mesh cleaner of include/rnb_mesh_clean.h (rnb_mesh_clean): connected components of an indexed triangle mesh, keep-largest, outward
 // orientation, stable compaction.
-//   k_cl_init / k_cl_validate   parent[v] = v; every index range-checked (nothing is dereferenced through an index before this kernel has passed), used[v] marked
+//   k_cl_init                   parent[v] = v (beside k_mesh_validate of mesh_common.cuh: nothing is dereferenced through an index before that kernel has passed)
 //   k_cl_hook                   union-find: one thread per triangle unites its corners, the larger root hooked under the smaller by compare-and-swap
 //   k_cl_flatten                parent[v] = root of v
 //   k_cl_roots / k_cl_relabel   roots of used vertices -> component ids by an exclusive sum (ascending label = table order); parent[] becomes the component id per vertex
@@ -10,19 +10,18 @@
 //   k_cl_tris<WRITE>            kept triangles: per-workgroup counts -> exclusive sum -> renumbered indices, second and third swapped where the component is flipped
 // Why the labels do not depend on the schedule: parent[x] <= x always, a compare-and-swap only ever replaces a root r by a smaller root, and a non-root never becomes
 // a root again; so when k_cl_hook has finished, the root of a component is its smallest vertex. Path halving only writes an ancestor into a non-root's parent.
-// Everything that numbers a vertex or a triangle is a prefix sum, as in kernels_mesh.cuh. Vector loads, stores and atomics only.
+// Everything that numbers a vertex or a triangle is a prefix sum, as in kernels_mesh.cuh (mesh_common.cuh). Vector loads, stores and atomics only.
 #pragma once
-#include "kernels_mesh.cuh"
+#include "mesh_common.cuh"
 #include "../../include/rnb_mesh_clean.h"
 
 namespace rnb {
 
-constexpr uint32_t CL_NONE = 0xFFFFFFFFu;
 constexpr uint32_t CL_WG = 256;
 constexpr uint32_t CL_BAD_INDEX = 1u, CL_BAD_TERM = 2u; // bits of ClResult::flags
 
 struct ClResult { // written by the kernels, read by the driver
-	uint32_t flags;
+	uint32_t flags;     // first: k_mesh_validate is handed its address
 	uint32_t best;      // component id KEEP_LARGEST selects
 	uint32_t n_kept;
 	uint32_t pad;
@@ -57,13 +56,6 @@ __global__ __launch_bounds__(CL_WG) void k_cl_init(uint32_t* __restrict__ parent
 	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
 	if (v < nv) parent[v] = v;
 }
-__global__ __launch_bounds__(CL_WG) void k_cl_validate(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t nv, uint32_t* __restrict__ used, ClResult* __restrict__ res) {
-	const uint32_t t = blockIdx.x * CL_WG + threadIdx.x;
-	if (t >= nt) return;
-	const uint32_t a = idx[3 * (size_t)t], b = idx[3 * (size_t)t + 1], c = idx[3 * (size_t)t + 2];
-	if (a >= nv || b >= nv || c >= nv) { res->flags = CL_BAD_INDEX; return; } // (every writer writes the same value; the later bits are set after this kernel)
-	used[a] = 1u; used[b] = 1u; used[c] = 1u;
-}
 __global__ __launch_bounds__(CL_WG) void k_cl_hook(const uint32_t* __restrict__ idx, const uint32_t nt, uint32_t* parent) {
 	const uint32_t t = blockIdx.x * CL_WG + threadIdx.x;
 	if (t >= nt) return;
@@ -88,11 +80,11 @@ __global__ __launch_bounds__(CL_WG) void k_cl_roots(const uint32_t* __restrict__
 	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
 	if (v < nv) cid[v] = (used[v] && parent[v] == v) ? 1u : 0u;
 }
-// parent[v] <- component id of v (CL_NONE for a vertex no triangle uses); the root writes its label into the table. cid holds the exclusive sums of k_cl_roots' flags.
+// parent[v] <- component id of v (MESH_NONE for a vertex no triangle uses); the root writes its label into the table. cid holds the exclusive sums of k_cl_roots' flags.
 __global__ __launch_bounds__(CL_WG) void k_cl_relabel(uint32_t* __restrict__ parent, const uint32_t* __restrict__ used, const uint32_t* __restrict__ cid, rnb_mesh_component* __restrict__ table, const uint32_t nv) {
 	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
 	if (v >= nv) return;
-	if (!used[v]) { parent[v] = CL_NONE; return; }
+	if (!used[v]) { parent[v] = MESH_NONE; return; }
 	const uint32_t r = parent[v], c = cid[r]; // (a thread writes its own entry only and reads its own entry and cid: no other thread's write is observed)
 	if (r == v) table[c].label = v;
 	parent[v] = c;
@@ -117,16 +109,6 @@ __device__ __forceinline__ bool cl_terms(const float* __restrict__ verts, const 
 	return true;
 }
 
-__device__ __forceinline__ long long cl_wave_sum(long long x) {
-#pragma unroll
-	for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-	return x;
-}
-__device__ __forceinline__ uint32_t cl_wave_sum(uint32_t x) {
-#pragma unroll
-	for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
-	return x;
-}
 __device__ __forceinline__ void cl_emit(rnb_mesh_component* table, const uint32_t c, const long long area, const long long vol, const uint32_t nt, const uint32_t nvx) {
 	if (area) (void)atomicAdd((unsigned long long*)&table[c].area_q, (unsigned long long)area);
 	if (vol) (void)atomicAdd((unsigned long long*)&table[c].volume_q, (unsigned long long)vol);
@@ -135,7 +117,7 @@ __device__ __forceinline__ void cl_emit(rnb_mesh_component* table, const uint32_
 }
 
 // Adds one item per thread (a triangle's terms, or one vertex) to the record of its component. One component usually owns almost every item, so per-item atomics would
-// all go to one address. Instead: the lanes of a wavefront that share a component are summed with shuffles (up to 4 distinct components per wavefront, the rest falls back
+// all go to one address. Instead: the lanes of a wavefront that share a component are summed with shuffles (wave_group_next: up to MESH_GROUP_ROUNDS = 4 distinct components per wavefront, the rest falls back
 // to one atomic set per lane); a wavefront whose 64 lanes share one component hands its sums to LDS, and if the 4 wavefronts of the workgroup agree the workgroup issues
 // ONE set of atomics. Atomics per million triangles of one dominant component: 10^6 / 256 = 3 907 workgroups x 3 (area, volume, count: global_atomic_add_x2 twice and
 // global_atomic_add once) = 11.7 k instead of 3 M (derived; not yet checked against a counter pass, profiles/mesh_clean.md); the vertex pass adds 1 per 256 vertices. Integer adds: the sums do not depend on any of this.
@@ -145,29 +127,24 @@ __device__ __forceinline__ void cl_accumulate(rnb_mesh_component* __restrict__ t
 	__shared__ uint32_t s_c[4], s_nt[4], s_nv[4];
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	bool to_lds = false;
-	for (int it = 0; it < 4; ++it) {
-		const uint64_t todo = __ballot(valid);
-		if (!todo) break; // (uniform)
-		const int leader = __ffsll((unsigned long long)todo) - 1;
-		const uint32_t c0 = __shfl(c, leader, 64);
-		const bool mine = valid && c == c0;
-		const uint64_t mask = __ballot(mine);
-		const long long sa = cl_wave_sum(mine ? area : 0ll), sv = cl_wave_sum(mine ? vol : 0ll);
-		const uint32_t st = cl_wave_sum(mine ? nt : 0u), sn = cl_wave_sum(mine ? nvx : 0u);
-		if (it == 0 && mask == ~0ull) { // the whole wavefront is one component
+	for (int it = 0; it < MESH_GROUP_ROUNDS; ++it) {
+		WaveGroup g;
+		if (!wave_group_next(c, valid, g)) break;
+		const long long sa = wave_sum(g.mine ? area : 0ll), sv = wave_sum(g.mine ? vol : 0ll);
+		const uint32_t st = wave_sum(g.mine ? nt : 0u), sn = wave_sum(g.mine ? nvx : 0u);
+		if (it == 0 && g.mask == ~0ull) { // the whole wavefront is one component
 			to_lds = true;
-			if (lane == 0) { s_c[wave] = c0; s_area[wave] = sa; s_vol[wave] = sv; s_nt[wave] = st; s_nv[wave] = sn; }
-		} else if ((int)lane == leader) cl_emit(table, c0, sa, sv, st, sn);
-		valid = valid && !mine;
+			if (lane == 0) { s_c[wave] = g.key; s_area[wave] = sa; s_vol[wave] = sv; s_nt[wave] = st; s_nv[wave] = sn; }
+		} else if ((int)lane == g.leader) cl_emit(table, g.key, sa, sv, st, sn);
 	}
 	if (valid) cl_emit(table, c, area, vol, nt, nvx);
-	if (!to_lds && lane == 0) s_c[wave] = CL_NONE;
+	if (!to_lds && lane == 0) s_c[wave] = MESH_NONE;
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		if (s_c[0] != CL_NONE && s_c[0] == s_c[1] && s_c[0] == s_c[2] && s_c[0] == s_c[3])
+		if (s_c[0] != MESH_NONE && s_c[0] == s_c[1] && s_c[0] == s_c[2] && s_c[0] == s_c[3])
 			cl_emit(table, s_c[0], (s_area[0] + s_area[1]) + (s_area[2] + s_area[3]), (s_vol[0] + s_vol[1]) + (s_vol[2] + s_vol[3]), s_nt[0] + s_nt[1] + s_nt[2] + s_nt[3], s_nv[0] + s_nv[1] + s_nv[2] + s_nv[3]);
 		else
-			for (uint32_t w = 0; w < 4; ++w) if (s_c[w] != CL_NONE) cl_emit(table, s_c[w], s_area[w], s_vol[w], s_nt[w], s_nv[w]);
+			for (uint32_t w = 0; w < 4; ++w) if (s_c[w] != MESH_NONE) cl_emit(table, s_c[w], s_area[w], s_vol[w], s_nt[w], s_nv[w]);
 	}
 }
 
@@ -176,7 +153,7 @@ template <bool TRI>
 __global__ __launch_bounds__(CL_WG) void k_cl_sums(const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t n, const uint32_t* __restrict__ comp,
                                                   rnb_mesh_component* __restrict__ table, ClResult* __restrict__ res) {
 	const uint32_t i = blockIdx.x * CL_WG + threadIdx.x;
-	uint32_t c = CL_NONE;
+	uint32_t c = MESH_NONE;
 	long long area = 0, vol = 0;
 	bool valid = false;
 	if (i < n) {
@@ -187,7 +164,7 @@ __global__ __launch_bounds__(CL_WG) void k_cl_sums(const float* __restrict__ ver
 			if (!cl_terms(verts, a, b, d, &area, &vol)) atomicOr(&res->flags, CL_BAD_TERM);
 		} else {
 			c = comp[i];
-			valid = c != CL_NONE;
+			valid = c != MESH_NONE;
 		}
 	}
 	cl_accumulate(table, c, valid, area, vol, TRI ? 1u : 0u, TRI ? 0u : 1u);
@@ -201,7 +178,7 @@ __global__ __launch_bounds__(1024) void k_cl_select(rnb_mesh_component* __restri
 	__shared__ uint32_t s_id[1024];
 	const uint32_t t = threadIdx.x;
 	long long best_a = -1, sum = 0;
-	uint32_t best_id = CL_NONE;
+	uint32_t best_id = MESH_NONE;
 	for (uint32_t i = t; i < n_comp; i += 1024u) { // ascending ids per thread: the first of equal areas stays
 		const long long a = table[i].area_q;
 		sum += a;
@@ -240,7 +217,7 @@ __global__ __launch_bounds__(CL_WG) void k_cl_vflag(const uint32_t* __restrict__
 	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
 	if (v >= nv) return;
 	const uint32_t c = comp[v];
-	vmap[v] = (c != CL_NONE && (cflags[c] & 1u)) ? 1u : 0u;
+	vmap[v] = (c != MESH_NONE && (cflags[c] & 1u)) ? 1u : 0u;
 }
 // vmap: exclusive sums of k_cl_vflag's flags = the new index of a kept vertex
 __global__ __launch_bounds__(CL_WG) void k_cl_verts(const uint32_t* __restrict__ comp, const uint32_t* __restrict__ cflags, const uint32_t* __restrict__ vmap, const uint32_t nv,
@@ -249,7 +226,7 @@ __global__ __launch_bounds__(CL_WG) void k_cl_verts(const uint32_t* __restrict__
 	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
 	if (v >= nv) return;
 	const uint32_t c = comp[v];
-	if (c == CL_NONE || !(cflags[c] & 1u)) return;
+	if (c == MESH_NONE || !(cflags[c] & 1u)) return;
 	const size_t s = 3 * (size_t)v, d = 3 * (size_t)vmap[v];
 	overts[d] = verts[s]; overts[d + 1] = verts[s + 1]; overts[d + 2] = verts[s + 2];
 	if (colors) { ocolors[d] = colors[s]; ocolors[d + 1] = colors[s + 1]; ocolors[d + 2] = colors[s + 2]; }

@@ -1,6 +1,6 @@
 // kernels_mesh_simplify.cuh — the mesh simplifier of include/rnb_mesh_simplify.h (rnb_mesh_simplify): vertex clustering on a uniform cell grid, the representative
 // of a cell placed by quadric error minimisation.
-//   k_sp_validate      every index range-checked (nothing is dereferenced through an index before this kernel has passed), used[v] marked
+//   (k_mesh_validate of mesh_common.cuh comes first: nothing is dereferenced through an index before that kernel has passed; it marks used[v])
 //   k_sp_cells         used vertex -> finite check, its cell key, one bit per occupied cell set with an atomic OR
 //   k_sp_popc          set bits per 32-cell word -> (scan_exclusive) -> the rank of a key among the occupied keys = its cluster id, ascending key
 //   k_sp_members       vertex -> cluster id; count, sum of local positions, colours and normals of the cluster's members (fixed point)
@@ -9,23 +9,21 @@
 //   k_sp_solve         one thread per cluster: mean or regularised quadric minimiser by the adjugate, clamped to the cell; position, colour, normal of the output vertex
 // Nothing here depends on the schedule: ids and output slots are prefix sums, sums are 64-bit integers. sp_accumulate first adds up the lanes of a wavefront that hold
 // the same cluster with shuffles (the extractor's output is brick-major: neighbouring vertices and triangles share cells) and issues the N sums of such a group as ONE
-// atomic instruction of N lanes on N neighbouring 8-byte words; lanes left over after SP_ROUNDS groups issue their own. Operation for operation what
+// atomic instruction of N lanes on N neighbouring 8-byte words; lanes left over after MESH_GROUP_ROUNDS groups (wave_group_next) issue their own. Operation for operation what
 // tests/mesh_simplify_reference.py computes (this file is compiled with -ffp-contract=off; the pragma says so once more where it matters). Vector loads, stores and atomics only.
 #pragma once
-#include "kernels_mesh_clean.cuh"
+#include "mesh_common.cuh"
 #include "../../include/rnb_mesh_simplify.h"
 
 namespace rnb {
 
-constexpr uint32_t SP_NONE = 0xFFFFFFFFu;
 constexpr uint32_t SP_WG = 256;
 constexpr uint32_t SP_BAD_INDEX = 1u, SP_BAD_VALUE = 2u, SP_BAD_TERM = 4u; // bits of SpResult::flags
-constexpr int SP_ROUNDS = 4;
 // the record of a cluster: SP_NSUM 64-bit sums
 constexpr uint32_t SP_A = 0, SP_B = 6, SP_COUNT = 9, SP_X = 10, SP_COL = 13, SP_NRM = 16, SP_NSUM = 19;
 
 struct SpResult { // written by the kernels, read by the driver
-	uint32_t flags;
+	uint32_t flags; // first: k_mesh_validate is handed its address
 	uint32_t n_clamped;
 	uint32_t n_fallback;
 	uint32_t pad;
@@ -66,20 +64,16 @@ template <int N>
 __device__ __forceinline__ void sp_accumulate(long long* __restrict__ sums, const uint32_t first, const uint32_t c, bool valid, const long long (&v)[N]) {
 	const uint32_t lane = threadIdx.x & 63u;
 #pragma unroll 1
-	for (int it = 0; it < SP_ROUNDS; ++it) {
-		const uint64_t todo = __ballot(valid);
-		if (!todo) return; // (uniform)
-		const int leader = __ffsll((unsigned long long)todo) - 1;
-		const uint32_t c0 = __shfl(c, leader, 64);
-		const bool mine = valid && c == c0;
+	for (int it = 0; it < MESH_GROUP_ROUNDS; ++it) {
+		WaveGroup g;
+		if (!wave_group_next(c, valid, g)) return;
 		long long out = 0;
 #pragma unroll
 		for (int k = 0; k < N; ++k) {
-			const long long s = cl_wave_sum(mine ? v[k] : 0ll);
+			const long long s = wave_sum(g.mine ? v[k] : 0ll);
 			if ((int)lane == k) out = s;
 		}
-		if ((int)lane < N && out) (void)atomicAdd((unsigned long long*)(sums + (size_t)c0 * SP_NSUM + first + lane), (unsigned long long)out);
-		valid = valid && !mine;
+		if ((int)lane < N && out) (void)atomicAdd((unsigned long long*)(sums + (size_t)g.key * SP_NSUM + first + lane), (unsigned long long)out);
 	}
 	if (valid) {
 #pragma unroll
@@ -88,19 +82,12 @@ __device__ __forceinline__ void sp_accumulate(long long* __restrict__ sums, cons
 	}
 }
 
-__global__ __launch_bounds__(SP_WG) void k_sp_validate(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t nv, uint32_t* __restrict__ used, SpResult* __restrict__ res) {
-	const uint32_t t = blockIdx.x * SP_WG + threadIdx.x;
-	if (t >= nt) return;
-	const uint32_t a = idx[3 * (size_t)t], b = idx[3 * (size_t)t + 1], c = idx[3 * (size_t)t + 2];
-	if (a >= nv || b >= nv || c >= nv) { (void)atomicOr(&res->flags, SP_BAD_INDEX); return; }
-	used[a] = 1u; used[b] = 1u; used[c] = 1u; // (every writer writes the same value)
-}
-// vkey[v] = the key of a used vertex (< 2^30: RNB_MESH_SIMPLIFY_MAX_CELLS), SP_NONE otherwise; bits: one per cell
+// vkey[v] = the key of a used vertex (< 2^30: RNB_MESH_SIMPLIFY_MAX_CELLS), MESH_NONE otherwise; bits: one per cell
 __global__ __launch_bounds__(SP_WG) void k_sp_cells(const SpGrid g, const float* __restrict__ verts, const float* __restrict__ colors, const float* __restrict__ normals, const uint32_t nv,
                                                    const uint32_t* __restrict__ used, uint32_t* __restrict__ vkey, uint32_t* __restrict__ bits, SpResult* __restrict__ res) {
 	const uint32_t v = blockIdx.x * SP_WG + threadIdx.x;
 	if (v >= nv) return;
-	uint32_t key = SP_NONE;
+	uint32_t key = MESH_NONE;
 	if (used[v]) {
 		const size_t s = 3 * (size_t)v;
 		if (sp_finite3(verts + s) && (!colors || sp_finite3(colors + s)) && (!normals || sp_finite3(normals + s))) {
@@ -123,10 +110,10 @@ __global__ __launch_bounds__(SP_WG) void k_sp_members(const SpGrid g, const floa
                                                      long long* __restrict__ sums, SpResult* __restrict__ res) {
 #pragma clang fp contract(off)
 	const uint32_t v = blockIdx.x * SP_WG + threadIdx.x;
-	uint32_t c = SP_NONE;
+	uint32_t c = MESH_NONE;
 	long long q[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // count, x, colour, normal
-	const uint32_t key = v < nv ? vcl[v] : SP_NONE;
-	if (key != SP_NONE) {
+	const uint32_t key = v < nv ? vcl[v] : MESH_NONE;
+	if (key != MESH_NONE) {
 		c = rank[key >> 5] + __popc(bits[key >> 5] & ((1u << (key & 31u)) - 1u));
 		vcl[v] = c;
 		ckey[c] = key; // (every member writes the same value)
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(SP_WG) void k_sp_members(const SpGrid g, const floa
 		}
 		if (!ok) (void)atomicOr(&res->flags, SP_BAD_TERM);
 	}
-	sp_accumulate<10>(sums, SP_COUNT, c, c != SP_NONE, q);
+	sp_accumulate<10>(sums, SP_COUNT, c, c != MESH_NONE, q);
 }
 
 // the nine terms of rule 3 for the triangle (a, b, c), its corners given in the cluster's frame; false: nothing to add (zero area) -- *bad is set when a term is refused
@@ -175,7 +162,7 @@ __global__ __launch_bounds__(SP_WG) void k_sp_quadric(const SpGrid g, const floa
 #pragma clang fp contract(off)
 	const uint32_t t = blockIdx.x * SP_WG + threadIdx.x;
 	const bool live = t < nt;
-	uint32_t cl[3] = {SP_NONE, SP_NONE, SP_NONE};
+	uint32_t cl[3] = {MESH_NONE, MESH_NONE, MESH_NONE};
 	double p[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, ctr[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
 	if (live) {
 #pragma unroll

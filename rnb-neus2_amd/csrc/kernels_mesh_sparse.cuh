@@ -8,9 +8,10 @@
 //   k_ms_faces<WRITE>        k_mc_faces per brick: corners and edge -> vertex entries looked up through the brick words (this welds brick faces)
 //   k_ms_vertex_coords / k_ms_vertex_attr   network inputs at the vertices; logistic of the colour head, normalised SDF gradient
 // One 32-bit word per brick: bit 0 kept, bit 1 evaluated, bits 2.. the slot of its values. Everything that numbers a vertex or a triangle is a prefix sum in
-// brick-major order (workgroup counts + scan_exclusive + wg_exclusive_256, as the dense path): no atomics.
+// brick-major order (workgroup counts + scan_exclusive + wg_exclusive_256, as the dense path): no atomics. The vertex positions and the corner / edge numbering are
+// mesh_common.cuh's (mc_emit_verts, mc_corner, mc_edge), which the dense kernels use too: the two paths agree bit for bit by construction.
 #pragma once
-#include "kernels_mesh.cuh"
+#include "mesh_common.cuh"
 #include "../../include/rnb_mesh.h"
 
 namespace rnb {
@@ -29,8 +30,6 @@ struct MsArgs {
 	float thresh;
 	float sc[3], mn[3];     // lattice point p sits at mn + p * sc in the mesh
 };
-
-constexpr uint32_t MS_NONE = 0xFFFFFFFFu;
 
 __device__ __forceinline__ uint32_t ms_brick_of(const MsArgs& a, const uint32_t gx, const uint32_t gy, const uint32_t gz) {
 	return (gx >> a.lb) + a.nb[0] * ((gy >> a.lb) + a.nb[1] * (gz >> a.lb));
@@ -179,7 +178,7 @@ __device__ __forceinline__ MsPoint ms_point(const MsArgs& a, uint32_t* as_out) {
 
 // k_mc_verts for the lattice points of the bricks that kept an edge table. An edge carries a vertex if its ends lie on different sides of the threshold AND one of the
 // (up to four) cells around it belongs to a kept brick; then both ends are corners of that cell, so the far end's brick was evaluated. The position is k_mc_verts' own
-// arithmetic on global lattice coordinates. vidx: [n_active][3][brick^3], MS_NONE = no vertex.
+// arithmetic (mc_emit_verts) on global lattice coordinates. vidx: [n_active][3][brick^3], MESH_NONE = no vertex.
 template <bool WRITE>
 __global__ __launch_bounds__(MC_WG) void k_ms_verts(const MsArgs a, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, float* __restrict__ verts, uint32_t* __restrict__ vidx) {
 	uint32_t as;
@@ -220,21 +219,10 @@ __global__ __launch_bounds__(MC_WG) void k_ms_verts(const MsArgs a, uint32_t* __
 		return;
 	}
 	if (!p.valid) return;
-	uint32_t id = wg_offset[blockIdx.x] + local;
+	uint32_t ids[3];
+	mc_emit_verts(p.g, cross, a.thresh, f0, f1, a.sc, a.mn, wg_offset[blockIdx.x] + local, verts, ids);
 #pragma unroll
-	for (int d = 0; d < 3; ++d) {
-		uint32_t out = MS_NONE;
-		if (cross & (1u << d)) {
-			const float dt = (a.thresh - f0) / (f1[d] - f0);
-			float q[3] = {(float)p.g[0], (float)p.g[1], (float)p.g[2]};
-			q[d] += dt;
-			verts[(size_t)id * 3 + 0] = q[0] * a.sc[0] + a.mn[0];
-			verts[(size_t)id * 3 + 1] = q[1] * a.sc[1] + a.mn[1];
-			verts[(size_t)id * 3 + 2] = q[2] * a.sc[2] + a.mn[2];
-			out = id++;
-		}
-		vidx[(((size_t)as * 3 + d) << (3 * a.lb)) + p.local] = out;
-	}
+	for (int d = 0; d < 3; ++d) vidx[(((size_t)as * 3 + d) << (3 * a.lb)) + p.local] = ids[d];
 }
 
 // k_mc_faces for the cells of the kept bricks among those: the cell whose lowest corner is this lattice point.
@@ -246,12 +234,11 @@ __global__ __launch_bounds__(MC_WG) void k_ms_faces(const MsArgs a, const McTabl
 	uint32_t mask = 0;
 	if (p.valid && (a.word[p.brick] & 1u) && p.g[0] + 1 < a.r[0] && p.g[1] + 1 < a.r[1] && p.g[2] + 1 < a.r[2]) {
 		bool all = true;
-		// corner numbering of src/marching_cubes.cu:261-275: 0 (0,0,0) 1 (1,0,0) 2 (1,1,0) 3 (0,1,0), 4..7 the same at z + 1
 #pragma unroll
 		for (uint32_t c = 0; c < 8; ++c) {
-			const uint32_t cy = (c >> 1) & 1u, cx = (c & 1u) ^ cy, cz = c >> 2;
+			const McOffset o = mc_corner(c);
 			float v;
-			if (!ms_value(a, p.g[0] + cx, p.g[1] + cy, p.g[2] + cz, &v)) { all = false; continue; } // (cannot happen: a kept brick's +1 neighbours are evaluated)
+			if (!ms_value(a, p.g[0] + o.x, p.g[1] + o.y, p.g[2] + o.z, &v)) { all = false; continue; } // (cannot happen: a kept brick's +1 neighbours are evaluated)
 			if (v > a.thresh) mask |= 1u << c;
 		}
 		if (mask == 255u || !all) mask = 0;
@@ -266,12 +253,10 @@ __global__ __launch_bounds__(MC_WG) void k_ms_faces(const MsArgs a, const McTabl
 	if (!n) return;
 	uint32_t* dst = indices + (size_t)wg_offset[blockIdx.x] + local;
 	for (uint32_t k = 0; k < n; ++k) {
-		const uint32_t e = (uint32_t)T->tri[mask][k];
-		// edge e of the cell -> (lattice point carrying it, axis): edges 0-3 in the z plane, 4-7 in the z + 1 plane, 8-11 along z
-		const uint32_t ox = (0x622u >> e) & 1u, oy = (0xC44u >> e) & 1u, oz = (0x0F0u >> e) & 1u, ax = e < 8u ? (e & 1u) : 2u;
-		const uint32_t hx = p.g[0] + ox, hy = p.g[1] + oy, hz = p.g[2] + oz;
+		const McOffset o = mc_edge((uint32_t)T->tri[mask][k]);
+		const uint32_t hx = p.g[0] + o.x, hy = p.g[1] + o.y, hz = p.g[2] + o.z;
 		const uint32_t hs = a.word[ms_brick_of(a, hx, hy, hz)] >> 2; // (evaluated, and it keeps a table: the edge carries a vertex)
-		dst[k] = vidx[(((size_t)a.aoff[hs] * 3 + ax) << (3 * a.lb)) + ms_local_of(a, hx, hy, hz)];
+		dst[k] = vidx[(((size_t)a.aoff[hs] * 3 + o.axis) << (3 * a.lb)) + ms_local_of(a, hx, hy, hz)];
 	}
 }
 

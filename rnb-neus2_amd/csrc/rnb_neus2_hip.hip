@@ -2040,6 +2040,8 @@ int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float latti
 	return RNB_OK;
 } RNB_GUARD
 
+// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify) ----
+extern "C++" {
 namespace {
 // elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
 uint64_t scan_scratch_elems(uint64_t n) {
@@ -2048,7 +2050,7 @@ uint64_t scan_scratch_elems(uint64_t n) {
 	return total;
 }
 // in-place exclusive prefix sums of n counts (device), total to *total_out; `scratch` holds scan_scratch_elems(n) uint32 (allocated once per
-// rnb_marching_cubes call and shared by its two scans)
+// call and shared by its scans)
 int scan_exclusive(uint32_t* data, uint64_t n, hipStream_t s, uint32_t* total_out, uint32_t* scratch) {
 	std::vector<uint32_t*> levels{data};
 	std::vector<uint64_t> sizes{n};
@@ -2070,7 +2072,63 @@ int scan_exclusive(uint32_t* data, uint64_t n, hipStream_t s, uint32_t* total_ou
 	HIP_TRY(hipStreamSynchronize(s));
 	return RNB_OK;
 }
+// Phase one of a count / write kernel pair: the <false> instantiation leaves one count per workgroup in wg; they become the workgroups' exclusive offsets, their sum goes
+// to *total (synchronises). The write launch stays with the caller, who allocates for the total in between.
+template <typename K, typename... A>
+int count_and_scan(hipStream_t s, uint32_t n_wg, uint32_t* wg, uint32_t* scratch, uint32_t* total, K count_kernel, A... args) {
+	hipLaunchKernelGGL(count_kernel, dim3(n_wg), dim3(MC_WG), 0, s, args...);
+	HIP_TRY(hipGetLastError());
+	return scan_exclusive(wg, n_wg, s, total, scratch);
+}
+
+// The device memory of one mesh call: what is still held when the object goes out of scope is released; bytes held now and at the peak.
+struct MeshWorkspace {
+	std::vector<std::pair<void*, size_t>> held;
+	size_t cur = 0, peak = 0;
+	template <typename T>
+	bool alloc(T** p, size_t count) {
+		*p = nullptr;
+		const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+		if (hipMalloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+		held.emplace_back((void*)*p, bytes);
+		cur += bytes; peak = std::max(peak, cur);
+		return true;
+	}
+	template <typename T>
+	void release(T*& p) { // free now
+		for (auto& h : held) if (h.first == (void*)p && p) { (void)hipFree(h.first); cur -= h.second; h.first = nullptr; }
+		p = nullptr;
+	}
+	void* keep(void* p) { // the caller owns it from here on (it still counts as held)
+		for (auto& h : held) if (h.first == p) h.first = nullptr;
+		return p;
+	}
+	~MeshWorkspace() { for (auto& h : held) if (h.first) (void)hipFree(h.first); }
+};
+
+// What rnb_mesh_clean and rnb_mesh_simplify ask of their input mesh, said in the entry point's name; *out is zeroed as soon as it is known not to be the input.
+int check_mesh_input(const char* name, const rnb_mesh* in, rnb_mesh* out) {
+	const std::string n(name);
+	if (in == out) return fail(RNB_ERR_INVALID, n + ": in and out must be different objects");
+	std::memset(out, 0, sizeof(*out));
+	if (in->n_indices % 3u) return fail(RNB_ERR_INVALID, n + ": n_indices is not a multiple of 3");
+	if ((in->n_verts && !in->verts) || (in->n_indices && !in->indices)) return fail(RNB_ERR_INVALID, n + ": null vertex or index buffer");
+	if (in->n_indices && in->n_verts == 0) return fail(RNB_ERR_INVALID, n + ": an index is out of range (the mesh has no vertices)");
+	return RNB_OK;
+}
+// The output mesh of a stage, held by the workspace: nvo vertices with the attributes asked for, nto triangles (a count of 0 still gets a buffer: MeshWorkspace::alloc).
+bool alloc_mesh(MeshWorkspace& ws, rnb_mesh* m, uint32_t nvo, uint32_t nto, bool has_colors, bool has_normals) {
+	std::memset(m, 0, sizeof(*m));
+	m->n_verts = nvo; m->n_indices = nto * 3u;
+	return ws.alloc(&m->verts, (size_t)nvo * 3) && ws.alloc(&m->indices, (size_t)nto * 3) && (!has_colors || ws.alloc(&m->colors, (size_t)nvo * 3)) && (!has_normals || ws.alloc(&m->normals, (size_t)nvo * 3));
+}
+// *out = m, whose buffers the caller owns from here on.
+void hand_over(MeshWorkspace& ws, const rnb_mesh& m, rnb_mesh* out) {
+	*out = m;
+	ws.keep(m.verts); ws.keep(m.indices); ws.keep(m.colors); ws.keep(m.normals);
+}
 } // namespace
+} // extern "C++"
 
 // the marching-cubes case table of host/mesh.hpp on the device, uploaded on first use
 static int ensure_mc_table(rnb_ctx* c) {
@@ -2101,27 +2159,20 @@ int rnb_marching_cubes(rnb_ctx* c, void* stream, const float* density, const uin
 	for (int d = 0; d < 3; ++d) { a.sc[d] = (aabb_max[d] - aabb_min[d]) / (float)res[d]; a.mn[d] = aabb_min[d]; }
 	const uint64_t n_wg64 = (res3 + MC_WG - 1) / MC_WG;
 	const uint32_t n_wg = (uint32_t)n_wg64;
-	uint32_t* wg = nullptr;
-	uint32_t* scan_scratch = nullptr;
-	int32_t* vidx = nullptr;
+	MeshWorkspace ws;
+	uint32_t *wg = nullptr, *scan_scratch = nullptr, *vidx = nullptr, *indices = nullptr;
 	float* verts = nullptr;
-	uint32_t* indices = nullptr;
-	auto cleanup = [&](int rc) { if (wg) (void)hipFree(wg); if (scan_scratch) (void)hipFree(scan_scratch); if (vidx) (void)hipFree(vidx); if (rc != RNB_OK) { if (verts) (void)hipFree(verts); if (indices) (void)hipFree(indices); } return rc; };
-	if (hipMalloc((void**)&wg, (size_t)n_wg * 4) != hipSuccess || hipMalloc((void**)&scan_scratch, scan_scratch_elems(n_wg) * 4) != hipSuccess || hipMalloc((void**)&vidx, (size_t)res3 * 3 * 4) != hipSuccess) return cleanup(fail(RNB_ERR_NOMEM, "hipMalloc failed for the marching-cubes scratch (12 bytes per lattice point)"));
+	if (!ws.alloc(&wg, n_wg) || !ws.alloc(&scan_scratch, scan_scratch_elems(n_wg)) || !ws.alloc(&vidx, (size_t)res3 * 3)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the marching-cubes scratch (12 bytes per lattice point)");
 	uint32_t nv = 0, ni = 0;
-	hipLaunchKernelGGL(k_mc_verts<false>, dim3(n_wg), dim3(MC_WG), 0, s, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr);
-	int rc = scan_exclusive(wg, n_wg, s, &nv, scan_scratch);
-	if (rc != RNB_OK) return cleanup(rc);
-	if (nv && hipMalloc((void**)&verts, (size_t)nv * 12) != hipSuccess) return cleanup(fail(RNB_ERR_NOMEM, "hipMalloc failed for the vertices"));
+	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &nv, k_mc_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr); rc != RNB_OK) return rc;
+	if (nv && !ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the vertices");
 	hipLaunchKernelGGL(k_mc_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
-	hipLaunchKernelGGL(k_mc_faces<false>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, wg, (const uint32_t*)nullptr, vidx, (uint32_t*)nullptr);
-	rc = scan_exclusive(wg, n_wg, s, &ni, scan_scratch);
-	if (rc != RNB_OK) return cleanup(rc);
-	if (ni && hipMalloc((void**)&indices, (size_t)ni * 4) != hipSuccess) return cleanup(fail(RNB_ERR_NOMEM, "hipMalloc failed for the indices"));
-	hipLaunchKernelGGL(k_mc_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, vidx, indices);
-	if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return cleanup(fail(RNB_ERR_DEVICE, "rnb_marching_cubes: kernel failure"));
-	*verts_out = verts; *indices_out = indices; *n_verts = nv; *n_indices = ni;
-	return cleanup(RNB_OK);
+	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &ni, k_mc_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr); rc != RNB_OK) return rc;
+	if (ni && !ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the indices");
+	hipLaunchKernelGGL(k_mc_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
+	if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return fail(RNB_ERR_DEVICE, "rnb_marching_cubes: kernel failure");
+	*verts_out = (float*)ws.keep(verts); *indices_out = (uint32_t*)ws.keep(indices); *n_verts = nv; *n_indices = ni; // (null where the count is 0; the scratch goes with ws)
+	return RNB_OK;
 } RNB_GUARD
 
 int rnb_generate_training_samples(rnb_ctx* c, void* stream, uint32_t n_rays, uint32_t n_rays_total, uint32_t max_samples) try {
@@ -2726,36 +2777,7 @@ int rnb_mesh_free(rnb_ctx* c, rnb_mesh* m) try {
 	return RNB_OK;
 } RNB_GUARD
 
-extern "C++" {
-namespace {
 constexpr uint32_t MESH_DEFAULT_BRICK = 16; // measured against 32 (tools/bench_mesh.py, profiles/mesh_sparse.md): fewer points evaluated around the surface
-// The device memory of one rnb_extract_mesh call: what is still held when the object goes out of scope is released; bytes held now and at the peak.
-struct MeshWorkspace {
-	std::vector<std::pair<void*, size_t>> held;
-	size_t cur = 0, peak = 0;
-	template <typename T>
-	bool alloc(T** p, size_t count) {
-		*p = nullptr;
-		const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-		if (hipMalloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-		held.emplace_back((void*)*p, bytes);
-		cur += bytes; peak = std::max(peak, cur);
-		return true;
-	}
-	template <typename T>
-	void release(T*& p) { // free now
-		for (auto& h : held) if (h.first == (void*)p && p) { (void)hipFree(h.first); cur -= h.second; h.first = nullptr; }
-		p = nullptr;
-	}
-	void* keep(void* p) { // the caller owns it from here on (it still counts as held)
-		for (auto& h : held) if (h.first == p) h.first = nullptr;
-		return p;
-	}
-	~MeshWorkspace() { for (auto& h : held) if (h.first) (void)hipFree(h.first); }
-};
-} // namespace
-} // extern "C++"
-
 int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_mesh* out, rnb_mesh_stats* stats) try {
 	if (!c || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: null argument");
 	std::memset(out, 0, sizeof(*out));
@@ -2792,10 +2814,8 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 	if (!ws.alloc(&a.word, a.n_bricks) || !ws.alloc(&bwg, n_bwg) || !ws.alloc(&bscan, scan_scratch_elems(n_bwg))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick words");
 	hipLaunchKernelGGL(k_ms_classify, dim3((a.n_bricks + 3) / 4), dim3(256), 0, s, a, (double)opt->lattice_min, (double)opt->lattice_max - (double)opt->lattice_min,
 	                   opt->cull == RNB_MESH_CULL_OCCUPANCY ? (const uint8_t*)c->bitfield.p : (const uint8_t*)nullptr);
-	hipLaunchKernelGGL(k_ms_mark<false>, dim3(n_bwg), dim3(MC_WG), 0, s, a, bwg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-	HIP_TRY(hipGetLastError());
 	uint32_t n_eval = 0;
-	int rc = scan_exclusive(bwg, n_bwg, s, &n_eval, bscan);
+	int rc = count_and_scan(s, n_bwg, bwg, bscan, &n_eval, k_ms_mark<false>, a, bwg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
 	if (rc != RNB_OK) return rc;
 	if (!ws.alloc(&list, n_eval)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick list");
 	a.list = list;
@@ -2854,16 +2874,10 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 			a.alist = alist;
 			hipLaunchKernelGGL(k_ms_list, dim3((n_eval + 255) / 256), dim3(256), 0, s, n_eval, act, aoff, alist);
 			// 4. vertices, then triangles: count, scan, write (the dense path's scheme over the bricks' workgroups)
-			hipLaunchKernelGGL(k_ms_verts<false>, dim3(n_wg), dim3(MC_WG), 0, s, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr);
-			HIP_TRY(hipGetLastError());
-			rc = scan_exclusive(wg, n_wg, s, &nv, wscan);
-			if (rc != RNB_OK) return rc;
+			if ((rc = count_and_scan(s, n_wg, wg, wscan, &nv, k_ms_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
 			if (!ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
 			hipLaunchKernelGGL(k_ms_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
-			hipLaunchKernelGGL(k_ms_faces<false>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr);
-			HIP_TRY(hipGetLastError());
-			rc = scan_exclusive(wg, n_wg, s, &ni, wscan);
-			if (rc != RNB_OK) return rc;
+			if ((rc = count_and_scan(s, n_wg, wg, wscan, &ni, k_ms_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr)) != RNB_OK) return rc;
 			if (!ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
 			hipLaunchKernelGGL(k_ms_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
 			HIP_TRY(hipGetLastError());
@@ -2899,9 +2913,7 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 		ws.release(coords); ws.release(net);
 	}
 	HIP_TRY(hipStreamSynchronize(s));
-	out->verts = (float*)ws.keep(verts); out->indices = (uint32_t*)ws.keep(indices);
-	out->colors = (float*)ws.keep(colors); out->normals = (float*)ws.keep(normals);
-	out->n_verts = nv; out->n_indices = ni;
+	hand_over(ws, rnb_mesh{verts, indices, colors, normals, nv, ni}, out);
 	if (stats) {
 		std::memset(stats, 0, sizeof(*stats));
 		stats->n_bricks = a.n_bricks; stats->n_kept = n_kept; stats->n_evaluated = n_eval; stats->n_sign_change = n_act;
@@ -2933,14 +2945,11 @@ int rnb_mesh_clean_table_free(rnb_ctx* c, rnb_mesh_component* table) try {
 int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_clean_options* opt, rnb_mesh* out, rnb_mesh_component** table_dev, rnb_mesh_clean_stats* stats) try {
 	if (table_dev) *table_dev = nullptr;
 	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: null argument");
-	if (in == out) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: in and out must be different objects");
+	if (int rc = check_mesh_input("rnb_mesh_clean", in, out); rc != RNB_OK) return rc;
 	const rnb_mesh m = *in;
-	std::memset(out, 0, sizeof(*out));
 	if (opt->abi_version != RNB_MESH_CLEAN_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: options abi_version mismatch (expected RNB_MESH_CLEAN_ABI_VERSION)");
 	if (opt->keep != RNB_MESH_KEEP_ALL && opt->keep != RNB_MESH_KEEP_LARGEST) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown keep mode");
 	if (opt->orient != RNB_MESH_ORIENT_NONE && opt->orient != RNB_MESH_ORIENT_OUTWARD) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown orient mode");
-	if (m.n_indices % 3u) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: n_indices is not a multiple of 3");
-	if ((m.n_verts && !m.verts) || (m.n_indices && !m.indices)) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: null vertex or index buffer");
 	const auto t_begin = std::chrono::steady_clock::now();
 	hipStream_t s = as_stream(stream);
 	join_tail_host(c);
@@ -2949,14 +2958,12 @@ int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_
 	MeshWorkspace ws;
 	ClResult hres;
 	std::memset(&hres, 0, sizeof(hres));
-	hres.best = CL_NONE;
+	hres.best = MESH_NONE;
 	uint32_t n_comp = 0, nvo = 0, nto = 0;
 	rnb_mesh_component* table = nullptr;
-	float *overts = nullptr, *ocolors = nullptr, *onormals = nullptr;
-	uint32_t* oidx = nullptr;
+	rnb_mesh o;
 	if (nt) {
-		const uint32_t g_v = (nv + CL_WG - 1) / CL_WG, g_t = (nt + CL_WG - 1) / CL_WG; // nv >= 1 is checked right below (every index would be out of range)
-		if (nv == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: an index is out of range (the mesh has no vertices)");
+		const uint32_t g_v = (nv + CL_WG - 1) / CL_WG, g_t = (nt + CL_WG - 1) / CL_WG; // (nv >= 1: check_mesh_input)
 		uint32_t *parent = nullptr, *used = nullptr, *cid = nullptr, *scan = nullptr, *twg = nullptr, *cflags = nullptr;
 		ClResult* dres = nullptr;
 		if (!ws.alloc(&parent, nv) || !ws.alloc(&used, nv) || !ws.alloc(&cid, nv) || !ws.alloc(&twg, g_t) || !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) || !ws.alloc(&dres, 1))
@@ -2965,7 +2972,7 @@ int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_
 		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
 		// 1. every index is range-checked before any is used as an address
 		hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
-		hipLaunchKernelGGL(k_cl_validate, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, dres);
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, CL_BAD_INDEX);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
@@ -2996,29 +3003,21 @@ int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_
 		HIP_TRY(hipGetLastError());
 		rc = scan_exclusive(vmap, nv, s, &nvo, scan);
 		if (rc != RNB_OK) return rc;
-		hipLaunchKernelGGL(k_cl_tris<false>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-		HIP_TRY(hipGetLastError());
-		rc = scan_exclusive(twg, g_t, s, &nto, scan);
-		if (rc != RNB_OK) return rc;
-		if (!ws.alloc(&overts, (size_t)nvo * 3) || !ws.alloc(&oidx, (size_t)nto * 3) || (m.colors && !ws.alloc(&ocolors, (size_t)nvo * 3)) || (m.normals && !ws.alloc(&onormals, (size_t)nvo * 3)))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
-		hipLaunchKernelGGL(k_cl_verts, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, overts, ocolors, onormals);
-		hipLaunchKernelGGL(k_cl_tris<true>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, oidx);
+		if ((rc = count_and_scan(s, g_t, twg, scan, &nto, k_cl_tris<false>, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
+		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
+		hipLaunchKernelGGL(k_cl_verts, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, o.verts, o.colors, o.normals);
+		hipLaunchKernelGGL(k_cl_tris<true>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(s));
 		if (n_comp && hres.best < n_comp) { // the label of the selected component, for the statistics
-			uint32_t label = CL_NONE;
+			uint32_t label = MESH_NONE;
 			HIP_TRY(hipMemcpy(&label, &table[hres.best].label, 4, hipMemcpyDeviceToHost));
 			hres.best = label;
-		} else hres.best = CL_NONE;
+		} else hres.best = MESH_NONE;
 		ws.release(parent); ws.release(cid); ws.release(scan); ws.release(twg); ws.release(cflags); ws.release(dres);
-	} else {
-		if (!ws.alloc(&overts, 1) || !ws.alloc(&oidx, 1) || (m.colors && !ws.alloc(&ocolors, 1)) || (m.normals && !ws.alloc(&onormals, 1)) || (table_dev && !ws.alloc(&table, 1)))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
-	}
-	out->verts = (float*)ws.keep(overts); out->indices = (uint32_t*)ws.keep(oidx);
-	out->colors = (float*)ws.keep(ocolors); out->normals = (float*)ws.keep(onormals);
-	out->n_verts = nvo; out->n_indices = nto * 3u;
+	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr) || (table_dev && !ws.alloc(&table, 1)))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
+	hand_over(ws, o, out);
 	if (table_dev) *table_dev = (rnb_mesh_component*)ws.keep(table);
 	if (stats) {
 		std::memset(stats, 0, sizeof(*stats));
@@ -3048,9 +3047,8 @@ int rnb_mesh_simplify_default_options(rnb_mesh_simplify_options* opt) try {
 
 int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_simplify_options* opt, rnb_mesh* out, rnb_mesh_simplify_stats* stats) try {
 	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: null argument");
-	if (in == out) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: in and out must be different objects");
+	if (int rc = check_mesh_input("rnb_mesh_simplify", in, out); rc != RNB_OK) return rc;
 	const rnb_mesh m = *in;
-	std::memset(out, 0, sizeof(*out));
 	if (opt->abi_version != RNB_MESH_SIMPLIFY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: options abi_version mismatch (expected RNB_MESH_SIMPLIFY_ABI_VERSION)");
 	if (opt->placement != RNB_MESH_PLACE_QUADRIC && opt->placement != RNB_MESH_PLACE_MEAN) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: unknown placement");
 	if (!(opt->cell > 0.0f) || !std::isfinite(opt->cell)) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: cell must be finite and > 0");
@@ -3061,9 +3059,6 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 		n_cells *= opt->dims[k];
 	}
 	if (n_cells > RNB_MESH_SIMPLIFY_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims hold " + std::to_string(n_cells) + " cells, more than RNB_MESH_SIMPLIFY_MAX_CELLS (2^30)");
-	if (m.n_indices % 3u) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: n_indices is not a multiple of 3");
-	if ((m.n_verts && !m.verts) || (m.n_indices && !m.indices)) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: null vertex or index buffer");
-	if (m.n_indices && m.n_verts == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: an index is out of range (the mesh has no vertices)");
 	const auto t_begin = std::chrono::steady_clock::now();
 	hipStream_t s = as_stream(stream);
 	join_tail_host(c);
@@ -3073,8 +3068,7 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 	SpResult hres;
 	std::memset(&hres, 0, sizeof(hres));
 	uint32_t n_cl = 0, nvo = 0, nto = 0;
-	float *overts = nullptr, *ocolors = nullptr, *onormals = nullptr;
-	uint32_t* oidx = nullptr;
+	rnb_mesh o;
 	if (nt) {
 		SpGrid g;
 		for (int k = 0; k < 3; ++k) { g.origin[k] = (double)opt->origin[k]; g.dims[k] = opt->dims[k]; }
@@ -3091,7 +3085,7 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 		HIP_TRY(hipMemsetAsync(bits, 0, (size_t)n_words * 4, s));
 		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
 		// 1. every index is range-checked before any is used as an address; the occupied cells; cluster ids = ranks of the occupied keys
-		hipLaunchKernelGGL(k_sp_validate, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, dres);
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, SP_BAD_INDEX);
 		hipLaunchKernelGGL(k_sp_cells, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)used, vcl, bits, dres);
 		hipLaunchKernelGGL(k_sp_popc, dim3(g_w), dim3(SP_WG), 0, s, (const uint32_t*)bits, rank, n_words);
 		HIP_TRY(hipGetLastError());
@@ -3108,7 +3102,7 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 		HIP_TRY(hipMemsetAsync(cused, 0, std::max<size_t>(n_cl, 1) * 4, s));
 		hipLaunchKernelGGL(k_sp_members, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)bits, (const uint32_t*)rank, vcl, ckey, sums, dres);
 		hipLaunchKernelGGL(k_sp_quadric, dim3(g_t), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, sums, dres);
-		// 3. the surviving triangles and the clusters they use, numbered by prefix sums
+		// 3. the surviving triangles and the clusters they use, numbered by prefix sums (not count_and_scan: the count launch feeds two scans, the clusters' first)
 		hipLaunchKernelGGL(k_sp_tris<false>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, cused, (const uint32_t*)nullptr, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(cmap, cused, std::max<size_t>(n_cl, 1) * 4, hipMemcpyDeviceToDevice, s));
@@ -3120,22 +3114,17 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 		if (rc != RNB_OK) return rc;
 		ws.release(bits); ws.release(rank);
 		// 4. the output: one solve per cluster, the triangles in input order
-		if (!ws.alloc(&overts, (size_t)nvo * 3) || !ws.alloc(&oidx, (size_t)nto * 3) || (m.colors && !ws.alloc(&ocolors, (size_t)nvo * 3)) || (m.normals && !ws.alloc(&onormals, (size_t)nvo * 3)))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
+		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
 		hipLaunchKernelGGL(k_sp_solve, dim3((n_cl + SP_WG - 1) / SP_WG), dim3(SP_WG), 0, s, g, opt->placement, n_cl, (const long long*)sums, (const uint32_t*)ckey, (const uint32_t*)cused, (const uint32_t*)cmap,
-		                   overts, ocolors, onormals, dres);
-		hipLaunchKernelGGL(k_sp_tris<true>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, (uint32_t*)nullptr, (const uint32_t*)cmap, (uint32_t*)nullptr, (const uint32_t*)twg, oidx);
+		                   o.verts, o.colors, o.normals, dres);
+		hipLaunchKernelGGL(k_sp_tris<true>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, (uint32_t*)nullptr, (const uint32_t*)cmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		ws.release(vcl); ws.release(scan); ws.release(twg); ws.release(sums); ws.release(ckey); ws.release(cused); ws.release(cmap); ws.release(dres);
-	} else {
-		if (!ws.alloc(&overts, 1) || !ws.alloc(&oidx, 1) || (m.colors && !ws.alloc(&ocolors, 1)) || (m.normals && !ws.alloc(&onormals, 1)))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
-	}
-	out->verts = (float*)ws.keep(overts); out->indices = (uint32_t*)ws.keep(oidx);
-	out->colors = (float*)ws.keep(ocolors); out->normals = (float*)ws.keep(onormals);
-	out->n_verts = nvo; out->n_indices = nto * 3u;
+	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
+	hand_over(ws, o, out);
 	if (stats) {
 		std::memset(stats, 0, sizeof(*stats));
 		stats->n_verts_in = nv; stats->n_tris_in = nt; stats->n_clusters = n_cl; stats->n_verts_out = nvo; stats->n_tris_out = nto; stats->n_tris_collapsed = nt - nto;

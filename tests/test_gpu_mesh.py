@@ -39,6 +39,27 @@ def test_marching_cubes_equals_host_loop(gpu, shape):
         assert len(got_v) > 100
 
 
+def test_marching_cubes_of_a_lattice_without_a_surface(gpu):
+    """A 3 x 3 x 3 lattice wholly on one side of the threshold: RNB_OK, zero counts and NULL buffers. The (2, 2, 2) call that follows, one corner above the threshold,
+    returns the host loop's mesh: nothing of the empty call is left behind."""
+    import ctypes as C
+    from rnb_neus2_amd import _abi
+    mn, mx = (C.c_float * 3)(-1.0, 0.0, 2.0), (C.c_float * 3)(1.0, 3.0, 2.5)
+    for level in (-1.0, 1.0):  # all below, all above
+        ptr = gpu.upload(np.full((3, 3, 3), level, np.float32))
+        pv, pi, nv, ni = C.c_void_p(7), C.c_void_p(7), C.c_uint32(7), C.c_uint32(7)
+        rc = gpu.f.marching_cubes(gpu._h, None, C.c_void_p(ptr), (C.c_uint32 * 3)(3, 3, 3), mn, mx, 0.25, C.byref(pv), C.byref(pi), C.byref(nv), C.byref(ni))
+        gpu.device_free(ptr)
+        assert rc == _abi.OK and (nv.value, ni.value, pv.value, pi.value) == (0, 0, None, None)
+    density = np.zeros((2, 2, 2), np.float32)
+    density[1, 0, 1] = 1.0
+    want_v, want_i = mesh_checks.host_marching_cubes(density, 0.25, tuple(mn), tuple(mx))
+    ptr = gpu.upload(density)
+    got_v, got_i = gpu.marching_cubes(ptr, (2, 2, 2), tuple(mn), tuple(mx), 0.25)
+    gpu.device_free(ptr)
+    assert len(want_i) == 3 and np.array_equal(got_i, want_i) and np.array_equal(got_v.view(np.uint32), want_v.view(np.uint32))
+
+
 @pytest.mark.parametrize("shape", [(19, 23, 31), (12, 12, 12)])
 def test_marching_cubes_triangle_set_equals_the_numpy_statement(gpu, shape):
     """Parity with the reference's triangulation, pinned independently: the device extraction against tests/mc_numpy.py -- plain numpy

@@ -1,6 +1,6 @@
 """The mesh cleaner on the MI355X (include/rnb_mesh_clean.h) against the numpy statement of tests/mesh_clean_reference.py, bit for bit: vertices, indices, colours,
 normals, the component table and the counts of the statistics, on uploaded meshes (three spheres, thousands of components under a random numbering, a strip of 2^20
-triangles), under permutations of the triangles, on invalid input, on the mesh of a model, beside training, and through build/mesh."""
+triangles, strips laid out for the corners of the wavefront reduction), under permutations of the triangles, on invalid input, on the mesh of a model, beside training, and through build/mesh."""
 import ctypes as C
 import os
 import subprocess
@@ -92,6 +92,34 @@ def test_thousands_of_components_and_a_long_strip_under_random_numbering(ctx):
         got, want = _check(ctx, pv, pt.astype(np.uint32).ravel(), keep="all", orient="outward")
         assert got["stats"]["n_components"] == 1 and got["table"]["label"][0] == 0 and got["table"]["n_triangles"][0] == 1 << 20
         print("strip of 2^20 triangles, %s: %.2f ms" % (label, got["stats"]["ms"]))
+
+
+def _strips(sizes):
+    """Disjoint triangle strips of the given numbers of triangles, one component each, vertices and triangles numbered strip after strip: strip c has sizes[c] + 2
+    vertices zigzagging along x at height z = 0.1 * (c + 1), its rows 0.01 * (c + 1) apart (every component its own area)."""
+    v, t, base = [], [], 0
+    for c, n in enumerate(sizes):
+        k = np.arange(n + 2)
+        v.append(np.stack([0.002 * k, 0.01 * (c + 1) * (k % 2), np.full(n + 2, 0.1 * (c + 1))], 1))
+        t.append(base + np.stack([k[:-2], k[:-2] + 1, k[:-2] + 2], 1))
+        base += n + 2
+    return np.concatenate(v).astype(np.float32), np.concatenate(t)
+
+
+@pytest.mark.parametrize("sizes", [(256,), (64, 64, 64, 64), (10, 20, 30, 4), (10, 20, 14, 12, 8), (257,)])
+def test_wavefront_reduction_corners(ctx, sizes):
+    """What one 256-thread workgroup of k_cl_sums<true> (one triangle per lane, in input order) can meet: one component in all four wavefronts (one set of atomics from
+    LDS), a component per wavefront (four sets from LDS), exactly 4 components inside one wavefront (the last shuffle round), 5 inside one (the fifth falls back to one
+    set per lane), and 257 triangles (a tail workgroup with a single live lane). Each as built and with the triangles shuffled inside every wavefront, so that the lanes
+    of a group are not neighbours and the leader is not the first of its strip."""
+    v, t = _strips(sizes)
+    assert len(t) == sum(sizes)
+    rng = np.random.default_rng(len(sizes))
+    shuffled = np.concatenate([t[w:w + 64][rng.permutation(len(t[w:w + 64]))] for w in range(0, len(t), 64)])
+    for tris in (t, shuffled):
+        for keep in ("all", "largest"):
+            got, _ = _check(ctx, v, tris.astype(np.uint32).ravel(), keep=keep)
+            assert got["stats"]["n_components"] == len(sizes) and sorted(got["table"]["n_triangles"]) == sorted(sizes)
 
 
 def test_permuted_triangles_and_repeated_calls(ctx):

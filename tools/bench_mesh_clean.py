@@ -31,7 +31,7 @@ def kernel_bytes(nv, nt, nvo, nto, n_comp, attrs):
     as one pass over the array they gather from)."""
     return {
         "k_cl_init": 4 * nv,
-        "k_cl_validate": 12 * nt + 4 * nv,
+        "k_mesh_validate": 12 * nt + 4 * nv,
         "k_cl_hook": 12 * nt + 4 * nv,
         "k_cl_flatten": 8 * nv,
         "k_cl_roots": 12 * nv,

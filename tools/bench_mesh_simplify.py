@@ -30,7 +30,7 @@ def kernel_bytes(nv, nt, n_cells, n_cl, nvo, nto, attrs):
     atomics of the two accumulation kernels as one pass over the 152-byte cluster records)."""
     words = (n_cells + 31) // 32
     return {
-        "k_sp_validate": 12 * nt + 4 * nv,
+        "k_mesh_validate": 12 * nt + 4 * nv,
         "k_sp_cells": 4 * nv + 12 * nv * (1 + attrs) + 4 * nv + 4 * words,
         "k_sp_popc": 8 * words,
         "k_sp_members": 8 * nv + 12 * nv * (1 + attrs) + 8 * words + 4 * n_cl + 80 * n_cl,
