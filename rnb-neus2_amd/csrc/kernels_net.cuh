@@ -56,7 +56,7 @@ __device__ __forceinline__ void encode_all_lm(const LevelMeta* __restrict__ lm, 
 
 // The same encode with the gathers of DEPTH levels in flight (common.cuh: level_issue / level_consume). Levels [0, n_live) are encoded, the others give zeros
 // (grid.h:192-210); n_live is wave-uniform. Fully unrolled: the in-flight values live in registers v[l % DEPTH].
-template <bool GRAD, int DEPTH, int ND = 0>
+template <bool GRAD, int DEPTH>
 __device__ __forceinline__ void encode_all_pipelined(const LevelMeta* __restrict__ lm, const uint32_t n_levels, const uint32_t valid_level, const uint32_t* __restrict__ grid,
                                                      const float x, const float y, const float z, half_t (&feat)[28], float (&dydx)[GRAD ? 28 : 1][3]) {
 	const uint32_t n_live = min(n_levels, valid_level + 1u);
@@ -65,15 +65,14 @@ __device__ __forceinline__ void encode_all_pipelined(const LevelMeta* __restrict
 	// level's table instead (its values are dropped below) -- only before training step 660, when fewer than 14 levels are live.
 	const uint32_t last = n_live ? n_live - 1u : 0u;
 #pragma unroll
-	// ND: the first ND levels are dense (host-checked): their x-pairs travel in one gather (level_issue<true>); a slot whose level is not live yet gathers from a level in FRONT of it, which is dense too
-	for (uint32_t l = 0; l < (uint32_t)DEPTH; ++l) { if (l < (uint32_t)ND) level_issue<true>(lm, grid, min(l, last), x, y, z, v[l]); else level_issue<false>(lm, grid, min(l, last), x, y, z, v[l]); }
+	for (uint32_t l = 0; l < (uint32_t)DEPTH; ++l) level_issue(lm, grid, min(l, last), x, y, z, v[l]);
 #pragma unroll
 	for (uint32_t level = 0; level < 14; ++level) {
 		half_t f0, f1;
 		float d0[3], d1[3];
 		const bool live = level < n_live;
 		level_consume<GRAD>(lm, min(level, last), x, y, z, v[level % DEPTH], f0, f1, d0, d1);
-		if (level + DEPTH < 14) { if (level + DEPTH < (uint32_t)ND) level_issue<true>(lm, grid, min(level + (uint32_t)DEPTH, last), x, y, z, v[level % DEPTH]); else level_issue<false>(lm, grid, min(level + (uint32_t)DEPTH, last), x, y, z, v[level % DEPTH]); }
+		if (level + DEPTH < 14) level_issue(lm, grid, min(level + (uint32_t)DEPTH, last), x, y, z, v[level % DEPTH]);
 		feat[level * 2 + 0] = live ? f0 : (half_t)0.f;
 		feat[level * 2 + 1] = live ? f1 : (half_t)0.f;
 		if (GRAD) {
@@ -102,7 +101,6 @@ struct PointArgs {
 	int want_density;          // 0: sdf + bias, 1: density
 	float sdf_bias;
 	const uint32_t* range;     // optional (device): evaluate points range[0] .. range[1] - 1 of xyz / splat_idx instead of 0 .. n - 1 (k_shard_range; n bounds the launch)
-	uint32_t xcd;              // (round 6; RNB_POINT_XCD=0 for the A/B) workgroup b (XCD b % 8) walks the b % 8-th eighth of the tiles: cell-ordered points that are neighbours in space share one L2
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -147,7 +145,7 @@ __device__ __forceinline__ void poison_lds(char* smem_raw, const size_t bytes, c
 #endif
 }
 
-template <bool EMU, int PIPE_DEPTH = 0, int ND = 0>
+template <bool EMU, int DEPTH>
 __device__ __forceinline__ void point_query_chained_body(const GridMeta& G, const NetW& net, const PointArgs& a, const half_t* __restrict__ wimg, char* smem_raw, LevelMeta* lm) {
 	poison_lds(smem_raw, LDS_POINT2, threadIdx.x, WG);
 	half_t* wts = reinterpret_cast<half_t*>(smem_raw);
@@ -168,7 +166,8 @@ __device__ __forceinline__ void point_query_chained_body(const GridMeta& G, cons
 	if (a.range) { s_first = a.range[0]; s_end = min(a.range[1], a.n); }
 	const uint32_t n_tiles = (s_end - s_first + TILE - 1) / TILE;
 	const int r16 = lane & 15, hq = lane >> 4;
-	const bool by_xcd = a.xcd != 0u && (gridDim.x & 7u) == 0u;
+	// workgroup b (XCD b % 8) walks the b % 8-th eighth of the tiles: cell-ordered points that are neighbours in space share one L2 (286 -> 274 us per occupancy update)
+	const bool by_xcd = (gridDim.x & 7u) == 0u;
 	const uint32_t t8 = by_xcd ? (n_tiles + 7u) / 8u : n_tiles, t_base = by_xcd ? (blockIdx.x & 7u) * t8 : 0u, t_stop = min(n_tiles, t_base + t8);
 	const uint32_t t_stride = (by_xcd ? gridDim.x / 8u : gridDim.x) * WAVES_PER_WG;
 	for (uint32_t tile = t_base + (by_xcd ? blockIdx.x / 8u : blockIdx.x) * WAVES_PER_WG + wave; tile < t_stop; tile += t_stride) {
@@ -180,8 +179,7 @@ __device__ __forceinline__ void point_query_chained_body(const GridMeta& G, cons
 		if (valid && a.splat_idx) cell = a.splat_idx[s];
 		half_t feat[28];
 		float dummy[1][3];
-		if (PIPE_DEPTH) encode_all_pipelined<false, PIPE_DEPTH ? PIPE_DEPTH : 1, ND>(lm, n_levels, valid_level, net.grid, x, y, z, feat, dummy);
-		else encode_all_lm<false>(lm, n_levels, valid_level, net.grid, x, y, z, feat, dummy);
+		encode_all_pipelined<false, DEPTH>(lm, n_levels, valid_level, net.grid, x, y, z, feat, dummy);
 		write_sdf_in_row(X, lane, x, y, z, feat);
 		wave_lds_sync();
 		h8 bz[4][2];
@@ -208,34 +206,24 @@ __device__ __forceinline__ void point_query_chained_body(const GridMeta& G, cons
 		wave_lds_sync(); // X, Z are rewritten by the next tile
 	}
 }
-__global__ __launch_bounds__(WG, 4) void k_point_query_chained(const GridMeta G, const NetW net, const PointArgs a, const half_t* __restrict__ wimg) {
-	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	point_query_chained_body<false>(G, net, a, wimg, smem_raw, lm);
-}
-template <int DEPTH, int ND = 0>
+template <int DEPTH>
 __global__ __launch_bounds__(WG, 3) void k_point_query_chained_pipe(const GridMeta G, const NetW net, const PointArgs a, const half_t* __restrict__ wimg) {
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	point_query_chained_body<false, DEPTH, ND>(G, net, a, wimg, smem_raw, lm);
+	point_query_chained_body<false, DEPTH>(G, net, a, wimg, smem_raw, lm);
 }
 // rnb_config::accumulate = RNB_ACCUM_HALF: the reference's half accumulators (mlp.cuh, mfma_emul16)
-__global__ __launch_bounds__(WG, 2) void k_point_query_chained_emul(const GridMeta G, const NetW net, const PointArgs a, const half_t* __restrict__ wimg) {
-	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	point_query_chained_body<true>(G, net, a, wimg, smem_raw, lm);
-}
-template <int DEPTH, int ND = 0>
+template <int DEPTH>
 __global__ __launch_bounds__(WG, 2) void k_point_query_chained_emul_pipe(const GridMeta G, const NetW net, const PointArgs a, const half_t* __restrict__ wimg) {
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	point_query_chained_body<true, DEPTH, ND>(G, net, a, wimg, smem_raw, lm);
+	point_query_chained_body<true, DEPTH>(G, net, a, wimg, smem_raw, lm);
 }
 
 constexpr int FWD2_WAVE_HALFS = TILE * S32 + TILE * 8 + TILE;
 constexpr size_t LDS_FWD2 = (size_t)(W_FWD_END + WAVES_PER_WG * FWD2_WAVE_HALFS) * sizeof(half_t);
 
-template <bool EMU, int PIPE_DEPTH = 0, int ND = 0>
+template <bool EMU, int DEPTH>
 __device__ __forceinline__ void forward_chained_body(const GridMeta& G, const NetW& net, const FwdArgs& a, char* smem_raw, LevelMeta* lm) {
 	poison_lds(smem_raw, LDS_FWD2, threadIdx.x, WG);
 	half_t* wts = reinterpret_cast<half_t*>(smem_raw);
@@ -266,8 +254,7 @@ __device__ __forceinline__ void forward_chained_body(const GridMeta& G, const Ne
 		}
 		half_t feat[28];
 		float dydx[28][3];
-		if (PIPE_DEPTH) encode_all_pipelined<true, PIPE_DEPTH ? PIPE_DEPTH : 1, ND>(lm, n_levels, valid_level, net.grid, c[0], c[1], c[2], feat, dydx);
-		else encode_all_lm<true>(lm, n_levels, valid_level, net.grid, c[0], c[1], c[2], feat, dydx);
+		encode_all_pipelined<true, DEPTH>(lm, n_levels, valid_level, net.grid, c[0], c[1], c[2], feat, dydx);
 		write_sdf_in_row(X, lane, c[0], c[1], c[2], feat);
 		wave_lds_sync();
 		// z1 = relu(W0 sdf_in) (registers) ; dz1 = W1[0,:] (.) relu'(z1) (registers)   (nerf_network.h:159-176)
@@ -389,28 +376,18 @@ __device__ __forceinline__ void forward_chained_body(const GridMeta& G, const Ne
 		wave_lds_sync();
 	}
 }
-__global__ __launch_bounds__(WG, 2) void k_forward_chained(const GridMeta G, const NetW net, const FwdArgs a) {
-	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	forward_chained_body<false>(G, net, a, smem_raw, lm);
-}
-template <int DEPTH, int ND = 0>
+template <int DEPTH>
 __global__ __launch_bounds__(WG, 2) void k_forward_chained_pipe(const GridMeta G, const NetW net, const FwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	forward_chained_body<false, DEPTH, ND>(G, net, a, smem_raw, lm);
+	forward_chained_body<false, DEPTH>(G, net, a, smem_raw, lm);
 }
 // rnb_config::accumulate = RNB_ACCUM_HALF: the reference's half accumulators (mlp.cuh, mfma_emul16)
-__global__ __launch_bounds__(WG, 2) void k_forward_chained_emul(const GridMeta G, const NetW net, const FwdArgs a) {
-	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	forward_chained_body<true>(G, net, a, smem_raw, lm);
-}
-template <int DEPTH, int ND = 0>
+template <int DEPTH>
 __global__ __launch_bounds__(WG, 2) void k_forward_chained_emul_pipe(const GridMeta G, const NetW net, const FwdArgs a) {
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
-	forward_chained_body<true, DEPTH, ND>(G, net, a, smem_raw, lm);
+	forward_chained_body<true, DEPTH>(G, net, a, smem_raw, lm);
 }
 
 
@@ -1788,13 +1765,7 @@ struct ScatterArgs {
 	float* grid_grad;    // GRADS_FP32 + off_grid
 	uint32_t* grid_grad16; // rnb_config::accumulate = RNB_ACCUM_HALF: GRADS_FP16 + off_grid, one half2 per table entry (the reference's gradient vector, trainer.h:78-84)
 	unsigned long long* grid_fixed; // rnb_config::deterministic: [n_grid_params] 64-bit fixed-point accumulators (scale 2^24), narrowed into the gradient vector by k_fixed_narrow
-	uint32_t prio;                  // RNB_SCATTER_PRIO (A/B, round 6): the scatter's wavefronts raise their issue priority (s_setprio) above the side streams' kernels that share their SIMDs
 };
-__device__ __forceinline__ void scatter_prio(const uint32_t prio) {
-	if (prio == 1u) __builtin_amdgcn_s_setprio(1);
-	else if (prio == 2u) __builtin_amdgcn_s_setprio(2);
-	else if (prio >= 3u) __builtin_amdgcn_s_setprio(3);
-}
 
 // rnb_config::deterministic. An addend of the scatter is a half value (grid.h:415-416: the reference narrows every addend to half before its atomicAdd), i.e. an integer
 // multiple of 2^-24 below 2^16 in magnitude: times 2^24 it is an integer below 2^40, exact in fp32 and in a 64-bit integer. Integer additions commute, so a sum of such
@@ -1881,7 +1852,6 @@ struct ScatterLdsArgs { ScatterArgs a; uint32_t n_levels; uint32_t samples_per_w
 // LDS layout: level l's table at float offset 2 * G.offsets[l]. The per-sample loads of a walk are issued four samples ahead.
 template <bool HALF>
 __device__ __forceinline__ void grid_scatter_lds_body(const GridMeta& G, const ScatterLdsArgs& p) {
-	scatter_prio(p.a.prio);
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	float* tab = reinterpret_cast<float*>(smem_raw);
 	const ScatterArgs& a = p.a;
@@ -1972,7 +1942,6 @@ __global__ __launch_bounds__(512) void k_grid_scatter_lds_h(const GridMeta G, co
 // wavefront only takes a slot from the kernels of the side streams (march, optimizer chunks), which were starved beside the scatter
 // (k_march_write 48 -> 186 us beside the one-shot grid of 65 k wavefronts, profiles/r03_*).
 __global__ __launch_bounds__(256) void k_grid_scatter_quad(const GridMeta G, const ScatterArgs a, const uint32_t level0, const uint32_t n_vblocks) {
-	scatter_prio(a.prio);
 	const uint32_t level = blockIdx.y + level0;
 	if (level > G.valid_level) return;
 	float* gg = a.grid_grad + (size_t)G.offsets[level] * 2;
@@ -2086,7 +2055,6 @@ struct ScatterRlPlan { uint32_t n; uint32_t wg_start[17]; uint64_t k_log2; };
 // HALF (rnb_config::accumulate = RNB_ACCUM_HALF): lanes (dx, dy), registers (dz, feature), packed half atomics (see k_grid_scatter_quad_h); a run is still summed in fp32.
 template <bool HALF, bool SHARE = false>
 __device__ __forceinline__ void grid_scatter_quad_rl_body(const GridMeta& G, const ScatterArgs& a, const uint32_t level0, const ScatterRlPlan& plan) {
-	scatter_prio(a.prio);
 #pragma unroll 1
 	for (uint32_t vb = blockIdx.x; vb < plan.wg_start[plan.n]; vb += gridDim.x) { // virtual workgroups (see k_grid_scatter_quad)
 		uint32_t li = 0;
@@ -2192,7 +2160,6 @@ constexpr uint32_t RL_MAX_K = 16;
 constexpr size_t LDS_SCATTER_RL = (size_t)RL_MAX_K * 64 * 32; // 16 B {x y z dn0} + 8 B {dn1 dn2} + 8 B g12 per sample
 template <bool HALF, bool SHARE = false>
 __device__ __forceinline__ void grid_scatter_quad_rl_staged_body(const GridMeta& G, const ScatterArgs& a, const uint32_t level0, const ScatterRlPlan& plan) {
-	scatter_prio(a.prio);
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	f4* sA = reinterpret_cast<f4*>(smem_raw);                                  // [K * 64] x y z dn0
 	float2* sB = reinterpret_cast<float2*>(smem_raw + (size_t)RL_MAX_K * 64 * 16); // [K * 64] dn1 dn2
@@ -2296,12 +2263,10 @@ __device__ __forceinline__ void grid_scatter_quad_rl_staged_body(const GridMeta&
 		if (n_mine) flush();
 	}
 }
-__global__ __launch_bounds__(256) void k_grid_scatter_quad_rl(const GridMeta G, const ScatterArgs a, const uint32_t level0, const ScatterRlPlan plan) { grid_scatter_quad_rl_staged_body<false>(G, a, level0, plan); }
 __global__ __launch_bounds__(256) void k_grid_scatter_quad_rl_h(const GridMeta G, const ScatterArgs a, const uint32_t level0, const ScatterRlPlan plan) { grid_scatter_quad_rl_staged_body<true>(G, a, level0, plan); }
-// RNB_SCATTER_RL_STAGED=0 (A/B): the walk with its operands loaded from global memory four samples ahead (rounds 2-4)
-__global__ __launch_bounds__(256) void k_grid_scatter_quad_rl_direct(const GridMeta G, const ScatterArgs a, const uint32_t level0, const ScatterRlPlan plan) { grid_scatter_quad_rl_body<false>(G, a, level0, plan); }
+// large batches: the walk with its operands loaded from global memory four samples ahead (rounds 2-4)
 __global__ __launch_bounds__(256) void k_grid_scatter_quad_rl_direct_h(const GridMeta G, const ScatterArgs a, const uint32_t level0, const ScatterRlPlan plan) { grid_scatter_quad_rl_body<true>(G, a, level0, plan); }
-// face sharing (round 6, RNB_SCATTER_SHARE)
+// fp32 accumulate mode: the two forms with face sharing (round 6)
 __global__ __launch_bounds__(256) void k_grid_scatter_quad_rl_share(const GridMeta G, const ScatterArgs a, const uint32_t level0, const ScatterRlPlan plan) { grid_scatter_quad_rl_staged_body<false, true>(G, a, level0, plan); }
 __global__ __launch_bounds__(256) void k_grid_scatter_quad_rl_direct_share(const GridMeta G, const ScatterArgs a, const uint32_t level0, const ScatterRlPlan plan) { grid_scatter_quad_rl_body<false, true>(G, a, level0, plan); }
 

@@ -100,17 +100,8 @@ __global__ void k_shard_range(const uint32_t* __restrict__ ends, const uint32_t 
 	out[threadIdx.x] = v;
 }
 
-// ema_grid_samples_nerf (testbed_nerf.cu:655-685)
-__global__ void k_ema_grid(const uint32_t n_elements, const float decay, float* __restrict__ grid_out, const float* __restrict__ grid_in) {
-	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
-	if (i >= n_elements) return;
-	const float importance = grid_in[i];
-	const float prev_val = grid_out[i];
-	grid_out[i] = (prev_val < 0.f) ? prev_val : fmaxf(prev_val * decay, importance);
-}
-
-// k_ema_grid + k_mean_partial in one launch (round 4: an occupancy update is a chain of small dependent launches on the critical path of every 16th
-// step, ~5 us each). Block b owns cells [2048 b, 2048 (b + 1)): the update of k_ema_grid, and -- for the blocks of the first mip -- k_mean_partial's
+// ema_grid_samples_nerf (testbed_nerf.cu:655-685) + k_mean_partial in one launch (round 4: an occupancy update is a chain of small dependent launches on the critical path of every 16th
+// step, ~5 us each). Block b owns cells [2048 b, 2048 (b + 1)): the exponential-moving-average update of its cells, and -- for the blocks of the first mip -- k_mean_partial's
 // sum of exactly those cells in exactly its order (thread t: cells t, t + 256, ...; the same tree), so `partial` holds the same 1024 doubles.
 __global__ __launch_bounds__(256) void k_ema_mean(const uint32_t n_elements, const float decay, float* __restrict__ grid_out, const float* __restrict__ grid_in, double* __restrict__ partial) {
 	__shared__ double sh[256];
@@ -467,13 +458,11 @@ struct MarchArgs {
 	uint32_t k1;        // 0 = single round
 	uint32_t part;      // k_march_write: 0 = everything; 1 = what the first network evaluation reads (idx1, the coordinates of the heads); 2 = the rest
 	// per-ray loss constants (target colour, light, masks) depend on the ray and the dataset only: worked out here, off the
-	// step's critical path, for the loss passes to pick up (k_march_write -> k_loss_pass1)
+	// step's critical path, for the loss passes to pick up (k_ray_constants -> k_loss_pass1)
 	LossFlags F;
 	float light_dirs[9];
-	float* ray_const;   // [n_rays kept][RAY_CONST_FLOATS]
 	// outputs
 	uint32_t* ray_indices; float* rays; uint32_t* numsteps; float* coords; uint32_t* counters;
-	uint32_t prio;             // RNB_MARCH_PRIO (A/B): s_setprio of the march kernels' wavefronts
 	uint32_t use_bbox;         // RNB_MARCH_BBOX (round 6): 0 off; 1 (default): the thread-per-ray march ends where the ray leaves the bounding box of the non-empty blocks; 2: + one jump to that box's entry (k_march_count_bbox)
 	unsigned long long* stats; // RNB_MARCH_STATS=1 (measurement aid, k_march_count_skip): [0] wavefronts, [1] loop iterations, [2] rays, [3] rays that skipped, [4] start-overs, [5] rounds spent looking for a re-entry cell, [6] rays ended early
 };
@@ -506,8 +495,7 @@ __device__ __forceinline__ uint32_t march(const SceneAabb& A, const uint8_t* __r
 }
 
 template <bool SC>
-__global__ __launch_bounds__(512) void k_march_count(const MarchArgs a) { // (launched with 128 ... 512 threads: RNB_MARCH_NARROW_WGS)
-	if (a.prio == 1u) __builtin_amdgcn_s_setprio(1); else if (a.prio == 2u) __builtin_amdgcn_s_setprio(2); else if (a.prio >= 3u) __builtin_amdgcn_s_setprio(3);
+__global__ __launch_bounds__(512) void k_march_count(const MarchArgs a) { // (launched with 128 threads; the bound admits up to 512)
 	extern __shared__ __attribute__((aligned(16))) uint32_t coarse_lds[];
 	if (SC) { load_coarse(coarse_lds, a.coarse, a.n_blocks_lds, threadIdx.x, blockDim.x); __syncthreads(); }
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
@@ -780,7 +768,6 @@ __device__ __forceinline__ float lattice_advance(float t, int n) { // t_{k+n} of
 
 template <int WGS = 256>
 __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
-	if (a.prio == 1u) __builtin_amdgcn_s_setprio(1); else if (a.prio == 2u) __builtin_amdgcn_s_setprio(2); else if (a.prio >= 3u) __builtin_amdgcn_s_setprio(3);
 	constexpr int MG = 16;
 	constexpr bool SC = true;
 	extern __shared__ __attribute__((aligned(16))) uint32_t coarse_lds[];
@@ -1446,15 +1433,11 @@ struct ScanChainArgs {
 	unsigned long long* words2; // [n_tiles][4]: ticket << 32 | {kept rays, kept samples, kept first-round samples}: tiles at and behind an overflow of max_samples only
 	uint32_t ticket;
 	uint32_t* error; // mapped host word: a wait gave up
-	uint32_t plain;  // RNB_CHAIN_PLAIN (round 6): the tiles' words travel as agent-scope atomic STORES and LOADS (sc1: served at the memory side, seen by every XCD) instead of read-modify-write
-	                 // atomics, which queue behind the gradient scatter's backlog of atomics there
 };
-__device__ __forceinline__ void chain_put(unsigned long long* p, const unsigned long long v, const bool plain) {
-	if (plain) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else atomicExch(p, v);
-}
-__device__ __forceinline__ unsigned long long chain_get(unsigned long long* p, const bool plain) {
-	return plain ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : atomicAdd(p, 0ull);
-}
+// k_scan_rays_chain's tiles exchange their words by agent-scope atomic STORES and LOADS (sc1: served at the memory side, seen by every XCD), not by read-modify-write
+// atomics, which queue behind the gradient scatter's backlog of atomics there (profiles/r06_ab_chain_plain.txt)
+__device__ __forceinline__ void chain_put(unsigned long long* p, const unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned long long chain_get(unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // `bad` (in/out, uniform over the workgroup): a wait of this tile or of a tile in front of it gave up. The HIP programming model does not promise that
 // lower-numbered workgroups are scheduled first (they are on this hardware, one dispatcher per queue handing out workgroups in order), so the
 // spin is bounded; a tile that gives up would otherwise go on with a stale word of an earlier launch. Instead it marks the word it publishes
@@ -1506,14 +1489,14 @@ __global__ __launch_bounds__(SCAN_WG) void k_scan_rays_chain(const ScanChainArgs
 	uint32_t e2 = block_exclusive_scan<SCAN_NW>(f1, lane, wave, wsum, t_f1);
 	// exchange A (wavefront 0: lane q polls tile q < tile)
 	uint32_t fa[3] = {0, 0, 0}, incl_front = 0, flagA = 0; // wavefront 0 keeps the front tiles' sums for exchange B
-	if (tid < 3) chain_put(a.words + tile * 4 + tid, ((unsigned long long)a.ticket << 32) | (tid == 0 ? total : tid == 1 ? t_pos : t_f1), a.plain != 0u);
+	if (tid < 3) chain_put(a.words + tile * 4 + tid, ((unsigned long long)a.ticket << 32) | (tid == 0 ? total : tid == 1 ? t_pos : t_f1));
 	if (tid < 64) {
 		if (tid < tile) {
 			unsigned long long w0, w1, w2;
 			uint32_t spins = 0;
 			bool got;
 			do {
-				w0 = chain_get(a.words + tid * 4 + 0, a.plain != 0u); w1 = chain_get(a.words + tid * 4 + 1, a.plain != 0u); w2 = chain_get(a.words + tid * 4 + 2, a.plain != 0u);
+				w0 = chain_get(a.words + tid * 4 + 0); w1 = chain_get(a.words + tid * 4 + 1); w2 = chain_get(a.words + tid * 4 + 2);
 				got = (uint32_t)(w0 >> 32) == a.ticket && (uint32_t)(w1 >> 32) == a.ticket && (uint32_t)(w2 >> 32) == a.ticket;
 				if (got) break;
 				__builtin_amdgcn_s_sleep(2);
@@ -1552,7 +1535,7 @@ __global__ __launch_bounds__(SCAN_WG) void k_scan_rays_chain(const ScanChainArgs
 		e0 = block_exclusive_scan<SCAN_NW>(v[0], lane, wave, wsum, t0);
 		e2 = block_exclusive_scan<SCAN_NW>(v[2], lane, wave, wsum, t2);
 		(void)block_exclusive_scan<SCAN_NW>(v[1], lane, wave, wsum, t1);
-		if (tid < 3) chain_put(a.words2 + tile * 4 + tid, ((unsigned long long)a.ticket << 32) | (tid == 0 ? (t0 | (bad ? CHAIN_POISON : 0u)) : tid == 1 ? t1 : t2), a.plain != 0u);
+		if (tid < 3) chain_put(a.words2 + tile * 4 + tid, ((unsigned long long)a.ticket << 32) | (tid == 0 ? (t0 | (bad ? CHAIN_POISON : 0u)) : tid == 1 ? t1 : t2));
 		if (tid < 64) {
 			uint32_t fb[3] = {fa[1], fa[0], fa[2]}, fl = 0; // a tile in front of the overflow: all of its rays with samples are kept
 			if (tid < tile && incl_front > a.max_samples) {
@@ -1560,7 +1543,7 @@ __global__ __launch_bounds__(SCAN_WG) void k_scan_rays_chain(const ScanChainArgs
 				uint32_t spins = 0;
 				bool got;
 				do {
-					w0 = chain_get(a.words2 + tid * 4 + 0, a.plain != 0u); w1 = chain_get(a.words2 + tid * 4 + 1, a.plain != 0u); w2 = chain_get(a.words2 + tid * 4 + 2, a.plain != 0u);
+					w0 = chain_get(a.words2 + tid * 4 + 0); w1 = chain_get(a.words2 + tid * 4 + 1); w2 = chain_get(a.words2 + tid * 4 + 2);
 					got = (uint32_t)(w0 >> 32) == a.ticket && (uint32_t)(w1 >> 32) == a.ticket && (uint32_t)(w2 >> 32) == a.ticket;
 					if (got) break;
 					__builtin_amdgcn_s_sleep(2);
@@ -1821,32 +1804,13 @@ __device__ __forceinline__ void ray_constants(const LossArgs& a, const uint32_t 
 // recorded by the counting pass into NerfCoordinates (pos = o + t*dir is the same expression the march evaluated).
 // LR lanes per ray: 64 while rays are few and long (early training: ~30 marched samples per ray), 16 once the batch has grown
 // to ~100 k rays with ~8 samples each (a wavefront per ray would leave 7 of 8 lanes idle).
-// The per-ray constants of the loss (pixel fetches, two RNG jumps, sRGB, the light triplet: ~2000 instructions) are worked out by
-// ONE thread per ray -- the first WGS / LR threads of the workgroup, one for each of its rays -- and not by every
-// lane of the ray's group (that was most of this kernel: 65 -> see DESIGN.md section 6).
+// The per-ray constants of the loss (pixel fetches, two RNG jumps, sRGB, the light triplet: ~2000 instructions) are k_ray_constants' work, one thread per kept ray, behind this kernel.
 // WGS (round 6): 256 threads per workgroup. The 1024 of rounds 2-5 dated from the per-ray constants living here; a 16-wavefront workgroup waits for 16 wave slots to fall free at
 // once beside the gradient scatter's short workgroups -- 13 us of writing took 60-160 us there (profiles/r06_timeline_*), as k_dw_finish had in round 4. No barrier, no LDS: any size gives the same stores.
 template <int LR, int WGS = 256>
 __global__ __launch_bounds__(WGS) void k_march_write(const MarchArgs a) {
 	constexpr uint32_t RAYS = WGS / LR;
 	const bool head = a.part != 2, rest = a.part != 1;
-	if (a.ray_const && rest && threadIdx.x < RAYS) { // thread t: the constants of the workgroup's ray t
-		const uint32_t i = blockIdx.x * RAYS + threadIdx.x;
-		const uint32_t s = i < a.n_rays ? a.slot[i] : 0xffffffffu;
-		if (s != 0xffffffffu) {
-			RayConstIn in;
-			in.rng = a.rng; in.ray_offset = a.ray_offset; in.n_rays_global = a.n_rays_global; in.n_rays_total = a.n_rays_total; in.n_images = a.n_images;
-			in.views = a.views; in.F = a.F; in.light_dirs = a.light_dirs;
-			struct { float rgbtarget[4], light[3], mask_certainty, mask_gt; } rc;
-			ray_constants_core(in, i, rc);
-			float* q = a.ray_const + (size_t)s * RAY_CONST_FLOATS;
-#pragma unroll
-			for (int k = 0; k < 4; ++k) q[k] = rc.rgbtarget[k];
-#pragma unroll
-			for (int k = 0; k < 3; ++k) q[4 + k] = rc.light[k];
-			q[7] = rc.mask_certainty; q[8] = rc.mask_gt;
-		}
-	}
 	const uint32_t i = blockIdx.x * RAYS + threadIdx.x / LR;
 	const uint32_t lane = threadIdx.x & (LR - 1);
 	if (i >= a.n_rays) return;
@@ -1885,8 +1849,8 @@ __global__ __launch_bounds__(WGS) void k_march_write(const MarchArgs a) {
 }
 
 
-// The per-ray constants of the loss as a launch of their own, one thread per KEPT ray (round 4). Inside k_march_write the first RAYS threads of a 1024-thread
-// workgroup work them out (~2000 dependent instructions, pixel fetches) while its other wavefronts have long finished: the workgroup holds its slots for that
+// The per-ray constants of the loss as a launch of their own, one thread per KEPT ray (round 4). Inside k_march_write (rounds 2-4) the first RAYS threads of a 1024-thread
+// workgroup worked them out (~2000 dependent instructions, pixel fetches) while its other wavefronts had long finished: the workgroup held its slots for that
 // chain, and the kernel took 50-80 us beside the optimizer for 15-30 us of writing. Needs RAY_INDICES (k_march_write).
 __global__ __launch_bounds__(64) void k_ray_constants(const MarchArgs a, float* __restrict__ ray_const) {
 	const uint32_t s = blockIdx.x * 64 + threadIdx.x;

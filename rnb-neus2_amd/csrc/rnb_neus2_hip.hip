@@ -19,7 +19,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <limits>
 #include <new>
 #include <stdexcept>
@@ -121,7 +120,6 @@ struct rnb_ctx {
 	Profiler prof;
 	GridMeta grid;
 	uint64_t n_grid_params = 0, n_params = 0;
-	uint32_t n_dense_lead = 0; // build_grid_tables
 	uint64_t off_sdf = 0, off_rgb = 0, off_grid = 0, off_var = 0;
 	SceneAabb aabb;
 	int n_cus = 256;
@@ -199,84 +197,25 @@ struct rnb_ctx {
 	DevBuf<uint32_t> unfinished;
 	uint32_t fwd_k1 = 48;      // head length of the two-round network evaluation (0 = one round); the longest head of the adaptive rule
 	bool fwd_k1_fixed = false; // RNB_FWD_K1: that value for every step
-	bool gen_split = false; // the last generated batch wrote its sample records in two launches (knobs.march_write_split)
+	bool gen_split = false; // the last generated batch wrote its sample records in two launches (generate_training_samples)
 	uint32_t gen_k1 = 0, cur_k1 = 0; // head length the last generated batch / the running step was laid out with (k1_for)
-	// Tuning / A-B knobs, read from the environment once at creation (measurement aids, not part of the interface).
+	// Comparator and diagnostic knobs, read from the environment once at creation (README.md lists them; the tests and the A/B tools set them, nothing else does).
 	struct Knobs {
-		bool march_narrow = false, fwd_bwd_generic = false, loss_wave_per_ray = false;
-		// RNB_SCATTER_WG_PER_CU: resident workgroups of the atomic scatter kernels per CU (0 = one workgroup per 64 samples, round 2's launch). Default
-		// by mode, measured in round 3 (window, ms/step): --no-albedo 0: 0.650, 2: 0.666, 4: 0.667, 8: 0.664; albedo 0: 0.826, 2: 0.796, 4: 0.808, 8: 0.828
-		// (there the weight-gradient GEMMs of the side stream are the long pole and need the wave slots)
-		int scatter_wg_per_cu = -1;
-		uint32_t fbs_wg_per_cu = 2; // RNB_FBS_WG_PER_CU: workgroups of k_fwd_bwd_sdf per CU (its launch bounds allow two)
-		bool march_running_sums = false; // RNB_MARCH_RUNNING_SUMS: the 16-lanes-per-ray march with the 16 running sums per round everywhere (round 2), no closed form
-		bool march_late = false; // RNB_MARCH_LATE: the next step's march waits for k_fwd_bwd instead of starting after the loss pass
-		uint32_t march_narrow_from = 18432; // rays per step from which the per-ray kernels switch to their large-batch forms (RNB_MARCH_NARROW_FROM). ms/step small / large forms, end of round 2: 16.2 k rays 0.697 / 0.707, 19.1 k 0.713 / 0.704, 22.3 k 0.740 / 0.710
-		bool dp_order = false; // scatter order of the data-parallel exchange even with one rank (RNB_DP_FORCE_COLLECTIVES)
-		bool scan_chain = true; // RNB_SCAN_CHAIN=0: the ray scans as in rounds 1-3 (one 1024-thread workgroup for small batches, three tiled launches for large ones)
-		uint32_t march_wave_per_ray_below = 4096; // RNB_MARCH_WAVE_PER_RAY_BELOW=n: one wavefront per ray for batches of at most n rays (single-cascade scenes). At an eighth of the batch
-		                                          // (1.8 k rays per step): 0.2985 -> 0.2890 ms/step with 4096 (2560: 0.2887); bit-exact at every size (the full-size tests were run with n = 100 000)
-		int scatter_order = -1; // RNB_SCATTER_ORDER: 0 = B, A1, A2, C (rounds 1-3); 1 = A1, A2, B, C; 2 = A (one launch), B, C; default: 2 below march_narrow_from rays per step, 0 from there on
-		bool scatter_c_side = false; // RNB_SCATTER_C_SIDE=1 (A/B, round 6): rnb_ctx::sc.c_side -- group C and its optimizer chunk at the end of the weight-gradient stream instead of last on the critical stream. Late 0.6040 -> 0.5991,
-		                             // but steps 1000-1200 0.5617 -> 0.5802, window 0.5483 -> 0.5589: an event that crosses streams costs ~16 us from the producer's end to the consumer's start however idle the
-		                             // consumer's queue has been (C starts 16 us behind group B and takes 62 instead of 37 us beside the optimizer's chunk; the evaluation still starts 16 us behind the last event):
-		                             // profiles/r06_ab_c_side.txt. Off.
-		bool unsafe_skip_joins = false; // RNB_UNSAFE_SKIP_JOINS=1: MEASUREMENT ONLY (the results are then unordered): the critical stream waits for none of the side streams in front of the network evaluation --
-		                                // what the three barrier packets cost
-		bool join_fold = false; // RNB_JOIN_FOLD=1 (A/B, round 6): rnb_ctx::join_pending -- one event in front of the network evaluation instead of three. SLOWER: window 0.5470 -> 0.5553, late 0.6022 -> 0.6065
-		                        // (the packets whose events are long signalled cost the critical stream little; the folded event arrives two hops later): profiles/r06_ab_join_fold.txt. Off.
-		bool defer_tail = true; // RNB_DEFER_TAIL=0: the critical stream itself waits for the side stream's weight images at the end of the optimizer (rounds 1-3)
-		bool poll_loss = true; // RNB_POLL_LOSS=0: the host waits for the completion event of k_reduce_losses_rollover (rounds 1-3) instead of polling the readback's sequence word
-		bool fused_update = true; // RNB_FUSED_UPDATE=0: the occupancy update's grid / bitfield chain as the seven launches of rounds 1-3 (k_ema_grid, k_mean_*, k_grid_to_bitfield, pools, k_coarse_bitfield)
+		bool march_narrow = false, fwd_bwd_generic = false, loss_wave_per_ray = false; // RNB_MARCH_NARROW, RNB_FWD_BWD_GENERIC, RNB_LOSS_WAVE_PER_RAY: the large-batch march / the generic training kernel / one wavefront per ray in the loss passes, whatever the batch
+		uint32_t march_narrow_from = 18432; // RNB_MARCH_NARROW_FROM: rays per step from which the per-ray kernels switch to their large-batch forms
+		bool dp_order = false; // RNB_DP_FORCE_COLLECTIVES: scatter order of the data-parallel exchange even with one rank
 		bool loss_scan_fused_always = false; // RNB_LOSS_SCAN_FUSED=2 (tests): at every batch size
 		bool loss_scan_fused = true; // RNB_LOSS_SCAN_FUSED=0: the compaction offsets by k_scan_compact* in front of the two pass-2 launches (default: formed inside k_loss_pass2_rays)
 		bool loss_flat = true; // RNB_LOSS_FLAT=0: pass 2 of the loss as one launch with 64 / 16 lanes per ray (default: k_loss_pass2_rays, then k_loss_pass2_samples with one lane per compacted sample; needs the chain records)
-		bool loss_chain_records = true; // RNB_LOSS_CHAIN_RECORDS=0: pass 2 of the loss replays the compositing recurrence itself (rounds 1-3) instead of reading the running values pass 1 left
-		int ray_const_dense = 2; // RNB_RAY_CONST_DENSE=0: the loss's per-ray constants inside k_march_write (rounds 2-4); 1: k_ray_constants (one thread per kept ray) behind a k_march_write that is never split;
-		                         // 2 (default): behind k_march_write split as before. ms/step at steps 1000 / 2000 / 6000: 0: 0.6019 / 0.5884 / 0.6292, 1: 0.6088 / 0.5954 / 0.6269, 2: 0.5999 / 0.5877 / (= 1)
-		int march_write_split = -1; // RNB_MARCH_WRITE_SPLIT=0|1: k_march_write of a march generated ahead as one launch (rounds 1-3) / always split; default: split below 65 536 rays per step. Split: what the first network evaluation reads (idx1, the heads'
-		                               // coordinates) in a first launch, whose completion the critical stream waits for; the rest (ray constants, ray records, the tails' coordinates) in a second one
-		                               // that runs beside that evaluation and is joined in front of the loss pass
-		bool scatter_plain = false; // RNB_SCATTER_PLAIN=1 (A/B, tests): no LDS-privatised and no run-length scatter -- every corner of every level is its own L2 atomic, as in the reference; with
+		bool loss_chain_records = true; // RNB_LOSS_CHAIN_RECORDS=0: pass 2 of the loss replays the compositing recurrence itself instead of reading the running values pass 1 left
+		bool scatter_plain = false; // RNB_SCATTER_PLAIN=1: no LDS-privatised and no run-length scatter -- every corner of every level is its own L2 atomic, as in the reference; with
 		                            // accumulate = RNB_ACCUM_HALF every one of a corner's four addends is (k_grid_scatter_quad_h_per_addend), which reproduces the reference's sequential half sums
 		                            // on the coarse levels too
-		int dbg_scatter_lo = -1, dbg_scatter_hi = -1; // RNB_DEBUG_SCATTER_LEVELS=lo,hi (measurement aid, WRONG gradients): while the per-kernel profiler is on, the atomic scatter kernels only walk levels [lo, hi)
-		bool scatter_c_early = false; // RNB_SCATTER_C_EARLY=1: group C (LDS-privatised coarse levels, no global atomics to speak of) + its optimizer chunk on the optimizer's stream beside group A
-		                              // instead of last on the caller's stream. Measured again in round 5 (round 2: 42 -> 158 us): the kernel stretches 40 -> 167 us beside the atomic kernels and the march
-		                              // (which keep their times) and holds the optimizer's chunks back: 0.5846 -> 0.6404 ms/step at step 1000, 0.6217 -> 0.6753 at 6000 (profiles/r05_ab_scatter_c_early.txt). Off.
-		int scatter_rl_staged = -1; // RNB_SCATTER_RL_STAGED=0|1: the run-length scatter loads its operands from global memory inside the walk (rounds 2-4) / stages them in LDS (round 5). Alone the two take
-		                            // the same time (112 / 101 / 112 us staged vs 112 / 97 / 111 direct at steps 1000 / 2000 / 6000: the walk is NOT a chain of load -> atomic-acknowledge round trips,
-		                            // which is what the staging removes); in the step the staged form's 40 registers and 32 KB of LDS leave the march beside it more of the CU while the batch is
-		                            // few long rays: 0.6078 -> 0.5971 ms/step at step 1000, 0.5900 -> 0.5929 at 2000, 0.6334 -> 0.6360 at 6000 (profiles/r05_ab_scatter_rl_staged.txt).
-		                            // Default: staged below march_narrow_from rays per step (the regime of the A-B-C scatter order), direct from there on
-		bool march_skip_narrow = false; // RNB_MARCH_SKIP_NARROW=1: the same skipping in the one-thread-per-ray march of the large batches. Bit-identical (tests, 6100 lockstep steps) and SLOWER: k_march_count 192 -> 221 us
-		                                // at step 2000, window 0.5611 -> 0.5715 ms/step, late 0.6073 -> 0.6204: a wavefront's 64 rays finish with the slowest, and the one ray in 64 that cannot skip keeps the old
-		                                // cost while every lane pays the 64-point scan and the re-entry search (profiles/r06_ab_march_skip_narrow.txt). Off.
-		uint32_t march_narrow_wgs = 128; // RNB_MARCH_NARROW_WGS=64|128|256|512 (A/B, round 6): threads (= rays) per workgroup of the thread-per-ray march. Window / late, ms/step: 64: 0.5512 / 0.6069, 128: 0.5502 / 0.6043,
-		                                 // 256: 0.5589 / 0.6117, 512: 0.5712 / 0.6190 (a workgroup keeps its slots until its slowest ray is through) -- profiles/r06_ab_march_wgs.txt
-		int march_wgs = 1024; // RNB_MARCH_WGS=256|512|1024 (round 6): threads per workgroup of k_march_count_skip. Every workgroup first loads the occupancy's LDS form (~44 KB at step 1000) for its WGS / 16 rays:
-		                      // 64 rays per load instead of 16. Steps 1000-1200 / window: 256: 0.5637 / 0.5502, 512: 0.5608 / 0.5498, 1024: 0.5592 / 0.5492 (bit-identical: the pinned states)
-		int march_skip = 1; // RNB_MARCH_SKIP=0: k_march_count_wide<16> as in rounds 2-5 (every round from box entry to box exit); 1 (round 6): k_march_count_skip; 2: its start-over path forced (tests)
-		bool dw_late = false; // RNB_DW_LATE=1 (A/B)
-		int march_bbox = 1; // RNB_MARCH_BBOX=0: the thread-per-ray march walks from the scene box's entry to its exit (rounds 1-5); 1 (round 6, default): it ends where the ray leaves the occupied region's bounding
-		                    // box: window 0.5609 -> 0.5531 ms/step, late 0.6152 -> 0.6086; 2: + one jump to that box's entry (k_march_count_bbox): bit-identical, but the jump and its re-entry search cost what they save
-		                    // (0.5624 / 0.6165; profiles/r06_ab_march_bbox.txt) -- kept as a knob
-		int march_prio = 0; // RNB_MARCH_PRIO=0..3 (A/B): s_setprio of k_march_count / k_march_count_skip
-		int scatter_prio = 0; // RNB_SCATTER_PRIO=0..3 (A/B): s_setprio of the scatter kernels' wavefronts
-		bool scatter_share = true;  // RNB_SCATTER_SHARE=1 (A/B, round 6): face sharing in the run-length scatter (kernels_net.cuh: share_face)
-		int scatter_kmin = 0, scatter_rl_upto = 0; // RNB_SCATTER_KMIN, RNB_SCATTER_RL_UPTO (A/B, plan_scatter_groups)
-		bool scatter_anyorder = true;  // RNB_SCATTER_ANYORDER=1 (A/B): the scatter groups behind the first one are launched with hipExtAnyOrderLaunch -- they touch other levels, so a group may start in the tail of the one in front of it
-		int encode_depth = 4; // RNB_ENCODE_DEPTH=0|2|4|7: levels whose gathers k_forward_chained / k_point_query_chained keep in flight (round 5; 0: one level at a time behind branches, rounds 1-4).
-		                      // Interleaved medians, ms/step at steps 1000 / 2000 / 6000: 0: 0.5964 / 0.5884 / 0.6298; 2: 0.5773 / 0.5810 / 0.6209; 4: 0.5775 / 0.5769 / 0.6199; 7: 0.5781 / 0.5776 / 0.6262
-		                      // (profiles/r05_ab_encode_depth.txt). The half mode's evaluation kernels take depth 4 too (254 VGPRs, 4 spilled dwords); the training kernels (rolled level loop, two workgroups per CU: no gain) keep the old form
-		int march_write_wg = 256; // RNB_MARCH_WRITE_WG=1024 (A/B, round 6): threads per workgroup of k_march_write
-		bool chain_plain = true; // RNB_CHAIN_PLAIN=0 (A/B, round 6): ScanChainArgs::plain -- k_scan_rays_chain's tiles exchange their sums by agent-scope atomic stores / loads instead of read-modify-write atomics (which wait behind
-		                         // the scatter's backlog at the memory side): window 0.5524 -> 0.5512, late 0.6084 -> 0.6066, medians of 4 (profiles/r06_ab_chain_plain.txt)
-		bool point_xcd = true; // RNB_POINT_XCD=0 (A/B, round 6): PointArgs::xcd -- the occupancy update's cell-ordered points in eight contiguous parts, one per XCD (workgroups go round the XCDs): 286 -> 274 us per update
-		bool dw_sliced = true; // RNB_DW_SLICED=0 (A/B): the half mode's weight gradients in the training kernel's own tiling (deviation D1', rounds 4-5) instead of the reference's split-K order
-		bool encode_pair = false; // RNB_ENCODE_PAIR=1 (A/B, round 6): when the configuration's first five levels are dense (the default's are: 16^3 ... 71^3), the depth-4 evaluation kernels gather their x-pairs with one 8-byte load
-		                          // (level_issue<true>): bit-identical, 18 % fewer gather instructions -- and SLOWER: 0.5538 vs 0.5500 ms/step over steps 1000-2000, 0.6092 vs 0.6058 at step 6000 (profiles/r06_ab_encode_pair.txt;
-		                          // a 4-byte-aligned 8-byte gather that straddles a 64-byte line costs a second pass, and the coarse levels were L2 hits to begin with). Off.
+		int march_skip = 1; // RNB_MARCH_SKIP=0: k_march_count_wide<16> (every round from box entry to box exit); 1: k_march_count_skip; 2: its start-over path forced (tests)
+		bool march_skip_narrow = false; // RNB_MARCH_SKIP_NARROW=1: the same skipping in the one-thread-per-ray march of the large batches (bit-identical, slower: profiles/r06_ab_march_skip_narrow.txt)
+		int march_bbox = 1; // RNB_MARCH_BBOX=0: the thread-per-ray march walks from the scene box's entry to its exit; 1: it ends where the ray leaves the occupied region's bounding box;
+		                    // 2: + one jump to that box's entry (k_march_count_bbox): bit-identical, no faster (profiles/r06_ab_march_bbox.txt)
+		bool dw_sliced = true; // RNB_DW_SLICED=0: the half mode's weight gradients in the training kernel's own tiling (deviation D1') instead of the reference's split-K order
 		bool grid_presort = true; // RNB_GRID_PRESORT=0: occupancy updates evaluate their samples in the reference's order (no pregenerate_grid_samples)
 	} knobs;
 	DevBuf<RayLoss> ray_loss;
@@ -317,21 +256,10 @@ struct rnb_ctx {
 	// costs the critical stream ~5 us (tools/probe_barriers.hip), so when the next step's march is about to be queued, the wait for ev_tail goes onto ITS stream,
 	// in front of k_march_write (slack there), and the critical stream reaches it through ev_march. tail_pending: nobody has waited for ev_tail yet.
 	bool tail_pending = false;
-	// (round 6) join_pending: the next step's march was already queued when the optimizer was launched, so the weight-gradient stream -- idle behind its weight images -- has taken the
-	// joins: it waits for ev_adam and ev_march and records ev_join, and the critical stream reaches all three side streams through that ONE event at the head of the next step
-	// (three barrier packets: 17-18 us of idle queue in front of every network evaluation, profiles/r06_timeline_*). ev_march_rest (a split k_march_write) stays a wait of its own
-	// behind the first network evaluation. Whoever else consumes what the side streams wrote (join_tail_host) waits for it on the host.
-	// (On the march stream behind k_ray_constants instead, measured: the first evaluation then waits for the second k_march_write too, window 0.5517 -> 0.5748.)
-	bool join_pending = false;
-	hipEvent_t ev_join = nullptr;
-	hipEvent_t ev_loss = nullptr, ev_march = nullptr, ev_fb = nullptr, ev_dw = nullptr, ev_adam = nullptr, ev_tail = nullptr, ev_march_rest = nullptr, ev_all = nullptr, ev_sc[4] = {nullptr, nullptr, nullptr, nullptr};
+	hipEvent_t ev_loss = nullptr, ev_march = nullptr, ev_fb = nullptr, ev_dw = nullptr, ev_adam = nullptr, ev_tail = nullptr, ev_march_rest = nullptr, ev_all = nullptr, ev_sc[3] = {nullptr, nullptr, nullptr};
 	// Scatter groups of the queued backward pass: B = middle levels [split1, split0) (final at ev_sc[0]), A = fine levels [split0, off_var) in two
-	// halves (ev_sc[1], ev_sc[3]; the second starts at split_mid), C = coarse levels [off_grid, split1) last; the MLPs + variance follow the dW GEMMs (ev_dw).
-	struct { bool valid = false, exchanged = false, dp = false, sharded = false, all_final_recorded = false, dw_joined = true, c_early = false; uint64_t split[2] = {0, 0}, split_mid = 0; int order = 0;
-	         // (round 6, RNB_SCATTER_C_SIDE) c_side: group C has NOT been launched by the backward pass: the optimizer launches it (c_launch) with its optimizer chunk at the END of the
-	         // weight-gradient stream, behind the last atomic group (c_after), so that the critical stream falls idle behind its last atomic group and works off the barrier packets of the
-	         // joins while the side streams finish (each costs it ~5 us, tools/probe_barriers.hip -- 16-18 us of idle queue in front of every network evaluation)
-	         bool c_side = false; hipEvent_t c_after = nullptr; std::function<void(hipStream_t, hipEvent_t)> c_launch; } sc;
+	// halves (ev_sc[1], ev_sc[2]; the second starts at split_mid), C = coarse levels [off_grid, split1) last; the MLPs + variance follow the dW GEMMs (ev_dw).
+	struct { bool valid = false, exchanged = false, dp = false, sharded = false, all_final_recorded = false, dw_joined = true; uint64_t split[2] = {0, 0}, split_mid = 0; int order = 0; } sc; // order: 0 = B, A1, A2, C; 2 = A (one launch), B, C
 	// level groups of the gradient scatter (forward_backward), fixed at creation: C = [0, e_c) LDS, B = [e_c, l_fine) run-length quads, A = [l_fine, L) plain quads
 	struct ScatterGroups { uint32_t e_c = 0, l_fine = 0, Ks[RNB_MAX_LEVELS] = {}; uint64_t k_log2 = 0; } sg;
 	hipStream_t backward_stream = nullptr; // the stream the last backward pass was queued on
@@ -340,11 +268,11 @@ struct rnb_ctx {
 	uint64_t param_capacity = 0; // allocated length of the parameter-shaped arrays: padded so that the data-parallel shards are equal
 	bool dp_order() const { return cfg.world_size > 1 || knobs.dp_order; }
 	struct { bool begun = false, early_done = false; AdamArgs args; } opt; // optimizer state of the running step (it may be applied in two pieces) // scatter groups of the current backward pass (see forward_backward)
-	struct { bool valid = false, loss_cleared = false; uint32_t n_rays = 0, n_rays_total = 0, max_inference = 0, k1 = 0; bool split = false, march_joined = false; } pre; // samples already generated for the next step
+	struct { bool valid = false, loss_cleared = false; uint32_t n_rays = 0, n_rays_total = 0, max_inference = 0, k1 = 0; bool split = false; } pre; // samples already generated for the next step
 	struct Readback { double sums[3]; uint32_t counters[4]; uint32_t fwd[2]; uint32_t seq, pad; }* host_rb = nullptr; // pinned, device-mapped; same layout as the device block k_reduce_losses fills; seq: see poll_loss()
 	uint32_t rb_seq = 0;     // sequence number of the last step whose readback was launched in polling mode
 	bool loss_polled = true; // the host has seen that step's readback (or the step publishes through ev_loss instead)
-	bool poll_loss() const { return overlap() && !dp_order() && knobs.poll_loss; }
+	bool poll_loss() const { return overlap() && !dp_order(); }
 	void* host_rb_dev = nullptr;
 	bool overlap() const { return cfg.overlap != 0 && !prof.on && s_march != nullptr; }
 
@@ -368,15 +296,8 @@ static bool prep_due(uint32_t step) { // testbed.cu:2805
 	const uint32_t n_prep_to_skip = std::min(std::max(step / 16u, 1u), 16u);
 	return step % n_prep_to_skip == 0;
 }
-// Group C of a training step's scatter was left to the optimizer (sc.c_side) and something else needs the gradients first: launch it on `s` now.
-static void flush_c_side(rnb_ctx* c, hipStream_t s) {
-	if (!c->sc.c_side) return;
-	c->sc.c_side = false;
-	c->sc.c_launch(s, nullptr);
-}
 // Safety net of the deferred join (rnb_ctx::tail_pending) for launches outside the training step's own sequence: wait on the host.
 static void join_tail_host(rnb_ctx* c) {
-	if (c->join_pending) { (void)hipEventSynchronize(c->ev_join); c->join_pending = false; }
 	if (c->tail_pending) { (void)hipEventSynchronize(c->ev_tail); c->tail_pending = false; }
 }
 
@@ -414,12 +335,6 @@ void build_grid_tables(rnb_ctx* c) { // grid.h:977-1012
 	}
 	for (uint32_t i = cfg.n_levels; i <= RNB_MAX_LEVELS; ++i) c->grid.offsets[i] = offset;
 	c->n_grid_params = (uint64_t)offset * 2;
-	c->n_dense_lead = 0; // the leading levels whose tables hold the whole lattice (fill_level_meta's rule): the pipelined encode gathers their x-pairs with one load (level_issue<true>)
-	for (uint32_t i = 0; i < cfg.n_levels; ++i) {
-		const uint64_t r = c->grid.resolution[i], size = c->grid.offsets[i + 1] - c->grid.offsets[i];
-		if (r * r * r > size) break;
-		c->n_dense_lead = i + 1;
-	}
 }
 
 void build_light_dirs(rnb_ctx* c) { // testbed_nerf.cu:1537-1554
@@ -496,7 +411,7 @@ int update_bitfield(rnb_ctx* c, hipStream_t s, bool wait = true, bool have_parti
 	const uint32_t n_blocks = 1024;
 	if (!have_partials) hipLaunchKernelGGL(k_mean_partial, dim3(n_blocks), dim3(256), 0, s, c->density_grid.p, c->mean_partial.p);
 	const uint32_t n_bytes_per_mip = GRID_CELLS / 8;
-	if (c->aabb.max_cascade == 0 && !c->bitfield_foreign && c->knobs.fused_update) {
+	if (c->aabb.max_cascade == 0 && !c->bitfield_foreign) {
 		// single-cascade scene: mean + level 0 + level 1 in one launch, the upper levels + the march's LDS form in a second one (kernels_ray.cuh)
 		hipLaunchKernelGGL(k_bitfield_sc, dim3(n_bytes_per_mip / 256), dim3(256), 0, s, c->density_grid.p, c->bitfield.p, c->mean_partial.p, c->density_mean.p);
 		LAUNCH_EV(k_pool_tail_coarse, dim3(2), dim3(1024), 0, s, (c->overlap() && !wait) ? c->ev_grid : nullptr, 2u, c->bitfield.p, c->coarse_bits.p, c->coarse_count.p, c->host_coarse_dev);
@@ -524,16 +439,12 @@ int launch_point_query(rnb_ctx* c, hipStream_t s, const float* xyz, uint32_t n, 
 	if (n == 0) return RNB_OK;
 	join_tail_host(c); // (inference launches too: the same side-stream launch writes the MLPs' and the variance's EMA weights)
 	PointArgs a;
-	a.xyz = xyz; a.n = n; a.out = out; a.splat_idx = splat_idx; a.grid_tmp = grid_tmp; a.want_density = want_density; a.sdf_bias = c->cfg.sdf_bias; a.range = range; a.xcd = c->knobs.point_xcd ? 1u : 0u;
+	a.xyz = xyz; a.n = n; a.out = out; a.splat_idx = splat_idx; a.grid_tmp = grid_tmp; a.want_density = want_density; a.sdf_bias = c->cfg.sdf_bias; a.range = range;
 	const uint32_t n_tiles = (n + TILE - 1) / TILE;
 	const uint32_t grid = std::min<uint32_t>((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG, (uint32_t)c->n_cus * 5); // 86 VGPRs, 28 KB of LDS: five workgroups per CU
-	if (c->half_acc() && c->knobs.encode_depth) hipLaunchKernelGGL(k_point_query_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr);
-	else if (c->half_acc()) hipLaunchKernelGGL(k_point_query_chained_emul, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr);
-	else if (c->knobs.encode_depth == 4 && c->knobs.encode_pair && c->n_dense_lead >= 5) hipLaunchKernelGGL((k_point_query_chained_pipe<4, 5>), dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr);
-	else if (c->knobs.encode_depth == 4) hipLaunchKernelGGL(k_point_query_chained_pipe<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr);
-	else if (c->knobs.encode_depth == 7) hipLaunchKernelGGL(k_point_query_chained_pipe<7>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr);
-	else if (c->knobs.encode_depth == 2) hipLaunchKernelGGL(k_point_query_chained_pipe<2>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr);
-	else hipLaunchKernelGGL(k_point_query_chained, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr);
+	const half_t* wimg = (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr;
+	if (c->half_acc()) hipLaunchKernelGGL(k_point_query_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, wimg);
+	else hipLaunchKernelGGL(k_point_query_chained_pipe<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, wimg);
 	HIP_TRY(hipGetLastError());
 	return RNB_OK;
 }
@@ -658,11 +569,10 @@ int update_density_grid_front(rnb_ctx* c, hipStream_t s, uint32_t n_uniform, uin
 int update_density_grid_back(rnb_ctx* c, hipStream_t s) { // testbed_nerf.cu:3491-3517
 	const uint32_t n_elements = GRID_CELLS * (c->aabb.max_cascade + 1);
 	int rc;
-	if (c->knobs.fused_update) hipLaunchKernelGGL(k_ema_mean, dim3(n_elements / 2048), dim3(256), 0, s, n_elements, c->cfg.density_grid_decay, c->density_grid.p, c->density_grid_tmp.p, c->mean_partial.p);
-	else hipLaunchKernelGGL(k_ema_grid, dim3((n_elements + 127) / 128), dim3(128), 0, s, n_elements, c->cfg.density_grid_decay, c->density_grid.p, c->density_grid_tmp.p);
+	hipLaunchKernelGGL(k_ema_mean, dim3(n_elements / 2048), dim3(256), 0, s, n_elements, c->cfg.density_grid_decay, c->density_grid.p, c->density_grid_tmp.p, c->mean_partial.p);
 	HIP_TRY(hipGetLastError());
 	++c->density_grid_ema_step;
-	rc = update_bitfield(c, s, !c->overlap(), c->knobs.fused_update);
+	rc = update_bitfield(c, s, !c->overlap(), true); // k_ema_mean has left the mean's partial sums
 	c->prof.mark(s, P_EMA_BITFIELD);
 	c->gs_todo.pending = true; // queued by the caller once the kernels that wait for THIS update are in their queue
 	return rc;
@@ -702,13 +612,8 @@ int launch_forward(rnb_ctx* c, hipStream_t s, const float* coords, const uint32_
 	a.wimg = (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr;
 	const uint32_t n_tiles = (n_max + TILE - 1) / TILE;
 	const uint32_t grid = std::min<uint32_t>((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG, (uint32_t)c->n_cus * 2);
-	if (c->half_acc() && c->knobs.encode_depth) hipLaunchKernelGGL(k_forward_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
-	else if (c->half_acc()) hipLaunchKernelGGL(k_forward_chained_emul, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
-	else if (c->knobs.encode_depth == 2) hipLaunchKernelGGL(k_forward_chained_pipe<2>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
-	else if (c->knobs.encode_depth == 4 && c->knobs.encode_pair && c->n_dense_lead >= 5) hipLaunchKernelGGL((k_forward_chained_pipe<4, 5>), dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
-	else if (c->knobs.encode_depth == 4) hipLaunchKernelGGL(k_forward_chained_pipe<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
-	else if (c->knobs.encode_depth == 7) hipLaunchKernelGGL(k_forward_chained_pipe<7>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
-	else hipLaunchKernelGGL(k_forward_chained, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
+	if (c->half_acc()) hipLaunchKernelGGL(k_forward_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
+	else hipLaunchKernelGGL(k_forward_chained_pipe<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
 	HIP_TRY(hipGetLastError());
 	return RNB_OK;
 }
@@ -751,10 +656,13 @@ static bool lattice_is_linear() {
 	return true;
 }
 
+// One wavefront per ray for batches of at most this many rays (single-cascade scenes). At an eighth of the batch (1.8 k rays per step): 0.2985 -> 0.2890 ms/step; bit-exact at every size
+constexpr uint32_t MARCH_WAVE_PER_RAY_BELOW = 4096;
+
 MarchArgs march_args(rnb_ctx* c, uint32_t n_rays, uint32_t n_rays_total, uint32_t max_samples) {
 	MarchArgs a;
 	static const bool linear = lattice_is_linear();
-	a.lattice_ok = (linear && !c->knobs.march_running_sums) ? 1u : 0u;
+	a.lattice_ok = linear ? 1u : 0u;
 	a.n_rays = n_rays;
 	a.n_rays_global = n_rays * c->cfg.world_size;
 	a.ray_offset = c->cfg.rank * n_rays;
@@ -776,10 +684,8 @@ MarchArgs march_args(rnb_ctx* c, uint32_t n_rays, uint32_t n_rays_total, uint32_
 	a.base1 = c->ray_base1.p; a.idx1 = c->idx1.p; a.k1 = k1_for(c, n_rays);
 	a.F = loss_flags(c);
 	for (int k = 0; k < 9; ++k) a.light_dirs[k] = c->light_dirs[k];
-	a.ray_const = c->ray_const.p;
 	a.part = 0;
 	a.stats = c->march_stats.p;
-	a.prio = (uint32_t)c->knobs.march_prio;
 	a.use_bbox = (uint32_t)c->knobs.march_bbox;
 	return a;
 }
@@ -804,9 +710,9 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 			if (c->knobs.march_skip == 2) a.lattice_ok |= 2u; // (tests: no re-entry cell is accepted -- every ray walks every voxel up to the occupied box's exit)
 			hipLaunchKernelGGL(k_march_count_bbox, dim3(blocks), dim3(128), march_lds, s, a);
 			a.lattice_ok &= 1u;
-		} else if (sc) hipLaunchKernelGGL(k_march_count<true>, dim3((n_rays + c->knobs.march_narrow_wgs - 1) / c->knobs.march_narrow_wgs), dim3(c->knobs.march_narrow_wgs), march_lds, s, a);
+		} else if (sc) hipLaunchKernelGGL(k_march_count<true>, dim3(blocks), dim3(128), march_lds, s, a); // 128 rays per workgroup: it keeps its slots until its slowest ray is through (profiles/r06_ab_march_wgs.txt)
 		else hipLaunchKernelGGL(k_march_count<false>, dim3(blocks), dim3(128), 0, s, a);
-	} else if (sc && n_rays <= c->knobs.march_wave_per_ray_below) {
+	} else if (sc && n_rays <= MARCH_WAVE_PER_RAY_BELOW) {
 		// a batch so small that 16 lanes per ray leave most SIMDs without a wavefront (a rank of a strong-scaling job: 1.8 k rays = 0.4 wavefronts per SIMD): the kernel
 		// is then one wavefront's dependent chain of ~50 rounds, and a whole wavefront per ray quarters the rounds (at 12.6 k rays the same form lost, 660 vs 184 us: DESIGN.md section 6)
 		hipLaunchKernelGGL((k_march_count_wide<64, true, 256>), dim3((n_rays + 3) / 4), dim3(256), march_lds, s, a);
@@ -815,9 +721,7 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 		if (sc && c->knobs.march_skip && a.lattice_ok) {
 			// round 6: the same rounds, minus the stretches of the ray that cannot hold a sample (kernels_ray.cuh: k_march_count_skip); bit-identical sample set and t
 			if (c->knobs.march_skip == 2) a.lattice_ok |= 2u;
-			if (c->knobs.march_wgs == 512) hipLaunchKernelGGL((k_march_count_skip<512>), dim3((n_rays + 31) / 32), dim3(512), march_lds + COARSE_WORDS * sizeof(uint32_t), s, a);
-			else if (c->knobs.march_wgs == 1024) hipLaunchKernelGGL((k_march_count_skip<1024>), dim3((n_rays + 63) / 64), dim3(1024), march_lds + COARSE_WORDS * sizeof(uint32_t), s, a);
-			else hipLaunchKernelGGL((k_march_count_skip<256>), grid, dim3(256), march_lds + COARSE_WORDS * sizeof(uint32_t), s, a);
+			hipLaunchKernelGGL((k_march_count_skip<1024>), dim3((n_rays + 63) / 64), dim3(1024), march_lds + COARSE_WORDS * sizeof(uint32_t), s, a); // 64 rays per load of the occupancy's LDS form (profiles/r06_ab_march_wgs.txt)
 			a.lattice_ok &= 1u;
 		} else if (sc) hipLaunchKernelGGL((k_march_count_wide<16, true>), grid, dim3(256), march_lds, s, a);
 		else hipLaunchKernelGGL((k_march_count_wide<16, false>), grid, dim3(256), 0, s, a);
@@ -825,10 +729,10 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 	c->prof.mark(s, P_MARCH_COUNT);
 	if (wait_before_scans) HIP_TRY(hipStreamWaitEvent(s, wait_before_scans, 0)); // (launch_premarch: the previous step's second loss pass may still be reading what the scans and k_march_write overwrite)
 	const uint32_t n_scan_tiles = (n_rays + SCAN_TILE - 1) / SCAN_TILE;
-	if (c->knobs.scan_chain && n_scan_tiles <= 64) { // one launch, one workgroup per 4096-ray tile (k_scan_rays_chain)
+	if (n_scan_tiles <= 64) { // one launch, one workgroup per 4096-ray tile (k_scan_rays_chain)
 		ScanChainArgs q;
 		q.n = n_rays; q.max_samples = max_samples; q.k1 = a.k1; q.steps = c->ray_steps.p; q.base = c->ray_base.p; q.slot = c->ray_slot.p; q.base1 = c->ray_base1.p;
-		q.counters = c->counters.p; q.fwd_counts = c->fwd_counts.p; q.words = c->scan_words.p; q.words2 = c->scan_words.p + 2 * 64 * 4; q.ticket = ++c->scan_ticket; q.error = c->host_coarse_dev + 5; q.plain = c->knobs.chain_plain ? 1u : 0u;
+		q.counters = c->counters.p; q.fwd_counts = c->fwd_counts.p; q.words = c->scan_words.p; q.words2 = c->scan_words.p + 2 * 64 * 4; q.ticket = ++c->scan_ticket; q.error = c->host_coarse_dev + 5;
 		hipLaunchKernelGGL(k_scan_rays_chain, dim3(n_scan_tiles), dim3(SCAN_WG), 0, s, q);
 	} else if (n_rays >= c->knobs.march_narrow_from) { // one workgroup per 4096-ray tile (<= 64 tiles) instead of one workgroup walking them
 		const uint32_t n_tiles = (n_rays + SCAN_TILE - 1) / SCAN_TILE;
@@ -839,27 +743,17 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 		hipLaunchKernelGGL(k_scan_rays, dim3(1), dim3(1024), 0, s, n_rays, max_samples, c->ray_steps.p, c->ray_base.p, c->ray_slot.p, c->counters.p, a.k1, c->ray_base1.p, c->fwd_counts.p);
 	c->prof.mark(s, P_SCAN_RAYS);
 	if (wait_before_write) HIP_TRY(hipStreamWaitEvent(s, wait_before_write, 0)); // (rnb_ctx::tail_pending)
-	const bool dense_const = c->knobs.ray_const_dense != 0;
-	float* const ray_const = a.ray_const;
-	if (dense_const) a.ray_const = nullptr; // k_ray_constants below
-	c->gen_split = rest_done != nullptr && a.k1 != 0 && (c->knobs.ray_const_dense == 1 ? false : (c->knobs.march_write_split < 0 ? n_rays < 65536u : c->knobs.march_write_split != 0)); // (measured: -2.7 / -3.5 us per step at 12.6 k / 50 k rays, +3.2 at 94 k: the join costs a barrier packet)
+	// A march generated ahead (rest_done) is written in two launches below 65 536 rays per step: what the first network evaluation reads (idx1, the heads' coordinates) in a first one,
+	// whose completion the critical stream waits for; the rest (ray records, the tails' coordinates, then the ray constants) in a second one that runs beside that evaluation and is
+	// joined in front of the loss pass (measured: -2.7 / -3.5 us per step at 12.6 k / 50 k rays, +3.2 at 94 k: the join costs a barrier packet)
+	c->gen_split = rest_done != nullptr && a.k1 != 0 && n_rays < 65536u;
 	for (uint32_t part = c->gen_split ? 1u : 0u; part <= (c->gen_split ? 2u : 0u); ++part) {
 		a.part = part;
-		hipEvent_t ev = part == 2 ? rest_done : done;
-		if (dense_const && part != 1) ev = nullptr; // the constants' launch carries the event
-		if (c->knobs.march_write_wg == 1024) { // RNB_MARCH_WRITE_WG=1024 (A/B): rounds 2-5
-			if (n_rays >= c->knobs.march_narrow_from) LAUNCH_EV((k_march_write<16, 1024>), dim3((n_rays + 63) / 64), dim3(1024), 0, s, ev, a);
-			else LAUNCH_EV((k_march_write<64, 1024>), dim3((n_rays + 15) / 16), dim3(1024), 0, s, ev, a);
-		} else if (c->knobs.march_write_wg == 64) {
-			if (n_rays >= c->knobs.march_narrow_from) LAUNCH_EV((k_march_write<16, 64>), dim3((n_rays + 3) / 4), dim3(64), 0, s, ev, a);
-			else LAUNCH_EV((k_march_write<64, 64>), dim3(n_rays), dim3(64), 0, s, ev, a);
-		} else if (c->knobs.march_write_wg == 128) {
-			if (n_rays >= c->knobs.march_narrow_from) LAUNCH_EV((k_march_write<16, 128>), dim3((n_rays + 7) / 8), dim3(128), 0, s, ev, a);
-			else LAUNCH_EV((k_march_write<64, 128>), dim3((n_rays + 1) / 2), dim3(128), 0, s, ev, a);
-		} else if (n_rays >= c->knobs.march_narrow_from) LAUNCH_EV((k_march_write<16, 256>), dim3((n_rays + 15) / 16), dim3(256), 0, s, ev, a);
+		const hipEvent_t ev = part == 1 ? done : nullptr; // otherwise the constants' launch carries the event
+		if (n_rays >= c->knobs.march_narrow_from) LAUNCH_EV((k_march_write<16, 256>), dim3((n_rays + 15) / 16), dim3(256), 0, s, ev, a);
 		else LAUNCH_EV((k_march_write<64, 256>), dim3((n_rays + 3) / 4), dim3(256), 0, s, ev, a);
 	}
-	if (dense_const) LAUNCH_EV(k_ray_constants, dim3((n_rays + 63) / 64), dim3(64), 0, s, c->gen_split ? rest_done : done, a, ray_const); // one thread per kept ray
+	LAUNCH_EV(k_ray_constants, dim3((n_rays + 63) / 64), dim3(64), 0, s, c->gen_split ? rest_done : done, a, c->ray_const.p); // one thread per kept ray
 	c->prof.mark(s, P_MARCH_WRITE);
 	c->prof.units[P_MARCH_COUNT] += n_rays;
 	HIP_TRY(hipGetLastError());
@@ -914,7 +808,7 @@ int compute_loss(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32_t n_rays_tot
 	// the offsets formed inside k_loss_pass2_rays: step 1000 (13 k rays, 4 tiles) 0.6065 -> 0.6015 ms/step; step 6000 (95 k rays, 24 tiles: 5.9 k workgroups polling) 0.6274 -> 0.6270: up to 8 tiles
 	if (flat && c->knobs.loss_scan_fused && (n_rays + SCAN_TILE - 1) / SCAN_TILE <= (c->knobs.loss_scan_fused_always ? 64u : 8u)) {
 		a.scan_words = c->scan_words.p + 64 * 4; a.scan_ticket = ++c->scan_ticket; a.scan_error = c->host_coarse_dev + 6; a.scan_total = c->counters.p + 1;
-	} else if (n_rays >= c->knobs.march_narrow_from && c->knobs.scan_chain && (n_rays + SCAN_TILE - 1) / SCAN_TILE <= 64) {
+	} else if (n_rays >= c->knobs.march_narrow_from && (n_rays + SCAN_TILE - 1) / SCAN_TILE <= 64) {
 		hipLaunchKernelGGL(k_scan_compact_chain, dim3((n_rays + SCAN_TILE - 1) / SCAN_TILE), dim3(SCAN_WG), 0, s, n_rays, c->ncomp.p, c->cbase.p, c->counters.p,
 		                   c->scan_words.p + 64 * 4, ++c->scan_ticket, c->host_coarse_dev + 6);
 	} else if (n_rays >= c->knobs.march_narrow_from) {
@@ -960,13 +854,13 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 	const bool half = c->half_acc();
 	if (!c->grads_clean) HIP_TRY(hipMemsetAsync(c->grad_ptr(0), 0, c->n_params * c->grad_elem(), s));
 	c->grads_clean = false;
-	c->sc.valid = false; c->sc.exchanged = false; c->sc.sharded = false; c->sc.all_final_recorded = false; c->sc.dw_joined = true; c->sc.c_early = false; c->sc.c_side = false;
+	c->sc.valid = false; c->sc.exchanged = false; c->sc.sharded = false; c->sc.all_final_recorded = false; c->sc.dw_joined = true;
 	TrainArgs a;
 	a.coords = c->coords_compacted.p; a.dout = c->dloss_dout.p; a.B = B; a.B_global = B * c->cfg.world_size; a.sdf_bias = c->cfg.sdf_bias; a.t = c->ts; a.skip_rgb = c->cfg.apply_no_albedo ? 1u : 0u;
 	const bool split = c->rgb_split(); // albedo mode: k_rgb_fwd_bwd + k_fwd_bwd_sdf_full instead of the generic kernel and its weight-gradient GEMMs
 	a.wimg = !c->wimg_valid ? nullptr : (!c->knobs.fwd_bwd_generic) ? c->wimg_fbs.p : c->wimg_train.p;
 	const bool sdf_only = (a.skip_rgb && !c->knobs.fwd_bwd_generic) || split; // the training kernels leave one weight-gradient partial per workgroup themselves
-	const uint32_t fb_grid = sdf_only ? std::min<uint32_t>((B / TILE + WAVES_PER_WG - 1) / WAVES_PER_WG, (uint32_t)c->n_cus * c->knobs.fbs_wg_per_cu) : c->fwd_grid;
+	const uint32_t fb_grid = sdf_only ? std::min<uint32_t>((B / TILE + WAVES_PER_WG - 1) / WAVES_PER_WG, (uint32_t)c->n_cus * 2) : c->fwd_grid; // two workgroups of k_fwd_bwd_sdf per CU (its launch bounds allow two)
 	// half mode, round 6: the weight gradients in the reference's split-K order (k_dw_sliced): the training kernels export their GEMM operands feature-major instead of accumulating
 	// in their own tiling (deviation D1' of rounds 4-5; RNB_DW_SLICED=0: that form).
 	const bool sliced = half && sdf_only && c->knobs.dw_sliced; // (sdf_only: the SDF-only training kernel or the albedo mode's two -- not the generic kernel of RNB_FWD_BWD_GENERIC)
@@ -1072,9 +966,10 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 	//   B  middle  [e_c, l_fine) run-length quad kernel: a cell spans several march steps (~590 / resolution); same bound + the latency of the walk
 	//   C  coarse  [0, e_c)      LDS-privatised tables (beside the atomic groups on the optimizer's stream it stretches 42 -> 158 us and the
 	//                            step loses 4 %, measured in round 2: it stays last on the caller's stream)
-	// albedo mode, round 4 (k_rgb_fwd_bwd + k_fwd_bwd_sdf_full, march held back behind them): 0: 0.806, 1: 0.783, 2: 0.760, 3: 0.774, 4: 0.800 -- there the march is the
-	// long pole beside the scatter and gets the wave slots a capped scatter leaves
-	const uint32_t scatter_cap = c->knobs.scatter_wg_per_cu >= 0 ? (uint32_t)c->knobs.scatter_wg_per_cu : ((sdf_only && !split) ? 0u : 2u);
+	// Resident workgroups of the atomic scatter kernels per CU (0 = no cap: one workgroup per 64 samples), by mode. ms/step, --no-albedo 0: 0.650, 2: 0.666, 4: 0.667; albedo mode, round 4
+	// (k_rgb_fwd_bwd + k_fwd_bwd_sdf_full, march held back behind them): 0: 0.806, 1: 0.783, 2: 0.760, 3: 0.774, 4: 0.800 -- there the march is the long pole beside the scatter
+	// and gets the wave slots a capped scatter leaves
+	const uint32_t scatter_cap = (sdf_only && !split) ? 0u : 2u;
 	ScatterArgs sa;
 	sa.g12 = T.g12; sa.srec = T.srec; sa.B = B; sa.grid_grad = half ? nullptr : c->grads.p + c->off_grid;
 	sa.grid_grad16 = half ? reinterpret_cast<uint32_t*>(c->grads16.p + c->off_grid) : nullptr; // (off_grid is even: half2 entries are 4-byte aligned)
@@ -1083,7 +978,6 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 	// vector it finds in the other modes, at the same points
 	const bool fixed = c->fixed_acc();
 	sa.grid_fixed = fixed ? c->grads_fixed.p : nullptr;
-	sa.prio = side_streams ? (uint32_t)c->knobs.scatter_prio : 0u;
 	auto narrow = [&](hipStream_t st, hipEvent_t done, uint32_t l0, uint32_t l1) { // levels [l0, l1)
 		const uint64_t lo = (uint64_t)c->grid.offsets[l0] * 2, hi = (uint64_t)c->grid.offsets[l1] * 2;
 		if (hi <= lo) { if (done) (void)hipEventRecord(done, st); return; }
@@ -1091,13 +985,11 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 		LAUNCH_EV(k_fixed_narrow, dim3(blocks), dim3(256), 0, st, done, c->grads_fixed.p, half ? nullptr : c->grads.p + c->off_grid, half ? c->grads16.p + c->off_grid : nullptr, lo, hi);
 	};
 	// `done` (if any) fires when the group's last kernel has completed; a group without kernels records it the plain way
-	const bool dbg_levels = c->prof.on && c->knobs.dbg_scatter_lo >= 0;
-	// RNB_SCATTER_ANYORDER: every scatter launch behind the step's first one may start before the kernel in front of it has drained (other levels: no dependency); the first one keeps
+	// Every scatter launch behind the step's first one may start before the kernel in front of it has drained (other levels: no dependency); the first one keeps
 	// its barrier (it needs k_fwd_bwd's operands), and so does everything behind the scatter
 	bool sc_first = true;
-	auto sc_flags = [&]() -> uint32_t { const bool any = c->knobs.scatter_anyorder && side_streams && !sc_first; sc_first = false; return any ? (uint32_t)hipExtAnyOrderLaunch : 0u; };
+	auto sc_flags = [&]() -> uint32_t { const bool any = side_streams && !sc_first; sc_first = false; return any ? (uint32_t)hipExtAnyOrderLaunch : 0u; };
 	auto launch_a = [&](hipStream_t st, hipEvent_t done, uint32_t l0, uint32_t l1) { // levels [l0, l1) of the group
-		if (dbg_levels) { l0 = std::max(l0, (uint32_t)c->knobs.dbg_scatter_lo); l1 = std::max(l0, std::min(l1, (uint32_t)c->knobs.dbg_scatter_hi)); }
 		const uint32_t n_vb = (B * 4 + 255) / 256, cap = scatter_cap ? std::max(1u, (uint32_t)c->n_cus * scatter_cap / std::max(1u, l1 - l0)) : n_vb;
 		if (l1 > l0 && fixed) {
 			LAUNCH_EVF(k_grid_scatter_quad_fixed, dim3(std::min(n_vb, cap), l1 - l0), dim3(256), 0, st, nullptr, sc_flags(), c->meta(), sa, l0, n_vb);
@@ -1108,26 +1000,23 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 		else if (done) (void)hipEventRecord(done, st);
 	};
 	auto launch_b = [&](hipStream_t st, hipEvent_t done) { // one launch for all these levels, each with the workgroups its run length needs
-		uint32_t e_c = sg.e_c, l_fine = sg.l_fine; // (shadow the group's bounds: the measurement aid narrows them)
-		if (dbg_levels) { e_c = std::max(e_c, (uint32_t)c->knobs.dbg_scatter_lo); l_fine = std::min(l_fine, (uint32_t)c->knobs.dbg_scatter_hi); }
 		if (l_fine <= e_c) { if (done) (void)hipEventRecord(done, st); return; }
 		ScatterRlPlan plan;
-		plan.n = l_fine - e_c; plan.k_log2 = sg.k_log2 >> (4 * (e_c - sg.e_c));
+		plan.n = l_fine - e_c; plan.k_log2 = sg.k_log2;
 		uint32_t wg = 0;
 		for (uint32_t q = 0; q < plan.n; ++q) { plan.wg_start[q] = wg; wg += (((B + sg.Ks[e_c + q] - 1) / sg.Ks[e_c + q]) * 4 + 255) / 256; }
 		plan.wg_start[plan.n] = wg;
 		const uint32_t cap_rl = scatter_cap ? (uint32_t)c->n_cus * scatter_cap : wg;
-		const bool staged = c->knobs.scatter_rl_staged >= 0 ? c->knobs.scatter_rl_staged != 0 : (c->cur_n_rays != 0 && c->cur_n_rays < c->knobs.march_narrow_from);
+		// operands staged in LDS while the batch is few long rays (the regime of the A-B-C scatter order), loaded inside the walk from there on (profiles/r05_ab_scatter_rl_staged.txt)
+		const bool staged = c->cur_n_rays != 0 && c->cur_n_rays < c->knobs.march_narrow_from;
 		if (fixed) {
 			LAUNCH_EVF(k_grid_scatter_quad_rl_fixed, dim3(std::min(wg, cap_rl)), dim3(256), 0, st, nullptr, sc_flags(), c->meta(), sa, e_c, plan);
 			narrow(st, done, e_c, l_fine);
 		} else if (!staged) {
 			if (half) LAUNCH_EVF(k_grid_scatter_quad_rl_direct_h, dim3(std::min(wg, cap_rl)), dim3(256), 0, st, done, sc_flags(), c->meta(), sa, e_c, plan);
-			else if (c->knobs.scatter_share) LAUNCH_EVF(k_grid_scatter_quad_rl_direct_share, dim3(std::min(wg, cap_rl)), dim3(256), 0, st, done, sc_flags(), c->meta(), sa, e_c, plan);
-			else LAUNCH_EVF(k_grid_scatter_quad_rl_direct, dim3(std::min(wg, cap_rl)), dim3(256), 0, st, done, sc_flags(), c->meta(), sa, e_c, plan);
+			else LAUNCH_EVF(k_grid_scatter_quad_rl_direct_share, dim3(std::min(wg, cap_rl)), dim3(256), 0, st, done, sc_flags(), c->meta(), sa, e_c, plan);
 		} else if (half) LAUNCH_EVF(k_grid_scatter_quad_rl_h, dim3(std::min(wg, cap_rl)), dim3(256), LDS_SCATTER_RL, st, done, sc_flags(), c->meta(), sa, e_c, plan);
-		else if (c->knobs.scatter_share) LAUNCH_EVF(k_grid_scatter_quad_rl_share, dim3(std::min(wg, cap_rl)), dim3(256), LDS_SCATTER_RL, st, done, sc_flags(), c->meta(), sa, e_c, plan);
-		else LAUNCH_EVF(k_grid_scatter_quad_rl, dim3(std::min(wg, cap_rl)), dim3(256), LDS_SCATTER_RL, st, done, sc_flags(), c->meta(), sa, e_c, plan);
+		else LAUNCH_EVF(k_grid_scatter_quad_rl_share, dim3(std::min(wg, cap_rl)), dim3(256), LDS_SCATTER_RL, st, done, sc_flags(), c->meta(), sa, e_c, plan);
 	};
 	auto launch_c = [&](hipStream_t st, hipEvent_t done) {
 		if (!e_c) { if (done) (void)hipEventRecord(done, st); return; }
@@ -1156,8 +1045,7 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 		hipStream_t sd = c->s_dw;
 		HIP_TRY(hipStreamWaitEvent(sd, c->ev_fb, 0));
 		c->sc.dp = c->dp_order();
-		const bool dw_late = c->knobs.dw_late && !c->sc.dp && !split; // RNB_DW_LATE=1 (A/B): k_dw_finish behind the first scatter group instead of beside it
-		if (!dw_late) launch_dw(sd, c->ev_dw);
+		launch_dw(sd, c->ev_dw);
 		const uint32_t a_mid = l_fine + (L - l_fine + 1) / 2;
 		// Data parallel: C, B, then A, so that the parameters in front of A's levels (MLPs, C, B: one contiguous block) are final at
 		// ev_sc[0] + ev_dw and their exchange runs beside the scatter of A; A's levels + variance are the second block.
@@ -1165,48 +1053,17 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 		// Order of the groups by batch shape (round 4, ms/step over 160 steps, one box, B-A1-A2-C / A1-A2-B-C / A-B-C): step 1000, 14 k rays: 0.6446 / 0.6473 / 0.6325;
 		// 1200, 18.5 k: 0.6435 / 0.6594 / 0.6394; 1400, 24 k: 0.6304 / 0.6324 / 0.6388; 1800, 41 k: 0.6132 / 0.6142 / 0.6161; 6000, 94 k: 0.6452 / 0.6482 / 0.6470
 		// (profiles/r04_sweep_scatter_order.txt): the fine levels first and in one launch while the batch is few long rays (the regime of the 16-lanes-per-ray march).
-		c->sc.order = c->sc.dp ? 0 : c->knobs.scatter_order >= 0 ? c->knobs.scatter_order : ((c->cur_n_rays < c->knobs.march_narrow_from && !split) ? 2 : 0); // (albedo mode, step 1000: 0.763 with A-B-C vs 0.755 with B-A1-A2-C: its march is held behind the training kernels)
-		c->sc.c_early = !c->sc.dp && c->knobs.scatter_c_early && e_c != 0;
-		if (c->sc.c_early) { // C beside the first atomic group: LDS + VALU work next to wavefronts that wait for the memory side
-			HIP_TRY(hipStreamWaitEvent(c->s_adam, c->ev_fb, 0));
-			launch_c(c->s_adam, c->ev_sc[2]);
-		}
+		c->sc.order = (!c->sc.dp && c->cur_n_rays < c->knobs.march_narrow_from && !split) ? 2 : 0; // (albedo mode, step 1000: 0.763 with A-B-C vs 0.755 with B-A1-A2-C: its march is held behind the training kernels)
 		if (c->sc.order == 0) { // B, A1, A2 (, C)
 			launch_b(s, c->ev_sc[0]);
-			if (dw_late) { HIP_TRY(hipStreamWaitEvent(sd, c->ev_sc[0], 0)); launch_dw(sd, c->ev_dw); }
 			launch_a(s, c->ev_sc[1], l_fine, a_mid);
-			launch_a(s, c->ev_sc[3], a_mid, L);
-		} else if (c->sc.order == 1) { // A1, A2, B, C: the fine levels' atomics before any optimizer chunk shares the memory side with them
-			launch_a(s, c->ev_sc[1], l_fine, a_mid);
-			if (dw_late) { HIP_TRY(hipStreamWaitEvent(sd, c->ev_sc[1], 0)); launch_dw(sd, c->ev_dw); }
-			launch_a(s, c->ev_sc[3], a_mid, L);
-			launch_b(s, c->ev_sc[0]);
+			launch_a(s, c->ev_sc[2], a_mid, L);
 		} else { // A (one launch), B, C
 			launch_a(s, c->ev_sc[1], l_fine, L);
-			if (dw_late) { HIP_TRY(hipStreamWaitEvent(sd, c->ev_sc[1], 0)); launch_dw(sd, c->ev_dw); }
 			launch_b(s, c->ev_sc[0]);
 		}
 		c->sc.split_mid = c->off_grid + (uint64_t)c->grid.offsets[a_mid] * 2;
-		c->sc.c_side = false;
-		if (c->sc.c_early) HIP_TRY(hipStreamWaitEvent(s, c->ev_sc[2], 0)); // (every gradient is final when `s` is: rnb_gradient_part_wait, stage calls)
-		else if (!c->sc.dp && !join_dw && c->knobs.scatter_c_side && e_c != 0 && !dbg_levels) {
-			// the training step (the optimizer follows): group C is handed to the optimizer's launch (rnb_ctx::sc.c_side); flush_c_side launches it here for whoever asks for the gradients first
-			const ScatterArgs sa_v = sa; const uint32_t e_c_v = e_c, B_v = B; const bool fixed_v = fixed, half_v = half;
-			c->sc.c_launch = [c, sa_v, e_c_v, B_v, fixed_v, half_v](hipStream_t st, hipEvent_t done) {
-				ScatterLdsArgs la; la.a = sa_v; la.n_levels = e_c_v;
-				const uint32_t n_wg = std::max(1u, std::min<uint32_t>(128u, (B_v + 1023) / 1024));
-				la.samples_per_wg = ((B_v + n_wg - 1) / n_wg + 3) / 4 * 4;
-				if (fixed_v) {
-					LAUNCH_EV(k_grid_scatter_lds_fixed, dim3(n_wg, 2), dim3(512), (size_t)c->grid.offsets[e_c_v] * 8, st, nullptr, c->meta(), la);
-					const uint64_t lo = 0, hi = (uint64_t)c->grid.offsets[e_c_v] * 2;
-					const uint32_t blocks = (uint32_t)std::min<uint64_t>(2048, ((hi - lo) / 2 + 255) / 256);
-					LAUNCH_EV(k_fixed_narrow, dim3(blocks), dim3(256), 0, st, done, c->grads_fixed.p, half_v ? nullptr : c->grads.p + c->off_grid, half_v ? c->grads16.p + c->off_grid : nullptr, lo, hi);
-				} else if (half_v) LAUNCH_EV(k_grid_scatter_lds_h, dim3(n_wg), dim3(512), (size_t)c->grid.offsets[e_c_v] * 8, st, done, c->meta(), la);
-				else LAUNCH_EV(k_grid_scatter_lds, dim3(n_wg), dim3(512), (size_t)c->grid.offsets[e_c_v] * 8, st, done, c->meta(), la);
-			};
-			c->sc.c_side = true;
-			c->sc.c_after = c->sc.order == 0 ? c->ev_sc[3] : c->ev_sc[0]; // the last atomic group of the order
-		} else if (!c->sc.dp) launch_c(s, nullptr); // last: its levels hold 32 k parameters, so almost nothing of the optimizer is left after the scatter (-6 % step time vs. first)
+		if (!c->sc.dp) launch_c(s, nullptr); // last: its levels hold 32 k parameters, so almost nothing of the optimizer is left after the scatter (-6 % step time vs. first)
 		if (c->sc.dp || join_dw) HIP_TRY(hipStreamWaitEvent(s, c->ev_dw, 0));
 		c->sc.dw_joined = c->sc.dp || join_dw; // the training step leaves the join to the optimizer, which continues on the side stream (optimizer_step)
 		c->sc.valid = true; // parameter ranges of the groups (grid entries are 2 parameters each)
@@ -1282,9 +1139,6 @@ static void plan_scatter_groups(rnb_ctx* c) {
 		for (l = 0; l < L; ++l) {
 			const float run = 590.f / (float)c->grid.resolution[l]; // compacted samples of a ray that share a cell of this level
 			g.Ks[l] = run >= 5.f ? 16 : run >= 2.5f ? 8 : run >= 1.2f ? 4 : 1; // below ~1 sample per cell the plain quad kernel is faster (measured)
-			// A/B (round 6, face sharing): RNB_SCATTER_KMIN = the shortest walk of a run-length level; RNB_SCATTER_RL_UPTO = levels below it walk (at least 4 samples) even where a cell holds < 1.2 samples
-			if (c->knobs.scatter_rl_upto > 0 && l < (uint32_t)c->knobs.scatter_rl_upto && g.Ks[l] == 1) g.Ks[l] = 4;
-			if (c->knobs.scatter_kmin > 0 && g.Ks[l] > 1) g.Ks[l] = std::max<uint32_t>(g.Ks[l], (uint32_t)c->knobs.scatter_kmin);
 		}
 	}
 	if (c->knobs.scatter_plain) { // RNB_SCATTER_PLAIN=1: every level through the plain kernel, one atomic per corner and sample -- the reference's own scatter structure (grid.h:366-495)
@@ -1342,7 +1196,6 @@ int optimizer_step(rnb_ctx* c, hipStream_t s) {
 	{ const int rc = optimizer_begin(c); if (rc != RNB_OK) return rc; }
 	c->prof.mark(s, P_NONE);
 	const bool chunked = !c->opt.early_done && c->overlap() && !c->sc.dp && c->sc.valid && !c->sc.exchanged;
-	if (c->sc.c_side && !(chunked && !c->sc.dw_joined)) flush_c_side(c, s); // only the path below that continues on the weight-gradient stream takes group C with it
 	if (!c->sc.dw_joined && !chunked) {
 		HIP_TRY(hipStreamWaitEvent(s, c->ev_dw, 0)); // the paths below step the MLPs on `s`
 		c->sc.dw_joined = true;
@@ -1357,21 +1210,13 @@ int optimizer_step(rnb_ctx* c, hipStream_t s) {
 		// The update is independent per parameter, so each scatter group's levels are stepped as soon as that group is done,
 		// on the side stream, beside the scatter of the next group; only the last half of group A is left for the end.
 		hipStream_t sa = c->s_adam;
-		if (c->sc.c_early) adam_launch(c, sa, c->off_grid, c->sc.split[1]); // group C's levels right behind their scatter on this stream
 		if (c->sc.order == 0) {
 			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[0], 0));
 			adam_launch(c, sa, c->sc.split[1], c->sc.split[0]);  // group B's levels, beside the scatter of group A
 			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[1], 0));
 			adam_launch(c, sa, c->sc.split[0], c->sc.split_mid);        // group A's levels, first half beside the second half's scatter
-			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[3], 0));
+			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[2], 0));
 			adam_launch(c, sa, c->sc.split_mid, c->off_var, c->ev_adam);
-		} else if (c->sc.order == 1) {
-			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[1], 0));
-			adam_launch(c, sa, c->sc.split[0], c->sc.split_mid);
-			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[3], 0));
-			adam_launch(c, sa, c->sc.split_mid, c->off_var);
-			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[0], 0));
-			adam_launch(c, sa, c->sc.split[1], c->sc.split[0], c->ev_adam);
 		} else {
 			HIP_TRY(hipStreamWaitEvent(sa, c->ev_sc[1], 0));
 			adam_launch(c, sa, c->sc.split[0], c->off_var);
@@ -1379,7 +1224,7 @@ int optimizer_step(rnb_ctx* c, hipStream_t s) {
 			adam_launch(c, sa, c->sc.split[1], c->sc.split[0], c->ev_adam);
 		}
 		if (c->sc.dw_joined) {
-			adam_launch(c, s, 0, c->sc.c_early ? c->off_grid : c->sc.split[1]); // MLPs + group C's levels (contiguous), variance; s has joined the side stream
+			adam_launch(c, s, 0, c->sc.split[1]); // MLPs + group C's levels (contiguous), variance; s has joined the side stream
 			adam_launch(c, s, c->off_var, c->n_params);
 		} else {
 			// behind the dW GEMMs on their stream: the MLPs' and the variance's parameters, then the LDS weight images of the next
@@ -1387,37 +1232,15 @@ int optimizer_step(rnb_ctx* c, hipStream_t s) {
 			hipStream_t sd = c->s_dw;
 			adam_launch(c, sd, 0, c->off_grid);
 			adam_launch(c, sd, c->off_var, c->n_params);
-			const bool c_side = c->sc.c_side;
-			c->sc.c_side = false;
-			LAUNCH_EV(k_prepare_weight_images, dim3(WIMG_WGS, 4), dim3(WG), 0, sd, c_side ? nullptr : c->ev_tail, c->net(false), c->wimg_fwd.p, c->wimg_fbs.p, c->wimg_train.p, c->wimg_rgb.p, c->half_acc() ? 1 : 0);
+			LAUNCH_EV(k_prepare_weight_images, dim3(WIMG_WGS, 4), dim3(WG), 0, sd, c->ev_tail, c->net(false), c->wimg_fwd.p, c->wimg_fbs.p, c->wimg_train.p, c->wimg_rgb.p, c->half_acc() ? 1 : 0);
 			images_done = true;
-			if (c_side) { // group C + its optimizer chunk end this stream (ev_tail); the critical stream is idle behind its last atomic group
-				HIP_TRY(hipStreamWaitEvent(sd, c->sc.c_after, 0));
-				c->sc.c_launch(sd, nullptr);
-				adam_launch(c, sd, c->off_grid, c->sc.split[1], c->ev_tail);
-				// the joins, in the order the events are expected to fire, so that only the last packet's latency is left when the last of them has: the march (queued already?), then by batch shape
-				// the optimizer's stream and this one
-				if (c->pre.valid) { HIP_TRY(hipStreamWaitEvent(s, c->ev_march, 0)); c->pre.march_joined = true; }
-				if (c->sc.order == 2) { HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); HIP_TRY(hipStreamWaitEvent(s, c->ev_adam, 0)); }
-				else { HIP_TRY(hipStreamWaitEvent(s, c->ev_adam, 0)); HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); }
-				c->sc.dw_joined = true;
-				return optimizer_finish(c, s, images_done);
-			}
-			if (!c->sc.c_early) adam_launch(c, s, c->off_grid, c->sc.split[1]);
+			adam_launch(c, s, c->off_grid, c->sc.split[1]);
 			// the join with the side stream: on the next step's march stream if that march is queued after this call (launch_premarch), else here
-			if (c->knobs.join_fold && c->pre.valid) { // the march of the next step is queued already (ev_march is recorded): the weight-gradient stream, idle behind its weight images, takes the joins (rnb_ctx::join_pending)
-				HIP_TRY(hipStreamWaitEvent(sd, c->ev_adam, 0));
-				HIP_TRY(hipStreamWaitEvent(sd, c->ev_march, 0));
-				HIP_TRY(hipEventRecord(c->ev_join, sd));
-				c->join_pending = true;
-				c->sc.dw_joined = true;
-				return optimizer_finish(c, s, images_done);
-			}
-			if (c->knobs.defer_tail && !c->pre.valid && !prep_due(c->cur_step + 1)) c->tail_pending = true;
-			else if (!c->knobs.unsafe_skip_joins) HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0));
+			if (!c->pre.valid && !prep_due(c->cur_step + 1)) c->tail_pending = true;
+			else HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0));
 			c->sc.dw_joined = true;
 		}
-		if (!c->knobs.unsafe_skip_joins) HIP_TRY(hipStreamWaitEvent(s, c->ev_adam, 0));
+		HIP_TRY(hipStreamWaitEvent(s, c->ev_adam, 0));
 	} else {
 		adam_launch(c, s, 0, c->n_params);
 	}
@@ -1512,7 +1335,7 @@ int rnb_destroy(rnb_ctx* c) try {
 	c->prof.destroy();
 	if (c->s_march) { (void)hipStreamSynchronize(c->s_march); (void)hipStreamDestroy(c->s_march); }
 	for (hipStream_t st : {c->s_dw, c->s_adam}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-	for (hipEvent_t e : {c->ev_join, c->ev_loss, c->ev_march, c->ev_fb, c->ev_dw, c->ev_adam, c->ev_tail, c->ev_march_rest, c->ev_all, c->ev_grid, c->ev_gs, c->ev_sc[0], c->ev_sc[1], c->ev_sc[2], c->ev_sc[3]}) if (e) (void)hipEventDestroy(e);
+	for (hipEvent_t e : {c->ev_loss, c->ev_march, c->ev_fb, c->ev_dw, c->ev_adam, c->ev_tail, c->ev_march_rest, c->ev_all, c->ev_grid, c->ev_gs, c->ev_sc[0], c->ev_sc[1], c->ev_sc[2]}) if (e) (void)hipEventDestroy(e);
 	if (c->host_rb) (void)hipHostFree(c->host_rb);
 	if (c->host_coarse) (void)hipHostFree(c->host_coarse);
 	delete c;
@@ -1630,13 +1453,8 @@ int rnb_create(const rnb_config* cfg, rnb_ctx** out) try {
 	HIP_TRY_C(hipMemset(c->mlp_out.p, 0, c->mlp_out.bytes()));
 	int rc = reset_optimizer_state(c);
 	if (rc != RNB_OK) { rnb_destroy(c); return rc; }
-	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
-	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_emul), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_emul_pipe<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
-	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_pipe<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_pipe<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
-	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_pipe<7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
-	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_pipe<4, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_TRAIN));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_full), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS_FULL));
@@ -1653,8 +1471,6 @@ int rnb_create(const rnb_config* cfg, rnb_ctx** out) try {
 		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count<true>), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max));
 		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count_wide<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max));
 		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count_wide<64, true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max));
-		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count_skip<256>), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max + (int)(COARSE_WORDS * sizeof(uint32_t))));
-		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count_skip<512>), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max + (int)(COARSE_WORDS * sizeof(uint32_t))));
 		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count_skip<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max + (int)(COARSE_WORDS * sizeof(uint32_t))));
 		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count_skip_narrow), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max + (int)(COARSE_WORDS * sizeof(uint32_t))));
 		HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_march_count_bbox), hipFuncAttributeMaxDynamicSharedMemorySize, march_lds_max));
@@ -1675,64 +1491,24 @@ HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_scatter_lds),
 		k.march_narrow = getenv("RNB_MARCH_NARROW") != nullptr; k.fwd_bwd_generic = getenv("RNB_FWD_BWD_GENERIC") != nullptr;
 		k.loss_wave_per_ray = getenv("RNB_LOSS_WAVE_PER_RAY") != nullptr; // the loss passes with one wavefront per ray whatever the batch (A/B, tests)
 		k.dp_order = getenv("RNB_DP_FORCE_COLLECTIVES") != nullptr;
-		k.march_late = getenv("RNB_MARCH_LATE") != nullptr;
-		k.march_running_sums = getenv("RNB_MARCH_RUNNING_SUMS") != nullptr;
 		if (const char* e = getenv("RNB_MARCH_NARROW_FROM")) k.march_narrow_from = (uint32_t)atoi(e);
-		if (const char* e = getenv("RNB_SCATTER_WG_PER_CU")) k.scatter_wg_per_cu = std::max(0, atoi(e));
-		if (const char* e = getenv("RNB_FBS_WG_PER_CU")) k.fbs_wg_per_cu = (uint32_t)std::max(1, std::min(2, atoi(e)));
 		if (const char* e = getenv("RNB_GRID_PRESORT")) k.grid_presort = atoi(e) != 0;
-		if (const char* e = getenv("RNB_FUSED_UPDATE")) k.fused_update = atoi(e) != 0;
-		if (const char* e = getenv("RNB_POLL_LOSS")) k.poll_loss = atoi(e) != 0;
-		if (const char* e = getenv("RNB_DEFER_TAIL")) k.defer_tail = atoi(e) != 0;
-		if (const char* e = getenv("RNB_JOIN_FOLD")) k.join_fold = atoi(e) != 0;
-		if (const char* e = getenv("RNB_SCATTER_C_SIDE")) k.scatter_c_side = atoi(e) != 0;
-		if (const char* e = getenv("RNB_UNSAFE_SKIP_JOINS")) k.unsafe_skip_joins = atoi(e) != 0;
-		if (const char* e = getenv("RNB_MARCH_WAVE_PER_RAY_BELOW")) k.march_wave_per_ray_below = (uint32_t)atoi(e);
-		if (const char* e = getenv("RNB_SCATTER_ORDER")) k.scatter_order = std::max(-1, std::min(2, atoi(e)));
-		if (const char* e = getenv("RNB_SCAN_CHAIN")) k.scan_chain = atoi(e) != 0;
 		if (const char* e = getenv("RNB_LOSS_SCAN_FUSED")) { k.loss_scan_fused = atoi(e) != 0; k.loss_scan_fused_always = atoi(e) == 2; }
 		if (const char* e = getenv("RNB_LOSS_FLAT")) k.loss_flat = atoi(e) != 0;
 		if (const char* e = getenv("RNB_LOSS_CHAIN_RECORDS")) k.loss_chain_records = atoi(e) != 0;
-		if (const char* e = getenv("RNB_RAY_CONST_DENSE")) k.ray_const_dense = atoi(e);
-		if (const char* e = getenv("RNB_MARCH_WRITE_SPLIT")) k.march_write_split = atoi(e) != 0 ? 1 : 0;
 		if (const char* e = getenv("RNB_SCATTER_PLAIN")) k.scatter_plain = atoi(e) != 0;
-		if (const char* e = getenv("RNB_MARCH_NARROW_WGS")) { const int w = atoi(e); k.march_narrow_wgs = (w == 64 || w == 256 || w == 512) ? (uint32_t)w : 128u; }
-		if (const char* e = getenv("RNB_MARCH_WGS")) { const int w = atoi(e); k.march_wgs = (w == 256 || w == 512) ? w : 1024; }
-		if (const char* e = getenv("RNB_MARCH_WRITE_WG")) { const int w = atoi(e); k.march_write_wg = (w == 1024 || w == 128 || w == 64) ? w : 256; }
-		if (const char* e = getenv("RNB_CHAIN_PLAIN")) k.chain_plain = atoi(e) != 0;
-		if (const char* e = getenv("RNB_POINT_XCD")) k.point_xcd = atoi(e) != 0;
 		if (const char* e = getenv("RNB_DW_SLICED")) k.dw_sliced = atoi(e) != 0;
-		if (const char* e = getenv("RNB_ENCODE_PAIR")) k.encode_pair = atoi(e) != 0;
-		if (const char* e = getenv("RNB_ENCODE_DEPTH")) { const int d = atoi(e); k.encode_depth = (d == 0 || d == 2 || d == 4 || d == 7) ? d : 4; }
-		if (const char* e = getenv("RNB_DEBUG_SCATTER_LEVELS")) { int lo = -1, hi = -1; if (sscanf(e, "%d,%d", &lo, &hi) == 2 && lo >= 0 && hi > lo) { k.dbg_scatter_lo = lo; k.dbg_scatter_hi = hi; } }
-		if (const char* e = getenv("RNB_SCATTER_C_EARLY")) k.scatter_c_early = atoi(e) != 0;
-		if (const char* e = getenv("RNB_SCATTER_RL_STAGED")) k.scatter_rl_staged = atoi(e) != 0 ? 1 : 0;
-		if (const char* e = getenv("RNB_SCATTER_ANYORDER")) k.scatter_anyorder = atoi(e) != 0;
-		if (const char* e = getenv("RNB_SCATTER_SHARE")) k.scatter_share = atoi(e) != 0;
 		if (const char* e = getenv("RNB_MARCH_SKIP")) k.march_skip = std::max(0, std::min(2, atoi(e)));
 		if (const char* e = getenv("RNB_MARCH_SKIP_NARROW")) k.march_skip_narrow = atoi(e) != 0;
-		if (const char* e = getenv("RNB_SCATTER_PRIO")) k.scatter_prio = std::max(0, std::min(3, atoi(e)));
-		if (const char* e = getenv("RNB_MARCH_PRIO")) k.march_prio = std::max(0, std::min(3, atoi(e)));
 		if (const char* e = getenv("RNB_MARCH_BBOX")) k.march_bbox = std::max(0, std::min(2, atoi(e)));
-		if (const char* e = getenv("RNB_DW_LATE")) k.dw_late = atoi(e) != 0;
-		if (const char* e = getenv("RNB_SCATTER_KMIN")) k.scatter_kmin = std::max(0, std::min(16, atoi(e)));
-		if (const char* e = getenv("RNB_SCATTER_RL_UPTO")) k.scatter_rl_upto = std::max(0, std::min(14, atoi(e)));
 	}
 	plan_scatter_groups(c);
-	{ // RNB_STREAM_PRIO="march,dw,adam" (A/B): HIP stream priorities of the three side streams (0 = normal, -1 = high, 1 = low)
-		int pr[3] = {0, 0, 0};
-		if (const char* e = getenv("RNB_STREAM_PRIO")) sscanf(e, "%d,%d,%d", &pr[0], &pr[1], &pr[2]);
-		hipStream_t* st[3] = {&c->s_march, &c->s_dw, &c->s_adam};
-		for (int i = 0; i < 3; ++i) {
-			if (pr[i] == 0) HIP_TRY_C(hipStreamCreateWithFlags(st[i], hipStreamNonBlocking));
-			else HIP_TRY_C(hipStreamCreateWithPriority(st[i], hipStreamNonBlocking, pr[i]));
-		}
-	}
+	for (hipStream_t* st : {&c->s_march, &c->s_dw, &c->s_adam}) HIP_TRY_C(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
 	// ev_loss publishes the step's counters to the HOST (system-scope release). The others only order kernels on this device:
 	// without the system-scope fence the queue is spared a cache writeback + invalidate at each of them.
 	HIP_TRY_C(hipEventCreateWithFlags(&c->ev_loss, hipEventDisableTiming));
 	const unsigned dev_flags = hipEventDisableTiming | (unsigned)hipEventDisableSystemFence;
-	for (hipEvent_t* e : {&c->ev_join, &c->ev_march, &c->ev_fb, &c->ev_dw, &c->ev_adam, &c->ev_tail, &c->ev_march_rest, &c->ev_all, &c->ev_grid, &c->ev_gs, &c->ev_sc[0], &c->ev_sc[1], &c->ev_sc[2], &c->ev_sc[3]}) HIP_TRY_C(hipEventCreateWithFlags(e, dev_flags));
+	for (hipEvent_t* e : {&c->ev_march, &c->ev_fb, &c->ev_dw, &c->ev_adam, &c->ev_tail, &c->ev_march_rest, &c->ev_all, &c->ev_grid, &c->ev_gs, &c->ev_sc[0], &c->ev_sc[1], &c->ev_sc[2]}) HIP_TRY_C(hipEventCreateWithFlags(e, dev_flags));
 	HIP_TRY_C(hipHostMalloc(reinterpret_cast<void**>(&c->host_rb), sizeof(*c->host_rb), hipHostMallocMapped));
 	std::memset(c->host_rb, 0, sizeof(*c->host_rb)); // (a recycled pinned block may hold a previous context's sequence word: wait_loss_readback would take it for this context's first step)
 	HIP_TRY_C(hipHostGetDevicePointer(&c->host_rb_dev, c->host_rb, 0));
@@ -1836,7 +1612,6 @@ int rnb_set_params(rnb_ctx* c, const float* params) try {
 
 int rnb_buffer(rnb_ctx* c, int id, void** ptr, uint64_t* n_bytes) try {
 	if (!c || !ptr || !n_bytes) return fail(RNB_ERR_INVALID, "null argument");
-	flush_c_side(c, c->backward_stream); // (a gradient vector asked for between a training step's backward pass and its optimizer)
 #define BUF(b) do { *ptr = (void*)(b).p; *n_bytes = (b).bytes(); return RNB_OK; } while (0)
 	const bool read_only = (id & RNB_BUF_READONLY) != 0;
 	id &= ~RNB_BUF_READONLY;
@@ -1846,7 +1621,7 @@ int rnb_buffer(rnb_ctx* c, int id, void** ptr, uint64_t* n_bytes) try {
 		if (rc != RNB_OK) return rc;
 		if (!read_only) c->opt_rec_current = false;
 	}
-	if (c->join_pending || id == RNB_BUF_PARAMS_FP16 || id == RNB_BUF_PARAMS_EMA) join_tail_host(c); // both are written by the side stream's optimizer launch (ev_tail)
+	if (id == RNB_BUF_PARAMS_FP16 || id == RNB_BUF_PARAMS_EMA) join_tail_host(c); // both are written by the side stream's optimizer launch (ev_tail)
 	if (!read_only) { // a possible write before the caller's next call: drop the cached forms now (a kept pointer written later: rnb_params_changed / rnb_bitfield_changed)
 		if (id == RNB_BUF_PARAMS_FP16) c->wimg_valid = false;
 		else if (id == RNB_BUF_DENSITY_BITFIELD) { discard_premarch(c); c->coarse_valid = false; c->gs_pre.valid = false; c->bitfield_foreign = true; }
@@ -2206,7 +1981,6 @@ int rnb_optimizer_step(rnb_ctx* c, void* stream) try {
 
 // Drops samples generated ahead of time for a step whose inputs have since changed (controller, flags, bitfield ...).
 static void discard_premarch(rnb_ctx* c) {
-	c->pre.march_joined = false;
 	if (!c->pre.valid) return;
 	(void)hipStreamSynchronize(c->s_march);
 	c->n_rays_total = c->pre.n_rays_total;
@@ -2224,8 +1998,6 @@ static uint32_t next_max_inference(rnb_ctx* c) { // testbed_nerf.cu:3891-3896
 // Occupancy update (when due), ray generation + march, network evaluation of all samples, loss + compaction.
 static int step_front(rnb_ctx* c, hipStream_t s) {
 	c->valid_level = compute_valid_level(c->cfg, (int)c->training_step); // testbed.cu:2792
-	const bool joined = c->join_pending; // ev_join: the optimizer's and the weight images' streams of the previous step AND ev_march
-	if (c->join_pending) { HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0)); c->join_pending = false; }
 	if (c->tail_pending) { HIP_TRY(hipStreamWaitEvent(s, c->ev_tail, 0)); c->tail_pending = false; } // no march was queued behind the optimizer to take the join
 	c->grid_updated = false;
 	c->prep_ms = 0.f;
@@ -2249,14 +2021,13 @@ static int step_front(rnb_ctx* c, hipStream_t s) {
 	const uint32_t n_rays = c->rays_per_batch;
 	if (c->pre.valid && (c->pre.n_rays != n_rays || c->pre.max_inference != max_inference)) discard_premarch(c);
 	uint32_t n_rays_total;
-	bool join_rest = false; // the second k_march_write of a march generated ahead is still to be waited for (knobs.march_write_split)
+	bool join_rest = false; // the second k_march_write of a march generated ahead is still to be waited for (rnb_ctx::gen_split)
 	if (c->pre.valid) { // generated beside the previous step's backward pass
 		n_rays_total = c->pre.n_rays_total;
 		c->pre.valid = false;
 		c->cur_k1 = c->pre.k1;
 		join_rest = c->pre.split;
-		if (!joined && !c->pre.march_joined && !c->knobs.unsafe_skip_joins) HIP_TRY(hipStreamWaitEvent(s, c->ev_march, 0));
-		c->pre.march_joined = false;
+		HIP_TRY(hipStreamWaitEvent(s, c->ev_march, 0));
 	} else {
 		n_rays_total = c->n_rays_total;
 		c->n_rays_total += n_rays * c->cfg.world_size;
@@ -2330,7 +2101,7 @@ static int launch_reduce_losses(rnb_ctx* c, hipStream_t s) {
 static int launch_premarch(rnb_ctx* c) {
 	if (!c->overlap() || c->pre.valid || prep_due(c->cur_step + 1)) return RNB_OK; // cur_step + 1: _finish may run before _apply
 	const uint32_t n_rays = c->rays_per_batch, max_inference = next_max_inference(c), n_rays_total = c->n_rays_total;
-	// The march starts right after the loss pass, i.e. beside k_fwd_bwd (RNB_MARCH_LATE=1: only when k_fwd_bwd is done). History,
+	// The march starts right after the loss pass, i.e. beside k_fwd_bwd. History,
 	// measured with tools/march_determinism.py: an earlier 16-lanes-per-ray kernel, which carried the index of the next visited
 	// position in four more ballot masks (SGPR pairs, spilled through VGPR lanes) and used packed fp32 instructions, came out
 	// beside k_fwd_bwd with a wrong direction for a few rays (wavefront lanes 48-63 only) in 2-3 % of the launches, 26-54 % beside
@@ -2345,7 +2116,7 @@ static int launch_premarch(rnb_ctx* c) {
 	// Albedo mode: always. Its two training kernels (k_rgb_fwd_bwd: one wavefront per SIMD with ~470 registers; k_fwd_bwd_sdf_full: two with 256) and the march
 	// exclude each other on a SIMD; a march that has started beside the first keeps the second at half occupancy (253 instead of 113 us, the step 0.79 instead of
 	// 0.76 ms). Behind them it runs beside the scatter, as it effectively does with --no-albedo, where k_fwd_bwd_sdf claims the registers first.
-	if (c->knobs.march_late || c->rgb_split()) HIP_TRY(hipStreamWaitEvent(c->s_march, c->ev_fb, 0));
+	if (c->rgb_split()) HIP_TRY(hipStreamWaitEvent(c->s_march, c->ev_fb, 0));
 	int rc = generate_training_samples(c, c->s_march, n_rays, n_rays_total, max_inference, c->ev_march, c->tail_pending ? c->ev_tail : nullptr, c->ev_march_rest,
 	                                   // the loss sums were published from INSIDE k_loss_pass2_samples (workgroup 0), whose other workgroups may still be reading the step's sample buffers when the host
 	                                   // gets here: k_march_count touches none of them, everything behind it waits for k_fwd_bwd*'s completion (same stream as the loss pass, behind it)
@@ -2354,7 +2125,6 @@ static int launch_premarch(rnb_ctx* c) {
 	c->tail_pending = false; // the next step reaches ev_tail through ev_march
 	c->pre.loss_cleared = true;
 	c->n_rays_total += n_rays * c->cfg.world_size;
-	c->pre.march_joined = false;
 	c->pre.valid = true; c->pre.n_rays = n_rays; c->pre.n_rays_total = n_rays_total; c->pre.max_inference = max_inference; c->pre.k1 = c->gen_k1; c->pre.split = c->gen_split;
 	return RNB_OK;
 }
@@ -2569,7 +2339,6 @@ int rnb_set_controller(rnb_ctx* c, uint32_t training_step, uint32_t rays_per_bat
 
 int rnb_gradient_parts(rnb_ctx* c, uint64_t ranges[3][2], uint32_t* n_parts) try {
 	if (!c || !ranges || !n_parts) return fail(RNB_ERR_INVALID, "null argument");
-	flush_c_side(c, c->backward_stream); // (a caller that exchanges gradients: group C belongs to the backward pass's stream again)
 	c->sc.exchanged = true; // the caller sums gradients across ranks: the optimizer must not start on a block before its exchange
 	if (c->sc.valid && c->sc.dp) { // scatter order C, B, A1, A2: everything in front of A's levels is final first (ev_sc[0]), then A1 (ev_sc[1])
 		const bool mid = c->sc.split_mid > c->sc.split[0] && c->sc.split_mid < c->off_var;
@@ -2590,13 +2359,11 @@ int rnb_gradient_parts(rnb_ctx* c, uint64_t ranges[3][2], uint32_t* n_parts) try
 
 int rnb_train_step_apply_early(rnb_ctx* c, void* stream) try {
 	if (!c) return fail(RNB_ERR_INVALID, "null ctx");
-	flush_c_side(c, c->backward_stream);
 	return optimizer_step_early(c, as_stream(stream));
 } RNB_GUARD
 
 int rnb_shard_layout(rnb_ctx* c, rnb_shard_part parts[RNB_MAX_SHARD_PARTS], uint32_t* n_parts, uint64_t* capacity) try {
 	if (!c || !parts || !n_parts || !capacity) return fail(RNB_ERR_INVALID, "null argument");
-	flush_c_side(c, c->backward_stream);
 	c->sc.exchanged = true;
 	c->sc.sharded = true;
 	shard_layout(c, parts, n_parts);
@@ -2606,7 +2373,6 @@ int rnb_shard_layout(rnb_ctx* c, rnb_shard_part parts[RNB_MAX_SHARD_PARTS], uint
 
 int rnb_train_step_apply_shard(rnb_ctx* c, uint32_t part, void* stream) try {
 	if (!c) return fail(RNB_ERR_INVALID, "null ctx");
-	flush_c_side(c, c->backward_stream);
 	return optimizer_step_shard(c, part, as_stream(stream));
 } RNB_GUARD
 
@@ -2621,7 +2387,6 @@ int rnb_train_step_apply_done(rnb_ctx* c, void* stream) try {
 
 int rnb_gradient_part_wait(rnb_ctx* c, uint32_t part, void* stream) try {
 	if (!c) return fail(RNB_ERR_INVALID, "null ctx");
-	flush_c_side(c, c->backward_stream);
 	// blocks 0 (and, in the data-parallel order, 1 = the first half of the fine levels) of the overlapped schedule have their own events; everything is final at the
 	// end of the backward pass
 	const bool early = part == 0 && c->sc.valid && (c->sc.dp || !c->sc.sharded);
