@@ -5,6 +5,9 @@ with -ffp-contract=off, so every product and sum rounds on its own, as numpy's d
 truncation toward zero for the cells. The march therefore finds the same samples, bit for bit. The composite follows composite_kernel_nerf (NeuS alpha,
 Normals / Depth modes) and shade_kernel_nerf; its transcendental functions differ from the device's in the last bits.
 
+The box is the scene's: [0.5 - s / 2, 0.5 + s / 2]^3 for aabb_scale s, with the cone angle 1 / 256 beyond the unit cube (dt = calc_dt(t) grows with t and picks
+a coarser occupancy cascade through mip_from_dt).
+
 Each ray is marched to the box exit in one go (the per-ray result does not depend on the rounds the library splits it into), the network is a callback
 net(coords float32 [n, 7]) -> float16 [n, 16] -- an analytic SDF (analytic_net) or the CPU checker's forward_infer on the same parameters.
 """
@@ -72,12 +75,23 @@ def _exponent(x):
     return np.frexp(x.astype(np.float32))[1]
 
 
-def mip_from_dt(dt, pos):
+def calc_dt(t, cone):
+    """testbed_nerf.cu:153-155: the step at distance t, MIN_STEP for cone angle 0."""
+    return np.fmin(np.fmax(t * f32(cone), MIN_STEP), MAX_STEP).astype(np.float32)
+
+
+def mip_from_pos(pos, max_cascade=CASCADES - 1):
     maxval = np.fmax(np.fmax(np.abs(pos[:, 0] - f32(0.5)), np.abs(pos[:, 1] - f32(0.5))), np.abs(pos[:, 2] - f32(0.5)))
-    mip = np.minimum(CASCADES - 1, np.maximum(0, _exponent(maxval) + 1))
+    return np.minimum(max_cascade, np.maximum(0, _exponent(maxval) + 1))
+
+
+def mip_from_dt(dt, pos, max_cascade=CASCADES - 1):
+    """testbed_nerf.cu:576-583. The tracer calls it without a max_cascade (generate_next_nerf_network_inputs, :863), so the clamp is CASCADES - 1 whatever the
+    scene's aabb_scale: a cascade beyond the scene's own is consulted where dt or the position asks for it."""
+    mip = mip_from_pos(pos, max_cascade)
     d = dt * f32(2 * GRIDSIZE)
     big = d >= f32(1)
-    return np.where(big, np.minimum(CASCADES - 1, np.maximum(_exponent(np.where(big, d, f32(1))), mip)), mip)
+    return np.where(big, np.minimum(max_cascade, np.maximum(_exponent(np.where(big, d, f32(1))), mip)), mip)
 
 
 def _expand(v):
@@ -93,37 +107,48 @@ def morton3d(x, y, z):
     return _expand(x) | (_expand(y) << np.uint32(1)) | (_expand(z) << np.uint32(2))
 
 
-def occupied(pos, bitfield, mip):
+def cell_index(pos, mip):
+    """cascaded_grid_idx_at (testbed_nerf.cu:439-451): the Morton index of the position's cell in cascade mip."""
     scale = np.ldexp(np.ones(len(pos), np.float32), -mip).astype(np.float32)
     p = ((pos - f32(0.5)) * scale[:, None] + f32(0.5)).astype(np.float32)
     # (int)(p * 128): truncation toward zero, then the clamp to the grid
     idx3 = np.clip(np.trunc(p * f32(GRIDSIZE)).astype(np.int64), 0, GRIDSIZE - 1)
-    idx = morton3d(idx3[:, 0], idx3[:, 1], idx3[:, 2]).astype(np.int64)
+    return morton3d(idx3[:, 0], idx3[:, 1], idx3[:, 2]).astype(np.int64)
+
+
+def occupied(pos, bitfield, mip):
+    idx = cell_index(pos, mip)
     byte = bitfield[idx // 8 + (GRIDSIZE ** 3 * mip.astype(np.int64)) // 8]
     return (byte >> (idx % 8).astype(np.uint8)) & 1 != 0
 
 
-def advance_to_next_voxel(t, pos, d, idir, res):
+def distance_to_next_voxel(pos, d, idir, res):
     resf = res.astype(np.float32)
     p = resf[:, None] * pos
     sgn = np.where(np.signbit(d), f32(-1), f32(1)).astype(np.float32)
     with np.errstate(invalid="ignore"):
         tt = (np.floor(p + f32(0.5) + f32(0.5) * sgn) - p) * idir
     tm = np.fmin(np.fmin(tt[:, 0], tt[:, 1]), tt[:, 2])  # fminf / fmaxf: a NaN operand (an axis-parallel direction) loses
-    dist = np.fmax(tm / resf, f32(0))
-    target = t + dist
-    t = t + MIN_STEP  # calc_dt with cone angle 0 (aabb_scale 1)
+    return np.fmax(tm / resf, f32(0)).astype(np.float32)
+
+
+def advance_to_next_voxel(t, pos, d, idir, res, cone=0.0):
+    """testbed_nerf.cu:311-323: steps of calc_dt(t) -- growing with t under a cone angle -- until the next voxel of the res^3 grid is reached."""
+    target = t + distance_to_next_voxel(pos, d, idir, res)
+    t = t + calc_dt(t, cone)
     go = t < target
     while go.any():
-        t = np.where(go, t + MIN_STEP, t)
+        t = np.where(go, t + calc_dt(t, cone), t)
         go = go & (t < target)
     return t.astype(np.float32)
 
 
-def march(o, d, bitfield, near=0.2, mn=0.0, mx=1.0):
-    """Every ray to the box exit (at most MAX_STEPS samples). Returns (ray index [S], coords float32 [S, 7]) in ray order, samples of a ray in march order,
-    and n_samples per ray. bitfield None = every cell occupied. Single cascade, cone angle 0 (aabb_scale 1, the scenes this project trains)."""
+def march(o, d, bitfield, near=0.2, mn=0.0, mx=1.0, cone=0.0, stats=None):
+    """Every ray to the exit of the box [mn, mx]^3 (at most MAX_STEPS samples). Returns (ray index [S], coords float32 [S, 7]) in ray order, samples of a ray
+    in march order, and n_samples per ray. bitfield None = every cell occupied. cone: the cone angle of the step, dt = calc_dt(t, cone). stats: a dict that
+    receives `mips`, how often each cascade was consulted (one count per position the march looked at, occupied or not)."""
     n = len(o)
+    mips = np.zeros(CASCADES, np.int64)
     mn, mx = f32(mn), f32(mx)
     diag = f32(mx - mn)
     tmin = ray_box(o, d, mn, mx)
@@ -141,8 +166,9 @@ def march(o, d, bitfield, near=0.2, mn=0.0, mx=1.0):
         inside = contains(pos, mn, mx)
         alive[a[~inside]] = False
         a, ta, pos = a[inside], ta[inside], pos[inside]
-        dt = np.full(len(a), MIN_STEP, np.float32)
+        dt = calc_dt(ta, cone)
         mip = mip_from_dt(dt, pos)
+        mips += np.bincount(mip, minlength=CASCADES)
         occ = np.ones(len(a), bool) if bitfield is None else occupied(pos, bitfield, mip)
         e = a[occ]
         if len(e):
@@ -158,7 +184,9 @@ def march(o, d, bitfield, near=0.2, mn=0.0, mx=1.0):
             alive[e[cnt[e] >= MAX_STEPS]] = False
         s = a[~occ]
         if len(s):
-            t[s] = advance_to_next_voxel(ta[~occ], pos[~occ], d[s], idir[s], (GRIDSIZE >> mip[~occ]).astype(np.int64))
+            t[s] = advance_to_next_voxel(ta[~occ], pos[~occ], d[s], idir[s], (GRIDSIZE >> mip[~occ]).astype(np.int64), cone)
+    if stats is not None:
+        stats["mips"] = mips
     if ray_ids:
         rid = np.concatenate(ray_ids)
         co = np.concatenate(coords)
@@ -171,8 +199,10 @@ def _logistic(x):
     return (1.0 / (1.0 + np.exp(-x.astype(np.float64)))).astype(np.float32)
 
 
-def composite(view, o, rid, coords, out, n_rays, min_transmittance=0.01, no_albedo=False, mn=0.0, mx=1.0):
-    """composite_kernel_nerf (testbed_nerf.cu:881-1118) in Normals + Depth modes and shade_kernel_nerf: float32 [n_rays, 9] in the channel order of rnb_render.h."""
+def composite(view, o, rid, coords, out, n_rays, min_transmittance=0.01, no_albedo=False, mn=0.0, mx=1.0, stats=None):
+    """composite_kernel_nerf (testbed_nerf.cu:881-1118) in Normals + Depth modes and shade_kernel_nerf: float32 [n_rays, 9] in the channel order of rnb_render.h.
+    stats: a dict that receives `wmax` and `w2`, the largest and the second largest weight of every ray (the depth is the largest one's: where the two are
+    close, another rounding of the network may pick the other sample)."""
     out = out.astype(np.float32)
     counts = np.bincount(rid, minlength=n_rays)
     first = np.concatenate([[0], np.cumsum(counts)[:-1]])
@@ -184,6 +214,7 @@ def composite(view, o, rid, coords, out, n_rays, min_transmittance=0.01, no_albe
     N = np.zeros((n_rays, 3), np.float32)
     A = np.zeros((n_rays, 3), np.float32)
     wmax = np.zeros(n_rays, np.float32)
+    w2 = np.zeros(n_rays, np.float32)
     depth = np.zeros(n_rays, np.float32)
     nsamp = np.zeros(n_rays, np.int64)
     live = counts > 0
@@ -219,12 +250,15 @@ def composite(view, o, rid, coords, out, n_rays, min_transmittance=0.01, no_albe
         better = weight > wmax[r]
         pos = c[:, 0:3] * diag + f32(mn)
         dep = esum3(fwd[0] * (pos[:, 0] - o[r, 0]), fwd[1] * (pos[:, 1] - o[r, 1]), fwd[2] * (pos[:, 2] - o[r, 2]))
+        w2[r] = np.where(better, wmax[r], np.maximum(w2[r], weight))
         wmax[r] = np.where(better, weight, wmax[r])
         depth[r] = np.where(better, dep, depth[r])
         if min_transmittance > 0:
             stop = W[r] > f32(1) - f32(min_transmittance)
             stopped[r[stop]] = True
             live[r[stop]] = False
+    if stats is not None:
+        stats["wmax"], stats["w2"] = wmax, w2
     res = np.zeros((n_rays, CHANNELS), np.float32)
     hit = W > 0
     nn = np.sqrt(esum3(N[:, 0] * N[:, 0], N[:, 1] * N[:, 1], N[:, 2] * N[:, 2]))
@@ -238,22 +272,35 @@ def composite(view, o, rid, coords, out, n_rays, min_transmittance=0.01, no_albe
     return res
 
 
-def render(view, net, bitfield=None, min_transmittance=0.01, near=0.2, no_albedo=False, chunk=1 << 16):
-    """The whole tracer: float32 [H, W, 9] (the layout of rnb_render) and the number of network samples."""
+def scene_box(aabb_scale=1):
+    """The box and the cone angle of a scene (testbed_nerf.cu:3198-3214): [0.5 - s / 2, 0.5 + s / 2]^3, cone angle 0 for s <= 1 and 1 / 256 beyond."""
+    s = f32(min(1 << (CASCADES - 1), int(aabb_scale)))
+    return f32(f32(0.5) - f32(0.5) * s), f32(f32(0.5) + f32(0.5) * s), (f32(0) if aabb_scale <= 1 else f32(1) / f32(256))
+
+
+def render(view, net, bitfield=None, min_transmittance=0.01, near=0.2, no_albedo=False, chunk=1 << 16, aabb_scale=1, stats=None):
+    """The whole tracer: float32 [H, W, 9] (the layout of rnb_render) and the number of network samples. stats: a dict that receives the march's `mips`
+    and its `coords`, and the composite's `wmax` and `w2` per pixel."""
     o, d = camera_rays(view)
-    rid, coords, cnt = march(o, d, bitfield, near)
+    mn, mx, cone = scene_box(aabb_scale)
+    rid, coords, cnt = march(o, d, bitfield, near, mn, mx, cone, stats)
+    if stats is not None:
+        stats["coords"] = coords
     out = np.zeros((len(coords), 16), np.float16)
     for k in range(0, len(coords), chunk):
         out[k:k + chunk] = net(coords[k:k + chunk])
-    res = composite(view, o, rid, coords, out, len(o), min_transmittance, no_albedo)
+    res = composite(view, o, rid, coords, out, len(o), min_transmittance, no_albedo, mn, mx, stats)
     return res.reshape(int(view["height"]), int(view["width"]), CHANNELS), len(coords)
 
 
-def analytic_net(sdf_and_grad, variance=0.8, albedo_logit=(0.0, 1.0, -1.0)):
+def analytic_net(sdf_and_grad, variance=0.8, albedo_logit=(0.0, 1.0, -1.0), mn=0.0, mx=1.0):
     """A network stand-in from an SDF on world positions: outputs 0..2 albedo logits, 3 the SDF, 4..6 its gradient, 7 the variance (inv_s = exp(10 variance)),
-    8..10 the warped direction echoed (the network's BENT_DIR outputs). Box [0, 1]^3, so the warped position is the position."""
+    8..10 the warped direction echoed (the network's BENT_DIR outputs). The box [mn, mx]^3 takes the warped position back to the world (in [0, 1]^3 they are
+    the same)."""
+    mn, diag = float(mn), float(mx) - float(mn)
+
     def net(coords):
-        sdf, grad = sdf_and_grad(coords[:, 0:3].astype(np.float64))
+        sdf, grad = sdf_and_grad(coords[:, 0:3].astype(np.float64) * diag + mn)
         o = np.zeros((len(coords), 16), np.float32)
         o[:, 0:3] = albedo_logit
         o[:, 3] = sdf
@@ -274,8 +321,9 @@ def sphere_sdf(center=(0.5, 0.5, 0.5), radius=0.25):
     return f
 
 
-def bitfield_from_sdf(sdf_and_grad, band=2.5 / GRIDSIZE):
-    """An occupancy bitfield (uint8 [128^3 / 8 * 8]) whose cascade-0 cells are occupied where |sdf(cell centre)| < band; the coarser cascades are empty."""
+def bitfield_from_sdf(sdf_and_grad, band=2.5 / GRIDSIZE, cascades=1):
+    """An occupancy bitfield (uint8 [128^3 / 8 * 8]) whose cells of the first `cascades` cascades are occupied where |sdf(cell centre)| < band * 2^cascade
+    (cascade m spans [0.5 - 2^m / 2, 0.5 + 2^m / 2]^3 with cells 2^m times as large); the coarser cascades are empty."""
     i = np.arange(GRIDSIZE ** 3, dtype=np.uint32)
     # morton3D_invert of the index: the cell's x, y, z
     def inv(x):
@@ -286,8 +334,11 @@ def bitfield_from_sdf(sdf_and_grad, band=2.5 / GRIDSIZE):
         x = (x | (x >> np.uint32(16))) & np.uint32(0x0000FFFF)
         return x
     xyz = np.stack([inv(i), inv(i >> np.uint32(1)), inv(i >> np.uint32(2))], axis=1).astype(np.float64)
-    sdf, _ = sdf_and_grad((xyz + 0.5) / GRIDSIZE)
-    occ = np.abs(sdf) < band
     bits = np.zeros(GRIDSIZE ** 3 // 8 * CASCADES, np.uint8)
-    bits[: GRIDSIZE ** 3 // 8] = np.packbits(occ.reshape(-1, 8)[:, ::-1], axis=1).ravel()
+    nb = GRIDSIZE ** 3 // 8
+    for m in range(cascades):
+        centre = (xyz + 0.5) / GRIDSIZE if m == 0 else ((xyz + 0.5) / GRIDSIZE - 0.5) * 2.0 ** m + 0.5
+        sdf, _ = sdf_and_grad(centre)
+        occ = np.abs(sdf) < band * 2.0 ** m
+        bits[m * nb:(m + 1) * nb] = np.packbits(occ.reshape(-1, 8)[:, ::-1], axis=1).ravel()
     return bits

@@ -1,5 +1,6 @@
-"""CPU tier of the inference tracer (include/rnb_render.h): the numpy statement of the tracer against the analytic maps of the synthetic scene, the C-ABI of the
-render header (exports, version, defaults, struct layout against the Python declarations) and the view-scaling helper. No GPU needed."""
+"""CPU tier of the inference tracer (include/rnb_render.h): the numpy statement of the tracer against the analytic maps of the synthetic scene (unit cube and a
+larger box) and its march helpers against the reference's own fragments (tests/golden/int_fixtures.json), the C-ABI of the render header (exports, version,
+defaults, struct layout against the Python declarations) and the view-scaling helper. No GPU needed."""
 import ctypes as C
 import os
 import re
@@ -69,6 +70,92 @@ def test_numpy_tracer_without_early_stop_marches_to_the_box_exit():
     assert stopped.sum() > 0.9 * (early[..., 6] > 0.5).sum()
     assert np.all(early[..., 8][stopped] < full[..., 8][stopped])
     assert np.array_equal(early[~stopped], full[~stopped])
+
+
+def _pcg32_draws(seed, n):
+    """The first n outputs of pcg32{seed} (stream 1)."""
+    M, mult, inc = (1 << 64) - 1, 0x5851f42d4c957f2d, 3
+    state = ((inc + seed) * mult + inc) & M  # seed(): state 0, one step, + seed, one step
+    out = []
+    for _ in range(n):
+        x, rot = (((state >> 18) ^ state) >> 27) & 0xffffffff, state >> 59
+        out.append(((x >> rot) | (x << ((-rot) & 31))) & 0xffffffff)
+        state = (state * mult + inc) & M
+    return out
+
+
+def test_numpy_march_helpers_reproduce_the_reference_fragments():
+    """calc_dt, mip_from_pos, mip_from_dt, the cell index, the occupancy bit, the distance to the next voxel and advance_to_next_voxel of
+    tests/render_reference.py over the `march` rows of tests/golden/int_fixtures.json (the reference's own functions, compiled for the host): bit for bit.
+    Half of the rows are cone angle 0 in the unit cube, half cone angle 1 / 256 in the aabb_scale 4 box at t up to 4, recorded with the scene's max_cascade
+    (0 and 2). The tracer clamps at CASCADES - 1 instead (render_reference.mip_from_dt); a row is used where that clamp gives the recorded cascade too --
+    which is every row, since neither the positions (|p - 0.5| < 1.95) nor dt * 256 < 4 ask for more than cascade 2."""
+    from tests import int_fixture_cases
+    fx = int_fixture_cases.load()
+    assert _pcg32_draws(1337, 6) + _pcg32_draws(42, 6) == fx["pcg32_next_uint_seeds_1337_42_0_deadbeefcafe_x6"][:12]
+    a = np.array(fx["march_cone_maxcascade_p3_d3_t_dt_mipfrompos_mip_idx_occupied_dist_advance"], dtype=np.uint32).reshape(-1, 16)
+    f = lambda c: a[:, c].view(np.float32)
+    cone, maxc, t = f(0), a[:, 1].astype(np.int64), f(8)
+    pos, d = np.stack([f(2), f(3), f(4)], axis=1), np.stack([f(5), f(6), f(7)], axis=1)
+    idir = (np.float32(1) / d).astype(np.float32)
+    dt = np.concatenate([rr.calc_dt(t[k:k + 1], cone[k]) for k in range(len(a))])
+    assert dt.dtype == np.float32 and np.array_equal(dt.view(np.uint32), a[:, 9])
+    assert np.array_equal(rr.mip_from_pos(pos, maxc), a[:, 10])
+    mip = rr.mip_from_dt(dt, pos, maxc)
+    assert np.array_equal(mip, a[:, 11])
+    used = rr.mip_from_dt(dt, pos) == a[:, 11]  # the tracer's clamp
+    assert used.sum() == len(a) == 128
+    assert (cone[used] > 0).sum() == 64 and (a[used, 11] > 0).sum() >= 32 and (a[used, 11] > 1).sum() > 0
+    assert (a[used, 11] > a[used, 10]).sum() > 0  # dt, not the position, chose the cascade
+    idx = rr.cell_index(pos, mip)
+    assert np.array_equal(idx, a[:, 12])
+    # the fragments' bitfield: byte i = draw i of pcg32{5}, top 8 bits; generated as far as the rows look (cascades 0 .. 2)
+    bits = np.zeros(rr.GRIDSIZE ** 3 // 8 * rr.CASCADES, np.uint8)
+    n = int((idx // 8 + rr.GRIDSIZE ** 3 // 8 * mip).max()) + 1
+    bits[:n] = np.array(_pcg32_draws(5, n), np.uint32) >> 24
+    occ = rr.occupied(pos, bits, mip)
+    assert np.array_equal(occ.astype(np.uint32), a[:, 13]) and 0 < occ.sum() < len(a)
+    res = (rr.GRIDSIZE >> mip).astype(np.int64)
+    assert np.array_equal(rr.distance_to_next_voxel(pos, d, idir, res).view(np.uint32), a[:, 14])
+    adv = np.concatenate([rr.advance_to_next_voxel(t[k:k + 1], pos[k:k + 1], d[k:k + 1], idir[k:k + 1], res[k:k + 1], cone[k]) for k in range(len(a))])
+    assert adv.dtype == np.float32 and np.array_equal(adv.view(np.uint32), a[:, 15])
+    # under the cone angle a voxel is left in steps that differ from the constant step: the rows tell the two apart
+    flat = np.concatenate([rr.advance_to_next_voxel(t[k:k + 1], pos[k:k + 1], d[k:k + 1], idir[k:k + 1], res[k:k + 1]) for k in range(len(a))])
+    assert (flat.view(np.uint32) != a[:, 15]).sum() >= 32
+
+
+@pytest.mark.parametrize("where,cam_radius,fx", [("outside", 2.5, 300.0), ("inside", 0.9, 100.0)])
+def test_numpy_tracer_reproduces_the_analytic_sphere_in_a_larger_box(where, cam_radius, fx):
+    """aabb_scale 2: the box [-0.5, 1.5]^3, cone angle 1 / 256, the bitfield's cascades 0 .. 2 around the sphere. From outside the box (2.5 from the centre) the
+    sphere is reached at t ~ 2.25, where dt = t / 256 is five times the constant step and the march consults cascade 2; from inside it (0.9 from the centre, t ~ 0.65)
+    the ray starts at near_distance and steps by the constant step in cascade 0. The same thresholds as in the unit cube."""
+    from rnb_neus2_amd import synthetic
+    res = 96
+    views, normals, _ = synthetic.make_scene(2, res, fx, cam_radius=cam_radius)
+    mn, mx, cone = rr.scene_box(2)
+    assert (mn, mx, cone) == (-0.5, 1.5, 1.0 / 256.0)
+    sdf = rr.sphere_sdf()
+    bits = rr.bitfield_from_sdf(sdf, cascades=3)
+    assert np.array_equal(bits[: len(bits) // rr.CASCADES], rr.bitfield_from_sdf(sdf)[: len(bits) // rr.CASCADES]) and bits[len(bits) // rr.CASCADES:].any()
+    for k in range(len(views)):
+        eye = np.asarray(views[k]["xform"], np.float64).reshape(3, 4)[:, 3]
+        assert bool(np.all((eye > mn) & (eye < mx))) == (where == "inside")
+        st = {}
+        img, n_net = rr.render(views[k], rr.analytic_net(sdf, mn=mn, mx=mx), bitfield=bits, aabb_scale=2, stats=st)
+        assert img.shape == (res, res, rr.CHANNELS) and n_net > 0
+        ang, iou = _angles_and_iou(img, views[k], normals[k])
+        print("%s view %d: IoU %.4f, normal angle mean %.3f deg, cascades consulted %s" % (where, k, iou, ang.mean(), st["mips"].tolist()))
+        assert iou > 0.99, iou
+        assert ang.mean() < 1.0, ang.mean()
+        hit = img[..., 6] > 0.5
+        assert np.allclose(img[hit][:, 3:6], [0.5, 1 / (1 + np.exp(-1)), 1 / (1 + np.exp(1))], atol=2e-4)
+        assert img[hit][:, 7].min() > cam_radius - 0.26 and img[hit][:, 7].max() < cam_radius
+        assert np.all(img[img[..., 6] == 0][:, 0:6] == 0)
+        assert np.all(img[..., 7][img[..., 6] <= 0.2] == 0)
+        if where == "outside":
+            assert st["mips"][2] > 0 and np.unique(st["coords"][:, 3]).size > 1  # cascade 2 consulted, dt varies
+        else:
+            assert st["mips"][0] > 0 and st["mips"][1] > 0
 
 
 def test_render_header_is_exported_by_the_hip_library():
