@@ -383,6 +383,62 @@ MESH_SIMPLIFY_PROTOTYPES = {
     "mesh_simplify": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshSimplifyOptions), C.POINTER(Mesh), C.POINTER(MeshSimplifyStats)]),
 }
 
+# ---- include/rnb_mesh_distance.h: the one-sided distance from one device mesh to another, a header of its own with its own version (the HIP library only) ----
+MESH_DISTANCE_ABI_VERSION = 1
+MESH_DISTANCE_MAX_LEVEL, MESH_DISTANCE_MAX_TAUS, MESH_DISTANCE_NONE = 3, 4, 0xFFFFFFFF
+MESH_DISTANCE_MAX_CELLS, MESH_DISTANCE_LARGE_CELLS, MESH_DISTANCE_MAX_LARGE, MESH_DISTANCE_MAX_ENTRIES = 256, 2048, 4096, 1 << 31
+MESH_DISTANCE_Q_SHIFT, MESH_DISTANCE_Q_TERM_LOG2 = 48, 12
+
+
+class MeshDistanceOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("level", C.c_uint32),
+        ("max_distance", C.c_float),
+        ("unit", C.c_float),
+        ("tau", C.c_float * 4),
+        ("cells", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshDistanceStats(C.Structure):
+    _fields_ = [
+        ("n_verts_from_used", C.c_uint32),
+        ("n_verts_to_used", C.c_uint32),
+        ("n_tris_from", C.c_uint32),
+        ("n_tris_to", C.c_uint32),
+        ("n_degenerate_from", C.c_uint32),
+        ("n_degenerate_to", C.c_uint32),
+        ("n_verts_beyond", C.c_uint32),
+        ("n_large", C.c_uint32),
+        ("n_samples", C.c_uint64),
+        ("n_beyond", C.c_uint64),
+        ("sum_w", C.c_int64),
+        ("sum_wd", C.c_int64),
+        ("sum_wd2", C.c_int64),
+        ("sum_within", C.c_int64 * 4),
+        ("max_distance", C.c_double),
+        ("dims", C.c_uint32 * 3),
+        ("reserved", C.c_uint32),
+        ("cell", C.c_double),
+        ("n_cell_entries", C.c_uint64),
+        ("n_pairs", C.c_uint64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("ms_grid", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: (list(getattr(self, name)) if name in ("sum_within", "dims") else getattr(self, name)) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_DISTANCE_PROTOTYPES = {
+    "mesh_distance_abi_version": (_u32, []),
+    "mesh_distance_default_options": (_i, [C.POINTER(MeshDistanceOptions)]),
+    "mesh_distance": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(Mesh), C.POINTER(MeshDistanceOptions), C.c_void_p, C.c_void_p, C.POINTER(MeshDistanceStats)]),
+}
+
 
 class Functions:
     """Bound, typed entry points of one library."""
@@ -404,8 +460,8 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False):
+def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
-    (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h); only the HIP library exports those."""
+    (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
-                     + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()))
+                     + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()))

@@ -6,6 +6,7 @@ everything to ``librnb_neus2_hip.so``. There is no CPU fallback: if the HIP libr
 """
 import contextlib
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -46,7 +47,7 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True)
+        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -57,6 +58,8 @@ def load_library():
             raise RuntimeError("mesh-clean ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_simplify_abi_version() != _abi.MESH_SIMPLIFY_ABI_VERSION:
             raise RuntimeError("mesh-simplify ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_distance_abi_version() != _abi.MESH_DISTANCE_ABI_VERSION:
+            raise RuntimeError("mesh-distance ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -482,7 +485,7 @@ class Context:
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
-                     simplify=None, placement="quadric"):
+                     simplify=None, placement="quadric", error=False):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -491,7 +494,13 @@ class Context:
         dict gains `clean_stats`. The one not given leaves its part alone (keep="all", orient="none"), as build/mesh --keep / --orient do. With both None (the
         default) nothing of that runs.
         simplify = N: after that, still on the device, the mesh goes through rnb_mesh_simplify (see simplify_mesh) on the grid simplify_grid(aabb_min, aabb_max, N) --
-        N^3 cubic cells from aabb_min, N along the longest edge of the box, the grid of build/mesh --simplify N -- with `placement`, and the dict gains `simplify_stats`. With None (the default) nothing of that runs."""
+        N^3 cubic cells from aabb_min, N along the longest edge of the box, the grid of build/mesh --simplify N -- with `placement`, and the dict gains `simplify_stats`. With None (the default) nothing of that runs.
+        error=True (with simplify only): the distance between the mesh handed to the simplifier and the one it returned is measured on the device before anything is
+        downloaded (rnb_mesh_distance in both directions, its default options; see mesh_distance) and returned under `simplify_error`: the dict of
+        mesh_distance(input, output, symmetric=True), A = the simplifier's input (a simplification that leaves no triangle fails the call: there is nothing to measure against). With False (the default) nothing
+        of that runs and the result is as it was."""
+        if error and simplify is None:
+            raise ValueError("error=True needs simplify")
         sopt = None if simplify is None else self._simplify_options(*self.simplify_grid(aabb_min, aabb_max, simplify), placement)
         copt = None if keep is None and orient is None else self._clean_options("all" if keep is None else keep, "none" if orient is None else orient)
         opt = _abi.MeshOptions()
@@ -520,9 +529,12 @@ class Context:
                 last = cleaned
             if sopt is not None:
                 self._check(self.f.mesh_simplify(self._h, _stream_handle(stream), C.byref(last), C.byref(sopt), C.byref(simplified), C.byref(sst)))
+                simplify_error = self._mesh_distance_symmetric(last, simplified, self._distance_options(), False, stream) if error else None
                 last = simplified
             out = self._download_mesh(last)
             out["stats"] = st.as_dict()
+            if sopt is not None and error:
+                out["simplify_error"] = simplify_error
             if copt is not None:
                 out["clean_stats"] = cst.as_dict()
             if sopt is not None:
@@ -639,6 +651,75 @@ class Context:
         finally:
             self.f.mesh_free(self._h, C.byref(simplified))
         return out
+
+    def _distance_options(self, level=1, max_distance=0.0, unit=2.0 ** -10, thresholds=(), cells=0):
+        thresholds = [float(x) for x in thresholds]
+        if len(thresholds) > _abi.MESH_DISTANCE_MAX_TAUS:
+            raise ValueError("at most %d thresholds" % _abi.MESH_DISTANCE_MAX_TAUS)
+        if any(not x > 0 for x in thresholds):
+            raise ValueError("a threshold must be > 0 (0 marks an unused slot of the C-ABI)")
+        opt = _abi.MeshDistanceOptions()
+        self._check(self.f.mesh_distance_default_options(C.byref(opt)))
+        if not 0 <= int(level) <= _abi.MESH_DISTANCE_MAX_LEVEL or not 0 <= int(cells) <= _abi.MESH_DISTANCE_MAX_CELLS:
+            raise ValueError("level must be 0 .. 3 and cells 0 .. 256")
+        opt.level, opt.max_distance, opt.unit, opt.cells = int(level), float(max_distance), float(unit), int(cells)
+        opt.tau[:len(thresholds)] = thresholds
+        return opt
+
+    def _mesh_distance_device(self, a, b, opt, per_vertex, stream):
+        """One rnb_mesh_distance call on two _abi.Mesh in device memory; the dict mesh_distance returns for one direction."""
+        st = _abi.MeshDistanceStats()
+        n_tau = sum(1 for x in opt.tau if x != 0)
+        dist = near = None
+        try:
+            if per_vertex:
+                dist, near = self.device_malloc(max(a.n_verts, 1) * 4), self.device_malloc(max(a.n_verts, 1) * 4)
+            self._check(self.f.mesh_distance(self._h, _stream_handle(stream), C.byref(a), C.byref(b), C.byref(opt), dist, near, C.byref(st)))
+            out = st.as_dict()
+            if per_vertex:
+                out["vert_dist"] = self.download(dist, a.n_verts, np.float32)
+                out["vert_nearest"] = self.download(near, a.n_verts, np.uint32)
+        finally:
+            for p in (dist, near):
+                if p:
+                    self.device_free(p)
+        unit, sw = float(opt.unit), st.sum_w
+        out["unit"] = unit
+        out["mean"] = st.sum_wd / sw * unit if sw else 0.0
+        out["rms"] = math.sqrt(st.sum_wd2 / sw) * unit if sw else 0.0
+        out["max"] = st.max_distance
+        out["within"] = [st.sum_within[k] / sw if sw else 0.0 for k in range(n_tau)]
+        out["quantisation"] = st.n_samples / sw * unit if sw else 0.0
+        return out
+
+    def _mesh_distance_symmetric(self, a, b, opt, per_vertex, stream):
+        out = self._mesh_distance_device(a, b, opt, per_vertex, stream)
+        back = self._mesh_distance_device(b, a, opt, per_vertex, stream)
+        out["reverse"] = back
+        out["chamfer"] = out["mean"] + back["mean"]
+        out["hausdorff"] = max(out["max"], back["max"])
+        out["fscore"] = [2.0 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(out["within"], back["within"])]
+        return out
+
+    def mesh_distance(self, a_verts, a_indices, b_verts, b_indices, level=1, max_distance=0.0, unit=2.0 ** -10, thresholds=(), cells=0, per_vertex=False, symmetric=False,
+                      stream=None):
+        """rnb_mesh_distance (include/rnb_mesh_distance.h) on two host meshes (verts float32[n,3], indices uint32[m] or [m/3,3]): the one-sided distance from the surface
+        of A to the surface of B. A is sampled at the centroids of the 4^level congruent sub-triangles of each of its triangles, each weighted with its area; the
+        distance of a sample is that to the nearest point of B (exact point-triangle distances in double precision), capped at max_distance when that is not 0.
+        Returns a dict: `mean` (area-weighted mean distance), `rms`, `max` (over the samples and A's used vertices), `within` (per threshold, the area fraction of A
+        with d <= threshold), all in the units of the coordinates; `quantisation`, the bound by which the fixed-point truncation of rule 5 can have lowered `mean`
+        (n_samples * 2^-48 / area * unit); and the raw sums and counts of rnb_mesh_distance_stats (sum_w, sum_wd, sum_wd2, sum_within in 2^-48 fixed point with
+        distances in `unit`; n_samples, n_beyond, the grid, n_pairs, ms). `unit` only scales the sums: choose it near the expected distances (the call refuses
+        w * (d / unit)^2 >= 2^12). `cells` (0 = automatic) changes the time, never a bit of the result. per_vertex=True adds `vert_dist` float32[n] and
+        `vert_nearest` uint32[n] (the nearest triangle of B, 0xFFFFFFFF for an unused vertex or one beyond max_distance).
+        symmetric=True runs B -> A as well (its dict under `reverse`) and adds `chamfer` = mean(A->B) + mean(B->A) (the sum of the two means of unsquared
+        distances, not halved), `hausdorff` = the larger of the two maxima, and per threshold `fscore` = 2 P R / (P + R) with precision P = within(A->B) and
+        recall R = within(B->A): A is the reconstruction, B the reference. Bit-reproducible. Leaves the training state as it was."""
+        opt = self._distance_options(level, max_distance, unit, thresholds, cells)
+        with self._device_mesh(a_verts, a_indices, None, None) as a, self._device_mesh(b_verts, b_indices, None, None) as b:
+            if symmetric:
+                return self._mesh_distance_symmetric(a, b, opt, per_vertex, stream)
+            return self._mesh_distance_device(a, b, opt, per_vertex, stream)
 
     def upload(self, array):
         """numpy array -> library-side buffer (device_malloc + copy); release with device_free."""

@@ -8,6 +8,7 @@
 #include "kernels_mesh_sparse.cuh"
 #include "kernels_mesh_clean.cuh"
 #include "kernels_mesh_simplify.cuh"
+#include "kernels_mesh_distance.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>
@@ -1815,7 +1816,7 @@ int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float latti
 	return RNB_OK;
 } RNB_GUARD
 
-// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify) ----
+// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance) ----
 extern "C++" {
 namespace {
 // elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
@@ -1881,7 +1882,8 @@ struct MeshWorkspace {
 	~MeshWorkspace() { for (auto& h : held) if (h.first) (void)hipFree(h.first); }
 };
 
-// What rnb_mesh_clean and rnb_mesh_simplify ask of their input mesh, said in the entry point's name; *out is zeroed as soon as it is known not to be the input.
+// What rnb_mesh_clean, rnb_mesh_simplify and rnb_mesh_distance (which has no output mesh and hands in one it discards) ask of their input mesh, said in the entry
+// point's name; *out is zeroed as soon as it is known not to be the input.
 int check_mesh_input(const char* name, const rnb_mesh* in, rnb_mesh* out) {
 	const std::string n(name);
 	if (in == out) return fail(RNB_ERR_INVALID, n + ": in and out must be different objects");
@@ -2895,6 +2897,160 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 		stats->n_verts_in = nv; stats->n_tris_in = nt; stats->n_clusters = n_cl; stats->n_verts_out = nvo; stats->n_tris_out = nto; stats->n_tris_collapsed = nt - nto;
 		stats->n_clamped = hres.n_clamped; stats->n_fallback = hres.n_fallback;
 		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh-to-mesh distance (include/rnb_mesh_distance.h) ----
+uint32_t rnb_mesh_distance_abi_version(void) { return RNB_MESH_DISTANCE_ABI_VERSION; }
+
+int rnb_mesh_distance_default_options(rnb_mesh_distance_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_DISTANCE_ABI_VERSION;
+	opt->level = 1u;
+	opt->unit = 1.0f / 1024.0f;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_mesh* to, const rnb_mesh_distance_options* opt, float* vert_dist_dev, uint32_t* vert_nearest_dev,
+                      rnb_mesh_distance_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !from || !to || !opt) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: null argument");
+	if (from == to) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: from and to must be different objects");
+	if (vert_dist_dev && (void*)vert_dist_dev == (void*)vert_nearest_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: vert_dist_dev and vert_nearest_dev must be different buffers");
+	if (opt->abi_version != RNB_MESH_DISTANCE_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: options abi_version mismatch (expected RNB_MESH_DISTANCE_ABI_VERSION)");
+	if (opt->level > RNB_MESH_DISTANCE_MAX_LEVEL) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: level must be 0 .. 3");
+	if (!(opt->unit > 0.0f) || !std::isfinite(opt->unit)) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: unit must be finite and > 0");
+	if (!(opt->max_distance >= 0.0f) || !std::isfinite(opt->max_distance)) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: max_distance must be finite and >= 0");
+	for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k)
+		if (!(opt->tau[k] >= 0.0f) || !std::isfinite(opt->tau[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a tau must be finite and >= 0");
+	if (opt->cells > RNB_MESH_DISTANCE_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: cells must be 0 .. 256");
+	{
+		rnb_mesh unused;
+		if (int rc = check_mesh_input("rnb_mesh_distance (from)", from, &unused); rc != RNB_OK) return rc;
+		if (int rc = check_mesh_input("rnb_mesh_distance (to)", to, &unused); rc != RNB_OK) return rc;
+	}
+	const rnb_mesh ma = *from, mb = *to;
+	const uint32_t nva = ma.n_verts, nta = ma.n_indices / 3u, nvb = mb.n_verts, ntb = mb.n_indices / 3u, nn = 1u << (2u * opt->level);
+	if ((uint64_t)nta * nn > 0xFFFFFFFFull) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: more than 2^32 - 1 samples (a lower level)");
+	if (nta && ntb == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	MeshWorkspace ws;
+	MdResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	for (int k = 0; k < 3; ++k) hres.bmin[k] = 0xFFFFFFFFu;
+	MdGrid g;
+	std::memset(&g, 0, sizeof(g));
+	uint32_t n_entries = 0;
+	float ms_grid = 0.0f;
+	int64_t sums[MD_NSUM] = {};
+	if (!nta) { // no sample: every vertex is unused
+		if (vert_dist_dev && nva) HIP_TRY(hipMemsetAsync(vert_dist_dev, 0, (size_t)nva * 4, s));
+		if (vert_nearest_dev && nva) HIP_TRY(hipMemsetAsync(vert_nearest_dev, 0xFF, (size_t)nva * 4, s));
+		HIP_TRY(hipStreamSynchronize(s));
+	} else {
+		const uint32_t g_va = (nva + MD_WG - 1) / MD_WG, g_ta = (nta + MD_WG - 1) / MD_WG, g_vb = (nvb + MD_WG - 1) / MD_WG, g_tb = (ntb + MD_WG - 1) / MD_WG; // (nva, nvb >= 1: check_mesh_input)
+		const MdMesh A{ma.verts, ma.indices, nva, nta}, B{mb.verts, mb.indices, nvb, ntb};
+		uint32_t *used_a = nullptr, *used_b = nullptr, *start = nullptr, *cursor = nullptr, *scan = nullptr, *entries = nullptr, *large = nullptr;
+		MdResult* dres = nullptr;
+		if (!ws.alloc(&used_a, nva) || !ws.alloc(&used_b, nvb) || !ws.alloc(&large, RNB_MESH_DISTANCE_MAX_LARGE) || !ws.alloc(&dres, 1))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the workspace of " + std::to_string(nva) + " and " + std::to_string(nvb) + " vertices");
+		HIP_TRY(hipMemsetAsync(used_a, 0, (size_t)nva * 4, s));
+		HIP_TRY(hipMemsetAsync(used_b, 0, (size_t)nvb * 4, s));
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		// 1. every index of either mesh is range-checked before any is used as an address; used vertices, B's box, B's degenerate triangles
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_ta), dim3(MD_WG), 0, s, (const uint32_t*)ma.indices, nta, nva, used_a, &dres->flags, MD_BAD_INDEX_FROM);
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_tb), dim3(MD_WG), 0, s, (const uint32_t*)mb.indices, ntb, nvb, used_b, &dres->flags, MD_BAD_INDEX_TO);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MD_BAD_INDEX_FROM) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of from is out of range (>= n_verts)");
+		if (hres.flags & MD_BAD_INDEX_TO) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of to is out of range (>= n_verts)");
+		hipLaunchKernelGGL(k_md_verts<false>, dim3(g_va), dim3(MD_WG), 0, s, (const float*)ma.verts, nva, (const uint32_t*)used_a, dres);
+		hipLaunchKernelGGL(k_md_verts<true>, dim3(g_vb), dim3(MD_WG), 0, s, (const float*)mb.verts, nvb, (const uint32_t*)used_b, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MD_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a coordinate of a used vertex is not finite");
+		ws.release(used_b);
+		const auto t_grid = std::chrono::steady_clock::now();
+		hipLaunchKernelGGL(k_md_degenerate, dim3(g_tb), dim3(MD_WG), 0, s, B, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		const uint32_t m = ntb - hres.n_deg_to;
+		if (!m) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
+		// 2. the grid over B's box, the cell lists
+		double longest = 0.0;
+		for (int k = 0; k < 3; ++k) {
+			const auto value = [](uint32_t image) { const uint32_t u = (image & 0x80000000u) ? (image ^ 0x80000000u) : ~image; float f; std::memcpy(&f, &u, 4); return (double)f; };
+			g.lo[k] = value(hres.bmin[k]); g.hi[k] = value(hres.bmax[k]);
+			longest = std::max(longest, g.hi[k] - g.lo[k]);
+		}
+		uint32_t n_axis = opt->cells;
+		if (!n_axis) n_axis = (uint32_t)std::min<double>(std::max<double>(std::floor(std::sqrt((double)(m / 2u))), 1.0), (double)RNB_MESH_DISTANCE_MAX_CELLS);
+		g.cell = longest / (double)n_axis; // > 0: a non-degenerate triangle has an extent
+		uint64_t n_cells = 1;
+		for (int k = 0; k < 3; ++k) {
+			g.dims[k] = (uint32_t)std::min<double>((double)n_axis, std::floor((g.hi[k] - g.lo[k]) / g.cell) + 1.0);
+			n_cells *= g.dims[k];
+		}
+		if (!ws.alloc(&start, n_cells) || !ws.alloc(&cursor, n_cells) || !ws.alloc(&scan, scan_scratch_elems(n_cells)))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the lists of " + std::to_string(n_cells) + " cells");
+		HIP_TRY(hipMemsetAsync(start, 0, (size_t)n_cells * 4, s));
+		hipLaunchKernelGGL(k_md_register<false>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, start, (uint32_t*)nullptr, large, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		int rc = scan_exclusive(start, n_cells, s, &n_entries, scan); // (synchronises: hres has arrived)
+		if (rc != RNB_OK) return rc;
+		if (hres.n_large > RNB_MESH_DISTANCE_MAX_LARGE)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_large) + " triangles of to overlap more than 2048 cells each, the large list holds 4096 (a coarser grid: fewer cells)");
+		if (hres.n_entries > RNB_MESH_DISTANCE_MAX_ENTRIES)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_entries) + " cell entries, more than 2^31 (a coarser grid: fewer cells)");
+		if (!ws.alloc(&entries, n_entries)) return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for " + std::to_string(n_entries) + " cell entries");
+		HIP_TRY(hipMemcpyAsync(cursor, start, (size_t)n_cells * 4, hipMemcpyDeviceToDevice, s));
+		hipLaunchKernelGGL(k_md_register<true>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, cursor, entries, (uint32_t*)nullptr, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		ms_grid = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_grid).count();
+		// 3. the queries: the vertices of A, then the sub-centroids of its triangles
+		MdQuery q;
+		std::memset(&q, 0, sizeof(q));
+		q.cap = (double)opt->max_distance; q.unit = (double)opt->unit; q.level = opt->level;
+		for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k) q.tau[k] = (double)opt->tau[k];
+		const MdSearch S{B, start, cursor, entries, large, hres.n_large};
+		const uint64_t n_threads = (uint64_t)nta * nn;
+		hipLaunchKernelGGL(k_md_query<true>, dim3(g_va), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)used_a, S, vert_dist_dev, vert_nearest_dev, dres);
+		hipLaunchKernelGGL(k_md_query<false>, dim3((uint32_t)((n_threads + MD_WG - 1) / MD_WG)), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)nullptr, S, (float*)nullptr, (uint32_t*)nullptr, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MD_BAD_TERM)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a term is not finite or not below 2^12 (a larger unit, or a max_distance)");
+		for (int k = 0; k < MD_NSUM; ++k) { // the two words of a sum, joined in 128 bits
+			const unsigned __int128 total = ((unsigned __int128)hres.hi[k] << 32) + hres.lo[k];
+			if (total >> 63) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a sum reaches 2^15 (a larger unit, or a max_distance)");
+			sums[k] = (int64_t)total;
+		}
+		ws.release(used_a); ws.release(start); ws.release(cursor); ws.release(scan); ws.release(entries); ws.release(large); ws.release(dres);
+	}
+	if (stats) {
+		stats->n_verts_from_used = hres.n_used_from; stats->n_verts_to_used = hres.n_used_to; stats->n_tris_from = nta; stats->n_tris_to = ntb;
+		stats->n_degenerate_from = hres.n_deg_from; stats->n_degenerate_to = hres.n_deg_to; stats->n_verts_beyond = hres.n_verts_beyond; stats->n_large = hres.n_large;
+		stats->n_samples = hres.n_samples; stats->n_beyond = hres.n_beyond;
+		stats->sum_w = sums[0]; stats->sum_wd = sums[1]; stats->sum_wd2 = sums[2];
+		for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k) stats->sum_within[k] = sums[3 + k];
+		std::memcpy(&stats->max_distance, &hres.max_bits, 8);
+		for (int k = 0; k < 3; ++k) stats->dims[k] = g.dims[k];
+		stats->cell = g.cell;
+		stats->n_cell_entries = hres.n_entries; stats->n_pairs = hres.n_pairs;
+		stats->peak_workspace = ws.peak;
+		stats->ms_grid = ms_grid;
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}
 	return RNB_OK;

@@ -3,7 +3,7 @@
 // snapshot by snapshot.hpp (its EMA weights, occupancy grid and network configuration).
 //
 //   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
-//        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean]]
+//        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean] [--report-error]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -12,11 +12,14 @@
 // them the other part is left alone (--keep alone does not turn anything, --orient alone keeps every component), as Context.extract_mesh(keep=, orient=) does.
 // With --simplify N the (cleaned) device mesh then goes through rnb_mesh_simplify (include/rnb_mesh_simplify.h): vertex clustering on N^3 cells over the scene's box
 // (origin aabb_min, cell = (aabb_max - aabb_min) / N), the representative of a cell placed by --placement (quadric by default). Ring normals are those of the simplified mesh.
+// With --report-error the distance between the simplifier's input and its output is measured on the device in both directions (rnb_mesh_distance,
+// include/rnb_mesh_distance.h, default options) and printed as one more line.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
 #include "../../include/rnb_mesh_clean.h"
 #include "../../include/rnb_mesh_simplify.h"
+#include "../../include/rnb_mesh_distance.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -52,12 +55,13 @@ const Flag FLAGS[] = {
 	{"orient", "MODE", "Clean the mesh on the device. outward: components of negative signed volume are turned inside out; none: triangles as extracted."},
 	{"simplify", "N", "Simplify the mesh on the device: vertex clustering on N^3 cells over the scene's box (1 .. 1024), after the cleaning."},
 	{"placement", "MODE", "--simplify only. quadric (default): the vertex of a cell minimises the quadric error of its triangles; mean: the mean of its vertices."},
+	{"report-error", nullptr, "--simplify only (takes no value). Measure the distance between the mesh before and after the simplification, both directions, and print it."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
 
 void print_help(std::ostream& os, const char* prog) {
 	os << "  " << prog << " {OPTIONS}\n\n    coloured mesh of a trained snapshot, extracted brick by brick\n\n  OPTIONS:\n\n      -h, --help\n                                        Display this help menu.\n";
-	for (const auto& f : FLAGS) os << "      --" << f.name << "=[" << f.meta << "]\n                                        " << f.help << "\n";
+	for (const auto& f : FLAGS) os << "      --" << f.name << (f.meta ? std::string("=[") + f.meta + "]" : std::string()) << "\n                                        " << f.help << "\n";
 }
 
 std::map<std::string, std::string> parse_cli(int argc, char** argv, bool& help) {
@@ -71,9 +75,15 @@ std::map<std::string, std::string> parse_cli(int argc, char** argv, bool& help) 
 		const size_t eq = name.find('=');
 		bool inline_value = eq != std::string::npos;
 		if (inline_value) { value = name.substr(eq + 1); name = name.substr(0, eq); }
-		bool known = false;
-		for (const auto& f : FLAGS) known = known || name == f.name;
+		bool known = false, takes_value = true;
+		for (const auto& f : FLAGS)
+			if (name == f.name) { known = true; takes_value = f.meta != nullptr; }
 		if (!known) throw ParseError("Flag could not be matched: " + name);
+		if (!takes_value) {
+			if (inline_value) throw ParseError("Flag '" + name + "' takes no argument");
+			a[name] = "1";
+			continue;
+		}
 		if (!inline_value) {
 			if (i + 1 >= argc) throw ParseError("Flag '" + name + "' requires an argument but received none");
 			value = argv[++i];
@@ -104,6 +114,7 @@ int main(int argc, char** argv) {
 	bool gradient = false, clean = false;
 	uint32_t keep = RNB_MESH_KEEP_ALL, orient = RNB_MESH_ORIENT_NONE; // with one of the two flags given, the other one leaves its part alone
 	uint32_t simplify = 0, placement = RNB_MESH_PLACE_QUADRIC;           // 0: no simplification
+	bool report_error = false;
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -139,6 +150,10 @@ int main(int argc, char** argv) {
 			if (!simplify) throw ParseError("Argument 'placement' is only used with --simplify");
 			if (a["placement"] == "mean") placement = RNB_MESH_PLACE_MEAN;
 			else if (a["placement"] != "quadric") throw ParseError("Argument 'placement' must be quadric or mean");
+		}
+		if (a.count("report-error")) {
+			if (!simplify) throw ParseError("Argument 'report-error' is only used with --simplify");
+			report_error = true;
 		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
@@ -197,6 +212,8 @@ int main(int argc, char** argv) {
 			std::memset(&cm, 0, sizeof(cm));
 		}
 		rnb_mesh_simplify_stats ss;
+		rnb_mesh_distance_stats es[2];
+		double error_unit = 0.0;
 		if (simplify) { // device to device, after the cleaning
 			rnb_mesh_simplify_options so;
 			RNB_CHECK(rnb_mesh_simplify_default_options(&so));
@@ -204,6 +221,13 @@ int main(int argc, char** argv) {
 			so.cell = (float)(((double)amax - (double)amin) / (double)simplify);
 			so.placement = placement;
 			RNB_CHECK(rnb_mesh_simplify(ctx, nullptr, &dm, &so, &cm, &ss));
+			if (report_error) { // before either mesh leaves the device: input -> output, output -> input
+				rnb_mesh_distance_options dopt;
+				RNB_CHECK(rnb_mesh_distance_default_options(&dopt));
+				RNB_CHECK(rnb_mesh_distance(ctx, nullptr, &dm, &cm, &dopt, nullptr, nullptr, &es[0]));
+				RNB_CHECK(rnb_mesh_distance(ctx, nullptr, &cm, &dm, &dopt, nullptr, nullptr, &es[1]));
+				error_unit = (double)dopt.unit;
+			}
 			RNB_CHECK(rnb_mesh_free(ctx, &dm));
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
@@ -227,6 +251,15 @@ int main(int argc, char** argv) {
 		                       cs.n_verts_in, cs.n_verts_out, cs.ms);
 		if (simplify) std::printf("simplify: %u clusters, %u -> %u triangles (%u collapsed), %u -> %u vertices, %u clamped, %u at the mean, %.1f ms\n", ss.n_clusters, ss.n_tris_in,
 		                          ss.n_tris_out, ss.n_tris_collapsed, ss.n_verts_in, ss.n_verts_out, ss.n_clamped, ss.n_fallback, ss.ms);
+		if (report_error) {
+			double mean[2], rms[2];
+			for (int k = 0; k < 2; ++k) {
+				mean[k] = es[k].sum_w ? (double)es[k].sum_wd / (double)es[k].sum_w * error_unit : 0.0;
+				rms[k] = es[k].sum_w ? std::sqrt((double)es[k].sum_wd2 / (double)es[k].sum_w) * error_unit : 0.0;
+			}
+			std::printf("simplify error: in -> out mean %.9g rms %.9g max %.9g, out -> in mean %.9g rms %.9g max %.9g, %.1f ms\n", mean[0], rms[0], es[0].max_distance, mean[1], rms[1],
+			            es[1].max_distance, es[0].ms + es[1].ms);
+		}
 		std::printf("#vertices=%zu #triangles=%zu\n", m.verts.size(), m.indices.size() / 3);
 		// --orient outward speaks of the file: the device turned every kept component counter-clockwise seen from outside, and the faces are written as they are
 		// (without it, the scene's from_na flag decides whether save_obj reverses them, as in the testbed). save_obj maps positions by a uniform scale and a shift,
