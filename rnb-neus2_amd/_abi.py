@@ -439,6 +439,52 @@ MESH_DISTANCE_PROTOTYPES = {
     "mesh_distance": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(Mesh), C.POINTER(MeshDistanceOptions), C.c_void_p, C.c_void_p, C.POINTER(MeshDistanceStats)]),
 }
 
+# ---- include/rnb_mesh_raster.h: a device mesh into one camera's depth, normal, colour, coverage and face maps, a header of its own with its own version (the HIP library only) ----
+MESH_RASTER_ABI_VERSION = 1
+MESH_RASTER_CHANNELS, MESH_RASTER_NONE, MESH_RASTER_MAX_SIZE = 9, 0xFFFFFFFF, 16384
+MESH_RASTER_SUBPIXEL_BITS, MESH_RASTER_MAX_COORD_LOG2, MESH_RASTER_SMALL_PIXELS, MESH_RASTER_MAX_COUNT = 8, 28, 16, 1 << 24
+MESH_RASTER_CULL_NONE, MESH_RASTER_CULL_BACK, MESH_RASTER_CULL_FRONT = 0, 1, 2
+MESH_RASTER_NORMALS_FACE, MESH_RASTER_NORMALS_VERTEX = 0, 1
+
+
+class MeshRasterOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("near", C.c_float),
+        ("cull", C.c_uint32),
+        ("normals", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshRasterStats(C.Structure):
+    _fields_ = [
+        ("n_tris", C.c_uint32),
+        ("n_behind", C.c_uint32),
+        ("n_out_of_range", C.c_uint32),
+        ("n_degenerate", C.c_uint32),
+        ("n_culled", C.c_uint32),
+        ("n_offscreen", C.c_uint32),
+        ("n_small", C.c_uint32),
+        ("n_large", C.c_uint32),
+        ("n_covered", C.c_uint32),
+        ("n_back_pixels", C.c_uint32),
+        ("n_fragments", C.c_uint64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_RASTER_PROTOTYPES = {
+    "mesh_raster_abi_version": (_u32, []),
+    "mesh_raster_default_options": (_i, [C.POINTER(MeshRasterOptions)]),
+    "mesh_raster": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(View), C.POINTER(MeshRasterOptions), C.c_void_p, C.c_void_p, C.POINTER(MeshRasterStats)]),
+}
+
 
 class Functions:
     """Bound, typed entry points of one library."""
@@ -460,8 +506,9 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False):
+def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
-    (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h); only the HIP library exports those."""
+    (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
+    mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
-                     + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()))
+                     + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ()))

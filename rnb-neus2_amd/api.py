@@ -47,7 +47,7 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True)
+        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -60,6 +60,8 @@ def load_library():
             raise RuntimeError("mesh-simplify ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_distance_abi_version() != _abi.MESH_DISTANCE_ABI_VERSION:
             raise RuntimeError("mesh-distance ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_raster_abi_version() != _abi.MESH_RASTER_ABI_VERSION:
+            raise RuntimeError("mesh-raster ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -102,6 +104,44 @@ def _view_struct(v):
     out.principal_point[:] = [float(x) for x in v["principal_point"]]
     out.xform[:] = [float(x) for x in np.asarray(v["xform"], dtype=np.float32).reshape(12)]
     return out
+
+
+def view_normal_metrics(image, view, normal_map):
+    """One view's comparison of a [H,W,9] image (the layout of rnb_render and of rasterize_mesh's `image`: world-frame normal in channels 0-2, coverage or opacity in 6) with the
+    scene's input normal map (uint16 [h,w,4]: the camera-frame normal as (x, -y, -z) in [0, 1], alpha = mask), by the definitions of host/view_metrics.hpp, which
+    build/render (render_metrics.json) and build/mesh --report-views use: mask = channel 6 > 0.5, input mask = alpha > 0, the input pixel whose area holds the pixel's
+    centre, the angle between the decoded input normal and the image's normal in the camera frame where both masks hold and both are non-zero. Returns a dict of
+    mean_angle_deg, median_angle_deg, mask_iou, pixels_compared."""
+    img = np.asarray(image, dtype=np.float32)
+    h, w = img.shape[:2]
+    t = np.asarray(normal_map)
+    if t.dtype != np.uint16 or t.ndim != 3 or t.shape[2] != 4:
+        raise ValueError("normal_map must be uint16 [h, w, 4]")
+    ih, iw = t.shape[:2]
+    x = np.asarray(view["xform"], dtype=np.float32).reshape(3, 4)
+    mask = img[..., 6] > np.float32(0.5)
+    nc = np.stack([(x[0, k] * img[..., 0] + x[1, k] * img[..., 1]) + x[2, k] * img[..., 2] for k in range(3)], axis=-1)  # R^T n, float32, in this order
+    ix = np.minimum(iw - 1, ((np.arange(w, dtype=np.float64) + 0.5) * iw / w).astype(np.int64))
+    iy = np.minimum(ih - 1, ((np.arange(h, dtype=np.float64) + 0.5) * ih / h).astype(np.int64))
+    t = t[iy][:, ix]
+    mask_in = t[..., 3] > 0
+    inter, uni = int((mask & mask_in).sum()), int((mask | mask_in).sum())
+    both = mask & mask_in
+    d = t[both][:, :3].astype(np.float64) / 65535.0 * 2.0 - 1.0
+    ti = d * np.array([1.0, -1.0, -1.0])
+    n = nc[both].astype(np.float64)
+    ln = np.sqrt((ti[:, 0] * ti[:, 0] + ti[:, 1] * ti[:, 1]) + ti[:, 2] * ti[:, 2])
+    lr = np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2])
+    ok = (ln > 0) & (lr > 0)
+    cs = ((ti[ok, 0] * n[ok, 0] + ti[ok, 1] * n[ok, 1]) + ti[ok, 2] * n[ok, 2]) / (ln[ok] * lr[ok])
+    angles = np.arccos(np.minimum(1.0, np.maximum(-1.0, cs))) * 180.0 / math.pi
+    mean = median = 0.0
+    if angles.size:
+        mean = float(sum(float(a) for a in angles) / angles.size)  # summed in pixel order, as the header does
+        a = np.sort(angles)
+        k = a.size
+        median = float(a[k // 2]) if k % 2 else float(0.5 * (a[k // 2 - 1] + a[k // 2]))
+    return dict(mean_angle_deg=mean, median_angle_deg=median, mask_iou=(inter / uni if uni else 1.0), pixels_compared=int(angles.size))
 
 
 def scaled_view(view, factor):
@@ -720,6 +760,72 @@ class Context:
             if symmetric:
                 return self._mesh_distance_symmetric(a, b, opt, per_vertex, stream)
             return self._mesh_distance_device(a, b, opt, per_vertex, stream)
+
+    def _raster_options(self, near, cull, shading):
+        culls = {"none": _abi.MESH_RASTER_CULL_NONE, "back": _abi.MESH_RASTER_CULL_BACK, "front": _abi.MESH_RASTER_CULL_FRONT}
+        shadings = {"face": _abi.MESH_RASTER_NORMALS_FACE, "vertex": _abi.MESH_RASTER_NORMALS_VERTEX}
+        if cull not in culls:
+            raise ValueError("cull must be 'none', 'back' or 'front'")
+        if shading not in shadings:
+            raise ValueError("shading must be 'face' or 'vertex'")
+        opt = _abi.MeshRasterOptions()
+        self._check(self.f.mesh_raster_default_options(C.byref(opt)))
+        opt.near, opt.cull, opt.normals = float(near), culls[cull], shadings[shading]
+        return opt
+
+    def _rasterize_device(self, m, view, opt, faces, stream):
+        """One rnb_mesh_raster call on an _abi.Mesh in device memory; the dict rasterize_mesh returns."""
+        h, w = int(view["height"]), int(view["width"])
+        n = h * w
+        st = _abi.MeshRasterStats()
+        img = fac = None
+        try:
+            img = self.device_malloc(max(n, 1) * _abi.MESH_RASTER_CHANNELS * 4)
+            if faces:
+                fac = self.device_malloc(max(n, 1) * 4)
+            self._check(self.f.mesh_raster(self._h, _stream_handle(stream), C.byref(m), C.byref(_view_struct(view)), C.byref(opt), img, fac, C.byref(st)))
+            out = st.as_dict()
+            out["image"] = self.download(img, n * _abi.MESH_RASTER_CHANNELS, np.float32).reshape(h, w, _abi.MESH_RASTER_CHANNELS)
+            if faces:
+                out["faces"] = self.download(fac, n, np.uint32).reshape(h, w)
+        finally:
+            for p in (img, fac):
+                if p:
+                    self.device_free(p)
+        return out
+
+    def rasterize_mesh(self, verts, indices, view, colors=None, normals=None, near=2.0 ** -10, cull="none", shading="face", faces=False, stream=None):
+        """rnb_mesh_raster (include/rnb_mesh_raster.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3], optional per-vertex colors / normals) and one
+        camera (a view dict as set_dataset and render take). Returns a dict: `image` float32 [H,W,9] in the channel layout of the render (0-2 unit normal in the world
+        frame, 3-5 colour or ones, 6 coverage, 7 camera-forward depth, 8 the number of triangles over the pixel's centre), with faces=True `faces` uint32 [H,W] (the
+        winning triangle, 0xFFFFFFFF where nothing covers), and beside them the fields of rnb_mesh_raster_stats (n_tris, n_behind, ..., n_fragments, peak_workspace, ms), as mesh_distance returns its own. cull: "none", "back" or "front"; shading:
+        "face" (the triangle's own normal) or "vertex" (the interpolated `normals`, which must then be given). Coverage is exact on 1/256-pixel snapped vertices, a pixel
+        centre on a shared edge belongs to exactly one triangle; a triangle with a vertex nearer than `near` is skipped and counted, not clipped. Bit-reproducible.
+        Leaves the training state as it was."""
+        opt = self._raster_options(near, cull, shading)
+        if shading == "vertex" and normals is None:
+            raise ValueError("shading='vertex' needs normals")
+        with self._device_mesh(verts, indices, colors, normals) as m:
+            return self._rasterize_device(m, view, opt, faces, stream)
+
+    def mesh_view_metrics(self, verts, indices, views, normal_maps, normals=None, near=2.0 ** -10, cull="none", shading="face", stream=None):
+        """The mesh's counterpart of build/render's render_metrics.json: the mesh rasterised into every view of `views` (rasterize_mesh) and compared with that view's
+        input normal map (`normal_maps`: uint16 [h,w,4] each) by view_normal_metrics. Returns dict(views=[one dict per view: mean_angle_deg, median_angle_deg, mask_iou,
+        pixels_compared, n_back_pixels, odd_count_pixels (pixels an odd number of triangles cover: 0 for a closed mesh), ms], mean={the means of the first three})."""
+        if len(views) != len(normal_maps):
+            raise ValueError("one normal map per view")
+        opt = self._raster_options(near, cull, shading)
+        if shading == "vertex" and normals is None:
+            raise ValueError("shading='vertex' needs normals")
+        per_view = []
+        with self._device_mesh(verts, indices, None, normals) as m:
+            for view, nm in zip(views, normal_maps):
+                r = self._rasterize_device(m, view, opt, False, stream)
+                e = view_normal_metrics(r["image"], view, nm)
+                e.update(n_back_pixels=r["n_back_pixels"], odd_count_pixels=int((r["image"][..., 8].astype(np.int64) & 1).sum()), ms=r["ms"])
+                per_view.append(e)
+        k = max(len(per_view), 1)
+        return dict(views=per_view, mean={key: sum(e[key] for e in per_view) / k for key in ("mean_angle_deg", "median_angle_deg", "mask_iou")})
 
     def upload(self, array):
         """numpy array -> library-side buffer (device_malloc + copy); release with device_free."""

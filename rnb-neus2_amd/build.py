@@ -6,9 +6,9 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG_DIR, "csrc", "rnb_neus2_hip.hip")
 OUT = os.path.join(PKG_DIR, "librnb_neus2_hip.so")
-DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "mesh_common.cuh", "kernels_mesh.cuh", "kernels_render.cuh", "kernels_mesh_sparse.cuh", "kernels_mesh_clean.cuh", "kernels_mesh_simplify.cuh", "kernels_mesh_distance.cuh")] + [
+DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "mesh_common.cuh", "kernels_mesh.cuh", "kernels_render.cuh", "kernels_mesh_sparse.cuh", "kernels_mesh_clean.cuh", "kernels_mesh_simplify.cuh", "kernels_mesh_distance.cuh", "kernels_mesh_raster.cuh")] + [
     os.path.join(PKG_DIR, "host", f) for f in ("mesh.hpp", "mc_table.hpp")] + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", f) for f in ("rnb_neus2.h", "rnb_render.h", "rnb_mesh.h", "rnb_mesh_clean.h", "rnb_mesh_simplify.h", "rnb_mesh_distance.h")]
+    os.path.join(os.path.dirname(PKG_DIR), "include", f) for f in ("rnb_neus2.h", "rnb_render.h", "rnb_mesh.h", "rnb_mesh_clean.h", "rnb_mesh_simplify.h", "rnb_mesh_distance.h", "rnb_mesh_raster.h")]
 
 # -ffp-contract=off: the index/ray arithmetic must match the CPU checker bit for bit (no FMA contraction).
 # -packed-fp32-ops (device target feature): no v_pk_{mul,add,fma}_f32. Measured on MI355X / ROCm 7.2 with tools/march_determinism.py: the
@@ -86,7 +86,7 @@ def build_testbed(force=False, verbose=False):
 
 RENDER_SRC = os.path.join(PKG_DIR, "host", "render_main.cpp")
 RENDER_OUT = os.path.join(ROOT, "build", "render")
-RENDER_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("render_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "snapshot.hpp")] + [
+RENDER_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("render_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "snapshot.hpp", "view_metrics.hpp")] + [
     os.path.join(ROOT, "include", f) for f in ("rnb_neus2.h", "rnb_render.h")]
 
 
@@ -107,8 +107,8 @@ def build_render(force=False, verbose=False):
 
 MESH_SRC = os.path.join(PKG_DIR, "host", "mesh_main.cpp")
 MESH_OUT = os.path.join(ROOT, "build", "mesh")
-MESH_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("mesh_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "snapshot.hpp", "mesh.hpp", "mc_table.hpp")] + [
-    os.path.join(ROOT, "include", f) for f in ("rnb_neus2.h", "rnb_mesh.h", "rnb_mesh_clean.h", "rnb_mesh_simplify.h", "rnb_mesh_distance.h")]
+MESH_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("mesh_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "snapshot.hpp", "mesh.hpp", "mc_table.hpp", "view_metrics.hpp")] + [
+    os.path.join(ROOT, "include", f) for f in ("rnb_neus2.h", "rnb_mesh.h", "rnb_mesh_clean.h", "rnb_mesh_simplify.h", "rnb_mesh_distance.h", "rnb_mesh_raster.h")]
 
 
 def build_mesh(force=False, verbose=False):

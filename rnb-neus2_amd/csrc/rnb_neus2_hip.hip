@@ -9,6 +9,7 @@
 #include "kernels_mesh_clean.cuh"
 #include "kernels_mesh_simplify.cuh"
 #include "kernels_mesh_distance.cuh"
+#include "kernels_mesh_raster.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>
@@ -1816,7 +1817,7 @@ int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float latti
 	return RNB_OK;
 } RNB_GUARD
 
-// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance) ----
+// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster) ----
 extern "C++" {
 namespace {
 // elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
@@ -3051,6 +3052,115 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 		stats->n_cell_entries = hres.n_entries; stats->n_pairs = hres.n_pairs;
 		stats->peak_workspace = ws.peak;
 		stats->ms_grid = ms_grid;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh rasteriser (include/rnb_mesh_raster.h) ----
+uint32_t rnb_mesh_raster_abi_version(void) { return RNB_MESH_RASTER_ABI_VERSION; }
+
+int rnb_mesh_raster_default_options(rnb_mesh_raster_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_RASTER_ABI_VERSION;
+	opt->near = 1.0f / 1024.0f;
+	opt->cull = RNB_MESH_RASTER_CULL_NONE;
+	opt->normals = RNB_MESH_RASTER_NORMALS_FACE;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, const rnb_mesh_raster_options* opt, float* out_dev, uint32_t* face_dev,
+                    rnb_mesh_raster_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !mesh || !view || !opt || !out_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: null argument");
+	if ((void*)out_dev == (void*)face_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: out_dev and face_dev must be different buffers");
+	if (opt->abi_version != RNB_MESH_RASTER_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: options abi_version mismatch (expected RNB_MESH_RASTER_ABI_VERSION)");
+	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: near must be finite and > 0");
+	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
+	if (opt->normals > RNB_MESH_RASTER_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals must be RNB_MESH_RASTER_NORMALS_FACE or _VERTEX");
+	for (int k = 0; k < 2; ++k) {
+		if (!(view->focal_length[k] > 0.0f) || !std::isfinite(view->focal_length[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: a focal length must be finite and > 0");
+		if (!std::isfinite(view->principal_point[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: the principal point must be finite");
+	}
+	for (int k = 0; k < 12; ++k)
+		if (!std::isfinite(view->xform[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an entry of xform is not finite");
+	if (view->width == 0 || view->height == 0 || view->width > RNB_MESH_RASTER_MAX_SIZE || view->height > RNB_MESH_RASTER_MAX_SIZE)
+		return fail(RNB_ERR_INVALID, "rnb_mesh_raster: width and height must be 1 .. 16384");
+	{
+		rnb_mesh unused;
+		if (int rc = check_mesh_input("rnb_mesh_raster", mesh, &unused); rc != RNB_OK) return rc;
+	}
+	if (opt->normals == RNB_MESH_RASTER_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals = VERTEX needs a mesh with normals");
+	const rnb_mesh m = *mesh;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, width = view->width, height = view->height, n_pix = width * height;
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	MrCamera cam;
+	std::memset(&cam, 0, sizeof(cam));
+	for (int r = 0; r < 3; ++r) {
+		cam.o[r] = (double)view->xform[4 * r + 3];
+		for (int k = 0; k < 3; ++k) cam.col[k][r] = (double)view->xform[4 * r + k];
+	}
+	cam.fx = (double)view->focal_length[0]; cam.fy = (double)view->focal_length[1];
+	cam.cxw = (double)view->principal_point[0] * (double)width; cam.cyh = (double)view->principal_point[1] * (double)height;
+	cam.near = (double)opt->near;
+	cam.w = width; cam.h = height; cam.cull = opt->cull; cam.normals = opt->normals;
+	const MrMesh M{m.verts, m.indices, m.colors, m.normals, nt};
+
+	MeshWorkspace ws;
+	MrResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	unsigned long long* keys = nullptr;
+	uint32_t *counts = nullptr, *used = nullptr, *list = nullptr;
+	MrResult* dres = nullptr;
+	if (!ws.alloc(&keys, n_pix) || !ws.alloc(&counts, n_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the workspace of " + std::to_string(n_pix) + " pixels and " + std::to_string(nv) + " vertices");
+	HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_pix * 8, s));
+	HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_pix * 4, s));
+	HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+	if (nt) {
+		const uint32_t g_t = (nt + MR_WG - 1) / MR_WG;
+		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MR_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, MR_BAD_INDEX);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MR_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an index is out of range (>= n_verts)");
+		ws.release(used);
+		// 2. setup, classes, the small triangles filled; the large ones counted, then listed and filled by a wavefront each
+		hipLaunchKernelGGL(k_mr_bin<false>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, (uint32_t*)nullptr, 0u, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		const uint32_t n_large = hres.n_class[MR_LARGE];
+		if (n_large) {
+			if (!ws.alloc(&list, n_large)) return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the list of " + std::to_string(n_large) + " large triangles");
+			hipLaunchKernelGGL(k_mr_bin<true>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, list, n_large, dres);
+			hipLaunchKernelGGL(k_mr_fill_large, dim3((n_large + MR_WG / 64u - 1) / (MR_WG / 64u)), dim3(MR_WG), 0, s, cam, M, (const uint32_t*)list, n_large, keys, counts);
+			HIP_TRY(hipGetLastError());
+		}
+	}
+	// 3. one thread per pixel (an empty mesh: every key is still all ones, the image is zeros)
+	const uint32_t g_p = (n_pix + MR_WG - 1) / MR_WG;
+	if (((uintptr_t)out_dev & 15u) == 0)
+		hipLaunchKernelGGL(k_mr_resolve<true>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
+	else
+		hipLaunchKernelGGL(k_mr_resolve<false>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	ws.release(keys); ws.release(counts); ws.release(used); ws.release(list); ws.release(dres);
+	if (hres.n_unresolved) return fail(RNB_ERR_DEVICE, "rnb_mesh_raster: " + std::to_string(hres.n_unresolved) + " pixels whose winner the resolve pass does not find covering them (the fill and the resolve disagree: a defect of the library)");
+	if (stats) {
+		stats->n_tris = nt;
+		stats->n_behind = hres.n_class[MR_BEHIND]; stats->n_out_of_range = hres.n_class[MR_OUT_OF_RANGE]; stats->n_degenerate = hres.n_class[MR_DEGENERATE];
+		stats->n_culled = hres.n_class[MR_CULLED]; stats->n_offscreen = hres.n_class[MR_OFFSCREEN]; stats->n_small = hres.n_class[MR_SMALL]; stats->n_large = hres.n_class[MR_LARGE];
+		stats->n_covered = hres.n_covered; stats->n_back_pixels = hres.n_back_pixels; stats->n_fragments = hres.n_fragments;
+		stats->peak_workspace = ws.peak;
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}
 	return RNB_OK;

@@ -3,7 +3,7 @@
 // snapshot by snapshot.hpp (its EMA weights, occupancy grid and network configuration).
 //
 //   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
-//        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean] [--report-error]]
+//        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean] [--report-error]] [--report-views [--views-out FILE]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -14,18 +14,23 @@
 // (origin aabb_min, cell = (aabb_max - aabb_min) / N), the representative of a cell placed by --placement (quadric by default). Ring normals are those of the simplified mesh.
 // With --report-error the distance between the simplifier's input and its output is measured on the device in both directions (rnb_mesh_distance,
 // include/rnb_mesh_distance.h, default options) and printed as one more line.
+// With --report-views the final mesh, still on the device and in the frame of the loaded views (before save_obj's scale and shift), is rasterised into every camera of the
+// scene (rnb_mesh_raster, include/rnb_mesh_raster.h, default options) and compared with the input normal maps by view_metrics.hpp, as build/render compares the model's
+// render: one line per view, the means, and <out>.views.json (or --views-out FILE) with the fields of render_metrics.json plus n_back_pixels and odd_count_pixels per view.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
 #include "../../include/rnb_mesh_clean.h"
 #include "../../include/rnb_mesh_simplify.h"
 #include "../../include/rnb_mesh_distance.h"
+#include "../../include/rnb_mesh_raster.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
 #include "msgpack_min.hpp"
 #include "png16.hpp"
 #include "snapshot.hpp"
+#include "view_metrics.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -56,6 +61,8 @@ const Flag FLAGS[] = {
 	{"simplify", "N", "Simplify the mesh on the device: vertex clustering on N^3 cells over the scene's box (1 .. 1024), after the cleaning."},
 	{"placement", "MODE", "--simplify only. quadric (default): the vertex of a cell minimises the quadric error of its triangles; mean: the mean of its vertices."},
 	{"report-error", nullptr, "--simplify only (takes no value). Measure the distance between the mesh before and after the simplification, both directions, and print it."},
+	{"report-views", nullptr, "(takes no value). Rasterise the final mesh into every camera of the scene and compare it with the input normal maps: normal angle and mask IoU per view."},
+	{"views-out", "FILE", "--report-views only. Where the per-view report is written (default: the output mesh's path + .views.json)."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -106,6 +113,55 @@ uint32_t parse_u32(const std::string& k, const std::string& s) {
 		if (rc_ != RNB_OK) throw std::runtime_error(std::string(#expr) + ": " + rnb_last_error()); \
 	} while (0)
 
+// --report-views: the device mesh rasterised into every camera of the scene and compared with the input normal maps (view_metrics.hpp, as build/render compares the
+// model's render). `report`: one line per view and the means, to print; `json`: the text of <out>.views.json.
+void report_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& mesh, const std::string& snap_path, std::string& report, std::string& json) {
+	using view_metrics::num;
+	rnb_mesh_raster_options ropt;
+	RNB_CHECK(rnb_mesh_raster_default_options(&ropt));
+	float* img_dev = nullptr;
+	size_t cap = 0;
+	double s_mean = 0, s_median = 0, s_iou = 0, s_ms = 0;
+	char line[256];
+	try {
+		for (uint32_t vi = 0; vi < ds.views.size(); ++vi) {
+			const rnb_view v = ds.views[vi]; // the loaded view as it is: the camera the model was trained with, at its own size
+			const png16::Image& in = ds.normals[vi];
+			const size_t np = (size_t)v.width * v.height;
+			if (np * RNB_MESH_RASTER_CHANNELS > cap) {
+				if (img_dev) RNB_CHECK(rnb_device_free(ctx, img_dev));
+				img_dev = nullptr;
+				cap = np * RNB_MESH_RASTER_CHANNELS;
+				RNB_CHECK(rnb_device_malloc(ctx, cap * 4, (void**)&img_dev));
+			}
+			rnb_mesh_raster_stats rs;
+			RNB_CHECK(rnb_mesh_raster(ctx, nullptr, &mesh, &v, &ropt, img_dev, nullptr, &rs));
+			std::vector<float> img(np * RNB_MESH_RASTER_CHANNELS);
+			RNB_CHECK(rnb_memcpy(ctx, img.data(), img_dev, img.size() * 4, RNB_D2H));
+			const view_metrics::Result vm = view_metrics::compare(img.data(), RNB_MESH_RASTER_CHANNELS, v.width, v.height, v.xform, in.rgba.data(), in.width, in.height);
+			uint64_t odd = 0;
+			for (size_t p = 0; p < np; ++p) odd += (uint64_t)img[p * RNB_MESH_RASTER_CHANNELS + 8] & 1u;
+			s_mean += vm.mean_angle_deg; s_median += vm.median_angle_deg; s_iou += vm.mask_iou; s_ms += rs.ms;
+			std::snprintf(line, sizeof(line), "view %u: %ux%u, mesh normal angle mean %.3f median %.3f deg, mask IoU %.4f, %u back-facing and %llu odd-count pixels, %.2f ms\n", vi, v.width,
+			              v.height, vm.mean_angle_deg, vm.median_angle_deg, vm.mask_iou, rs.n_back_pixels, (unsigned long long)odd, rs.ms);
+			report += line;
+			if (!json.empty()) json += ",\n";
+			json += "    {\"view\": " + std::to_string(vi) + ", \"width\": " + std::to_string(v.width) + ", \"height\": " + std::to_string(v.height) + ", " +
+			              view_metrics::json_fields(vm) + ", \"n_back_pixels\": " + std::to_string(rs.n_back_pixels) + ", \"odd_count_pixels\": " + std::to_string(odd) +
+			              ", \"frame_ms\": " + num(rs.ms) + "}";
+		}
+	} catch (...) {
+		if (img_dev) rnb_device_free(ctx, img_dev);
+		throw;
+	}
+	if (img_dev) RNB_CHECK(rnb_device_free(ctx, img_dev));
+	const double k = ds.views.empty() ? 1.0 : (double)ds.views.size();
+	std::snprintf(line, sizeof(line), "views: %zu, mesh normal angle mean %.3f median %.3f deg, mask IoU %.4f, %.2f ms per view\n", ds.views.size(), s_mean / k, s_median / k, s_iou / k, s_ms / k);
+	report += line;
+	json = "{\n  \"snapshot\": \"" + snap_path + "\",\n  \"n_triangles\": " + std::to_string(mesh.n_indices / 3u) + ",\n  \"views\": [\n" + json + "\n  ],\n  \"mean\": {\"mean_angle_deg\": " +
+	             num(s_mean / k) + ", \"median_angle_deg\": " + num(s_median / k) + ", \"mask_iou\": " + num(s_iou / k) + ", \"frame_ms\": " + num(s_ms / k) + "}\n}\n";
+}
+
 } // namespace
 
 int main(int argc, char** argv) {
@@ -114,7 +170,7 @@ int main(int argc, char** argv) {
 	bool gradient = false, clean = false;
 	uint32_t keep = RNB_MESH_KEEP_ALL, orient = RNB_MESH_ORIENT_NONE; // with one of the two flags given, the other one leaves its part alone
 	uint32_t simplify = 0, placement = RNB_MESH_PLACE_QUADRIC;           // 0: no simplification
-	bool report_error = false;
+	bool report_error = false, want_views = false;
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -155,6 +211,8 @@ int main(int argc, char** argv) {
 			if (!simplify) throw ParseError("Argument 'report-error' is only used with --simplify");
 			report_error = true;
 		}
+		if (a.count("report-views")) want_views = true;
+		if (a.count("views-out") && !want_views) throw ParseError("Argument 'views-out' is only used with --report-views");
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
 		print_help(std::cerr, argv[0]);
@@ -232,6 +290,9 @@ int main(int argc, char** argv) {
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		}
+		// --report-views: made here, while the mesh is on the device and in the frame of the loaded views; printed and written after the mesh's own lines, below
+		std::string views_report, views_json;
+		if (want_views) report_views(ctx, ds, dm, snap_path, views_report, views_json);
 		mesh::Mesh m;
 		m.verts.resize(dm.n_verts); m.colors.resize(dm.n_verts); m.indices.resize(dm.n_indices);
 		if (dm.n_verts) {
@@ -259,6 +320,14 @@ int main(int argc, char** argv) {
 			}
 			std::printf("simplify error: in -> out mean %.9g rms %.9g max %.9g, out -> in mean %.9g rms %.9g max %.9g, %.1f ms\n", mean[0], rms[0], es[0].max_distance, mean[1], rms[1],
 			            es[1].max_distance, es[0].ms + es[1].ms);
+		}
+		if (want_views) {
+			std::fputs(views_report.c_str(), stdout);
+			const std::string path = a.count("views-out") ? a["views-out"] : a["out"] + ".views.json";
+			std::FILE* f = std::fopen(path.c_str(), "wb");
+			if (!f) throw std::runtime_error("cannot write " + path);
+			std::fputs(views_json.c_str(), f);
+			std::fclose(f);
 		}
 		std::printf("#vertices=%zu #triangles=%zu\n", m.verts.size(), m.indices.size() / 3);
 		// --orient outward speaks of the file: the device turned every kept component counter-clockwise seen from outside, and the faces are written as they are

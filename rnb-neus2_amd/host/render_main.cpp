@@ -15,6 +15,7 @@
 #include "msgpack_min.hpp"
 #include "png16.hpp"
 #include "snapshot.hpp"
+#include "view_metrics.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -102,7 +103,7 @@ void save_npy(const std::string& path, const float* data, uint32_t h, uint32_t w
 
 uint16_t to_u16(float v) { return (uint16_t)std::lround(std::min(std::max(v, 0.0f), 1.0f) * 65535.0f); }
 
-std::string num(double v) { char b[64]; std::snprintf(b, sizeof(b), "%.6g", std::isfinite(v) ? v : 0.0); return b; }
+using view_metrics::num;
 
 } // namespace
 
@@ -194,56 +195,33 @@ int main(int argc, char** argv) {
 			RNB_CHECK(rnb_memcpy(ctx, img.data(), img_dev, img.size() * 4, RNB_D2H));
 			std::vector<uint16_t> nrm(np * 4), alb(np * 4);
 			std::vector<float> depth(np);
-			std::vector<double> angles;
-			uint64_t inter = 0, uni = 0;
+			view_metrics::Accumulator acc(v.width, v.height, in.rgba.data(), in.width, in.height); // the comparison with the input map: view_metrics.hpp
 			for (size_t p = 0; p < np; ++p) {
 				const float* c = img.data() + p * RNB_RENDER_CHANNELS;
 				const bool mask = c[6] > 0.5f;
 				// the camera-frame normal R^T n, stored as (x, -y, -z) in [0, 1] (synthetic.render_view's and the loss's encoding, ray_targets)
 				float nc[3];
-				for (int k = 0; k < 3; ++k) nc[k] = v.xform[0 * 4 + k] * c[0] + v.xform[1 * 4 + k] * c[1] + v.xform[2 * 4 + k] * c[2];
+				view_metrics::camera_normal(v.xform, c, nc);
 				const float m[3] = {nc[0], -nc[1], -nc[2]};
 				for (int k = 0; k < 3; ++k) nrm[p * 4 + k] = mask ? to_u16((m[k] + 1.0f) * 0.5f) : 0;
 				nrm[p * 4 + 3] = mask ? 65535 : 0;
 				for (int k = 0; k < 3; ++k) alb[p * 4 + k] = to_u16(c[3 + k]);
 				alb[p * 4 + 3] = mask ? 65535 : 0;
 				depth[p] = c[7];
-				// the input pixel whose area holds this pixel's centre
-				const uint32_t x = (uint32_t)(p % v.width), y = (uint32_t)(p / v.width);
-				const uint32_t ix = std::min(in.width - 1, (uint32_t)(((double)x + 0.5) * in.width / v.width));
-				const uint32_t iy = std::min(in.height - 1, (uint32_t)(((double)y + 0.5) * in.height / v.height));
-				const uint16_t* t = in.rgba.data() + ((size_t)iy * in.width + ix) * 4;
-				const bool mask_in = t[3] > 0;
-				inter += (mask && mask_in); uni += (mask || mask_in);
-				if (mask && mask_in) {
-					double ti[3] = {t[0] / 65535.0 * 2.0 - 1.0, -(t[1] / 65535.0 * 2.0 - 1.0), -(t[2] / 65535.0 * 2.0 - 1.0)};
-					const double ln = std::sqrt(ti[0] * ti[0] + ti[1] * ti[1] + ti[2] * ti[2]), lr = std::sqrt((double)nc[0] * nc[0] + (double)nc[1] * nc[1] + (double)nc[2] * nc[2]);
-					if (ln > 0 && lr > 0) {
-						const double cs = (ti[0] * nc[0] + ti[1] * nc[1] + ti[2] * nc[2]) / (ln * lr);
-						angles.push_back(std::acos(std::min(1.0, std::max(-1.0, cs))) * 180.0 / M_PI);
-					}
-				}
+				acc.add(p, mask, nc);
 			}
 			char name[32];
 			std::snprintf(name, sizeof(name), "%05u", vi);
 			png16::save(out + "/normals/" + name + ".png", nrm.data(), v.width, v.height, 4, 16);
 			png16::save(out + "/albedos/" + name + ".png", alb.data(), v.width, v.height, 4, 16);
 			save_npy(out + "/depth/" + name + ".npy", depth.data(), v.height, v.width);
-			double mean = 0, median = 0;
-			if (!angles.empty()) {
-				for (double x : angles) mean += x;
-				mean /= angles.size();
-				std::sort(angles.begin(), angles.end());
-				const size_t k = angles.size();
-				median = k % 2 ? angles[k / 2] : 0.5 * (angles[k / 2 - 1] + angles[k / 2]);
-			}
-			const double iou = uni ? (double)inter / (double)uni : 1.0;
+			const view_metrics::Result vm = acc.finish();
+			const double mean = vm.mean_angle_deg, median = vm.median_angle_deg, iou = vm.mask_iou;
 			s_mean += mean; s_median += median; s_iou += iou; s_ms += st.ms;
 			std::printf("view %u: %ux%u, normal angle mean %.3f median %.3f deg, mask IoU %.4f, %.2f ms\n", vi, v.width, v.height, mean, median, iou, st.ms);
 			if (!views_json.empty()) views_json += ",\n";
 			views_json += "    {\"view\": " + std::to_string(vi) + ", \"width\": " + std::to_string(v.width) + ", \"height\": " + std::to_string(v.height) +
-			              ", \"mean_angle_deg\": " + num(mean) + ", \"median_angle_deg\": " + num(median) + ", \"mask_iou\": " + num(iou) +
-			              ", \"pixels_compared\": " + std::to_string(angles.size()) + ", \"frame_ms\": " + num(st.ms) + "}";
+			              ", " + view_metrics::json_fields(vm) + ", \"frame_ms\": " + num(st.ms) + "}";
 		}
 		const double k = sel.empty() ? 1.0 : (double)sel.size();
 		std::FILE* f = std::fopen((out + "/render_metrics.json").c_str(), "wb");

@@ -37,6 +37,7 @@ _SPEC = """
 --device-postprocess | flag |        | clean the final mesh on the GPU (build/mesh --keep largest --orient outward on the stage-2 snapshot) instead of in Python
 --mesh-exe          | str   |        | --device-postprocess only: the mesh executable (default: build/mesh beside the testbed)
 --simplify          | int   |        | --device-postprocess only: simplify the final mesh on the GPU by vertex clustering on N^3 cells over the scene box (build/mesh --simplify N)
+--report-views      | flag  |        | --device-postprocess only: rasterise the final mesh into every input view and write its normal angle and mask IoU per view (build/mesh --report-views)
 """
 
 
@@ -65,13 +66,15 @@ def pipeline_kwargs(ns):
     """argparse namespace -> keywords of rnb_neus2_amd.pipeline.run_full_pipeline."""
     renamed = {"input": "input_path", "testbed": "testbed_path", "output": "output_dir", "supernormal": "super_normal", "l1": "use_l1",
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
-    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify")}
+    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
         kw["mesh_exe"] = ns.mesh_exe or None
         if ns.simplify is not None:
             kw["simplify"] = ns.simplify
+        if ns.report_views:
+            kw["report_views"] = True
     return kw
 
 
@@ -82,6 +85,8 @@ def main(argv=None):
         parser.error("--mesh-exe is only used with --device-postprocess")
     if ns.simplify is not None and not ns.device_postprocess:
         parser.error("--simplify is only used with --device-postprocess")
+    if ns.report_views and not ns.device_postprocess:
+        parser.error("--report-views is only used with --device-postprocess")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
         parser.error("--simplify must be 1 .. 1024")
     np.random.seed(ns.seed)
