@@ -4,7 +4,6 @@ The reference drives this path through ``Testbed`` (src/testbed.cu:2776-2872, sr
 ``Context`` keeps the same verbs (reset_network/init params, load dataset, train step, per-stage calls) and hands
 everything to ``librnb_neus2_hip.so``. There is no CPU fallback: if the HIP library is missing, loading fails.
 """
-import contextlib
 import ctypes as C
 import math
 import os
@@ -14,7 +13,7 @@ import numpy as np
 from . import _abi
 from ._abi import Config, View, StepStats, BUF, BUF_DTYPE
 
-__all__ = ["Context", "Config", "View", "StepStats", "load_library", "default_config", "library_path",
+__all__ = ["Context", "DeviceMesh", "Config", "View", "StepStats", "load_library", "default_config", "library_path",
            "load_sdf_init_weights", "RnbError", "BUF", "scaled_view", "RENDER_CHANNELS"]
 
 RENDER_CHANNELS = _abi.RENDER_CHANNELS
@@ -523,6 +522,28 @@ class Context:
         self.device_free(pi.value)
         return verts, idx
 
+    def extract_mesh_device(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
+                            cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None):
+        """rnb_extract_mesh (include/rnb_mesh.h) -> a DeviceMesh, its `stats` the rnb_mesh_stats of the call: the lattice and attribute arguments of extract_mesh, which
+        describes them; the mesh stays on the device for clean / simplify / distance_to / rasterize / download. Leaves the training state as it was."""
+        opt = _abi.MeshOptions()
+        self._check(self.f.mesh_default_options(C.byref(opt)))
+        opt.res[:] = [int(res)] * 3 if np.isscalar(res) else [int(x) for x in res]
+        opt.lattice_min, opt.lattice_max = float(lattice_min), float(lattice_max)
+        opt.aabb_min[:] = [float(x) for x in aabb_min]
+        opt.aabb_max[:] = [float(x) for x in aabb_max]
+        opt.thresh = float(thresh)
+        opt.use_inference_params = int(bool(inference))
+        if cull not in ("none", "occupancy", _abi.MESH_CULL_NONE, _abi.MESH_CULL_OCCUPANCY):
+            raise ValueError("cull must be 'none' or 'occupancy'")
+        opt.cull = {"none": _abi.MESH_CULL_NONE, "occupancy": _abi.MESH_CULL_OCCUPANCY}.get(cull, cull)
+        opt.brick = int(brick)
+        opt.attributes = (_abi.MESH_ATTR_COLORS if colors else 0) | (_abi.MESH_ATTR_NORMALS if normals else 0)
+        opt.max_points_in_flight = int(max_points_in_flight)
+        opt.max_active_points = int(max_active_points)
+        st = _abi.MeshStats()
+        return _returned_mesh(self, st, lambda m: self.f.extract_mesh(self._h, _stream_handle(stream), C.byref(opt), m, C.byref(st)))
+
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
                      simplify=None, placement="quadric", error=False):
@@ -541,56 +562,27 @@ class Context:
         of that runs and the result is as it was."""
         if error and simplify is None:
             raise ValueError("error=True needs simplify")
-        sopt = None if simplify is None else self._simplify_options(*self.simplify_grid(aabb_min, aabb_max, simplify), placement)
-        copt = None if keep is None and orient is None else self._clean_options("all" if keep is None else keep, "none" if orient is None else orient)
-        opt = _abi.MeshOptions()
-        self._check(self.f.mesh_default_options(C.byref(opt)))
-        opt.res[:] = [int(res)] * 3 if np.isscalar(res) else [int(x) for x in res]
-        opt.lattice_min, opt.lattice_max = float(lattice_min), float(lattice_max)
-        opt.aabb_min[:] = [float(x) for x in aabb_min]
-        opt.aabb_max[:] = [float(x) for x in aabb_max]
-        opt.thresh = float(thresh)
-        opt.use_inference_params = int(bool(inference))
-        if cull not in ("none", "occupancy", _abi.MESH_CULL_NONE, _abi.MESH_CULL_OCCUPANCY):
-            raise ValueError("cull must be 'none' or 'occupancy'")
-        opt.cull = {"none": _abi.MESH_CULL_NONE, "occupancy": _abi.MESH_CULL_OCCUPANCY}.get(cull, cull)
-        opt.brick = int(brick)
-        opt.attributes = (_abi.MESH_ATTR_COLORS if colors else 0) | (_abi.MESH_ATTR_NORMALS if normals else 0)
-        opt.max_points_in_flight = int(max_points_in_flight)
-        opt.max_active_points = int(max_active_points)
-        m, st = _abi.Mesh(), _abi.MeshStats()
-        self._check(self.f.extract_mesh(self._h, _stream_handle(stream), C.byref(opt), C.byref(m), C.byref(st)))
-        cleaned, cst = _abi.Mesh(), _abi.MeshCleanStats()
-        simplified, sst = _abi.Mesh(), _abi.MeshSimplifyStats()
-        try:
-            last = m
-            if copt is not None:  # device to device: the extracted mesh never visits the host
-                self._check(self.f.mesh_clean(self._h, _stream_handle(stream), C.byref(m), C.byref(copt), C.byref(cleaned), None, C.byref(cst)))
-                last = cleaned
-            if sopt is not None:
-                self._check(self.f.mesh_simplify(self._h, _stream_handle(stream), C.byref(last), C.byref(sopt), C.byref(simplified), C.byref(sst)))
-                simplify_error = self._mesh_distance_symmetric(last, simplified, self._distance_options(), False, stream) if error else None
-                last = simplified
-            out = self._download_mesh(last)
-            out["stats"] = st.as_dict()
-            if sopt is not None and error:
+        grid = None if simplify is None else self.simplify_grid(aabb_min, aabb_max, simplify)
+        chain = [self.extract_mesh_device(res, lattice_min, lattice_max, aabb_min, aabb_max, thresh, inference, cull, brick, colors, normals, max_points_in_flight,
+                                          max_active_points, stream)]
+        try:  # device to device: the extracted mesh never visits the host
+            if keep is not None or orient is not None:
+                chain.append(chain[-1].clean("all" if keep is None else keep, "none" if orient is None else orient, stream=stream))
+            if grid is not None:
+                chain.append(chain[-1].simplify(*grid, placement=placement, stream=stream))
+                if error:
+                    simplify_error = chain[-2].distance_to(chain[-1], symmetric=True, stream=stream)
+            out = chain[-1].download()
+            out["stats"] = chain[0].stats
+            if grid is not None and error:
                 out["simplify_error"] = simplify_error
-            if copt is not None:
-                out["clean_stats"] = cst.as_dict()
-            if sopt is not None:
-                out["simplify_stats"] = sst.as_dict()
+            if keep is not None or orient is not None:
+                out["clean_stats"] = chain[1].stats
+            if grid is not None:
+                out["simplify_stats"] = chain[-1].stats
         finally:
-            self.f.mesh_free(self._h, C.byref(m))
-            self.f.mesh_free(self._h, C.byref(cleaned))
-            self.f.mesh_free(self._h, C.byref(simplified))
-        return out
-
-    def _download_mesh(self, m):
-        out = dict(verts=self.download(m.verts, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32),
-                   indices=self.download(m.indices, m.n_indices, np.uint32) if m.n_indices else np.empty(0, np.uint32))
-        for key, ptr in (("colors", m.colors), ("normals", m.normals)):
-            if ptr:
-                out[key] = self.download(ptr, m.n_verts * 3, np.float32).reshape(-1, 3) if m.n_verts else np.empty((0, 3), np.float32)
+            for m in chain:  # whatever exists by now, oldest first
+                m.free()
         return out
 
     def _clean_options(self, keep, orient):
@@ -605,9 +597,8 @@ class Context:
         opt.keep, opt.orient = keeps[keep], orients[orient]
         return opt
 
-    @contextlib.contextmanager
-    def _device_mesh(self, verts, indices, colors, normals):
-        """A host mesh (verts float32[n,3], indices uint32[m] or [m/3,3], optional per-vertex colors / normals) as an _abi.Mesh on the device; the uploads are freed on exit."""
+    def upload_mesh(self, verts, indices, colors=None, normals=None):
+        """A host mesh (verts float32[n,3], indices uint32[m] or [m/3,3], optional per-vertex colors / normals) -> a DeviceMesh; free it (or use it in a `with`) to release the uploads."""
         v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
         arrays = dict(verts=v, indices=np.ascontiguousarray(indices, dtype=np.uint32).ravel())
         for key, a in (("colors", colors), ("normals", normals)):
@@ -615,16 +606,17 @@ class Context:
                 arrays[key] = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
                 if arrays[key].shape != v.shape:
                     raise ValueError("%s must have one row per vertex" % key)
-        m, ptrs = _abi.Mesh(), []
+        m = DeviceMesh(self, buffers=[])
         try:
             for key, a in arrays.items():
-                ptrs.append(self.upload(a) if a.size else self.device_malloc(4))
-                setattr(m, key, ptrs[-1])
-            m.n_verts, m.n_indices = v.shape[0], arrays["indices"].size
-            yield m
-        finally:
-            for p in ptrs:
-                self.device_free(p)
+                m._buffers.append(self.upload(a) if a.size else self.device_malloc(4))
+                setattr(m, key, m._buffers[-1])
+            _abi.Mesh.n_verts.__set__(m, v.shape[0])
+            m.n_indices = arrays["indices"].size
+        except BaseException:
+            m.free()
+            raise
+        return m
 
     def clean_mesh(self, verts, indices, colors=None, normals=None, keep="largest", orient="outward", table=False, stream=None):
         """rnb_mesh_clean (include/rnb_mesh_clean.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals. The
@@ -632,20 +624,13 @@ class Context:
         component of negative signed volume get their second and third index swapped; "none": as they come). Returns a dict of numpy arrays (verts, indices, colors /
         normals when given) in the input's order, `stats`, and with table=True `table`: one record per component (label, n_vertices, n_triangles, kept, area_q,
         volume_q), ascending label. For a dict m that extract_mesh returned: clean_mesh(m["verts"], m["indices"], m.get("colors"), m.get("normals")). Leaves the training state as it was."""
-        copt = self._clean_options(keep, orient)
-        cleaned, cst, tab = _abi.Mesh(), _abi.MeshCleanStats(), C.c_void_p()
-        try:
-            with self._device_mesh(verts, indices, colors, normals) as m:
-                self._check(self.f.mesh_clean(self._h, _stream_handle(stream), C.byref(m), C.byref(copt), C.byref(cleaned), C.byref(tab) if table else None, C.byref(cst)))
-            out = self._download_mesh(cleaned)
-            out["stats"] = cst.as_dict()
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            cleaned = m.clean(keep, orient, table, stream)
+        with cleaned:
+            out = cleaned.download()
+            out["stats"] = cleaned.stats
             if table:
-                dt = np.dtype(_abi.MESH_COMPONENT_DTYPE)
-                out["table"] = self.download(tab.value, cst.n_components, dt) if cst.n_components else np.empty(0, dt)
-        finally:
-            self.f.mesh_free(self._h, C.byref(cleaned))
-            if tab.value:
-                self.f.mesh_clean_table_free(self._h, tab)
+                out["table"] = cleaned.table
         return out
 
     @staticmethod
@@ -681,15 +666,11 @@ class Context:
         placement="quadric" (the regularised minimiser of the squared distances to the planes of the triangles that touch the cell, kept inside the cell) or "mean";
         colours are averaged, normals summed and normalised; triangles that lose a corner are dropped, the others keep order and winding. Bit-reproducible. Returns a
         dict of numpy arrays like clean_mesh, with `stats` = `simplify_stats` (counts, n_clamped, n_fallback, peak_workspace, ms). Leaves the training state as it was."""
-        sopt = self._simplify_options(origin, cell, dims, placement)
-        simplified, sst = _abi.Mesh(), _abi.MeshSimplifyStats()
-        try:
-            with self._device_mesh(verts, indices, colors, normals) as m:
-                self._check(self.f.mesh_simplify(self._h, _stream_handle(stream), C.byref(m), C.byref(sopt), C.byref(simplified), C.byref(sst)))
-            out = self._download_mesh(simplified)
-            out["stats"] = out["simplify_stats"] = sst.as_dict()
-        finally:
-            self.f.mesh_free(self._h, C.byref(simplified))
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            simplified = m.simplify(origin, cell, dims, placement, stream)
+        with simplified:
+            out = simplified.download()
+            out["stats"] = out["simplify_stats"] = simplified.stats
         return out
 
     def _distance_options(self, level=1, max_distance=0.0, unit=2.0 ** -10, thresholds=(), cells=0):
@@ -706,41 +687,6 @@ class Context:
         opt.tau[:len(thresholds)] = thresholds
         return opt
 
-    def _mesh_distance_device(self, a, b, opt, per_vertex, stream):
-        """One rnb_mesh_distance call on two _abi.Mesh in device memory; the dict mesh_distance returns for one direction."""
-        st = _abi.MeshDistanceStats()
-        n_tau = sum(1 for x in opt.tau if x != 0)
-        dist = near = None
-        try:
-            if per_vertex:
-                dist, near = self.device_malloc(max(a.n_verts, 1) * 4), self.device_malloc(max(a.n_verts, 1) * 4)
-            self._check(self.f.mesh_distance(self._h, _stream_handle(stream), C.byref(a), C.byref(b), C.byref(opt), dist, near, C.byref(st)))
-            out = st.as_dict()
-            if per_vertex:
-                out["vert_dist"] = self.download(dist, a.n_verts, np.float32)
-                out["vert_nearest"] = self.download(near, a.n_verts, np.uint32)
-        finally:
-            for p in (dist, near):
-                if p:
-                    self.device_free(p)
-        unit, sw = float(opt.unit), st.sum_w
-        out["unit"] = unit
-        out["mean"] = st.sum_wd / sw * unit if sw else 0.0
-        out["rms"] = math.sqrt(st.sum_wd2 / sw) * unit if sw else 0.0
-        out["max"] = st.max_distance
-        out["within"] = [st.sum_within[k] / sw if sw else 0.0 for k in range(n_tau)]
-        out["quantisation"] = st.n_samples / sw * unit if sw else 0.0
-        return out
-
-    def _mesh_distance_symmetric(self, a, b, opt, per_vertex, stream):
-        out = self._mesh_distance_device(a, b, opt, per_vertex, stream)
-        back = self._mesh_distance_device(b, a, opt, per_vertex, stream)
-        out["reverse"] = back
-        out["chamfer"] = out["mean"] + back["mean"]
-        out["hausdorff"] = max(out["max"], back["max"])
-        out["fscore"] = [2.0 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(out["within"], back["within"])]
-        return out
-
     def mesh_distance(self, a_verts, a_indices, b_verts, b_indices, level=1, max_distance=0.0, unit=2.0 ** -10, thresholds=(), cells=0, per_vertex=False, symmetric=False,
                       stream=None):
         """rnb_mesh_distance (include/rnb_mesh_distance.h) on two host meshes (verts float32[n,3], indices uint32[m] or [m/3,3]): the one-sided distance from the surface
@@ -755,11 +701,8 @@ class Context:
         symmetric=True runs B -> A as well (its dict under `reverse`) and adds `chamfer` = mean(A->B) + mean(B->A) (the sum of the two means of unsquared
         distances, not halved), `hausdorff` = the larger of the two maxima, and per threshold `fscore` = 2 P R / (P + R) with precision P = within(A->B) and
         recall R = within(B->A): A is the reconstruction, B the reference. Bit-reproducible. Leaves the training state as it was."""
-        opt = self._distance_options(level, max_distance, unit, thresholds, cells)
-        with self._device_mesh(a_verts, a_indices, None, None) as a, self._device_mesh(b_verts, b_indices, None, None) as b:
-            if symmetric:
-                return self._mesh_distance_symmetric(a, b, opt, per_vertex, stream)
-            return self._mesh_distance_device(a, b, opt, per_vertex, stream)
+        with self.upload_mesh(a_verts, a_indices) as a, self.upload_mesh(b_verts, b_indices) as b:
+            return a.distance_to(b, level, max_distance, unit, thresholds, cells, per_vertex, symmetric, stream)
 
     def _raster_options(self, near, cull, shading):
         culls = {"none": _abi.MESH_RASTER_CULL_NONE, "back": _abi.MESH_RASTER_CULL_BACK, "front": _abi.MESH_RASTER_CULL_FRONT}
@@ -773,27 +716,6 @@ class Context:
         opt.near, opt.cull, opt.normals = float(near), culls[cull], shadings[shading]
         return opt
 
-    def _rasterize_device(self, m, view, opt, faces, stream):
-        """One rnb_mesh_raster call on an _abi.Mesh in device memory; the dict rasterize_mesh returns."""
-        h, w = int(view["height"]), int(view["width"])
-        n = h * w
-        st = _abi.MeshRasterStats()
-        img = fac = None
-        try:
-            img = self.device_malloc(max(n, 1) * _abi.MESH_RASTER_CHANNELS * 4)
-            if faces:
-                fac = self.device_malloc(max(n, 1) * 4)
-            self._check(self.f.mesh_raster(self._h, _stream_handle(stream), C.byref(m), C.byref(_view_struct(view)), C.byref(opt), img, fac, C.byref(st)))
-            out = st.as_dict()
-            out["image"] = self.download(img, n * _abi.MESH_RASTER_CHANNELS, np.float32).reshape(h, w, _abi.MESH_RASTER_CHANNELS)
-            if faces:
-                out["faces"] = self.download(fac, n, np.uint32).reshape(h, w)
-        finally:
-            for p in (img, fac):
-                if p:
-                    self.device_free(p)
-        return out
-
     def rasterize_mesh(self, verts, indices, view, colors=None, normals=None, near=2.0 ** -10, cull="none", shading="face", faces=False, stream=None):
         """rnb_mesh_raster (include/rnb_mesh_raster.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3], optional per-vertex colors / normals) and one
         camera (a view dict as set_dataset and render take). Returns a dict: `image` float32 [H,W,9] in the channel layout of the render (0-2 unit normal in the world
@@ -802,11 +724,8 @@ class Context:
         "face" (the triangle's own normal) or "vertex" (the interpolated `normals`, which must then be given). Coverage is exact on 1/256-pixel snapped vertices, a pixel
         centre on a shared edge belongs to exactly one triangle; a triangle with a vertex nearer than `near` is skipped and counted, not clipped. Bit-reproducible.
         Leaves the training state as it was."""
-        opt = self._raster_options(near, cull, shading)
-        if shading == "vertex" and normals is None:
-            raise ValueError("shading='vertex' needs normals")
-        with self._device_mesh(verts, indices, colors, normals) as m:
-            return self._rasterize_device(m, view, opt, faces, stream)
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            return m.rasterize(view, near, cull, shading, faces, stream)
 
     def mesh_view_metrics(self, verts, indices, views, normal_maps, normals=None, near=2.0 ** -10, cull="none", shading="face", stream=None):
         """The mesh's counterpart of build/render's render_metrics.json: the mesh rasterised into every view of `views` (rasterize_mesh) and compared with that view's
@@ -814,13 +733,13 @@ class Context:
         pixels_compared, n_back_pixels, odd_count_pixels (pixels an odd number of triangles cover: 0 for a closed mesh), ms], mean={the means of the first three})."""
         if len(views) != len(normal_maps):
             raise ValueError("one normal map per view")
-        opt = self._raster_options(near, cull, shading)
+        self._raster_options(near, cull, shading)  # a bad argument fails before anything is uploaded, and with no view at all
         if shading == "vertex" and normals is None:
             raise ValueError("shading='vertex' needs normals")
         per_view = []
-        with self._device_mesh(verts, indices, None, normals) as m:
+        with self.upload_mesh(verts, indices, None, normals) as m:
             for view, nm in zip(views, normal_maps):
-                r = self._rasterize_device(m, view, opt, False, stream)
+                r = m.rasterize(view, near, cull, shading, stream=stream)
                 e = view_normal_metrics(r["image"], view, nm)
                 e.update(n_back_pixels=r["n_back_pixels"], odd_count_pixels=int((r["image"][..., 8].astype(np.int64) & 1).sum()), ms=r["ms"])
                 per_view.append(e)
@@ -891,3 +810,174 @@ class Context:
         rc = self.f.train_step_end(self._h, _stream_handle(stream), C.byref(st))
         self._check(rc, allow=(_abi.ERR_NO_SAMPLES,) if allow_no_samples else ())
         return st
+
+def _returned_mesh(ctx, stats, call):
+    """One C call that fills a new rnb_mesh (`call(byref(mesh))` returns its status) -> the DeviceMesh that owns it, with `stats` as its dict."""
+    out = DeviceMesh(ctx)
+    try:
+        ctx._check(call(C.byref(out)))
+    except BaseException:
+        out.free()  # (whatever a failed call left goes the way of a returned mesh)
+        raise
+    out._stats = stats.as_dict()
+    return out
+
+
+class DeviceMesh(_abi.Mesh):
+    """A mesh whose buffers are in device memory: the rnb_mesh of the C-ABI (it is the struct, so C.byref(m) goes to a raw call) together with the Context it belongs to, which
+    therefore cannot be collected first. Context.upload_mesh and Context.extract_mesh_device make one; clean and simplify return a new one and leave theirs as it was;
+    distance_to and rasterize measure; download brings the arrays to the host. Nothing visits the host in between.
+    `with m:` or m.free() releases the buffers, once: rnb_mesh_free for a mesh a stage returned, one device_free per buffer for an uploaded one. After that every method
+    raises ValueError before any call into the library. Free the meshes of a context before closing it: free() after Context.close() does nothing (the context's memory is
+    gone with it)."""
+
+    def __init__(self, ctx, buffers=None):
+        super().__init__()
+        self.ctx, self._buffers, self._stats, self._freed = ctx, buffers, None, False
+        self._table, self._table_host = C.c_void_p(), None
+
+    n_verts = property(lambda self: _abi.Mesh.n_verts.__get__(self))
+    n_triangles = property(lambda self: self.n_indices // 3)
+    has_colors = property(lambda self: bool(self.colors))
+    has_normals = property(lambda self: bool(self.normals))
+    stats = property(lambda self: self._stats, doc="The stats dict of the call that produced the mesh (rnb_mesh_stats, rnb_mesh_clean_stats, rnb_mesh_simplify_stats); None for an upload.")
+
+    def _live(self):
+        if self._freed:
+            raise ValueError("the device mesh has been freed")
+        return self.ctx
+
+    def free(self):
+        """Release the device buffers; a second call, or one after the context was closed, does nothing."""
+        if self._freed:
+            return
+        self._freed = True
+        c = self.ctx
+        if not c._h.value:
+            return
+        if self._buffers is not None:
+            for p in self._buffers:
+                c.device_free(p)
+            C.memset(C.byref(self), 0, C.sizeof(_abi.Mesh))
+        else:
+            c.f.mesh_free(c._h, C.byref(self))
+            if self._table:
+                c.f.mesh_clean_table_free(c._h, self._table)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        self._live()
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+    def download(self):
+        """-> dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when the mesh has them."""
+        c = self._live()
+        out = dict(verts=c.download(self.verts, self.n_verts * 3, np.float32).reshape(-1, 3) if self.n_verts else np.empty((0, 3), np.float32),
+                   indices=c.download(self.indices, self.n_indices, np.uint32) if self.n_indices else np.empty(0, np.uint32))
+        for key, ptr in (("colors", self.colors), ("normals", self.normals)):
+            if ptr:
+                out[key] = c.download(ptr, self.n_verts * 3, np.float32).reshape(-1, 3) if self.n_verts else np.empty((0, 3), np.float32)
+        return out
+
+    def clean(self, keep="largest", orient="outward", table=False, stream=None):
+        """rnb_mesh_clean (see Context.clean_mesh) -> the cleaned DeviceMesh; its `stats` are the clean stats. With table=True the component table is made as well and stays
+        on the device beside the mesh, released with it; `table` reads it."""
+        c = self._live()
+        opt, st, tab = c._clean_options(keep, orient), _abi.MeshCleanStats(), C.c_void_p()
+        out = _returned_mesh(c, st, lambda m: c.f.mesh_clean(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), m, C.byref(tab) if table else None, C.byref(st)))
+        out._table = tab
+        return out
+
+    @property
+    def table(self):
+        """After clean(table=True): one record per component (label, n_vertices, n_triangles, kept, area_q, volume_q), ascending label, as a numpy record array -- downloaded
+        when first read, so read it before the mesh is freed. None for any other mesh."""
+        if self._table_host is None and self._table:
+            dt, n = np.dtype(_abi.MESH_COMPONENT_DTYPE), self._stats["n_components"]
+            self._table_host = self._live().download(self._table.value, n, dt) if n else np.empty(0, dt)
+        return self._table_host
+
+    def simplify(self, origin, cell, dims, placement="quadric", stream=None):
+        """rnb_mesh_simplify on the grid of dims cells of edge `cell` from `origin` (see Context.simplify_mesh; Context.simplify_grid lays one over a box) -> the simplified
+        DeviceMesh; its `stats` are the simplify stats."""
+        c = self._live()
+        opt, st = c._simplify_options(origin, cell, dims, placement), _abi.MeshSimplifyStats()
+        return _returned_mesh(c, st, lambda m: c.f.mesh_simplify(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), m, C.byref(st)))
+
+    def _distance(self, other, opt, per_vertex, stream):
+        """One rnb_mesh_distance call, self -> other; the dict distance_to returns for one direction."""
+        c = self.ctx
+        st = _abi.MeshDistanceStats()
+        n_tau = sum(1 for x in opt.tau if x != 0)
+        dist = near = None
+        try:
+            if per_vertex:
+                dist, near = c.device_malloc(max(self.n_verts, 1) * 4), c.device_malloc(max(self.n_verts, 1) * 4)
+            c._check(c.f.mesh_distance(c._h, _stream_handle(stream), C.byref(self), C.byref(other), C.byref(opt), dist, near, C.byref(st)))
+            out = st.as_dict()
+            if per_vertex:
+                out["vert_dist"] = c.download(dist, self.n_verts, np.float32)
+                out["vert_nearest"] = c.download(near, self.n_verts, np.uint32)
+        finally:
+            for p in (dist, near):
+                if p:
+                    c.device_free(p)
+        unit, sw = float(opt.unit), st.sum_w
+        out["unit"] = unit
+        out["mean"] = st.sum_wd / sw * unit if sw else 0.0
+        out["rms"] = math.sqrt(st.sum_wd2 / sw) * unit if sw else 0.0
+        out["max"] = st.max_distance
+        out["within"] = [st.sum_within[k] / sw if sw else 0.0 for k in range(n_tau)]
+        out["quantisation"] = st.n_samples / sw * unit if sw else 0.0
+        return out
+
+    def distance_to(self, other, level=1, max_distance=0.0, unit=2.0 ** -10, thresholds=(), cells=0, per_vertex=False, symmetric=False, stream=None):
+        """rnb_mesh_distance from this mesh (A) to `other` (B), both on the device: the dict of Context.mesh_distance, which describes every argument and key."""
+        c = self._live()
+        other._live()
+        opt = c._distance_options(level, max_distance, unit, thresholds, cells)
+        out = self._distance(other, opt, per_vertex, stream)
+        if symmetric:
+            back = other._distance(self, opt, per_vertex, stream)
+            out["reverse"] = back
+            out["chamfer"] = out["mean"] + back["mean"]
+            out["hausdorff"] = max(out["max"], back["max"])
+            out["fscore"] = [2.0 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(out["within"], back["within"])]
+        return out
+
+    def rasterize(self, view, near=2.0 ** -10, cull="none", shading="face", faces=False, stream=None, out_ptr=None):
+        """rnb_mesh_raster of this mesh into one camera: the dict of Context.rasterize_mesh, which describes every argument and key. out_ptr: a device buffer of
+        height * width * 9 floats the image is written to and left in; the dict then has no `image`."""
+        c = self._live()
+        opt = c._raster_options(near, cull, shading)
+        if shading == "vertex" and not self.has_normals:
+            raise ValueError("shading='vertex' needs normals")
+        h, w = int(view["height"]), int(view["width"])
+        n = h * w
+        st = _abi.MeshRasterStats()
+        img, fac, own = out_ptr, None, []
+        try:
+            if img is None:
+                img = c.device_malloc(max(n, 1) * _abi.MESH_RASTER_CHANNELS * 4)
+                own.append(img)
+            if faces:
+                fac = c.device_malloc(max(n, 1) * 4)
+                own.append(fac)
+            c._check(c.f.mesh_raster(c._h, _stream_handle(stream), C.byref(self), C.byref(_view_struct(view)), C.byref(opt), img, fac, C.byref(st)))
+            out = st.as_dict()
+            if out_ptr is None:
+                out["image"] = c.download(img, n * _abi.MESH_RASTER_CHANNELS, np.float32).reshape(h, w, _abi.MESH_RASTER_CHANNELS)
+            if faces:
+                out["faces"] = c.download(fac, n, np.uint32).reshape(h, w)
+        finally:
+            for p in own:
+                c.device_free(p)
+        return out

@@ -278,7 +278,7 @@ def test_invalid_input_fails_cleanly_and_the_context_stays_usable(ctx, pair):
     # the raw call: stats are zeroed on a failure
     st = _abi.MeshDistanceStats()
     st.n_tris_to = 9
-    with ctx._device_mesh(a[0], a[1][:300], None, None) as ma, ctx._device_mesh(b[0], b[1], None, None) as mb:
+    with ctx.upload_mesh(a[0], a[1][:300], None, None) as ma, ctx.upload_mesh(b[0], b[1], None, None) as mb:
         opt = ctx._distance_options()
         opt.level = 4
         assert ctx.f.mesh_distance(ctx._h, None, C.byref(ma), C.byref(mb), C.byref(opt), None, None, C.byref(st)) == _abi.ERR_INVALID and st.n_tris_to == 0

@@ -235,7 +235,7 @@ def test_an_image_that_is_not_16_byte_aligned_gets_the_same_bytes(ctx, spheres):
     buf = ctx.device_malloc((n + 8) * 4)
     try:
         assert buf % 16 == 0
-        with ctx._device_mesh(v, i, col, None) as m:
+        with ctx.upload_mesh(v, i, col, None) as m:
             for off in (4, 8, 12):
                 st = _abi.MeshRasterStats()
                 ctx._check(ctx.f.mesh_raster(ctx._h, None, C.byref(m), C.byref(api._view_struct(view)), C.byref(opt), buf + off, None, C.byref(st)))

@@ -3,7 +3,7 @@
 
 Trains the config-4 synthetic scene (64 views, 800 x 800) to step 2000 in this process and reports how full the trained occupancy bitfield is. Then, interleaved
 in the same process (A B C A B C ..., --rounds rounds, the first untimed; medians and the spread max - min reported), it times at each --resolution
-  A  rnb_sdf_lattice + rnb_marching_cubes (mesh left on the device, freed),
+  A  rnb_sdf_lattice + rnb_marching_cubes (Context.sdf_lattice + Context.marching_cubes: the mesh is downloaded),
   B  rnb_extract_mesh with cull = NONE,
   C  rnb_extract_mesh with cull = OCCUPANCY,
 for every --brick, and B / C alone at the --sparse-only resolutions (where the dense path's 16 bytes per lattice point do not fit or its 2^32 limit applies).
@@ -12,41 +12,26 @@ for every --brick, and B / C alone at the --sparse-only resolutions (where the d
 
 Prints one JSON line (and writes it to --out when given).
 """
-import argparse
-import ctypes as C
 import json
-import os
 import sys
 import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mesh_bench_common as common
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--views", type=int, default=64)
-    ap.add_argument("--res", type=int, default=800, help="image resolution of the training views")
+    ap = common.arg_parser()
     ap.add_argument("--resolution", type=int, nargs="*", default=[512, 1024])
     ap.add_argument("--sparse-only", type=int, nargs="*", default=[2048])
     ap.add_argument("--brick", type=int, nargs="*", default=[16, 32])
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = common.parse_args(ap)
 
-    import rnb_neus2_amd as rnb
-    from rnb_neus2_amd import synthetic, _abi
+    from rnb_neus2_amd import _abi
 
-    views, normals, albedos = synthetic.make_scene(args.views, args.res)
-    c = rnb.Context()
-    c.init_params()
-    c.set_dataset(views, normals, albedos)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        c.train_step()
-    train_s = time.perf_counter() - t0
+    c, (views, normals, albedos), train_s = common.train_scene(args)
     bits = c.get("DENSITY_BITFIELD")
     n0 = _abi.GRIDSIZE ** 3 // 8
     fill = float(np.unpackbits(bits[:n0]).mean())  # cascade 0: the only one the unit box consults
@@ -54,38 +39,30 @@ def main():
     def dense(r):
         t = time.perf_counter()
         ptr = c.sdf_lattice(r)
-        pv, pi, nv, ni = C.c_void_p(), C.c_void_p(), C.c_uint32(), C.c_uint32()
-        res3 = (C.c_uint32 * 3)(r, r, r)
-        mn, mx = (C.c_float * 3)(0, 0, 0), (C.c_float * 3)(1, 1, 1)
-        c._check(c.f.marching_cubes(c._h, None, C.c_void_p(ptr), res3, mn, mx, 0.0, C.byref(pv), C.byref(pi), C.byref(nv), C.byref(ni)))
+        verts, idx = c.marching_cubes(ptr, r)
         ms = (time.perf_counter() - t) * 1e3
-        c.device_free(ptr), c.device_free(pv.value), c.device_free(pi.value)
-        return ms, dict(n_verts=nv.value, n_triangles=ni.value // 3)
+        c.device_free(ptr)
+        return ms, dict(n_verts=len(verts), n_triangles=len(idx) // 3)
 
     def sparse(r, cull, brick):
-        opt = _abi.MeshOptions()
-        c._check(c.f.mesh_default_options(C.byref(opt)))
-        opt.res[:] = [r, r, r]
-        opt.cull, opt.brick = cull, brick
-        m, st = _abi.Mesh(), _abi.MeshStats()
         t = time.perf_counter()
-        c._check(c.f.extract_mesh(c._h, None, C.byref(opt), C.byref(m), C.byref(st)))
+        m = c.extract_mesh_device(r, cull=cull, brick=brick)
         ms = (time.perf_counter() - t) * 1e3
-        info = dict(st.as_dict(), n_verts=m.n_verts, n_triangles=m.n_indices // 3)
+        with m:
+            info = dict(m.stats, n_verts=m.n_verts, n_triangles=m.n_triangles)
         info.pop("ms")
-        c.f.mesh_free(c._h, C.byref(m))
         return ms, info
 
     def summary(times, info):
-        t = np.asarray(times[1:] if len(times) > 1 else times)  # the first round is untimed
-        return dict(info, ms_median=round(float(np.median(t)), 2), ms_min=round(float(t.min()), 2), ms_max=round(float(t.max()), 2), spread_ms=round(float(t.max() - t.min()), 2))
+        t = times[1:] if len(times) > 1 else times  # the first round is untimed
+        return dict(info, **common.spread(times, "ms_", digits=2), spread_ms=round(max(t) - min(t), 2))
 
     results = []
     for r, with_dense in [(r, True) for r in args.resolution] + [(r, False) for r in args.sparse_only]:
         legs = ([("dense", lambda r=r: dense(r))] if with_dense else [])
         for b in args.brick:
-            legs.append(("none_brick%d" % b, lambda r=r, b=b: sparse(r, _abi.MESH_CULL_NONE, b)))
-            legs.append(("occupancy_brick%d" % b, lambda r=r, b=b: sparse(r, _abi.MESH_CULL_OCCUPANCY, b)))
+            legs.append(("none_brick%d" % b, lambda r=r, b=b: sparse(r, "none", b)))
+            legs.append(("occupancy_brick%d" % b, lambda r=r, b=b: sparse(r, "occupancy", b)))
         if not with_dense:
             legs = [l for l in legs if l[0].startswith("occupancy")]  # cull = NONE holds 2 bytes for every lattice point: 17 GB at 2048, left out
         times, infos = {k: [] for k, _ in legs}, {}
@@ -101,12 +78,7 @@ def main():
 
     res = dict(metric="mesh_extraction_ms", unit="ms", train_steps=args.steps, train_s=round(train_s, 2), bitfield_fill_cascade0=round(fill, 4), rounds=args.rounds,
                bricks=args.brick, results=results)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    common.report(res, args.out)
     c.close()
 
 

@@ -13,17 +13,13 @@ Trains the config-4 synthetic scene (64 views, 800 x 800) to step 2000 in this p
 
 Prints one JSON line (and writes it to --out when given).
 """
-import argparse
-import ctypes as C
 import json
 import os
 import sys
 import tempfile
 import time
 
-import numpy as np
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mesh_bench_common as common
 
 
 def kernel_bytes(nv, nt, nvo, nto, n_comp, attrs):
@@ -48,65 +44,37 @@ def kernel_bytes(nv, nt, nvo, nto, n_comp, attrs):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--views", type=int, default=64)
-    ap.add_argument("--res", type=int, default=800, help="image resolution of the training views")
+    ap = common.arg_parser()
     ap.add_argument("--resolution", type=int, nargs="*", default=[512, 1024])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-python", action="store_true")
     ap.add_argument("--kernels-only", action="store_true")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = common.parse_args(ap)
 
-    import rnb_neus2_amd as rnb
-    from rnb_neus2_amd import synthetic, _abi, meshproc
+    from rnb_neus2_amd import meshproc
 
-    views, normals, albedos = synthetic.make_scene(args.views, args.res)
-    c = rnb.Context()
-    c.init_params()
-    c.set_dataset(views, normals, albedos)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        c.train_step()
-    train_s = time.perf_counter() - t0
-
-    def extract(r):
-        opt = _abi.MeshOptions()
-        c._check(c.f.mesh_default_options(C.byref(opt)))
-        opt.res[:] = [r, r, r]
-        opt.attributes = _abi.MESH_ATTR_COLORS
-        m, st = _abi.Mesh(), _abi.MeshStats()
-        c._check(c.f.extract_mesh(c._h, None, C.byref(opt), C.byref(m), C.byref(st)))
-        return m, st
-
-    def clean(m):
-        out, st = _abi.Mesh(), _abi.MeshCleanStats()
-        c._check(c.f.mesh_clean(c._h, None, C.byref(m), C.byref(c._clean_options("largest", "outward")), C.byref(out), None, C.byref(st)))
-        c.f.mesh_free(c._h, C.byref(out))
-        return st.as_dict()
-
-    def spread(t):
-        t = np.asarray(t[1:] if len(t) > 1 else t)  # the first round is untimed
-        return dict(ms_median=round(float(np.median(t)), 3), ms_min=round(float(t.min()), 3), ms_max=round(float(t.max()), 3))
+    c, (views, normals, albedos), train_s = common.train_scene(args)
 
     results = []
     for r in args.resolution:
-        m, est = extract(r)
-        row = dict(resolution=r, extract_ms=round(est.ms, 2))
-        if args.kernels_only:
-            row["clean"] = clean(m)
-            c.f.mesh_free(c._h, C.byref(m))
-            results.append(row)
-            continue
-        # (a) the device call alone
-        runs = [clean(m) for _ in range(args.rounds)]
-        st = runs[-1]
-        row["clean"] = dict(spread([x["ms"] for x in runs]), **{k: v for k, v in st.items() if k != "ms"})
-        row["kernel_bytes"] = kernel_bytes(st["n_verts_in"], st["n_tris_in"], st["n_verts_out"], st["n_tris_out"], st["n_components"], 1)
-        row["kernel_bytes_total"] = int(sum(row["kernel_bytes"].values()))
-        host = c._download_mesh(m)
-        c.f.mesh_free(c._h, C.byref(m))
+        with c.extract_mesh_device(r, colors=True) as m:
+            row = dict(resolution=r, extract_ms=round(m.stats["ms"], 2))
+            clean = lambda: m.clean("largest", "outward")
+            if args.kernels_only:
+                with clean() as cm:
+                    row["clean"] = cm.stats
+                results.append(row)
+                continue
+            # (a) the device call alone
+            runs = []
+            for _ in range(args.rounds):
+                with clean() as cm:
+                    runs.append(cm.stats)
+            st = runs[-1]
+            row["clean"] = dict(common.spread([x["ms"] for x in runs], "ms_"), **{k: v for k, v in st.items() if k != "ms"})
+            row["kernel_bytes"] = kernel_bytes(st["n_verts_in"], st["n_tris_in"], st["n_verts_out"], st["n_tris_out"], st["n_components"], 1)
+            row["kernel_bytes_total"] = int(sum(row["kernel_bytes"].values()))
+            host = m.download()
         # (b) through the Python interface, downloads included
         plain, kept = [], []
         for _ in range(args.rounds):
@@ -116,8 +84,8 @@ def main():
             t = time.perf_counter()
             c.extract_mesh(r, colors=True, keep="largest")
             kept.append((time.perf_counter() - t) * 1e3)
-        row["extract_mesh"] = spread(plain)
-        row["extract_mesh_keep_largest"] = spread(kept)
+        row["extract_mesh"] = common.spread(plain, "ms_")
+        row["extract_mesh_keep_largest"] = common.spread(kept, "ms_")
         # (c) the Python stage on the same mesh, once
         if not args.no_python:
             with tempfile.TemporaryDirectory() as d:
@@ -143,12 +111,7 @@ def main():
         print(json.dumps(row), file=sys.stderr)
 
     res = dict(metric="mesh_clean_ms", unit="ms", train_steps=args.steps, train_s=round(train_s, 2), rounds=args.rounds, results=results)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    common.report(res, args.out)
     c.close()
 
 

@@ -14,8 +14,6 @@ render and of every mesh, over every --metric-stride-th view.
 Prints one JSON line (and writes it to --out when given). profiles/mesh_raster.md is written by hand from that line, as the other profiles are; the share of each kernel in a
 call comes from a run of its own under `rocprofv3 --kernel-trace --stats` (e.g. --steps 300 --resolution 1024 --cells 128 --caster --metric-stride 64).
 """
-import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -23,40 +21,23 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mesh_bench_common as common
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--views", type=int, default=64)
-    ap.add_argument("--res", type=int, default=800, help="image resolution of the training views")
+    ap = common.arg_parser()
     ap.add_argument("--resolution", type=int, nargs="*", default=[512, 1024])
     ap.add_argument("--cells", type=int, nargs="*", default=[128, 256, 512], help="N of the simplifications")
     ap.add_argument("--metric-stride", type=int, default=4, help="the metrics are taken on every n-th view")
     ap.add_argument("--caster", type=int, nargs="*", default=[512, 1024], help="resolutions whose cleaned mesh also goes through the host BVH caster")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = common.parse_args(ap)
 
-    import rnb_neus2_amd as rnb
-    from rnb_neus2_amd import api, synthetic, _abi, hostlib
+    from rnb_neus2_amd import api, _abi, hostlib
 
-    views, normals, albedos = synthetic.make_scene(args.views, args.res)
-    c = rnb.Context()
-    c.init_params()
-    c.set_dataset(views, normals, albedos)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        c.train_step()
-    train_s = time.perf_counter() - t0
+    c, (views, normals, albedos), train_s = common.train_scene(args)
     n_pix = args.res * args.res
     img = c.device_malloc(n_pix * _abi.MESH_RASTER_CHANNELS * 4)
-    structs = [api._view_struct(v) for v in views]
     metric_views = list(range(0, len(views), max(args.metric_stride, 1)))
-
-    def spread(t):
-        t = np.asarray(t)
-        return dict(median=round(float(np.median(t)), 3), min=round(float(t.min()), 3), max=round(float(t.max()), 3))
 
     def metrics(image_of):
         rows = [api.view_normal_metrics(image_of(k), views[k], normals[k]) for k in metric_views]
@@ -73,23 +54,20 @@ def main():
         c.render_into(views[k], img)
         return download()
 
-    model = dict(frame_ms=spread(render_ms), **metrics(render_image))
+    model = dict(frame_ms=common.spread(render_ms, untimed=0), **metrics(render_image))
     print(json.dumps(dict(model=model)), file=sys.stderr)
 
-    def raster(m, k, opt):
-        st = _abi.MeshRasterStats()
-        c._check(c.f.mesh_raster(c._h, None, C.byref(m), C.byref(structs[k]), C.byref(opt), img, None, C.byref(st)))
-        return st.as_dict()
+    def raster(m, k):
+        return m.rasterize(views[k], out_ptr=img)
 
     def measure(name, m):
-        opt = c._raster_options(2.0 ** -10, "none", "face")
-        raster(m, 0, opt)  # untimed
-        runs = [raster(m, k, opt) for k in range(len(views))]
-        ms = spread([r["ms"] for r in runs])
-        nt = m.n_indices // 3
+        raster(m, 0)  # untimed
+        runs = [raster(m, k) for k in range(len(views))]
+        ms = common.spread([r["ms"] for r in runs], untimed=0)
+        nt = m.n_triangles
 
         def image_of(k):
-            raster(m, k, opt)
+            raster(m, k)
             return download()
 
         row = dict(mesh=name, n_tris=nt, ms_per_view=ms, mtris_per_s=round(nt / ms["median"] / 1e3, 1), n_small=int(np.median([r["n_small"] for r in runs])),
@@ -102,53 +80,40 @@ def main():
 
     results = []
     for r in args.resolution:
-        opt = _abi.MeshOptions()
-        c._check(c.f.mesh_default_options(C.byref(opt)))
-        opt.res[:] = [r, r, r]
-        m, est = _abi.Mesh(), _abi.MeshStats()
         try:
-            c._check(c.f.extract_mesh(c._h, None, C.byref(opt), C.byref(m), C.byref(est)))
+            m = c.extract_mesh_device(r)
         except Exception as e:  # e.g. no memory on a card that others use
             results.append(dict(resolution=r, skipped=str(e)[:200]))
             continue
-        cm, cst = _abi.Mesh(), _abi.MeshCleanStats()
-        c._check(c.f.mesh_clean(c._h, None, C.byref(m), C.byref(c._clean_options("largest", "outward")), C.byref(cm), None, C.byref(cst)))
-        c.f.mesh_free(c._h, C.byref(m))
-        block = dict(resolution=r, extract_ms=round(est.ms, 2), clean_ms=round(cst.ms, 2), meshes=[measure("%d" % r, cm)])
-        if r in args.caster:  # the host caster on the same mesh: one ray per pixel of view 0
-            host = c._download_mesh(cm)
-            t0 = time.perf_counter()
-            caster = hostlib.MeshRayCaster(host["verts"], host["indices"].reshape(-1, 3))
-            build_s = time.perf_counter() - t0
-            x = np.asarray(views[0]["xform"], np.float64)
-            ys, xs = np.meshgrid(np.arange(args.res) + 0.5, np.arange(args.res) + 0.5, indexing="ij")
-            fx, fy = views[0]["focal_length"]
-            d = np.stack([(xs - 0.5 * args.res) / fx, (ys - 0.5 * args.res) / fy, np.ones_like(xs)], -1).reshape(-1, 3) @ x[:, :3].T
-            d = np.ascontiguousarray(d)
-            o = np.ascontiguousarray(np.broadcast_to(x[:, 3], d.shape))  # (contiguous before the clock starts: first_hit would copy them otherwise)
-            t0 = time.perf_counter()
-            t, tri = caster.first_hit(o, d)
-            block["host_caster"] = dict(build_ms=round(build_s * 1e3, 1), first_hit_ms=round((time.perf_counter() - t0) * 1e3, 1), n_hit=int((tri >= 0).sum()),
-                                        omp_num_threads=os.environ.get("OMP_NUM_THREADS"))  # (None: OpenMP's default, every CPU of the machine)
-            print(json.dumps(block["host_caster"]), file=sys.stderr)
-            del caster, host
-        for n in args.cells:
-            sm, sst = _abi.Mesh(), _abi.MeshSimplifyStats()
-            sopt = c._simplify_options(*c.simplify_grid((0, 0, 0), (1, 1, 1), n), "quadric")
-            c._check(c.f.mesh_simplify(c._h, None, C.byref(cm), C.byref(sopt), C.byref(sm), C.byref(sst)))
-            block["meshes"].append(measure("%d --simplify %d" % (r, n), sm))
-            c.f.mesh_free(c._h, C.byref(sm))
-        c.f.mesh_free(c._h, C.byref(cm))
+        with m:
+            cm = m.clean("largest", "outward")
+        with cm:
+            block = dict(resolution=r, extract_ms=round(m.stats["ms"], 2), clean_ms=round(cm.stats["ms"], 2), meshes=[measure("%d" % r, cm)])
+            if r in args.caster:  # the host caster on the same mesh: one ray per pixel of view 0
+                host = cm.download()
+                t0 = time.perf_counter()
+                caster = hostlib.MeshRayCaster(host["verts"], host["indices"].reshape(-1, 3))
+                build_s = time.perf_counter() - t0
+                x = np.asarray(views[0]["xform"], np.float64)
+                ys, xs = np.meshgrid(np.arange(args.res) + 0.5, np.arange(args.res) + 0.5, indexing="ij")
+                fx, fy = views[0]["focal_length"]
+                d = np.stack([(xs - 0.5 * args.res) / fx, (ys - 0.5 * args.res) / fy, np.ones_like(xs)], -1).reshape(-1, 3) @ x[:, :3].T
+                d = np.ascontiguousarray(d)
+                o = np.ascontiguousarray(np.broadcast_to(x[:, 3], d.shape))  # (contiguous before the clock starts: first_hit would copy them otherwise)
+                t0 = time.perf_counter()
+                t, tri = caster.first_hit(o, d)
+                block["host_caster"] = dict(build_ms=round(build_s * 1e3, 1), first_hit_ms=round((time.perf_counter() - t0) * 1e3, 1), n_hit=int((tri >= 0).sum()),
+                                            omp_num_threads=os.environ.get("OMP_NUM_THREADS"))  # (None: OpenMP's default, every CPU of the machine)
+                print(json.dumps(block["host_caster"]), file=sys.stderr)
+                del caster, host
+            for n in args.cells:
+                with cm.simplify(*c.simplify_grid((0, 0, 0), (1, 1, 1), n)) as sm:
+                    block["meshes"].append(measure("%d --simplify %d" % (r, n), sm))
         results.append(block)
 
     res = dict(metric="mesh_raster_ms_per_view", unit="ms", train_steps=args.steps, train_s=round(train_s, 2), views=len(views), image=args.res, metric_views=len(metric_views),
                model_render=model, results=results)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    common.report(res, args.out)
     c.device_free(img)
     c.close()
 

@@ -12,17 +12,13 @@ lack of memory is reported as such and skipped.
 
 Prints one JSON line (and writes it to --out when given).
 """
-import argparse
-import ctypes as C
 import json
 import os
 import sys
 import tempfile
 import time
 
-import numpy as np
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mesh_bench_common as common
 
 
 def kernel_bytes(nv, nt, n_cells, n_cl, nvo, nto, attrs):
@@ -43,96 +39,57 @@ def kernel_bytes(nv, nt, n_cells, n_cl, nvo, nto, attrs):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--views", type=int, default=64)
-    ap.add_argument("--res", type=int, default=800, help="image resolution of the training views")
+    ap = common.arg_parser()
     ap.add_argument("--resolution", type=int, nargs="*", default=[512, 1024, 2048])
     ap.add_argument("--divisors", type=int, nargs="*", default=[4, 8], help="N = resolution / divisor")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--placement", default="quadric", choices=["quadric", "mean"])
     ap.add_argument("--no-obj", action="store_true", help="skip the save_obj timings")
     ap.add_argument("--kernels-only", action="store_true")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = common.parse_args(ap)
 
-    import rnb_neus2_amd as rnb
-    from rnb_neus2_amd import synthetic, _abi, meshproc
+    from rnb_neus2_amd import meshproc
 
-    views, normals, albedos = synthetic.make_scene(args.views, args.res)
-    c = rnb.Context()
-    c.init_params()
-    c.set_dataset(views, normals, albedos)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        c.train_step()
-    train_s = time.perf_counter() - t0
-
-    def extract(r):
-        opt = _abi.MeshOptions()
-        c._check(c.f.mesh_default_options(C.byref(opt)))
-        opt.res[:] = [r, r, r]
-        opt.attributes = _abi.MESH_ATTR_COLORS
-        m, st = _abi.Mesh(), _abi.MeshStats()
-        c._check(c.f.extract_mesh(c._h, None, C.byref(opt), C.byref(m), C.byref(st)))
-        return m, st
-
-    def clean(m):
-        out, st = _abi.Mesh(), _abi.MeshCleanStats()
-        c._check(c.f.mesh_clean(c._h, None, C.byref(m), C.byref(c._clean_options("largest", "outward")), C.byref(out), None, C.byref(st)))
-        return out, st
-
-    def simplify(m, n, keep=False):
-        out, st = _abi.Mesh(), _abi.MeshSimplifyStats()
-        opt = c._simplify_options(*c.simplify_grid((0, 0, 0), (1, 1, 1), n), args.placement)
-        c._check(c.f.mesh_simplify(c._h, None, C.byref(m), C.byref(opt), C.byref(out), C.byref(st)))
-        host = c._download_mesh(out) if keep else None
-        c.f.mesh_free(c._h, C.byref(out))
-        return st.as_dict(), host
-
-    def spread(t):
-        t = np.asarray(t[1:] if len(t) > 1 else t)  # the first round is untimed
-        return dict(ms_median=round(float(np.median(t)), 3), ms_min=round(float(t.min()), 3), ms_max=round(float(t.max()), 3))
+    c, (views, normals, albedos), train_s = common.train_scene(args)
 
     def save_obj_s(host, d, name):
         t = time.perf_counter()
         meshproc.save_obj(os.path.join(d, name), meshproc.Mesh(host["verts"], host["indices"].reshape(-1, 3), host.get("colors")))
         return round(time.perf_counter() - t, 3)
 
+    def simplify(m, n, keep=False):
+        with m.simplify(*c.simplify_grid((0, 0, 0), (1, 1, 1), n), placement=args.placement) as out:
+            return out.stats, out.download() if keep else None
+
     results = []
     for r in args.resolution:
         try:
-            m, est = extract(r)
+            m = c.extract_mesh_device(r, colors=True)
         except Exception as e:  # e.g. 2048^3 on a card that others use
             results.append(dict(resolution=r, skipped=str(e)[:200]))
             continue
-        cm, cst = clean(m)
-        c.f.mesh_free(c._h, C.byref(m))
-        row = dict(resolution=r, extract_ms=round(est.ms, 2), clean_ms=round(cst.ms, 2), n_tris_extracted=cst.n_tris_in, n_tris_cleaned=cst.n_tris_out, simplify=[])
-        with tempfile.TemporaryDirectory() as d:
+        with m:
+            cm = m.clean("largest", "outward")
+        with cm, tempfile.TemporaryDirectory() as d:
+            cst = cm.stats
+            row = dict(resolution=r, extract_ms=round(m.stats["ms"], 2), clean_ms=round(cst["ms"], 2), n_tris_extracted=cst["n_tris_in"], n_tris_cleaned=cst["n_tris_out"], simplify=[])
             if not args.kernels_only and not args.no_obj:
-                row["save_obj_full_s"] = save_obj_s(c._download_mesh(cm), d, "full.obj")
+                row["save_obj_full_s"] = save_obj_s(cm.download(), d, "full.obj")
             for div in args.divisors:
                 n = r // div
                 runs = [simplify(cm, n, keep=(k == 0 and not args.kernels_only)) for k in range(1 if args.kernels_only else args.rounds)]
                 st = runs[-1][0]
-                cell = dict(n=n, **spread([x[0]["ms"] for x in runs]), **{k: v for k, v in st.items() if k != "ms"})
+                cell = dict(n=n, **common.spread([x[0]["ms"] for x in runs], "ms_"), **{k: v for k, v in st.items() if k != "ms"})
                 cell["kernel_bytes"] = kernel_bytes(st["n_verts_in"], st["n_tris_in"], n ** 3, st["n_clusters"], st["n_verts_out"], st["n_tris_out"], 1)
                 cell["kernel_bytes_total"] = int(sum(cell["kernel_bytes"].values()))
                 if not args.kernels_only and not args.no_obj:
                     cell["save_obj_simplified_s"] = save_obj_s(runs[0][1], d, "small.obj")
                 row["simplify"].append(cell)
-        c.f.mesh_free(c._h, C.byref(cm))
         results.append(row)
         print(json.dumps(row), file=sys.stderr)
 
     res = dict(metric="mesh_simplify_ms", unit="ms", placement=args.placement, train_steps=args.steps, train_s=round(train_s, 2), rounds=args.rounds, results=results)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    common.report(res, args.out)
     c.close()
 
 
