@@ -248,6 +248,11 @@ class Context:
         return out
 
     def put(self, name, array, offset=0):
+        """Copy a numpy array into (part of) a context buffer; offset in elements.
+        DENSITY_BITFIELD of a single-cascade scene (aabb_scale 1): the march looks a position ON a face of the box up in cascade 1, as the reference does, while the
+        skipping and bounding-box forms of the march plan a ray from cascade 0 alone. So cascade 1 may be set, where a face position reads it, only above a non-empty
+        4^3 block of cascade 0 -- as in every bitfield update_density_bitfield() builds (cascade 1 = the max-pool of cascade 0). A bitfield written otherwise gives
+        samples at face positions that differ from the reference's in those forms; nothing checks it."""
         ptr, nb = self.buffer(name)
         dt = np.dtype(BUF_DTYPE[name])
         a = np.ascontiguousarray(array, dtype=dt).ravel()

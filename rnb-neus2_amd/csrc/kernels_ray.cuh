@@ -247,6 +247,52 @@ __device__ __forceinline__ bool occupied_mip0(Vec3 pos, const uint8_t* __restric
 	return bitfield[idx >> 3] & (1 << (idx & 7u));
 }
 
+// A position ON a face of the unit box is in cascade 1, also in a single-cascade scene. mip_from_dt is called with its DEFAULT max_cascade (testbed_nerf.cu:569-583, 1339),
+// not the scene's: where |p - 0.5| = 0.5 in some coordinate, as the reference's own subtraction rounds it (a coordinate of exactly 1, or of at most 2^-26), frexp's exponent
+// is 0 and the position is looked up in CASCADE 1, at half the resolution, which is also the resolution of the jump that follows an empty answer. Everywhere else in the box
+// it is cascade 0 (occupied_mip0). Found by the march-geometry tests: eyes inside the box, a dense grid.
+__device__ __forceinline__ bool on_box_face(const Vec3& pos) {
+	return fmaxf(fmaxf(fabsf(pos.x - 0.5f), fabsf(pos.y - 0.5f)), fabsf(pos.z - 0.5f)) >= 0.5f;
+}
+
+// WHERE along a ray such a position can lie is decided once per ray, so that the march pays nothing for it at the positions in between: the positions at t >= face_check_from()
+// take the face test, the others are known to lie strictly inside the box.
+//  - A coordinate that moves by much more than its rounding error per step meets a face value only where the ray enters or leaves the box: at the ray's FIRST position (tested
+//    here, exactly) or within a step of its exit, t >= tmax - 2 steps (position k >= 1 lies a whole step behind the entry: C |d| from the entry face; a position in front of
+//    tmax - 2 C lies 2 C |d| from the exit face).
+//  - "Much more": C |d_c| > 1e-6 (|o_c| + tmax |d_c| + 1), i.e. > 16 ulp of the largest term of o_c + t d_c. A coordinate that moves less than that (the ray runs along it, or
+//    comes from so far that o + t d is formed to no better than a step's advance) is harmless if it stays 1e-3 away from 0 and 1 between the ray's two ends. A ray with a slow
+//    coordinate that does come that near a face, or whose first position lies on a face, takes the test everywhere: -inf. (One ray in ~10^5 of a ring of cameras: a
+//    wavefront with such a ray tests all its positions.)
+__device__ __forceinline__ float face_check_from(const Vec3& o, const Vec3& dir, const float startt, const float tmax) {
+	auto hugs = [&](const float oc, const float dc) { // (a NaN anywhere answers true)
+		const float a = fabsf(dc), c0 = oc + startt * dc, c1 = oc + tmax * dc;
+		const bool moves = MIN_CONE_STEPSIZE * a > 1e-6f * (fabsf(oc) + tmax * a + 1.0f);
+		const bool clear = fminf(c0, c1) > 1e-3f && fmaxf(c0, c1) < 1.0f - 1e-3f;
+		return !moves && !clear;
+	};
+	if (hugs(o.x, dir.x) || hugs(o.y, dir.y) || hugs(o.z, dir.z) || on_box_face(o + startt * dir)) return -3.0e38f;
+	return tmax - 2.0f * MIN_CONE_STEPSIZE;
+}
+
+// One visited position of the reference's loop in a single-cascade scene (testbed_nerf.cu:1337-1345): is `pos` inside the box (the return value); if so, is it occupied (`occ`),
+// and if not, `dist` = distance_to_next_voxel at the resolution of the cascade consulted. `check_face`: the position may lie on a face (face_check_from). Each side keeps its
+// resolution a constant, so that the division by it stays a multiplication.
+__device__ __forceinline__ bool probe_single_cascade(const SceneAabb& A, const Vec3& pos, const Vec3& dir, const Vec3& idir, const uint8_t* __restrict__ bitfield, const uint32_t* __restrict__ lds,
+                                                     const uint32_t n_blocks_lds, const bool check_face, bool& occ, float& dist) {
+	occ = false;
+	dist = 0.f;
+	if (!aabb_contains(A, pos)) return false;
+	if (check_face && on_box_face(pos)) {
+		occ = density_grid_occupied_at(pos, bitfield, 1u);
+		if (!occ) dist = distance_to_next_voxel(pos, dir, idir, GRIDSIZE >> 1);
+		return true;
+	}
+	occ = occupied_mip0(pos, bitfield, lds, n_blocks_lds);
+	if (!occ) dist = distance_to_next_voxel(pos, dir, idir, GRIDSIZE);
+	return true;
+}
+
 // grid_to_bitfield (testbed_nerf.cu:693-717)
 __global__ void k_grid_to_bitfield(const uint32_t n_elements, const uint32_t n_nonzero_elements, const float* __restrict__ grid, uint8_t* __restrict__ bitfield, const float* __restrict__ mean_density_ptr) {
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
@@ -467,30 +513,47 @@ struct MarchArgs {
 	unsigned long long* stats; // RNB_MARCH_STATS=1 (measurement aid, k_march_count_skip): [0] wavefronts, [1] loop iterations, [2] rays, [3] rays that skipped, [4] start-overs, [5] rounds spent looking for a re-entry cell, [6] rays ended early
 };
 
-// SC: one cascade and no cone (aabb_scale 1, every RNb scene): dt is the constant step and every position inside the box is in
-// mip 0 (mip_from_pos clamps to max_cascade = 0, mip_from_dt returns it because dt * 2 * GRIDSIZE < 1), so the per-position
-// frexp / scalbn / variable-resolution arithmetic folds into constants. Same values, fewer dependent instructions per voxel.
+// SC: one cascade and no cone (aabb_scale 1, every RNb scene): dt is the constant step and every position strictly inside the box is in
+// mip 0 (mip_from_dt returns mip_from_pos because dt * 2 * GRIDSIZE < 1), so the per-position frexp / scalbn / variable-resolution
+// arithmetic folds into constants; a position ON a face of the box is in mip 1 (probe_single_cascade). Same values, fewer dependent
+// instructions per voxel.
 template <bool SC, typename F>
-__device__ __forceinline__ uint32_t march(const SceneAabb& A, const uint8_t* __restrict__ bitfield, const uint32_t* __restrict__ coarse_lds, const uint32_t n_blocks_lds, const Vec3& o, const Vec3& dir, const float startt, const uint32_t max_steps, F&& emit, const float t_stop = 3.0e38f) {
+__device__ __forceinline__ uint32_t march(const SceneAabb& A, const uint8_t* __restrict__ bitfield, const uint32_t* __restrict__ coarse_lds, const uint32_t n_blocks_lds, const Vec3& o, const Vec3& dir, const float startt, const uint32_t max_steps, F&& emit, const float t_stop = 3.0e38f, const float t_face = -3.0e38f) {
 	const Vec3 idir = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z};
 	uint32_t j = 0;
 	float t = startt;
 	Vec3 pos;
-	while (aabb_contains(A, pos = o + t * dir) && j < max_steps && t <= t_stop) { // (t_stop: behind it no position can be occupied -- the reference walks on and emits nothing)
-		const float dt = SC ? MIN_CONE_STEPSIZE : calc_dt(t, A.cone_angle);
-		const uint32_t mip = SC ? 0u : (uint32_t)mip_from_dt(dt, pos);
-		if (SC ? occupied_mip0(pos, bitfield, coarse_lds, n_blocks_lds) : density_grid_occupied_at(pos, bitfield, mip)) {
-			emit(j, pos, dt, t);
-			++j;
-			t += dt;
-		} else if (SC) {
-			const float t_target = t + distance_to_next_voxel(pos, dir, idir, GRIDSIZE);
-			do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
-		} else {
-			const uint32_t res = GRIDSIZE >> mip;
-			t = advance_to_next_voxel(t, A.cone_angle, pos, dir, idir, res);
+	// (t_stop: behind it no position can be occupied -- the reference walks on and emits nothing. Single cascade: the walk up to t_face (face_check_from) without the face test,
+	// the rest -- a step or two at the box exit, or a whole ray that runs along a face -- with it)
+	auto walk = [&](const float t_last, const bool check_face) {
+		bool occ = false;
+		float dist = 0.f;
+		while ((SC ? probe_single_cascade(A, pos = o + t * dir, dir, idir, bitfield, coarse_lds, n_blocks_lds, check_face, occ, dist) : aabb_contains(A, pos = o + t * dir)) && j < max_steps && t <= t_last) {
+			const float dt = SC ? MIN_CONE_STEPSIZE : calc_dt(t, A.cone_angle);
+			const uint32_t mip = SC ? 0u : (uint32_t)mip_from_dt(dt, pos);
+			if (SC ? occ : density_grid_occupied_at(pos, bitfield, mip)) {
+				emit(j, pos, dt, t);
+				++j;
+				t += dt;
+			} else if (SC) {
+				const float t_target = t + dist;
+				do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
+			} else {
+				const uint32_t res = GRIDSIZE >> mip;
+				t = advance_to_next_voxel(t, A.cone_angle, pos, dir, idir, res);
+			}
 		}
-	}
+		return t <= t_last && j < max_steps; // false: the walk ended at its own limit, not at a position outside the box
+	};
+	if (SC) {
+		// (a wavefront with a ray that is tested everywhere walks once, testing everywhere: one thread walking its whole ray in the second loop, behind the first loop of
+		// the other 63, would double the wavefront's time)
+		if (!__any(t_face < t_stop)) walk(t_stop, false); // no ray of the wavefront comes to a position that may lie on a face (the bounding-box stop ends them first): the plain walk
+		else {
+			const float t_plain = __any(t_face < -1.0e38f) ? -3.0e38f : fminf(t_stop, t_face); // every position up to here lies strictly inside the box
+			if (!walk(t_plain, false) && t_plain < t_stop) walk(t_stop, true);
+		}
+	} else walk(t_stop, false);
 	return j;
 }
 
@@ -527,6 +590,7 @@ __global__ __launch_bounds__(512) void k_march_count(const MarchArgs a) { // (la
 		float* tt = a.ray_t + (size_t)i * RNB_MAX_STEPS;
 		float t_stop = 3.0e38f;
 		bool can_hit = true;
+		bool bbox_clear = false; // the occupied region's (dilated) bounding box keeps a block's width from every face of the scene box
 		if (SC && a.use_bbox) { // round 6: where the ray leaves the (dilated) bounding box of the non-empty blocks it is over; a ray that misses the box has no sample
 			const uint32_t* bb = a.coarse + COARSE_BBOX_OFF;
 			const float lo[3] = {((float)bb[0] - 1.0f) * (1.0f / 32.0f), ((float)bb[1] - 1.0f) * (1.0f / 32.0f), ((float)bb[2] - 1.0f) * (1.0f / 32.0f)};
@@ -542,8 +606,18 @@ __global__ __launch_bounds__(512) void k_march_count(const MarchArgs a) { // (la
 			}
 			if (t0 > t1) can_hit = false;
 			t_stop = t1 + 4.0f * MIN_CONE_STEPSIZE; // (the box is already a block = 18 steps wider than the non-empty blocks on every side)
+			bbox_clear = bb[0] >= 2u && bb[1] >= 2u && bb[2] >= 2u && bb[3] <= 29u && bb[4] <= 29u && bb[5] <= 29u;
 		}
-		if (can_hit) steps = march<SC>(a.A, a.bitfield, coarse_lds, a.n_blocks_lds, o, dir, startt, RNB_MAX_STEPS, [&](uint32_t j, const Vec3&, float, float t) { tt[j] = t; }, t_stop);
+		// Where a position of this ray may lie on a face of the box (face_check_from). The ordinary ray needs none of it: where the walk ends at the bounding box of an
+		// occupied region that keeps clear of the faces, two steps or more in front of the ray's exit, the exit is never reached, and a ray with a slow coordinate near a face
+		// -- it stays within 0.02 of that face (an eye nearer than 16: the slow coordinate moves by less than 0.011 a unit of t) -- cannot be inside that box at its end t1:
+		// what is left is the ray's first position, which lies ON the entry face if the start offset rounds away.
+		float t_face = 0.f;
+		if (SC && can_hit) {
+			if (bbox_clear && tmax < 16.0f && t_stop < tmax - 2.0f * MIN_CONE_STEPSIZE) t_face = on_box_face(o + startt * dir) ? -3.0e38f : 3.0e38f;
+			else t_face = face_check_from(o, dir, startt, tmax);
+		}
+		if (can_hit) steps = march<SC>(a.A, a.bitfield, coarse_lds, a.n_blocks_lds, o, dir, startt, RNB_MAX_STEPS, [&](uint32_t j, const Vec3&, float, float t) { tt[j] = t; }, t_stop, t_face);
 	}
 	float* st = a.setup + (size_t)i * 8;
 	st[0] = o.x; st[1] = o.y; st[2] = o.z; st[3] = dir.x; st[4] = dir.y; st[5] = dir.z; st[6] = startt; st[7] = alive;
@@ -575,7 +649,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 	const int gb = lane & ~(MG - 1); // first lane of the group inside the wavefront
 	const bool ray_exists = i < a.n_rays;
 	Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1}, idir = {0, 0, 1};
-	float t_cur = 0.f, startt = 0.f, alive = 0.f;
+	float t_cur = 0.f, startt = 0.f, alive = 0.f, t_face = 3.0e38f;
 	bool term = true;
 	if (ray_exists) {
 		const uint32_t gi = a.ray_offset + i;
@@ -601,6 +675,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 			t_cur = startt;
 			alive = 1.f;
 			term = false;
+			if (SC) t_face = face_check_from(o, dir, startt, tmax);
 		}
 	}
 	uint32_t j = 0;
@@ -608,6 +683,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 	float pending_target = 0.f;
 	float* tt = a.ray_t + (size_t)(ray_exists ? i : 0) * RNB_MAX_STEPS;
 	const float cone = a.A.cone_angle;
+	bool face_mode = false; // (single cascade) a ray of this wavefront has come to where its positions may lie on a face of the box (face_check_from): wave-uniform, and it stays
 	while (__any(!term)) {
 		// The next MG positions of the ray. Closed form of the lattice t_{k+1} = fl(t_k + C) (C = the constant step of the single-cascade scenes):
 		// while t stays inside one binade [2^(e-1), 2^e) every t_k is a multiple of that binade's ulp, so fl(t_k + C) = t_k + d with
@@ -647,17 +723,21 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 		}
 		// my position
 		const Vec3 pos = o + my_t * dir;
-		const bool inside = !term && aabb_contains(a.A, pos);
 		bool occ = false;
+		float dist = 0.f;
+		if (SC && !face_mode) face_mode = __any(!term && t_end >= t_face);
+		const bool inside = !term && (SC ? probe_single_cascade(a.A, pos, dir, idir, a.bitfield, coarse_lds, a.n_blocks_lds, face_mode, occ, dist) : aabb_contains(a.A, pos));
 		float t_target = 0.f;
 		uint32_t nxt = MG; // absolute index of the next visited position if mine is visited and empty
 		if (inside) {
-			const float dt = SC ? MIN_CONE_STEPSIZE : calc_dt(my_t, cone);
-			const uint32_t mip = SC ? 0u : (uint32_t)mip_from_dt(dt, pos);
-			occ = SC ? occupied_mip0(pos, a.bitfield, coarse_lds, a.n_blocks_lds) : density_grid_occupied_at(pos, a.bitfield, mip);
+			if (!SC) {
+				const float dt = calc_dt(my_t, cone);
+				const uint32_t mip = (uint32_t)mip_from_dt(dt, pos);
+				occ = density_grid_occupied_at(pos, a.bitfield, mip);
+				if (!occ) dist = distance_to_next_voxel(pos, dir, idir, GRIDSIZE >> mip);
+			}
 			if (!occ) {
-				const uint32_t res = GRIDSIZE >> mip;
-				t_target = my_t + distance_to_next_voxel(pos, dir, idir, res);
+				t_target = my_t + dist;
 				if (fast) { // smallest m in (g, MG) with t_cur + m d >= t_target, else MG
 					int m0 = (int)floorf(fminf((t_target - t_cur) * inv_dlt, 64.f));
 					m0 += (t_cur + (float)m0 * dlt < t_target) ? 1 : 0;
@@ -748,6 +828,12 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 // The lattice position behind n skipped steps is exact: inside a binade t + m d is exact (one fma: a multiple of the binade's ulp below the binade's end), across a binade
 // boundary the step is the reference's own addition.
 // ---------------------------------------------------------------------------------------------
+// The closed form is checked by the host on the binades of [0.25, 8) only (MarchArgs::lattice_ok), and below 2 steps' distance from the eye it is not even well formed (the
+// step is no longer small against the binade). So: a stretch is skipped only from a position in [0.25, LATTICE_SKIP_FROM_BELOW) -- a skip is shorter than 2 (64 sample points a
+// 1/32 apart; the box diagonal), so it ends below 8 --, and k_march_count_skip forms a round's 16 positions in closed form only while they stay inside [0.25, 8); outside,
+// both walk the reference's own additions (a camera inside the box or within 0.25 of it; a camera further than 6 from it). Found by the march-geometry tests: the closed form
+// at t < 0.25 differed from the reference's sums in the last bit of t on 13-75 % of the kept rays of cameras inside the box or within 0.25 of it.
+constexpr float LATTICE_SKIP_FROM_BELOW = 6.0f;
 __device__ __forceinline__ float lattice_advance(float t, int n) { // t_{k+n} of t_{k+1} = fl(t_k + MIN_CONE_STEPSIZE); t in [0.25, 8), MarchArgs::lattice_ok
 	while (n > 0) {
 		int e;
@@ -782,7 +868,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 	const int gb = lane & ~(MG - 1);
 	const bool ray_exists = i < a.n_rays;
 	Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1}, idir = {0, 0, 1};
-	float t_cur = 0.f, startt = 0.f, alive = 0.f, t_exit = 0.f;
+	float t_cur = 0.f, startt = 0.f, alive = 0.f, t_exit = 0.f, t_face = 3.0e38f;
 	bool term = true;
 	if (ray_exists) {
 		const uint32_t gi = a.ray_offset + i;
@@ -809,6 +895,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 			t_exit = tmax;
 			alive = 1.f;
 			term = false;
+			t_face = face_check_from(o, dir, startt, tmax);
 		}
 	}
 	// (1) the ray's stretches of interest: bit i = the dilated coarse occupancy at startt + i / 32 (the point clamped into the box: a sample point just outside the box still
@@ -840,11 +927,15 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 	const bool force_restart = (a.lattice_ok & 2u) != 0u; // RNB_MARCH_SKIP=2 (tests): no cell is ever accepted, every skipping ray takes the start-over path
 	float* tt = a.ray_t + (size_t)(ray_exists ? i : 0) * RNB_MAX_STEPS;
 	float bin_lo = 1.f, bin_hi = 0.f, dlt = 0.f, d2 = 0.f, inv_dlt = 0.f, inv_d2 = 0.f; // the binade of t_cur and its lattice steps (formed again when t_cur leaves it)
+	// does a ray of this wavefront start below t = 0.25 or reach t = 8 (its last round begins at or before the box exit and ends 17 steps behind it)? Then none of the wavefront's
+	// rounds uses the closed form. Decided once, wave-uniform: the loop below pays a scalar branch for it. (Every benchmarked camera stands 1 .. 2 from the box.)
+	bool face_mode = false; // a ray of this wavefront has come to where its positions may lie on a face of the box (face_check_from): wave-uniform, and it stays
+	const bool sums = __any(!term && !(startt >= 0.25f && t_exit < 8.0f - 34.0f * MIN_CONE_STEPSIZE));
 	uint32_t st_iters = 0, st_skips = 0, st_restarts = 0, st_anchor_rounds = 0, st_early = 0;
 	while (__any(!term)) {
 		++st_iters;
 		// ---- skip / end decision (group-uniform: every lane of a ray holds the same state) ----
-		if (!term && skipping && !anchoring && t_cur >= 0.25f) {
+		if (!term && skipping && !anchoring && t_cur >= 0.25f && t_cur < LATTICE_SKIP_FROM_BELOW) {
 			const int i_first = max((int)floorf((t_cur - startt) * 32.0f) - 1, 0);
 			const uint64_t ahead = i_first < 64 ? (interest >> i_first) : 0ull;
 			if ((ahead & 0xFull) == 0ull) { // this round's stretch and the two behind it: nothing
@@ -893,9 +984,29 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 			while (mb < MG && __builtin_fmaf((float)(mb + 1), dlt, t_cur) < bin_hi) ++mb;
 		}
 		const float tx = __builtin_fmaf((float)min(mb, MG), dlt, t_cur) + MIN_CONE_STEPSIZE;
-		auto lattice = [&](const int m) { return m <= mb ? __builtin_fmaf((float)m, dlt, t_cur) : __builtin_fmaf((float)(m - mb - 1), d2, tx); };
+		// ... all of which holds on [0.25, 8) (see LATTICE_SKIP_FROM_BELOW): a wavefront with a ray that leaves that range takes the reference's running sums instead (`sums`, above the
+		// loop: the sums are right at every t. Rolled loops, formed again wherever they are compared, as in k_march_count_wide)
+		auto lattice = [&](const int m) {
+			if (sums) {
+				float run = t_cur;
+#pragma unroll 1
+				for (int q = 0; q < m; ++q) run += MIN_CONE_STEPSIZE;
+				return run;
+			}
+			return m <= mb ? __builtin_fmaf((float)m, dlt, t_cur) : __builtin_fmaf((float)(m - mb - 1), d2, tx);
+		};
 		// the smallest m in [lo, MG) with lattice(m) >= target, else MG
 		auto first_at_or_after = [&](const float target, const int lo) {
+			if (sums) {
+				float run = t_cur;
+				int r = MG;
+#pragma unroll 1
+				for (int q = 0; q < MG; ++q) {
+					if (r == MG && q >= lo && run >= target) r = q;
+					run += MIN_CONE_STEPSIZE;
+				}
+				return r;
+			}
 			int m = (int)floorf(fminf(fmaxf((target - t_cur) * inv_dlt, -2.f), 64.f));
 			m += (__builtin_fmaf((float)m, dlt, t_cur) < target) ? 1 : 0;
 			m = max(m, lo);
@@ -909,14 +1020,15 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 		const float my_t = lattice(g);
 		const float t_end = lattice(MG);
 		const Vec3 pos = o + my_t * dir;
-		const bool inside = !term && aabb_contains(a.A, pos);
 		bool occ = false;
+		float dist = 0.f;
+		if (!face_mode) face_mode = __any(!term && t_end >= t_face);
+		const bool inside = !term && probe_single_cascade(a.A, pos, dir, idir, a.bitfield, coarse_lds, a.n_blocks_lds, face_mode, occ, dist);
 		float t_target = 0.f;
 		uint32_t nxt = MG;
 		if (inside) {
-			occ = occupied_mip0(pos, a.bitfield, coarse_lds, a.n_blocks_lds);
 			if (!occ) {
-				t_target = my_t + distance_to_next_voxel(pos, dir, idir, GRIDSIZE);
+				t_target = my_t + dist;
 				nxt = (uint32_t)first_at_or_after(t_target, g + 1);
 			}
 		}
@@ -1006,7 +1118,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 // The re-entry cell behind a jump to lattice position tq (thread-per-ray forms): walks positions tq, tq + dt, ... (the reference's own additions) until it has seen a cell from its
 // FIRST position to its last, all of them inside the box, empty, and jumping to the position behind the cell's last one; that position (a position the reference's chain visits,
 // see k_march_count_skip) is returned in t_found. false: none before t_limit (nothing has been changed; the caller walks on from where it stood).
-__device__ __forceinline__ bool find_reentry(const MarchArgs& a, const uint32_t* __restrict__ coarse_lds, const Vec3& o, const Vec3& dir, const Vec3& idir, float tq, const float t_limit, float& t_found) {
+__device__ __forceinline__ bool find_reentry(const MarchArgs& a, const uint32_t* __restrict__ coarse_lds, const Vec3& o, const Vec3& dir, const Vec3& idir, float tq, const float t_limit, const float t_face, float& t_found) {
 	auto cell_of = [&](const Vec3& p) {
 		const int cx = min(max((int)(p.x * GRIDSIZE), 0), (int)GRIDSIZE - 1), cy = min(max((int)(p.y * GRIDSIZE), 0), (int)GRIDSIZE - 1), cz = min(max((int)(p.z * GRIDSIZE), 0), (int)GRIDSIZE - 1);
 		return (uint32_t)cx | ((uint32_t)cy << 7) | ((uint32_t)cz << 14);
@@ -1020,9 +1132,10 @@ __device__ __forceinline__ bool find_reentry(const MarchArgs& a, const uint32_t*
 #pragma unroll 1
 	for (int k = 1; k < 48; ++k) {
 		if (cell_first >= 0.f) { // the vote of position t_prev
-			const bool in = aabb_contains(a.A, pq);
-			const bool occ = in && occupied_mip0(pq, a.bitfield, coarse_lds, a.n_blocks_lds);
-			const float target = t_prev + distance_to_next_voxel(pq, dir, idir, GRIDSIZE);
+			bool occ = false;
+			float dist = 0.f; // (stays 0 at an occupied or outside position: either fails the cell whatever its target)
+			const bool in = probe_single_cascade(a.A, pq, dir, idir, a.bitfield, coarse_lds, a.n_blocks_lds, t_prev >= t_face, occ, dist);
+			const float target = t_prev + dist;
 			cell_ok = cell_ok && in && !occ;
 			max_target = fmaxf(max_target, target); min_target = fminf(min_target, target);
 		}
@@ -1061,8 +1174,11 @@ __device__ __forceinline__ uint32_t march_skip_narrow(const MarchArgs& a, const 
 	uint32_t j = 0, n_skips = 0, n_fail = 0, n_early = 0;
 	float t = startt;
 	Vec3 pos;
-	while (aabb_contains(a.A, pos = o + t * dir) && j < RNB_MAX_STEPS) {
-		if (skipping && t >= 0.25f) {
+	bool occ = false;
+	float dist = 0.f;
+	const float t_face = face_check_from(o, dir, startt, t_exit);
+	while (probe_single_cascade(a.A, pos = o + t * dir, dir, idir, a.bitfield, coarse_lds, a.n_blocks_lds, t >= t_face, occ, dist) && j < RNB_MAX_STEPS) {
+		if (skipping && t >= 0.25f && t < LATTICE_SKIP_FROM_BELOW) {
 			const int i_first = max((int)floorf((t - startt) * 32.0f) - 1, 0);
 			const uint64_t ahead = i_first < 64 ? (interest >> i_first) : 0ull;
 			if ((ahead & 0xFull) == 0ull) {
@@ -1075,7 +1191,7 @@ __device__ __forceinline__ uint32_t march_skip_narrow(const MarchArgs& a, const 
 					Vec3 pq = o + tq * dir;
 					if (safely_inside(pq)) {
 						float t_re = 0.f;
-						const bool found = find_reentry(a, coarse_lds, o, dir, idir, tq, t_int - 17.0f * MIN_CONE_STEPSIZE, t_re);
+						const bool found = find_reentry(a, coarse_lds, o, dir, idir, tq, t_int - 17.0f * MIN_CONE_STEPSIZE, t_face, t_re);
 						if (found) tq = t_re;
 						if (found) { t = tq; ++n_skips; continue; } // t is a position the reference's chain visits: go on from it
 						skipping = false; ++n_fail;                 // nothing was changed: every voxel from here on
@@ -1083,12 +1199,12 @@ __device__ __forceinline__ uint32_t march_skip_narrow(const MarchArgs& a, const 
 				}
 			}
 		}
-		if (occupied_mip0(pos, a.bitfield, coarse_lds, a.n_blocks_lds)) {
+		if (occ) {
 			emit(j, pos, MIN_CONE_STEPSIZE, t);
 			++j;
 			t += MIN_CONE_STEPSIZE;
 		} else {
-			const float t_target = t + distance_to_next_voxel(pos, dir, idir, GRIDSIZE);
+			const float t_target = t + dist;
 			do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
 		}
 	}
@@ -1155,23 +1271,26 @@ __global__ __launch_bounds__(128) void k_march_count_bbox(const MarchArgs a) {
 			uint32_t jumped = 0, failed = 0;
 			float t = startt;
 			Vec3 pos;
-			while (aabb_contains(a.A, pos = o + t * dir) && j < RNB_MAX_STEPS && t <= t_stop) {
-				if (may_jump && t >= 0.25f && safely_inside(pos)) { // (the ray's first position lies ON the entry face: it is always visited the reference's way)
+			bool occ = false;
+			float dist = 0.f;
+			const float t_face = face_check_from(o, dir, startt, tmax);
+			while (probe_single_cascade(a.A, pos = o + t * dir, dir, idir, a.bitfield, coarse_lds, a.n_blocks_lds, t >= t_face, occ, dist) && j < RNB_MAX_STEPS && t <= t_stop) {
+				if (may_jump && t >= 0.25f && t < LATTICE_SKIP_FROM_BELOW && safely_inside(pos)) { // (the ray's first position lies ON the entry face: it is always visited the reference's way)
 					may_jump = false; // one attempt per ray
 					const int n = (int)floorf((t_in - 52.0f * MIN_CONE_STEPSIZE - t) * (1.0f / MIN_CONE_STEPSIZE)) - 2;
 					if (n >= 32) {
 						const float tq = lattice_advance(t, n);
 						float t_re = 0.f;
-						if (safely_inside(o + tq * dir) && find_reentry(a, coarse_lds, o, dir, idir, tq, t_in - 17.0f * MIN_CONE_STEPSIZE, t_re)) { t = t_re; jumped = 1; continue; }
+						if (safely_inside(o + tq * dir) && find_reentry(a, coarse_lds, o, dir, idir, tq, t_in - 17.0f * MIN_CONE_STEPSIZE, t_face, t_re)) { t = t_re; jumped = 1; continue; }
 						failed = 1;
 					}
 				}
-				if (occupied_mip0(pos, a.bitfield, coarse_lds, a.n_blocks_lds)) {
+				if (occ) {
 					tt[j] = t;
 					++j;
 					t += MIN_CONE_STEPSIZE;
 				} else {
-					const float t_target = t + distance_to_next_voxel(pos, dir, idir, GRIDSIZE);
+					const float t_target = t + dist;
 					do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
 				}
 			}

@@ -7,6 +7,8 @@ Later stages are always fed the ORACLE's outputs of the earlier stage, so each t
 import numpy as np
 import pytest
 
+from tests.march_geometry_cases import shell_bitfield as _shell_bitfield
+
 pytestmark = pytest.mark.gpu
 
 KW = dict(target_batch_size=1 << 13, max_rays_per_batch=1 << 13, initial_rays_per_batch=512, apply_no_albedo=1)
@@ -266,26 +268,6 @@ def test_generate_training_samples_bit_exact(pair):
         assert np.array_equal(gpu.get("COORDS", written * 7).view(np.uint32), cpu.get("COORDS", written * 7).view(np.uint32))
     # the overflow case dropped rays (max_samples = 20000 < total)
     assert cc[0] > 20000 and cc[3] <= 20000
-
-
-def _shell_bitfield(radius, half_width):
-    """Cascade-0 bitfield (Morton order, 128^3 cells) of a spherical shell around the cube's centre; the other cascades empty."""
-    g = (np.arange(128) + 0.5) / 128 - 0.5
-    z, y, x = np.meshgrid(g, g, g, indexing="ij")
-    occ = np.abs(np.sqrt(x * x + y * y + z * z) - radius) < half_width
-
-    def spread(v):
-        v = v.astype(np.uint32)
-        v = (v * 0x00010001) & 0xFF0000FF
-        v = (v * 0x00000101) & 0x0F00F00F
-        v = (v * 0x00000011) & 0xC30C30C3
-        v = (v * 0x00000005) & 0x49249249
-        return v
-    i = np.arange(128)
-    morton = spread(i)[None, None, :] | (spread(i)[None, :, None] << 1) | (spread(i)[:, None, None] << 2)
-    bits = np.zeros(128 ** 3, dtype=np.uint8)
-    bits[morton.ravel()] = occ.ravel()
-    return np.packbits(bits, bitorder="little")
 
 
 @pytest.mark.parametrize("kernel", ["wide", "thread_per_ray"])
