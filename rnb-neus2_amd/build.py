@@ -6,9 +6,10 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(PKG_DIR, "csrc", "rnb_neus2_hip.hip")
 OUT = os.path.join(PKG_DIR, "librnb_neus2_hip.so")
-DEPS = [os.path.join(PKG_DIR, "csrc", f) for f in ("rnb_neus2_hip.hip", "common.cuh", "mlp.cuh", "chain.cuh", "kernels_net.cuh", "kernels_ray.cuh", "mesh_common.cuh", "kernels_mesh.cuh", "kernels_render.cuh", "kernels_mesh_sparse.cuh", "kernels_mesh_clean.cuh", "kernels_mesh_simplify.cuh", "kernels_mesh_distance.cuh", "kernels_mesh_raster.cuh")] + [
-    os.path.join(PKG_DIR, "host", f) for f in ("mesh.hpp", "mc_table.hpp")] + [
-    os.path.join(os.path.dirname(PKG_DIR), "include", f) for f in ("rnb_neus2.h", "rnb_render.h", "rnb_mesh.h", "rnb_mesh_clean.h", "rnb_mesh_simplify.h", "rnb_mesh_distance.h", "rnb_mesh_raster.h")]
+# every file of csrc/ (one translation unit: rnb_neus2_hip.hip includes the kernel headers and the driver's parts), the two host headers it includes, the public headers
+CSRC_DIR, INCLUDE_DIR = os.path.join(PKG_DIR, "csrc"), os.path.join(os.path.dirname(PKG_DIR), "include")
+DEPS = [os.path.join(CSRC_DIR, f) for f in sorted(os.listdir(CSRC_DIR))] + [os.path.join(PKG_DIR, "host", f) for f in ("mesh.hpp", "mc_table.hpp")] + [
+    os.path.join(INCLUDE_DIR, f) for f in sorted(os.listdir(INCLUDE_DIR)) if f.endswith(".h")]
 
 # -ffp-contract=off: the index/ray arithmetic must match the CPU checker bit for bit (no FMA contraction).
 # -packed-fp32-ops (device target feature): no v_pk_{mul,add,fma}_f32. Measured on MI355X / ROCm 7.2 with tools/march_determinism.py: the

@@ -1,0 +1,820 @@
+// driver_mesh.hpp -- rnb_sdf_lattice, what the mesh drivers share (scan_exclusive, count_and_scan, MeshWorkspace, check_mesh_input, alloc_mesh, hand_over,
+// ensure_mc_table), rnb_marching_cubes and the stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster.
+// Needs, of rnb_neus2_hip.hip, which includes it: the context (aabb, bitfield, cfg, mc_table), as_stream, fail / HIP_TRY / RNB_GUARD, launch_point_query
+// and launch_forward.
+extern "C" {
+
+// ---- mesh extraction (src/testbed_nerf.cu:4218-4269, src/marching_cubes.cu:276-430, 794-822) ----
+int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float lattice_min, float lattice_max, float* out, int inference) try {
+	if (!c || !res || !out) return fail(RNB_ERR_INVALID, "null argument");
+	if (!res[0] || !res[1] || !res[2]) return fail(RNB_ERR_INVALID, "empty lattice");
+	hipStream_t s = as_stream(stream);
+	const uint64_t n = (uint64_t)res[0] * res[1] * res[2];
+	const uint32_t batch = 1u << 22; // lattice points per network launch (the reference: 2^20 per call, same arithmetic per point)
+	float* pos = nullptr;
+	half_t* val = nullptr;
+	if (hipMalloc((void**)&pos, (size_t)batch * 12) != hipSuccess || hipMalloc((void**)&val, (size_t)batch * 2) != hipSuccess) {
+		if (pos) (void)hipFree(pos);
+		return fail(RNB_ERR_NOMEM, "hipMalloc failed for the lattice batch");
+	}
+	const float diag = c->aabb.mx - c->aabb.mn;
+	int rc = RNB_OK;
+	for (uint64_t off = 0; off < n && rc == RNB_OK; off += batch) {
+		const uint32_t nb = (uint32_t)std::min<uint64_t>(batch, n - off);
+		hipLaunchKernelGGL(k_lattice_positions, dim3((nb + 255) / 256), dim3(256), 0, s, off, nb, res[0], res[1], res[2], lattice_min, lattice_max - lattice_min, c->aabb.mn, diag, pos);
+		rc = launch_point_query(c, s, pos, nb, val, nullptr, nullptr, 0, inference != 0);
+		if (rc != RNB_OK) break;
+		hipLaunchKernelGGL(k_half_to_float, dim3((nb + 255) / 256), dim3(256), 0, s, val, out + off, nb);
+		if (hipGetLastError() != hipSuccess) rc = fail(RNB_ERR_DEVICE, "rnb_sdf_lattice: kernel launch failed");
+	}
+	hipError_t e = hipStreamSynchronize(s);
+	(void)hipFree(pos); (void)hipFree(val);
+	if (rc != RNB_OK) return rc;
+	if (e != hipSuccess) return fail(RNB_ERR_DEVICE, std::string("rnb_sdf_lattice: ") + hipGetErrorString(e));
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster) ----
+extern "C++" {
+namespace {
+// elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
+uint64_t scan_scratch_elems(uint64_t n) {
+	uint64_t total = 0;
+	do { n = (n + 1023) / 1024; total += n; } while (n > 1);
+	return total;
+}
+// in-place exclusive prefix sums of n counts (device), total to *total_out; `scratch` holds scan_scratch_elems(n) uint32 (allocated once per
+// call and shared by its scans)
+int scan_exclusive(uint32_t* data, uint64_t n, hipStream_t s, uint32_t* total_out, uint32_t* scratch) {
+	std::vector<uint32_t*> levels{data};
+	std::vector<uint64_t> sizes{n};
+	while (true) {
+		const uint64_t nb = (sizes.back() + 1023) / 1024;
+		uint32_t* sums = scratch;
+		scratch += nb;
+		hipLaunchKernelGGL(k_scan_blocks, dim3((uint32_t)nb), dim3(1024), 0, s, levels.back(), sizes.back(), sums);
+		levels.push_back(sums); sizes.push_back(nb);
+		if (nb == 1) break;
+	}
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(total_out, levels.back(), 4, hipMemcpyDeviceToHost, s));
+	// levels.back() holds one value (the total); every level below gets its block offsets added, top-down
+	for (size_t k = levels.size() - 1; k >= 2; --k) { /* levels[k-1] was scanned by the launch that produced levels[k]; add it to levels[k-2] */
+		hipLaunchKernelGGL(k_scan_add, dim3((uint32_t)sizes[k - 1]), dim3(1024), 0, s, levels[k - 2], sizes[k - 2], levels[k - 1]);
+	}
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));
+	return RNB_OK;
+}
+// Phase one of a count / write kernel pair: the <false> instantiation leaves one count per workgroup in wg; they become the workgroups' exclusive offsets, their sum goes
+// to *total (synchronises). The write launch stays with the caller, who allocates for the total in between.
+template <typename K, typename... A>
+int count_and_scan(hipStream_t s, uint32_t n_wg, uint32_t* wg, uint32_t* scratch, uint32_t* total, K count_kernel, A... args) {
+	hipLaunchKernelGGL(count_kernel, dim3(n_wg), dim3(MC_WG), 0, s, args...);
+	HIP_TRY(hipGetLastError());
+	return scan_exclusive(wg, n_wg, s, total, scratch);
+}
+
+// The device memory of one mesh call: what is still held when the object goes out of scope is released; bytes held now and at the peak.
+struct MeshWorkspace {
+	std::vector<std::pair<void*, size_t>> held;
+	size_t cur = 0, peak = 0;
+	template <typename T>
+	bool alloc(T** p, size_t count) {
+		*p = nullptr;
+		const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+		if (hipMalloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+		held.emplace_back((void*)*p, bytes);
+		cur += bytes; peak = std::max(peak, cur);
+		return true;
+	}
+	template <typename T>
+	void release(T*& p) { // free now
+		for (auto& h : held) if (h.first == (void*)p && p) { (void)hipFree(h.first); cur -= h.second; h.first = nullptr; }
+		p = nullptr;
+	}
+	void* keep(void* p) { // the caller owns it from here on (it still counts as held)
+		for (auto& h : held) if (h.first == p) h.first = nullptr;
+		return p;
+	}
+	~MeshWorkspace() { for (auto& h : held) if (h.first) (void)hipFree(h.first); }
+};
+
+// What rnb_mesh_clean, rnb_mesh_simplify and rnb_mesh_distance (which has no output mesh and hands in one it discards) ask of their input mesh, said in the entry
+// point's name; *out is zeroed as soon as it is known not to be the input.
+int check_mesh_input(const char* name, const rnb_mesh* in, rnb_mesh* out) {
+	const std::string n(name);
+	if (in == out) return fail(RNB_ERR_INVALID, n + ": in and out must be different objects");
+	std::memset(out, 0, sizeof(*out));
+	if (in->n_indices % 3u) return fail(RNB_ERR_INVALID, n + ": n_indices is not a multiple of 3");
+	if ((in->n_verts && !in->verts) || (in->n_indices && !in->indices)) return fail(RNB_ERR_INVALID, n + ": null vertex or index buffer");
+	if (in->n_indices && in->n_verts == 0) return fail(RNB_ERR_INVALID, n + ": an index is out of range (the mesh has no vertices)");
+	return RNB_OK;
+}
+// The output mesh of a stage, held by the workspace: nvo vertices with the attributes asked for, nto triangles (a count of 0 still gets a buffer: MeshWorkspace::alloc).
+bool alloc_mesh(MeshWorkspace& ws, rnb_mesh* m, uint32_t nvo, uint32_t nto, bool has_colors, bool has_normals) {
+	std::memset(m, 0, sizeof(*m));
+	m->n_verts = nvo; m->n_indices = nto * 3u;
+	return ws.alloc(&m->verts, (size_t)nvo * 3) && ws.alloc(&m->indices, (size_t)nto * 3) && (!has_colors || ws.alloc(&m->colors, (size_t)nvo * 3)) && (!has_normals || ws.alloc(&m->normals, (size_t)nvo * 3));
+}
+// *out = m, whose buffers the caller owns from here on.
+void hand_over(MeshWorkspace& ws, const rnb_mesh& m, rnb_mesh* out) {
+	*out = m;
+	ws.keep(m.verts); ws.keep(m.indices); ws.keep(m.colors); ws.keep(m.normals);
+}
+} // namespace
+} // extern "C++"
+
+// the marching-cubes case table of host/mesh.hpp on the device, uploaded on first use
+static int ensure_mc_table(rnb_ctx* c) {
+	if (c->mc_table.p) return RNB_OK;
+	static const mesh::Tables T;
+	std::vector<McTable> h(1);
+	for (int m = 0; m < 256; ++m) {
+		int k = 0;
+		for (; T.tri[m][k] >= 0; ++k) h[0].tri[m][k] = T.tri[m][k];
+		h[0].n[m] = (uint8_t)k;
+		for (; k < 40; ++k) h[0].tri[m][k] = -1;
+	}
+	if (c->mc_table.alloc(1) != hipSuccess) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the case table");
+	HIP_TRY(hipMemcpy(c->mc_table.p, h.data(), sizeof(McTable), hipMemcpyHostToDevice));
+	return RNB_OK;
+}
+
+int rnb_marching_cubes(rnb_ctx* c, void* stream, const float* density, const uint32_t res[3], const float aabb_min[3], const float aabb_max[3], float thresh,
+                       float** verts_out, uint32_t** indices_out, uint32_t* n_verts, uint32_t* n_indices) try {
+	if (!c || !density || !res || !aabb_min || !aabb_max || !verts_out || !indices_out || !n_verts || !n_indices) return fail(RNB_ERR_INVALID, "null argument");
+	*verts_out = nullptr; *indices_out = nullptr; *n_verts = 0; *n_indices = 0;
+	const uint64_t res3 = (uint64_t)res[0] * res[1] * res[2];
+	if (res3 == 0 || res3 >= (1ull << 32)) return fail(RNB_ERR_INVALID, "lattice must hold 1 .. 2^32-1 points");
+	hipStream_t s = as_stream(stream);
+	if (int rc = ensure_mc_table(c); rc != RNB_OK) return rc;
+	McArgs a;
+	a.density = density; a.rx = res[0]; a.ry = res[1]; a.rz = res[2]; a.thresh = thresh;
+	for (int d = 0; d < 3; ++d) { a.sc[d] = (aabb_max[d] - aabb_min[d]) / (float)res[d]; a.mn[d] = aabb_min[d]; }
+	const uint64_t n_wg64 = (res3 + MC_WG - 1) / MC_WG;
+	const uint32_t n_wg = (uint32_t)n_wg64;
+	MeshWorkspace ws;
+	uint32_t *wg = nullptr, *scan_scratch = nullptr, *vidx = nullptr, *indices = nullptr;
+	float* verts = nullptr;
+	if (!ws.alloc(&wg, n_wg) || !ws.alloc(&scan_scratch, scan_scratch_elems(n_wg)) || !ws.alloc(&vidx, (size_t)res3 * 3)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the marching-cubes scratch (12 bytes per lattice point)");
+	uint32_t nv = 0, ni = 0;
+	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &nv, k_mc_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr); rc != RNB_OK) return rc;
+	if (nv && !ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the vertices");
+	hipLaunchKernelGGL(k_mc_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
+	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &ni, k_mc_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr); rc != RNB_OK) return rc;
+	if (ni && !ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the indices");
+	hipLaunchKernelGGL(k_mc_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
+	if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return fail(RNB_ERR_DEVICE, "rnb_marching_cubes: kernel failure");
+	*verts_out = (float*)ws.keep(verts); *indices_out = (uint32_t*)ws.keep(indices); *n_verts = nv; *n_indices = ni; // (null where the count is 0; the scratch goes with ws)
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- sparse mesh extraction (include/rnb_mesh.h) ----
+uint32_t rnb_mesh_abi_version(void) { return RNB_MESH_ABI_VERSION; }
+
+int rnb_mesh_default_options(rnb_mesh_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_ABI_VERSION;
+	for (int k = 0; k < 3; ++k) { opt->res[k] = 256; opt->aabb_min[k] = 0.f; opt->aabb_max[k] = 1.f; }
+	opt->lattice_min = 0.f; opt->lattice_max = 1.f;
+	opt->thresh = 0.f;
+	opt->use_inference_params = 1;
+	opt->cull = RNB_MESH_CULL_OCCUPANCY;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_free(rnb_ctx* c, rnb_mesh* m) try {
+	if (!c || !m) return fail(RNB_ERR_INVALID, "null argument");
+	if (m->verts) (void)hipFree(m->verts);
+	if (m->indices) (void)hipFree(m->indices);
+	if (m->colors) (void)hipFree(m->colors);
+	if (m->normals) (void)hipFree(m->normals);
+	std::memset(m, 0, sizeof(*m));
+	return RNB_OK;
+} RNB_GUARD
+
+constexpr uint32_t MESH_DEFAULT_BRICK = 16; // measured against 32 (tools/bench_mesh.py, profiles/mesh_sparse.md): fewer points evaluated around the surface
+int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_mesh* out, rnb_mesh_stats* stats) try {
+	if (!c || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: null argument");
+	std::memset(out, 0, sizeof(*out));
+	if (opt->abi_version != RNB_MESH_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: options abi_version mismatch (expected RNB_MESH_ABI_VERSION)");
+	for (int k = 0; k < 3; ++k) if (opt->res[k] == 0 || opt->res[k] > RNB_MESH_MAX_RES) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: res must be 1 .. 4096 per axis");
+	if (opt->cull != RNB_MESH_CULL_NONE && opt->cull != RNB_MESH_CULL_OCCUPANCY) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: unknown cull mode");
+	if (opt->attributes & ~(RNB_MESH_ATTR_COLORS | RNB_MESH_ATTR_NORMALS)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: unknown attribute bits");
+	const uint32_t B = opt->brick ? opt->brick : MESH_DEFAULT_BRICK;
+	if (B < 8 || B > 64 || (B & (B - 1))) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: brick must be a power of two, 8 .. 64 (0 = default)");
+	if (!std::isfinite(opt->lattice_min) || !std::isfinite(opt->lattice_max) || !std::isfinite(opt->thresh)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: lattice bounds and thresh must be finite");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
+	if (int rc = ensure_mc_table(c); rc != RNB_OK) return rc;
+
+	MeshWorkspace ws;
+	MsArgs a;
+	std::memset(&a, 0, sizeof(a));
+	a.lb = ilog2(B);
+	uint64_t n_bricks64 = 1;
+	for (int k = 0; k < 3; ++k) {
+		a.r[k] = opt->res[k]; a.nb[k] = (opt->res[k] + B - 1) / B; n_bricks64 *= a.nb[k];
+		a.sc[k] = (opt->aabb_max[k] - opt->aabb_min[k]) / (float)opt->res[k]; a.mn[k] = opt->aabb_min[k];
+	}
+	a.thresh = opt->thresh;
+	a.n_bricks = (uint32_t)n_bricks64; // at most (4096 / 8)^3 = 2^27
+	const uint32_t lb3 = 3 * a.lb;
+	const uint64_t brick_points = 1ull << lb3;
+	const bool inference = opt->use_inference_params != 0;
+
+	// 1. which bricks are kept, which are evaluated, and their slots
+	const uint32_t n_bwg = (a.n_bricks + MC_WG - 1) / MC_WG;
+	uint32_t *bwg = nullptr, *bscan = nullptr, *list = nullptr;
+	if (!ws.alloc(&a.word, a.n_bricks) || !ws.alloc(&bwg, n_bwg) || !ws.alloc(&bscan, scan_scratch_elems(n_bwg))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick words");
+	hipLaunchKernelGGL(k_ms_classify, dim3((a.n_bricks + 3) / 4), dim3(256), 0, s, a, (double)opt->lattice_min, (double)opt->lattice_max - (double)opt->lattice_min,
+	                   opt->cull == RNB_MESH_CULL_OCCUPANCY ? (const uint8_t*)c->bitfield.p : (const uint8_t*)nullptr);
+	uint32_t n_eval = 0;
+	int rc = count_and_scan(s, n_bwg, bwg, bscan, &n_eval, k_ms_mark<false>, a, bwg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+	if (rc != RNB_OK) return rc;
+	if (!ws.alloc(&list, n_eval)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick list");
+	a.list = list;
+	hipLaunchKernelGGL(k_ms_mark<true>, dim3(n_bwg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, bwg, list);
+	HIP_TRY(hipGetLastError());
+	uint64_t n_kept = 0;
+	{ // the kept count, for the statistics: the evaluated count is the scan's total
+		std::vector<uint32_t> h(a.n_bricks);
+		HIP_TRY(hipMemcpyAsync(h.data(), a.word, (size_t)a.n_bricks * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		for (uint32_t w : h) n_kept += w & 1u;
+	}
+	ws.release(bwg); ws.release(bscan);
+	const uint64_t n_active_points = (uint64_t)n_eval * brick_points;
+	if (opt->max_active_points && n_active_points > opt->max_active_points)
+		return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: " + std::to_string(n_active_points) + " lattice points would be held at once (" + std::to_string(n_eval) + " bricks of " +
+		            std::to_string(B) + "^3), max_active_points is " + std::to_string(opt->max_active_points));
+	if (n_eval >= (1u << 30)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: more than 2^30 bricks to evaluate");
+
+	uint32_t n_act = 0, nv = 0, ni = 0;
+	float* verts = nullptr;
+	uint32_t* indices = nullptr;
+	if (n_eval) {
+		// 2. the lattice values of the evaluated bricks, through the point-query kernel of rnb_sdf_lattice
+		half_t* vals = nullptr;
+		float* pos = nullptr;
+		uint64_t per_launch = opt->max_points_in_flight ? opt->max_points_in_flight : (1u << 22);
+		const uint32_t slots_per_launch = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per_launch >> lb3, 1), n_eval);
+		if (!ws.alloc(&vals, n_active_points) || !ws.alloc(&pos, (size_t)slots_per_launch * brick_points * 3))
+			return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for " + std::to_string(n_active_points) + " lattice values (set max_active_points to fail before allocating, or cull)");
+		a.vals = vals;
+		const float diag = c->aabb.mx - c->aabb.mn;
+		for (uint32_t s0 = 0; s0 < n_eval; s0 += slots_per_launch) {
+			const uint32_t np = (uint32_t)(std::min<uint32_t>(slots_per_launch, n_eval - s0) * brick_points); // at most 2^22 or one brick (2^18)
+			hipLaunchKernelGGL(k_ms_positions, dim3((np + 255) / 256), dim3(256), 0, s, a, s0, np, opt->lattice_min, opt->lattice_max - opt->lattice_min, c->aabb.mn, diag, pos);
+			HIP_TRY(hipGetLastError());
+			rc = launch_point_query(c, s, pos, np, vals + (size_t)s0 * brick_points, nullptr, nullptr, 0, inference);
+			if (rc != RNB_OK) return rc;
+		}
+		// 3. which of them see both sides of the threshold; only those keep an edge table
+		uint32_t *act = nullptr, *aoff = nullptr, *ascan = nullptr, *alist = nullptr;
+		if (!ws.alloc(&act, n_eval) || !ws.alloc(&aoff, n_eval) || !ws.alloc(&ascan, scan_scratch_elems(n_eval))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick flags");
+		hipLaunchKernelGGL(k_ms_sign, dim3(n_eval), dim3(256), 0, s, a, act);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(aoff, act, (size_t)n_eval * 4, hipMemcpyDeviceToDevice, s));
+		rc = scan_exclusive(aoff, n_eval, s, &n_act, ascan);
+		if (rc != RNB_OK) return rc;
+		ws.release(pos); ws.release(ascan);
+		a.act = act; a.aoff = aoff;
+		if (n_act) {
+			if ((uint64_t)n_act << (lb3 - 8) >= (1ull << 31)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: too many bricks with a sign change for one launch");
+			const uint32_t n_wg = n_act << (lb3 - 8);
+			uint32_t *wg = nullptr, *wscan = nullptr, *vidx = nullptr;
+			if (!ws.alloc(&alist, n_act) || !ws.alloc(&wg, n_wg) || !ws.alloc(&wscan, scan_scratch_elems(n_wg)) || !ws.alloc(&vidx, (size_t)n_act * 3 * brick_points))
+				return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the edge tables of " + std::to_string(n_act) + " bricks");
+			a.alist = alist;
+			hipLaunchKernelGGL(k_ms_list, dim3((n_eval + 255) / 256), dim3(256), 0, s, n_eval, act, aoff, alist);
+			// 4. vertices, then triangles: count, scan, write (the dense path's scheme over the bricks' workgroups)
+			if ((rc = count_and_scan(s, n_wg, wg, wscan, &nv, k_ms_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
+			if (!ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
+			hipLaunchKernelGGL(k_ms_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
+			if ((rc = count_and_scan(s, n_wg, wg, wscan, &ni, k_ms_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr)) != RNB_OK) return rc;
+			if (!ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
+			hipLaunchKernelGGL(k_ms_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			ws.release(wg); ws.release(wscan); ws.release(vidx); ws.release(alist);
+		}
+		ws.release(vals); ws.release(act); ws.release(aoff);
+	}
+	ws.release(a.word); ws.release(list);
+	if (!verts && !ws.alloc(&verts, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
+	if (!indices && !ws.alloc(&indices, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
+
+	// 5. attributes: the full network at the vertices, in batches
+	float *colors = nullptr, *normals = nullptr;
+	if (opt->attributes) {
+		if ((opt->attributes & RNB_MESH_ATTR_COLORS) && !ws.alloc(&colors, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the colours");
+		if ((opt->attributes & RNB_MESH_ATTR_NORMALS) && !ws.alloc(&normals, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the normals");
+		const uint32_t batch = std::min<uint32_t>(1u << 20, std::max(nv, 1u));
+		float* coords = nullptr;
+		half_t* net = nullptr;
+		if (!ws.alloc(&coords, (size_t)batch * 7) || !ws.alloc(&net, (size_t)batch * 16)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the attribute batch");
+		const float diag = c->aabb.mx - c->aabb.mn;
+		for (uint32_t v0 = 0; v0 < nv; v0 += batch) {
+			const uint32_t nb = std::min(batch, nv - v0);
+			hipLaunchKernelGGL(k_ms_vertex_coords, dim3((nb + 255) / 256), dim3(256), 0, s, verts + (size_t)v0 * 3, nb, c->aabb.mn, diag, coords);
+			HIP_TRY(hipGetLastError());
+			rc = launch_forward(c, s, coords, nullptr, nb, net, inference);
+			if (rc != RNB_OK) return rc;
+			hipLaunchKernelGGL(k_ms_vertex_attr, dim3((nb + 255) / 256), dim3(256), 0, s, net, nb, colors ? colors + (size_t)v0 * 3 : nullptr, normals ? normals + (size_t)v0 * 3 : nullptr);
+			HIP_TRY(hipGetLastError());
+		}
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(coords); ws.release(net);
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	hand_over(ws, rnb_mesh{verts, indices, colors, normals, nv, ni}, out);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_bricks = a.n_bricks; stats->n_kept = n_kept; stats->n_evaluated = n_eval; stats->n_sign_change = n_act;
+		stats->n_points_evaluated = n_active_points;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh cleaning (include/rnb_mesh_clean.h) ----
+uint32_t rnb_mesh_clean_abi_version(void) { return RNB_MESH_CLEAN_ABI_VERSION; }
+
+int rnb_mesh_clean_default_options(rnb_mesh_clean_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_CLEAN_ABI_VERSION;
+	opt->keep = RNB_MESH_KEEP_LARGEST;
+	opt->orient = RNB_MESH_ORIENT_OUTWARD;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_clean_table_free(rnb_ctx* c, rnb_mesh_component* table) try {
+	if (!c) return fail(RNB_ERR_INVALID, "null argument");
+	if (table) (void)hipFree(table);
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_clean_options* opt, rnb_mesh* out, rnb_mesh_component** table_dev, rnb_mesh_clean_stats* stats) try {
+	if (table_dev) *table_dev = nullptr;
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_clean", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_CLEAN_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: options abi_version mismatch (expected RNB_MESH_CLEAN_ABI_VERSION)");
+	if (opt->keep != RNB_MESH_KEEP_ALL && opt->keep != RNB_MESH_KEEP_LARGEST) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown keep mode");
+	if (opt->orient != RNB_MESH_ORIENT_NONE && opt->orient != RNB_MESH_ORIENT_OUTWARD) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown orient mode");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	MeshWorkspace ws;
+	ClResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	hres.best = MESH_NONE;
+	uint32_t n_comp = 0, nvo = 0, nto = 0;
+	rnb_mesh_component* table = nullptr;
+	rnb_mesh o;
+	if (nt) {
+		const uint32_t g_v = (nv + CL_WG - 1) / CL_WG, g_t = (nt + CL_WG - 1) / CL_WG; // (nv >= 1: check_mesh_input)
+		uint32_t *parent = nullptr, *used = nullptr, *cid = nullptr, *scan = nullptr, *twg = nullptr, *cflags = nullptr;
+		ClResult* dres = nullptr;
+		if (!ws.alloc(&parent, nv) || !ws.alloc(&used, nv) || !ws.alloc(&cid, nv) || !ws.alloc(&twg, g_t) || !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) || !ws.alloc(&dres, 1))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		// 1. every index is range-checked before any is used as an address
+		hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, CL_BAD_INDEX);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & CL_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: an index is out of range (>= n_verts)");
+		// 2. labels: one hooking launch, one flattening launch; roots -> component ids in ascending label order
+		hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, parent);
+		hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
+		hipLaunchKernelGGL(k_cl_roots, dim3(g_v), dim3(CL_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, cid, nv);
+		HIP_TRY(hipGetLastError());
+		int rc = scan_exclusive(cid, nv, s, &n_comp, scan);
+		if (rc != RNB_OK) return rc;
+		if (!ws.alloc(&table, n_comp) || !ws.alloc(&cflags, n_comp)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the table of " + std::to_string(n_comp) + " components");
+		HIP_TRY(hipMemsetAsync(table, 0, std::max<size_t>(n_comp, 1) * sizeof(rnb_mesh_component), s));
+		hipLaunchKernelGGL(k_cl_relabel, dim3(g_v), dim3(CL_WG), 0, s, parent, (const uint32_t*)used, (const uint32_t*)cid, table, nv);
+		const uint32_t* comp = parent;
+		// 3. per-component sums, the selection
+		hipLaunchKernelGGL(k_cl_sums<true>, dim3(g_t), dim3(CL_WG), 0, s, (const float*)m.verts, (const uint32_t*)m.indices, nt, comp, table, dres);
+		hipLaunchKernelGGL(k_cl_sums<false>, dim3(g_v), dim3(CL_WG), 0, s, (const float*)nullptr, (const uint32_t*)nullptr, nv, comp, table, dres);
+		hipLaunchKernelGGL(k_cl_select, dim3(1), dim3(1024), 0, s, table, n_comp, opt->keep, opt->orient, cflags, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & CL_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: the area or volume term of a triangle is not finite or not below 2^18");
+		ws.release(used);
+		// 4. compaction: the new vertex numbering (cid's memory is reused), the kept triangles per workgroup
+		uint32_t* vmap = cid;
+		hipLaunchKernelGGL(k_cl_vflag, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, vmap, nv);
+		HIP_TRY(hipGetLastError());
+		rc = scan_exclusive(vmap, nv, s, &nvo, scan);
+		if (rc != RNB_OK) return rc;
+		if ((rc = count_and_scan(s, g_t, twg, scan, &nto, k_cl_tris<false>, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
+		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
+		hipLaunchKernelGGL(k_cl_verts, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, o.verts, o.colors, o.normals);
+		hipLaunchKernelGGL(k_cl_tris<true>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		if (n_comp && hres.best < n_comp) { // the label of the selected component, for the statistics
+			uint32_t label = MESH_NONE;
+			HIP_TRY(hipMemcpy(&label, &table[hres.best].label, 4, hipMemcpyDeviceToHost));
+			hres.best = label;
+		} else hres.best = MESH_NONE;
+		ws.release(parent); ws.release(cid); ws.release(scan); ws.release(twg); ws.release(cflags); ws.release(dres);
+	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr) || (table_dev && !ws.alloc(&table, 1)))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
+	hand_over(ws, o, out);
+	if (table_dev) *table_dev = (rnb_mesh_component*)ws.keep(table);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_components = n_comp; stats->n_kept = hres.n_kept;
+		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
+		stats->largest_label = hres.best;
+		stats->hook_passes = nt ? 1u : 0u; stats->flatten_passes = nt ? 1u : 0u;
+		stats->area_q_in = hres.area_in; stats->area_q_out = hres.area_out;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh simplification (include/rnb_mesh_simplify.h) ----
+uint32_t rnb_mesh_simplify_abi_version(void) { return RNB_MESH_SIMPLIFY_ABI_VERSION; }
+
+int rnb_mesh_simplify_default_options(rnb_mesh_simplify_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_SIMPLIFY_ABI_VERSION;
+	opt->cell = 1.0f / 256.0f;
+	opt->dims[0] = opt->dims[1] = opt->dims[2] = 256u;
+	opt->placement = RNB_MESH_PLACE_QUADRIC;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_simplify_options* opt, rnb_mesh* out, rnb_mesh_simplify_stats* stats) try {
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_simplify", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_SIMPLIFY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: options abi_version mismatch (expected RNB_MESH_SIMPLIFY_ABI_VERSION)");
+	if (opt->placement != RNB_MESH_PLACE_QUADRIC && opt->placement != RNB_MESH_PLACE_MEAN) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: unknown placement");
+	if (!(opt->cell > 0.0f) || !std::isfinite(opt->cell)) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: cell must be finite and > 0");
+	uint64_t n_cells = 1;
+	for (int k = 0; k < 3; ++k) {
+		if (!std::isfinite(opt->origin[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: origin must be finite");
+		if (opt->dims[k] == 0 || opt->dims[k] > RNB_MESH_SIMPLIFY_MAX_DIM) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims must be 1 .. 4096 per axis");
+		n_cells *= opt->dims[k];
+	}
+	if (n_cells > RNB_MESH_SIMPLIFY_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims hold " + std::to_string(n_cells) + " cells, more than RNB_MESH_SIMPLIFY_MAX_CELLS (2^30)");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	MeshWorkspace ws;
+	SpResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	uint32_t n_cl = 0, nvo = 0, nto = 0;
+	rnb_mesh o;
+	if (nt) {
+		SpGrid g;
+		for (int k = 0; k < 3; ++k) { g.origin[k] = (double)opt->origin[k]; g.dims[k] = opt->dims[k]; }
+		g.cell = (double)opt->cell;
+		const uint32_t n_words = (uint32_t)((n_cells + 31u) / 32u);
+		const uint32_t g_v = (nv + SP_WG - 1) / SP_WG, g_t = (nt + SP_WG - 1) / SP_WG, g_w = (n_words + SP_WG - 1) / SP_WG;
+		uint32_t *used = nullptr, *vcl = nullptr, *bits = nullptr, *rank = nullptr, *scan = nullptr, *twg = nullptr, *ckey = nullptr, *cused = nullptr, *cmap = nullptr;
+		long long* sums = nullptr;
+		SpResult* dres = nullptr;
+		if (!ws.alloc(&used, nv) || !ws.alloc(&vcl, nv) || !ws.alloc(&bits, n_words) || !ws.alloc(&rank, n_words) || !ws.alloc(&twg, g_t) ||
+		    !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(std::max<uint64_t>(nv, n_words), g_t))) || !ws.alloc(&dres, 1))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(n_cells) + " cells");
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemsetAsync(bits, 0, (size_t)n_words * 4, s));
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		// 1. every index is range-checked before any is used as an address; the occupied cells; cluster ids = ranks of the occupied keys
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, SP_BAD_INDEX);
+		hipLaunchKernelGGL(k_sp_cells, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)used, vcl, bits, dres);
+		hipLaunchKernelGGL(k_sp_popc, dim3(g_w), dim3(SP_WG), 0, s, (const uint32_t*)bits, rank, n_words);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		int rc = scan_exclusive(rank, n_words, s, &n_cl, scan); // (synchronises: hres has arrived)
+		if (rc != RNB_OK) return rc;
+		if (hres.flags & SP_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: an index is out of range (>= n_verts)");
+		if (hres.flags & SP_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a coordinate or attribute of a used vertex is not finite");
+		ws.release(used);
+		// 2. the sums of every cluster
+		if (!ws.alloc(&sums, (size_t)n_cl * SP_NSUM) || !ws.alloc(&ckey, n_cl) || !ws.alloc(&cused, n_cl) || !ws.alloc(&cmap, n_cl))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the records of " + std::to_string(n_cl) + " clusters");
+		HIP_TRY(hipMemsetAsync(sums, 0, std::max<size_t>(n_cl, 1) * SP_NSUM * sizeof(long long), s));
+		HIP_TRY(hipMemsetAsync(cused, 0, std::max<size_t>(n_cl, 1) * 4, s));
+		hipLaunchKernelGGL(k_sp_members, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)bits, (const uint32_t*)rank, vcl, ckey, sums, dres);
+		hipLaunchKernelGGL(k_sp_quadric, dim3(g_t), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, sums, dres);
+		// 3. the surviving triangles and the clusters they use, numbered by prefix sums (not count_and_scan: the count launch feeds two scans, the clusters' first)
+		hipLaunchKernelGGL(k_sp_tris<false>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, cused, (const uint32_t*)nullptr, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(cmap, cused, std::max<size_t>(n_cl, 1) * 4, hipMemcpyDeviceToDevice, s));
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		rc = scan_exclusive(cmap, n_cl, s, &nvo, scan);
+		if (rc != RNB_OK) return rc;
+		if (hres.flags & SP_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a term is not finite or not below 2^22 (a vertex or triangle too far from its cell, in cell units)");
+		rc = scan_exclusive(twg, g_t, s, &nto, scan);
+		if (rc != RNB_OK) return rc;
+		ws.release(bits); ws.release(rank);
+		// 4. the output: one solve per cluster, the triangles in input order
+		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
+		hipLaunchKernelGGL(k_sp_solve, dim3((n_cl + SP_WG - 1) / SP_WG), dim3(SP_WG), 0, s, g, opt->placement, n_cl, (const long long*)sums, (const uint32_t*)ckey, (const uint32_t*)cused, (const uint32_t*)cmap,
+		                   o.verts, o.colors, o.normals, dres);
+		hipLaunchKernelGGL(k_sp_tris<true>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, (uint32_t*)nullptr, (const uint32_t*)cmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(vcl); ws.release(scan); ws.release(twg); ws.release(sums); ws.release(ckey); ws.release(cused); ws.release(cmap); ws.release(dres);
+	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
+	hand_over(ws, o, out);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_verts_in = nv; stats->n_tris_in = nt; stats->n_clusters = n_cl; stats->n_verts_out = nvo; stats->n_tris_out = nto; stats->n_tris_collapsed = nt - nto;
+		stats->n_clamped = hres.n_clamped; stats->n_fallback = hres.n_fallback;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh-to-mesh distance (include/rnb_mesh_distance.h) ----
+uint32_t rnb_mesh_distance_abi_version(void) { return RNB_MESH_DISTANCE_ABI_VERSION; }
+
+int rnb_mesh_distance_default_options(rnb_mesh_distance_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_DISTANCE_ABI_VERSION;
+	opt->level = 1u;
+	opt->unit = 1.0f / 1024.0f;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_mesh* to, const rnb_mesh_distance_options* opt, float* vert_dist_dev, uint32_t* vert_nearest_dev,
+                      rnb_mesh_distance_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !from || !to || !opt) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: null argument");
+	if (from == to) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: from and to must be different objects");
+	if (vert_dist_dev && (void*)vert_dist_dev == (void*)vert_nearest_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: vert_dist_dev and vert_nearest_dev must be different buffers");
+	if (opt->abi_version != RNB_MESH_DISTANCE_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: options abi_version mismatch (expected RNB_MESH_DISTANCE_ABI_VERSION)");
+	if (opt->level > RNB_MESH_DISTANCE_MAX_LEVEL) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: level must be 0 .. 3");
+	if (!(opt->unit > 0.0f) || !std::isfinite(opt->unit)) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: unit must be finite and > 0");
+	if (!(opt->max_distance >= 0.0f) || !std::isfinite(opt->max_distance)) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: max_distance must be finite and >= 0");
+	for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k)
+		if (!(opt->tau[k] >= 0.0f) || !std::isfinite(opt->tau[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a tau must be finite and >= 0");
+	if (opt->cells > RNB_MESH_DISTANCE_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: cells must be 0 .. 256");
+	{
+		rnb_mesh unused;
+		if (int rc = check_mesh_input("rnb_mesh_distance (from)", from, &unused); rc != RNB_OK) return rc;
+		if (int rc = check_mesh_input("rnb_mesh_distance (to)", to, &unused); rc != RNB_OK) return rc;
+	}
+	const rnb_mesh ma = *from, mb = *to;
+	const uint32_t nva = ma.n_verts, nta = ma.n_indices / 3u, nvb = mb.n_verts, ntb = mb.n_indices / 3u, nn = 1u << (2u * opt->level);
+	if ((uint64_t)nta * nn > 0xFFFFFFFFull) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: more than 2^32 - 1 samples (a lower level)");
+	if (nta && ntb == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	MeshWorkspace ws;
+	MdResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	for (int k = 0; k < 3; ++k) hres.bmin[k] = 0xFFFFFFFFu;
+	MdGrid g;
+	std::memset(&g, 0, sizeof(g));
+	uint32_t n_entries = 0;
+	float ms_grid = 0.0f;
+	int64_t sums[MD_NSUM] = {};
+	if (!nta) { // no sample: every vertex is unused
+		if (vert_dist_dev && nva) HIP_TRY(hipMemsetAsync(vert_dist_dev, 0, (size_t)nva * 4, s));
+		if (vert_nearest_dev && nva) HIP_TRY(hipMemsetAsync(vert_nearest_dev, 0xFF, (size_t)nva * 4, s));
+		HIP_TRY(hipStreamSynchronize(s));
+	} else {
+		const uint32_t g_va = (nva + MD_WG - 1) / MD_WG, g_ta = (nta + MD_WG - 1) / MD_WG, g_vb = (nvb + MD_WG - 1) / MD_WG, g_tb = (ntb + MD_WG - 1) / MD_WG; // (nva, nvb >= 1: check_mesh_input)
+		const MdMesh A{ma.verts, ma.indices, nva, nta}, B{mb.verts, mb.indices, nvb, ntb};
+		uint32_t *used_a = nullptr, *used_b = nullptr, *start = nullptr, *cursor = nullptr, *scan = nullptr, *entries = nullptr, *large = nullptr;
+		MdResult* dres = nullptr;
+		if (!ws.alloc(&used_a, nva) || !ws.alloc(&used_b, nvb) || !ws.alloc(&large, RNB_MESH_DISTANCE_MAX_LARGE) || !ws.alloc(&dres, 1))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the workspace of " + std::to_string(nva) + " and " + std::to_string(nvb) + " vertices");
+		HIP_TRY(hipMemsetAsync(used_a, 0, (size_t)nva * 4, s));
+		HIP_TRY(hipMemsetAsync(used_b, 0, (size_t)nvb * 4, s));
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		// 1. every index of either mesh is range-checked before any is used as an address; used vertices, B's box, B's degenerate triangles
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_ta), dim3(MD_WG), 0, s, (const uint32_t*)ma.indices, nta, nva, used_a, &dres->flags, MD_BAD_INDEX_FROM);
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_tb), dim3(MD_WG), 0, s, (const uint32_t*)mb.indices, ntb, nvb, used_b, &dres->flags, MD_BAD_INDEX_TO);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MD_BAD_INDEX_FROM) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of from is out of range (>= n_verts)");
+		if (hres.flags & MD_BAD_INDEX_TO) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of to is out of range (>= n_verts)");
+		hipLaunchKernelGGL(k_md_verts<false>, dim3(g_va), dim3(MD_WG), 0, s, (const float*)ma.verts, nva, (const uint32_t*)used_a, dres);
+		hipLaunchKernelGGL(k_md_verts<true>, dim3(g_vb), dim3(MD_WG), 0, s, (const float*)mb.verts, nvb, (const uint32_t*)used_b, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MD_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a coordinate of a used vertex is not finite");
+		ws.release(used_b);
+		const auto t_grid = std::chrono::steady_clock::now();
+		hipLaunchKernelGGL(k_md_degenerate, dim3(g_tb), dim3(MD_WG), 0, s, B, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		const uint32_t m = ntb - hres.n_deg_to;
+		if (!m) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
+		// 2. the grid over B's box, the cell lists
+		double longest = 0.0;
+		for (int k = 0; k < 3; ++k) {
+			const auto value = [](uint32_t image) { const uint32_t u = (image & 0x80000000u) ? (image ^ 0x80000000u) : ~image; float f; std::memcpy(&f, &u, 4); return (double)f; };
+			g.lo[k] = value(hres.bmin[k]); g.hi[k] = value(hres.bmax[k]);
+			longest = std::max(longest, g.hi[k] - g.lo[k]);
+		}
+		uint32_t n_axis = opt->cells;
+		if (!n_axis) n_axis = (uint32_t)std::min<double>(std::max<double>(std::floor(std::sqrt((double)(m / 2u))), 1.0), (double)RNB_MESH_DISTANCE_MAX_CELLS);
+		g.cell = longest / (double)n_axis; // > 0: a non-degenerate triangle has an extent
+		uint64_t n_cells = 1;
+		for (int k = 0; k < 3; ++k) {
+			g.dims[k] = (uint32_t)std::min<double>((double)n_axis, std::floor((g.hi[k] - g.lo[k]) / g.cell) + 1.0);
+			n_cells *= g.dims[k];
+		}
+		if (!ws.alloc(&start, n_cells) || !ws.alloc(&cursor, n_cells) || !ws.alloc(&scan, scan_scratch_elems(n_cells)))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the lists of " + std::to_string(n_cells) + " cells");
+		HIP_TRY(hipMemsetAsync(start, 0, (size_t)n_cells * 4, s));
+		hipLaunchKernelGGL(k_md_register<false>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, start, (uint32_t*)nullptr, large, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		int rc = scan_exclusive(start, n_cells, s, &n_entries, scan); // (synchronises: hres has arrived)
+		if (rc != RNB_OK) return rc;
+		if (hres.n_large > RNB_MESH_DISTANCE_MAX_LARGE)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_large) + " triangles of to overlap more than 2048 cells each, the large list holds 4096 (a coarser grid: fewer cells)");
+		if (hres.n_entries > RNB_MESH_DISTANCE_MAX_ENTRIES)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_entries) + " cell entries, more than 2^31 (a coarser grid: fewer cells)");
+		if (!ws.alloc(&entries, n_entries)) return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for " + std::to_string(n_entries) + " cell entries");
+		HIP_TRY(hipMemcpyAsync(cursor, start, (size_t)n_cells * 4, hipMemcpyDeviceToDevice, s));
+		hipLaunchKernelGGL(k_md_register<true>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, cursor, entries, (uint32_t*)nullptr, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		ms_grid = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_grid).count();
+		// 3. the queries: the vertices of A, then the sub-centroids of its triangles
+		MdQuery q;
+		std::memset(&q, 0, sizeof(q));
+		q.cap = (double)opt->max_distance; q.unit = (double)opt->unit; q.level = opt->level;
+		for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k) q.tau[k] = (double)opt->tau[k];
+		const MdSearch S{B, start, cursor, entries, large, hres.n_large};
+		const uint64_t n_threads = (uint64_t)nta * nn;
+		hipLaunchKernelGGL(k_md_query<true>, dim3(g_va), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)used_a, S, vert_dist_dev, vert_nearest_dev, dres);
+		hipLaunchKernelGGL(k_md_query<false>, dim3((uint32_t)((n_threads + MD_WG - 1) / MD_WG)), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)nullptr, S, (float*)nullptr, (uint32_t*)nullptr, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MD_BAD_TERM)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a term is not finite or not below 2^12 (a larger unit, or a max_distance)");
+		for (int k = 0; k < MD_NSUM; ++k) { // the two words of a sum, joined in 128 bits
+			const unsigned __int128 total = ((unsigned __int128)hres.hi[k] << 32) + hres.lo[k];
+			if (total >> 63) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a sum reaches 2^15 (a larger unit, or a max_distance)");
+			sums[k] = (int64_t)total;
+		}
+		ws.release(used_a); ws.release(start); ws.release(cursor); ws.release(scan); ws.release(entries); ws.release(large); ws.release(dres);
+	}
+	if (stats) {
+		stats->n_verts_from_used = hres.n_used_from; stats->n_verts_to_used = hres.n_used_to; stats->n_tris_from = nta; stats->n_tris_to = ntb;
+		stats->n_degenerate_from = hres.n_deg_from; stats->n_degenerate_to = hres.n_deg_to; stats->n_verts_beyond = hres.n_verts_beyond; stats->n_large = hres.n_large;
+		stats->n_samples = hres.n_samples; stats->n_beyond = hres.n_beyond;
+		stats->sum_w = sums[0]; stats->sum_wd = sums[1]; stats->sum_wd2 = sums[2];
+		for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k) stats->sum_within[k] = sums[3 + k];
+		std::memcpy(&stats->max_distance, &hres.max_bits, 8);
+		for (int k = 0; k < 3; ++k) stats->dims[k] = g.dims[k];
+		stats->cell = g.cell;
+		stats->n_cell_entries = hres.n_entries; stats->n_pairs = hres.n_pairs;
+		stats->peak_workspace = ws.peak;
+		stats->ms_grid = ms_grid;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- mesh rasteriser (include/rnb_mesh_raster.h) ----
+uint32_t rnb_mesh_raster_abi_version(void) { return RNB_MESH_RASTER_ABI_VERSION; }
+
+int rnb_mesh_raster_default_options(rnb_mesh_raster_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_RASTER_ABI_VERSION;
+	opt->near = 1.0f / 1024.0f;
+	opt->cull = RNB_MESH_RASTER_CULL_NONE;
+	opt->normals = RNB_MESH_RASTER_NORMALS_FACE;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, const rnb_mesh_raster_options* opt, float* out_dev, uint32_t* face_dev,
+                    rnb_mesh_raster_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !mesh || !view || !opt || !out_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: null argument");
+	if ((void*)out_dev == (void*)face_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: out_dev and face_dev must be different buffers");
+	if (opt->abi_version != RNB_MESH_RASTER_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: options abi_version mismatch (expected RNB_MESH_RASTER_ABI_VERSION)");
+	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: near must be finite and > 0");
+	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
+	if (opt->normals > RNB_MESH_RASTER_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals must be RNB_MESH_RASTER_NORMALS_FACE or _VERTEX");
+	for (int k = 0; k < 2; ++k) {
+		if (!(view->focal_length[k] > 0.0f) || !std::isfinite(view->focal_length[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: a focal length must be finite and > 0");
+		if (!std::isfinite(view->principal_point[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: the principal point must be finite");
+	}
+	for (int k = 0; k < 12; ++k)
+		if (!std::isfinite(view->xform[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an entry of xform is not finite");
+	if (view->width == 0 || view->height == 0 || view->width > RNB_MESH_RASTER_MAX_SIZE || view->height > RNB_MESH_RASTER_MAX_SIZE)
+		return fail(RNB_ERR_INVALID, "rnb_mesh_raster: width and height must be 1 .. 16384");
+	{
+		rnb_mesh unused;
+		if (int rc = check_mesh_input("rnb_mesh_raster", mesh, &unused); rc != RNB_OK) return rc;
+	}
+	if (opt->normals == RNB_MESH_RASTER_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals = VERTEX needs a mesh with normals");
+	const rnb_mesh m = *mesh;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, width = view->width, height = view->height, n_pix = width * height;
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	MrCamera cam;
+	std::memset(&cam, 0, sizeof(cam));
+	for (int r = 0; r < 3; ++r) {
+		cam.o[r] = (double)view->xform[4 * r + 3];
+		for (int k = 0; k < 3; ++k) cam.col[k][r] = (double)view->xform[4 * r + k];
+	}
+	cam.fx = (double)view->focal_length[0]; cam.fy = (double)view->focal_length[1];
+	cam.cxw = (double)view->principal_point[0] * (double)width; cam.cyh = (double)view->principal_point[1] * (double)height;
+	cam.near = (double)opt->near;
+	cam.w = width; cam.h = height; cam.cull = opt->cull; cam.normals = opt->normals;
+	const MrMesh M{m.verts, m.indices, m.colors, m.normals, nt};
+
+	MeshWorkspace ws;
+	MrResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	unsigned long long* keys = nullptr;
+	uint32_t *counts = nullptr, *used = nullptr, *list = nullptr;
+	MrResult* dres = nullptr;
+	if (!ws.alloc(&keys, n_pix) || !ws.alloc(&counts, n_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the workspace of " + std::to_string(n_pix) + " pixels and " + std::to_string(nv) + " vertices");
+	HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_pix * 8, s));
+	HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_pix * 4, s));
+	HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+	if (nt) {
+		const uint32_t g_t = (nt + MR_WG - 1) / MR_WG;
+		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MR_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, MR_BAD_INDEX);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MR_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an index is out of range (>= n_verts)");
+		ws.release(used);
+		// 2. setup, classes, the small triangles filled; the large ones counted, then listed and filled by a wavefront each
+		hipLaunchKernelGGL(k_mr_bin<false>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, (uint32_t*)nullptr, 0u, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		const uint32_t n_large = hres.n_class[MR_LARGE];
+		if (n_large) {
+			if (!ws.alloc(&list, n_large)) return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the list of " + std::to_string(n_large) + " large triangles");
+			hipLaunchKernelGGL(k_mr_bin<true>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, list, n_large, dres);
+			hipLaunchKernelGGL(k_mr_fill_large, dim3((n_large + MR_WG / 64u - 1) / (MR_WG / 64u)), dim3(MR_WG), 0, s, cam, M, (const uint32_t*)list, n_large, keys, counts);
+			HIP_TRY(hipGetLastError());
+		}
+	}
+	// 3. one thread per pixel (an empty mesh: every key is still all ones, the image is zeros)
+	const uint32_t g_p = (n_pix + MR_WG - 1) / MR_WG;
+	if (((uintptr_t)out_dev & 15u) == 0)
+		hipLaunchKernelGGL(k_mr_resolve<true>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
+	else
+		hipLaunchKernelGGL(k_mr_resolve<false>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	ws.release(keys); ws.release(counts); ws.release(used); ws.release(list); ws.release(dres);
+	if (hres.n_unresolved) return fail(RNB_ERR_DEVICE, "rnb_mesh_raster: " + std::to_string(hres.n_unresolved) + " pixels whose winner the resolve pass does not find covering them (the fill and the resolve disagree: a defect of the library)");
+	if (stats) {
+		stats->n_tris = nt;
+		stats->n_behind = hres.n_class[MR_BEHIND]; stats->n_out_of_range = hres.n_class[MR_OUT_OF_RANGE]; stats->n_degenerate = hres.n_class[MR_DEGENERATE];
+		stats->n_culled = hres.n_class[MR_CULLED]; stats->n_offscreen = hres.n_class[MR_OFFSCREEN]; stats->n_small = hres.n_class[MR_SMALL]; stats->n_large = hres.n_class[MR_LARGE];
+		stats->n_covered = hres.n_covered; stats->n_back_pixels = hres.n_back_pixels; stats->n_fragments = hres.n_fragments;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+
+} // extern "C"

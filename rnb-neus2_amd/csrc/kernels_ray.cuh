@@ -1,6 +1,6 @@
 // kernels_ray.cuh — occupancy grid, ray marching and loss kernels.
 //   k_grid_samples / k_ema_grid / k_mean_* / k_grid_to_bitfield / k_bitfield_max_pool   testbed_nerf.cu:585-740, 3424-3517
-//   k_march_count / k_scan_rays / k_march_write                                         testbed_nerf.cu:1216-1387
+//   k_march_count / k_scan_rays_chain / k_march_write                                   testbed_nerf.cu:1216-1387
 //   k_loss_pass1 / k_scan_compact / k_loss_pass2 / k_rollover                            testbed_nerf.cu:1396-2097, 4044-4052
 // Sample slots are assigned in ray order by prefix sums instead of the reference's atomicAdd order (any order is a
 // legal outcome of the reference's race; ray order makes the step reproducible and the sample stream coalesced).
@@ -1344,12 +1344,7 @@ __global__ __launch_bounds__(128) void k_march_count_skip_narrow(const MarchArgs
 	a.steps[i] = steps;
 }
 
-// Single-workgroup exclusive scans over the rays (n <= 2^18): base = scan(steps); survivors = base + steps <= max_samples;
-// slot = scan(survivor). counters[0] = sum(steps) (numsteps_counter), [2] = #survivors (ray_counter), [3] = samples written.
-// Exclusive prefix sums over the rays, tile by tile (1024 coalesced elements per tile, wave shuffles + one LDS hop):
-//   base  = samples before the ray (numsteps prefix, testbed_nerf.cu:1344-1346)          -> counters[0] = total
-//   slot  = index among the rays that keep their samples (0xffffffff = dropped)            -> counters[2], counters[3]
-//   base1 = offset of the ray's first-round samples in idx1 (two-round network evaluation) -> fwd_counts[0]
+// inclusive prefix sum over the 64 lanes of a wavefront
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, const uint32_t lane) {
 #pragma unroll
 	for (uint32_t off = 1; off < 64; off <<= 1) {
@@ -1359,81 +1354,15 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, const uint32
 	return v;
 }
 
-__global__ __launch_bounds__(1024) void k_scan_rays(const uint32_t n, const uint32_t max_samples, const uint32_t* __restrict__ steps,
-                                                    uint32_t* __restrict__ base, uint32_t* __restrict__ slot, uint32_t* __restrict__ counters,
-                                                    const uint32_t k1, uint32_t* __restrict__ base1, uint32_t* __restrict__ fwd_counts) {
-	__shared__ uint32_t wsum[4][16];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	constexpr uint32_t E = 4; // consecutive rays per thread (one 16-byte load): 4096 per tile; 16 per thread measured slower (strided lanes)
-	uint32_t carry[4] = {0, 0, 0, 0}; // steps, kept rays, kept samples, first-round samples
-	// the next tile's counts are requested before this tile's scans: late in training the batch is ~100 k rays = 23 tiles, and one
-	// workgroup cannot hide a global load behind anything else
-	uint32_t st_next[E];
-#pragma unroll
-	for (uint32_t e = 0; e < E; ++e) st_next[e] = tid * E + e < n ? steps[tid * E + e] : 0u;
-	for (uint32_t t0 = 0; t0 < n; t0 += 1024 * E) {
-		const uint32_t i0 = t0 + tid * E;
-		uint32_t st[E];
-#pragma unroll
-		for (uint32_t e = 0; e < E; ++e) st[e] = st_next[e];
-#pragma unroll
-		for (uint32_t e = 0; e < E; ++e) st_next[e] = i0 + 1024 * E + e < n ? steps[i0 + 1024 * E + e] : 0u;
-		// pass A: sample offsets
-		uint32_t mine = 0;
-#pragma unroll
-		for (uint32_t e = 0; e < E; ++e) mine += st[e];
-		const uint32_t inc = wave_inclusive_scan(mine, lane);
-		if (lane == 63) wsum[0][wave] = inc;
-		__syncthreads();
-		uint32_t wprefix = 0, ttotal = 0;
-#pragma unroll
-		for (uint32_t w = 0; w < 16; ++w) { const uint32_t x = wsum[0][w]; wprefix += w < wave ? x : 0u; ttotal += x; }
-		uint32_t run = carry[0] + wprefix + inc - mine;
-		uint32_t runs[E];
-		bool ok[E];
-		uint32_t v[3] = {0, 0, 0};
-#pragma unroll
-		for (uint32_t e = 0; e < E; ++e) {
-			runs[e] = run;
-			ok[e] = st[e] > 0 && run + st[e] <= max_samples; // testbed_nerf.cu:1348-1355
-			run += st[e];
-			v[0] += ok[e] ? 1u : 0u; v[1] += ok[e] ? st[e] : 0u; v[2] += ok[e] ? min(st[e], k1) : 0u;
-		}
-		// pass B: the three sums that depend on `ok`
-		uint32_t vi[3];
-#pragma unroll
-		for (int k = 0; k < 3; ++k) { vi[k] = wave_inclusive_scan(v[k], lane); if (lane == 63) wsum[1 + k][wave] = vi[k]; }
-		__syncthreads();
-		uint32_t pre[3] = {0, 0, 0}, tot[3] = {0, 0, 0};
-#pragma unroll
-		for (uint32_t w = 0; w < 16; ++w)
-#pragma unroll
-			for (int k = 0; k < 3; ++k) { const uint32_t x = wsum[1 + k][w]; pre[k] += w < wave ? x : 0u; tot[k] += x; }
-		uint32_t srun = carry[1] + pre[0] + vi[0] - v[0], frun = carry[3] + pre[2] + vi[2] - v[2];
-#pragma unroll
-		for (uint32_t e = 0; e < E; ++e) {
-			if (i0 + e < n) {
-				base[i0 + e] = runs[e];
-				slot[i0 + e] = ok[e] ? srun : 0xffffffffu;
-				if (k1) base1[i0 + e] = frun;
-			}
-			srun += ok[e] ? 1u : 0u;
-			frun += ok[e] ? min(st[e], k1) : 0u;
-		}
-		carry[0] += ttotal; carry[1] += tot[0]; carry[2] += tot[1]; carry[3] += tot[2];
-		__syncthreads(); // wsum is rewritten by the next tile
-	}
-	if (tid == 0) { counters[0] = carry[0]; counters[2] = carry[1]; counters[3] = carry[2]; fwd_counts[0] = carry[3]; fwd_counts[1] = 0; fwd_counts[2] = 0; fwd_counts[3] = 0; }
-}
-
-// The same scans with one workgroup per 4096-ray tile, for batches of tens of thousands of rays (one workgroup walks 23 tiles at
-// 94 k rays: 0.13 ms of a chain that the next kernels wait for): (1) tile sums of the sample counts, (2) offsets + which rays
-// keep their samples + tile sums of the three dependent counts, (3) slots. Integer work: bit-identical to k_scan_rays.
+// The scans over the rays work on tiles of 4096 rays, one workgroup each (k_scan_rays_chain, k_scan_compact_chain, the fused scan of k_loss_pass2_rays).
 constexpr uint32_t SCAN_TILE = 4096;
+// The largest cfg.max_rays_per_batch rnb_create accepts, and the tiles that makes: the one-launch scans exchange their tiles' sums with one lane per tile (chain_prefix)
+constexpr uint32_t MAX_RAYS_PER_BATCH = 1u << 18, SCAN_MAX_TILES = 64;
 // Workgroups of 256 threads, 16 rays per thread: beside the scatter kernels a CU rarely has the 16 free wavefront slots a
-// 1024-thread workgroup needs at once (k_scan_rays_base waited 45 us for them, measured), 4 are found at once.
+// 1024-thread workgroup needs at once (a scan of that shape waited 45 us for them, measured), 4 are found at once.
 constexpr uint32_t SCAN_WG = 256, SCAN_EPT = SCAN_TILE / SCAN_WG, SCAN_NW = SCAN_WG / 64;
-// exclusive prefix of `mine` over the NW wavefronts of the workgroup; `total` = sum over the workgroup
+// Exclusive prefix sum of `mine` over the threads of a workgroup of NW wavefronts (wave shuffles + one LDS hop through wsum[NW]); `total` = the workgroup's sum,
+// in every thread. Two barriers: wsum may be reused by the next call at once.
 template <uint32_t NW>
 __device__ __forceinline__ uint32_t block_exclusive_scan(const uint32_t mine, const uint32_t lane, const uint32_t wave, uint32_t* __restrict__ wsum, uint32_t& total) {
 	const uint32_t inc = wave_inclusive_scan(mine, lane);
@@ -1446,104 +1375,20 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(const uint32_t mine, co
 	total = tot;
 	return pre + inc - mine;
 }
-// sum of vals[0 .. count) (count <= 64), by the first wavefront; result in every thread of the workgroup
-__device__ __forceinline__ uint32_t tile_prefix(const uint32_t* __restrict__ vals, const uint32_t stride, const uint32_t count, const uint32_t tid, uint32_t* __restrict__ sh) {
-	if (tid < 64) {
-		uint32_t v = tid < count ? vals[(size_t)tid * stride] : 0u;
-#pragma unroll
-		for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-		if (tid == 0) *sh = v;
-	}
-	__syncthreads();
-	const uint32_t r = *sh;
-	__syncthreads();
-	return r;
-}
 
-__global__ __launch_bounds__(SCAN_WG) void k_scan_rays_sums(const uint32_t n, const uint32_t* __restrict__ steps, uint32_t* __restrict__ tile_sum) {
-	__shared__ uint32_t wsum[16];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const uint32_t i0 = blockIdx.x * SCAN_TILE + tid * SCAN_EPT;
-	uint32_t mine = 0;
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) mine += i0 + e < n ? steps[i0 + e] : 0u;
-	uint32_t total;
-	(void)block_exclusive_scan<SCAN_NW>(mine, lane, wave, wsum, total);
-	if (tid == 0) tile_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(SCAN_WG) void k_scan_rays_base(const uint32_t n, const uint32_t max_samples, const uint32_t k1, const uint32_t* __restrict__ steps,
-                                                         const uint32_t* __restrict__ tile_sum, uint32_t* __restrict__ base, uint32_t* __restrict__ tile_v, uint32_t* __restrict__ counters) {
-	__shared__ uint32_t wsum[16];
-	__shared__ uint32_t sh;
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const uint32_t tile_base = tile_prefix(tile_sum, 1, blockIdx.x, tid, &sh);
-	const uint32_t i0 = blockIdx.x * SCAN_TILE + tid * SCAN_EPT;
-	uint32_t st[SCAN_EPT], mine = 0;
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) { st[e] = i0 + e < n ? steps[i0 + e] : 0u; mine += st[e]; }
-	uint32_t total;
-	uint32_t run = tile_base + block_exclusive_scan<SCAN_NW>(mine, lane, wave, wsum, total);
-	uint32_t v[3] = {0, 0, 0};
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) {
-		if (i0 + e < n) base[i0 + e] = run;
-		const bool ok = st[e] > 0 && run + st[e] <= max_samples; // testbed_nerf.cu:1348-1355
-		run += st[e];
-		v[0] += ok ? 1u : 0u; v[1] += ok ? st[e] : 0u; v[2] += ok ? min(st[e], k1) : 0u;
-	}
-#pragma unroll
-	for (int k = 0; k < 3; ++k) {
-		uint32_t t;
-		(void)block_exclusive_scan<SCAN_NW>(v[k], lane, wave, wsum, t);
-		if (tid == 0) tile_v[blockIdx.x * 3 + k] = t;
-	}
-	if (blockIdx.x == gridDim.x - 1 && tid == 0) counters[0] = tile_base + total; // numsteps_counter
-}
-
-__global__ __launch_bounds__(SCAN_WG) void k_scan_rays_slots(const uint32_t n, const uint32_t max_samples, const uint32_t k1, const uint32_t* __restrict__ steps,
-                                                          const uint32_t* __restrict__ base, const uint32_t* __restrict__ tile_v, uint32_t* __restrict__ slot,
-                                                          uint32_t* __restrict__ base1, uint32_t* __restrict__ counters, uint32_t* __restrict__ fwd_counts) {
-	__shared__ uint32_t wsum[16];
-	__shared__ uint32_t sh;
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	uint32_t pre[3];
-#pragma unroll
-	for (int k = 0; k < 3; ++k) pre[k] = tile_prefix(tile_v + k, 3, blockIdx.x, tid, &sh);
-	const uint32_t i0 = blockIdx.x * SCAN_TILE + tid * SCAN_EPT;
-	uint32_t st[SCAN_EPT], v0 = 0, v2 = 0, v1 = 0;
-	bool ok[SCAN_EPT];
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) {
-		st[e] = i0 + e < n ? steps[i0 + e] : 0u;
-		const uint32_t b = i0 + e < n ? base[i0 + e] : 0u;
-		ok[e] = st[e] > 0 && b + st[e] <= max_samples;
-		v0 += ok[e] ? 1u : 0u; v1 += ok[e] ? st[e] : 0u; v2 += ok[e] ? min(st[e], k1) : 0u;
-	}
-	uint32_t t0, t1, t2;
-	uint32_t srun = pre[0] + block_exclusive_scan<SCAN_NW>(v0, lane, wave, wsum, t0);
-	uint32_t frun = pre[2] + block_exclusive_scan<SCAN_NW>(v2, lane, wave, wsum, t2);
-	(void)block_exclusive_scan<SCAN_NW>(v1, lane, wave, wsum, t1);
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) {
-		if (i0 + e < n) {
-			slot[i0 + e] = ok[e] ? srun : 0xffffffffu;
-			if (k1) base1[i0 + e] = frun;
-		}
-		srun += ok[e] ? 1u : 0u;
-		frun += ok[e] ? min(st[e], k1) : 0u;
-	}
-	if (blockIdx.x == gridDim.x - 1 && tid == 0) { counters[2] = pre[0] + t0; counters[3] = pre[1] + t1; fwd_counts[0] = pre[2] + t2; fwd_counts[1] = 0; fwd_counts[2] = 0; fwd_counts[3] = 0; }
-}
-
-// The three tiled kernels above in ONE launch. A tile's sums do not depend on the tiles in front of it, so every workgroup publishes them at once
-// (value + the launch's ticket in one 64-bit word) and then adds up the words of the tiles in front of it as they arrive -- no chain from tile to
-// tile, two such exchanges per launch (the sample offsets first, then the three sums that depend on which rays fit). Workgroups start in index
-// order, so a workgroup that waits only waits for workgroups that are already running. The words are polled with returning atomics: a load, agent
-// scope included, is answered by the polling XCD's own L2 once the line is there (profiles/r03_ab_tickets.txt). Integer work: the numbers of
-// k_scan_rays. Why: the scans sit in the middle of the chain march -> scans -> write that the next step's network evaluation waits for; as one
-// 1024-thread workgroup (small batches) the scan waited for 16 free wavefront slots on one CU beside the scatter (65 us for 21 us of work), as three
-// launches (large batches) it took 48 us for 23.
+// k_scan_rays_chain: the exclusive prefix sums over the rays between the march and the writer (testbed_nerf.cu:1344-1355), one workgroup per 4096-ray tile, ONE launch:
+//   base  = samples in front of the ray (prefix of steps)                                     -> counters[0] = their total (numsteps_counter)
+//   slot  = index among the rays that keep their samples -- steps > 0 and base + steps <= max_samples -- or 0xffffffff (dropped)
+//                                                                                              -> counters[2] = rays kept (ray_counter), counters[3] = samples kept
+//   base1 = offset of the ray's first-round samples, min(steps, k1), in idx1 (two-round network evaluation) -> fwd_counts[0]; fwd_counts[1..3] = 0
+// A tile's sums do not depend on the tiles in front of it, so every workgroup publishes them at once (value + the launch's ticket in one 64-bit word) and then
+// adds up the words of the tiles in front of it as they arrive -- no chain from tile to tile. Workgroups start in index order, so a workgroup that waits only
+// waits for workgroups that are already running. A tile polls one lane per tile in front of it, hence at most SCAN_MAX_TILES = 64 tiles:
+static_assert(MAX_RAYS_PER_BATCH == SCAN_MAX_TILES * SCAN_TILE && SCAN_MAX_TILES <= 64, "a chain tile polls the tiles in front of it with one lane of a wavefront each");
+// History: the words were first polled with returning atomics -- a load, agent scope included, is answered by the polling XCD's own L2 once the line is there
+// (profiles/r03_ab_tickets.txt). The scans sit in the middle of the chain march -> scans -> write that the next step's network evaluation waits for; as one
+// 1024-thread workgroup (small batches) the scan waited for 16 free wavefront slots on one CU beside the scatter (65 us for 21 us of work), as three launches with a
+// workgroup per tile (large batches) it took 48 us for 23. Both forms are gone; this launch serves every batch size.
 struct ScanChainArgs {
 	uint32_t n, max_samples, k1;
 	const uint32_t* steps;
@@ -1697,7 +1542,8 @@ __global__ __launch_bounds__(SCAN_WG) void k_scan_rays_chain(const ScanChainArgs
 	}
 }
 
-// The compaction offsets (k_scan_compact_sums + k_scan_compact_offsets) the same way, one exchange: on the critical stream of the large-batch regime.
+// Exclusive prefix sums of ncomp (compacted samples per ray; zero beyond the kept rays) over the rays, one workgroup per 4096-ray tile, one exchange of the tiles' sums
+// (chain_prefix): cbase = compacted samples in front of the ray, counters[1] = their total (numsteps_counter_compacted). On the critical stream of the large-batch regime.
 __global__ __launch_bounds__(SCAN_WG) void k_scan_compact_chain(const uint32_t n, const uint32_t* __restrict__ ncomp, uint32_t* __restrict__ cbase, uint32_t* __restrict__ counters,
                                                              unsigned long long* __restrict__ words, const uint32_t ticket, uint32_t* __restrict__ error) {
 	__shared__ uint32_t wsum[16];
@@ -1768,7 +1614,7 @@ struct LossArgs {
 	uint32_t *ray_of, *slot_of;
 	// ... which also pad the compacted batch (fill_rollover*, common_device.h:514-535) and -- in the training step -- reduce and publish the step's loss sums
 	// (what k_rollover / k_reduce_losses_rollover do behind the one-launch forms): a kernel boundary on the critical stream costs 6-9 us here
-	// ... and form the compaction offsets themselves (k_scan_compact* of the one-launch forms): scan_words != null
+	// ... and form the compaction offsets themselves (as k_scan_compact_chain does for the one-launch forms): scan_words != null
 	unsigned long long* scan_words; // [64]: ticket << 32 | kept samples of a 4096-ray tile, published by the tile's first workgroup
 	uint32_t scan_ticket;
 	uint32_t* scan_error;  // mapped host word: a wait gave up
@@ -2170,35 +2016,6 @@ __global__ __launch_bounds__(1024) void k_scan_compact(const uint32_t n_max, con
 		__syncthreads();
 	}
 	if (tid == 0) counters[1] = carry;
-}
-
-// k_scan_compact with one workgroup per 4096-ray tile (large batches): tile sums, then offsets. ncomp is zero beyond the kept rays.
-__global__ __launch_bounds__(SCAN_WG) void k_scan_compact_sums(const uint32_t n, const uint32_t* __restrict__ ncomp, uint32_t* __restrict__ tile_sum) {
-	__shared__ uint32_t wsum[16];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const uint32_t i0 = blockIdx.x * SCAN_TILE + tid * SCAN_EPT;
-	uint32_t mine = 0;
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) mine += i0 + e < n ? ncomp[i0 + e] : 0u;
-	uint32_t total;
-	(void)block_exclusive_scan<SCAN_NW>(mine, lane, wave, wsum, total);
-	if (tid == 0) tile_sum[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(SCAN_WG) void k_scan_compact_offsets(const uint32_t n, const uint32_t* __restrict__ ncomp, const uint32_t* __restrict__ tile_sum,
-                                                               uint32_t* __restrict__ cbase, uint32_t* __restrict__ counters) {
-	__shared__ uint32_t wsum[16];
-	__shared__ uint32_t sh;
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-	const uint32_t tile_base = tile_prefix(tile_sum, 1, blockIdx.x, tid, &sh);
-	const uint32_t i0 = blockIdx.x * SCAN_TILE + tid * SCAN_EPT;
-	uint32_t v[SCAN_EPT], mine = 0;
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) { v[e] = i0 + e < n ? ncomp[i0 + e] : 0u; mine += v[e]; }
-	uint32_t total;
-	uint32_t run = tile_base + block_exclusive_scan<SCAN_NW>(mine, lane, wave, wsum, total);
-#pragma unroll
-	for (uint32_t e = 0; e < SCAN_EPT; ++e) { if (i0 + e < n) cbase[i0 + e] = run; run += v[e]; }
-	if (blockIdx.x == gridDim.x - 1 && tid == 0) counters[1] = tile_base + total; // numsteps_counter_compacted
 }
 
 // Pass 2 (testbed_nerf.cu:1836-2095).

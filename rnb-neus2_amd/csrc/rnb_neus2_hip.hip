@@ -1,6 +1,8 @@
 // rnb_neus2_hip.hip — C-ABI of include/rnb_neus2.h over the gfx950 kernels (host driver).
 // Host-side sequencing follows Testbed::train / train_nerf / train_nerf_step (src/testbed.cu:2776-2872,
 // src/testbed_nerf.cu:3560-4123). No CPU fallback: every entry point runs HIP kernels or fails.
+// One translation unit (tools/kernel_resources.sh and the guards of __graft_entry__.build() read ONE code object): the drivers of the inference tracer and of
+// the mesh stages, which take little from the training state, are the headers driver_render.hpp and driver_mesh.hpp, included once each at the end of this file.
 #include "kernels_net.cuh"
 #include "kernels_ray.cuh"
 #include "kernels_mesh.cuh"
@@ -41,10 +43,16 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
 		if (e_ != hipSuccess) return fail(RNB_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
 	} while (0)
 
+// A device array that is released with its owner (the context, a workspace). Not copyable; two buffers trade roles through swap().
 template <typename T>
 struct DevBuf {
 	T* p = nullptr;
 	size_t n = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf&) = delete;
+	DevBuf& operator=(const DevBuf&) = delete;
+	~DevBuf() { free(); }
+	void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
 	hipError_t alloc(size_t count) {
 		n = count;
 		if (count == 0) { p = nullptr; return hipSuccess; }
@@ -117,6 +125,18 @@ struct Profiler {
 
 static inline uint32_t ilog2(uint32_t v) { uint32_t r = 0; while (v > 1) { v >>= 1; ++r; } return r; }
 
+// rnb_render's workspace (kernels_render.cuh), sized for `cap` rays in flight and grown on demand: two ray arrays (compaction goes from one to the other),
+// the alive flags / their prefix sums and the scan's block sums, the tile's results, the round's network inputs and outputs (RENDER_MAX_N samples per ray),
+// and the counters {records to evaluate, hit pixels, samples (64 bits)}
+struct RenderWorkspace {
+	uint32_t cap = 0;
+	DevBuf<RenderRay> rays[2];
+	DevBuf<uint32_t> keep, scan, counts;
+	DevBuf<float> res, coords;
+	DevBuf<half_t> out;
+	void release_arrays() { rays[0].free(); rays[1].free(); keep.free(); scan.free(); res.free(); coords.free(); out.free(); cap = 0; } // (everything sized by `cap`; the counters stay)
+};
+
 struct rnb_ctx {
 	rnb_config cfg;
 	Profiler prof;
@@ -182,7 +202,7 @@ struct rnb_ctx {
 	DevBuf<float> chain_rec; // per marched-sample slot: the compositing recurrence's running values, left by pass 1 of the loss for pass 2 (LossArgs::chain_rec)
 	DevBuf<float> ray_setup, ray_dunnorm, ray_t;
 	DevBuf<double> loss_partial; // per-tile loss sums of large batches
-	DevBuf<uint32_t> ray_steps, ray_base, ray_slot, ncomp, cbase, scan_tiles; // scan_tiles: [64] tile sums + [64][3] dependent tile sums of the multi-workgroup ray scan
+	DevBuf<uint32_t> ray_steps, ray_base, ray_slot, ncomp, cbase;
 	// two-round network evaluation (step_front): head of every ray first, tails of the rays that need them second
 	DevBuf<uint32_t> ray_base1, idx1, idx2, fwd_counts;
 	DevBuf<unsigned long long> scan_words; // k_scan_rays_chain / k_scan_compact_chain: [64 tiles][4] sums with the launch's ticket, one block each
@@ -207,7 +227,7 @@ struct rnb_ctx {
 		uint32_t march_narrow_from = 18432; // RNB_MARCH_NARROW_FROM: rays per step from which the per-ray kernels switch to their large-batch forms
 		bool dp_order = false; // RNB_DP_FORCE_COLLECTIVES: scatter order of the data-parallel exchange even with one rank
 		bool loss_scan_fused_always = false; // RNB_LOSS_SCAN_FUSED=2 (tests): at every batch size
-		bool loss_scan_fused = true; // RNB_LOSS_SCAN_FUSED=0: the compaction offsets by k_scan_compact* in front of the two pass-2 launches (default: formed inside k_loss_pass2_rays)
+		bool loss_scan_fused = true; // RNB_LOSS_SCAN_FUSED=0: the compaction offsets by k_scan_compact / k_scan_compact_chain in front of the two pass-2 launches (default: formed inside k_loss_pass2_rays)
 		bool loss_flat = true; // RNB_LOSS_FLAT=0: pass 2 of the loss as one launch with 64 / 16 lanes per ray (default: k_loss_pass2_rays, then k_loss_pass2_samples with one lane per compacted sample; needs the chain records)
 		bool loss_chain_records = true; // RNB_LOSS_CHAIN_RECORDS=0: pass 2 of the loss replays the compositing recurrence itself instead of reading the running values pass 1 left
 		bool scatter_plain = false; // RNB_SCATTER_PLAIN=1: no LDS-privatised and no run-length scatter -- every corner of every level is its own L2 atomic, as in the reference; with
@@ -222,14 +242,7 @@ struct rnb_ctx {
 	} knobs;
 	DevBuf<RayLoss> ray_loss;
 	DevBuf<McTable> mc_table; // marching-cubes case table, uploaded on first use
-	// rnb_render's workspace (kernels_render.cuh), sized for render_cap rays in flight and grown on demand: two ray arrays (compaction goes from one to the other),
-	// the alive flags / their prefix sums and the scan's block sums, the tile's results, the round's network inputs and outputs (RENDER_MAX_N samples per ray),
-	// and the counters {records to evaluate, hit pixels, samples (64 bits)}
-	uint32_t render_cap = 0;
-	DevBuf<RenderRay> render_rays[2];
-	DevBuf<uint32_t> render_keep, render_scan, render_counts;
-	DevBuf<float> render_res, render_coords;
-	DevBuf<half_t> render_out;
+	RenderWorkspace render; // rnb_render's (driver_render.hpp)
 	// training scratch
 	DevBuf<half_t> fm;       // feature-major operand arrays
 	DevBuf<uint32_t> g12;
@@ -535,15 +548,15 @@ int update_density_grid_front(rnb_ctx* c, hipStream_t s, uint32_t n_uniform, uin
 	                    c->gs_pre.rng_state == c->density_grid_rng.state && c->gs_pre.rng_inc == c->density_grid_rng.inc;
 	c->gs_pre.valid = false;
 	c->last_update_sorted = sorted;
-	if (sorted && c->tmp_alt_clear) std::swap(c->density_grid_tmp, c->density_grid_tmp_alt); // cleared behind the previous update, ordered by ev_gs below
+	if (sorted && c->tmp_alt_clear) c->density_grid_tmp.swap(c->density_grid_tmp_alt); // cleared behind the previous update, ordered by ev_gs below
 	else HIP_TRY(hipMemsetAsync(c->density_grid_tmp.p, 0, sizeof(float) * n_elements, s));
 	c->tmp_alt_clear = false;
 	if (sorted) { // generated after the previous update (pregenerate_grid_samples): the staging pair holds the reference's order, gs_sorted_* the cell order
 		HIP_TRY(hipStreamWaitEvent(s, c->ev_gs, 0));
-		std::swap(c->grid_sample_pos, c->gs_stage_pos); // RNB_BUF_GRID_SAMPLE_POS / _IDX: the samples of the LAST update, as always
-		std::swap(c->grid_sample_idx, c->gs_stage_idx);
-		std::swap(c->gs_sorted_pos, c->gs_eval_pos);     // the next pregenerate_grid_samples writes the other pair
-		std::swap(c->gs_sorted_idx, c->gs_eval_idx);
+		c->grid_sample_pos.swap(c->gs_stage_pos); // RNB_BUF_GRID_SAMPLE_POS / _IDX: the samples of the LAST update, as always
+		c->grid_sample_idx.swap(c->gs_stage_idx);
+		c->gs_sorted_pos.swap(c->gs_eval_pos);     // the next pregenerate_grid_samples writes the other pair
+		c->gs_sorted_idx.swap(c->gs_eval_idx);
 		c->density_grid_rng.advance();
 		c->density_grid_rng.advance();
 	} else {
@@ -628,6 +641,12 @@ static LossFlags loss_flags(const rnb_ctx* c) {
 	return F;
 }
 
+// The batch regime: from knobs.march_narrow_from rays per step on (late in training: many short rays) the per-ray kernels -- march writer, loss passes, compaction
+// scan, run-length scatter, loss reduction -- take their large-batch forms. (The march kernel itself has knobs.march_narrow on top: generate_training_samples.)
+static bool large_batch(const rnb_ctx* c, uint32_t n_rays) { return n_rays >= c->knobs.march_narrow_from; }
+// 4096-ray tiles of the scans (kernels_ray.cuh): one workgroup each, at most SCAN_MAX_TILES of them
+static uint32_t scan_tiles_of(uint32_t n_rays) { return (n_rays + SCAN_TILE - 1) / SCAN_TILE; }
+
 // Head length of the two-round network evaluation for a batch of n_rays rays. The results do not depend on it (tests/test_gpu_fullsize.py); the step time
 // does, sharply (tools/sweep_k1.sh, profiles/r04_sweep_k1.txt, ms/step of 200-step slices with a fixed head of 12 / 16 / 24 / 32 / 40 / 48 / 64):
 //   step 1000, 13 k rays: .755 .753 .728 .656 .621 .615 .620     step 2000, 48 k: .626 .608 .602 .617 .628 .644 .658
@@ -703,7 +722,7 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 	// kernel, which in turn wins below ~30 k rays (0.20 vs 0.30 ms at 14 k), where a ray per thread leaves the GPU to latency.
 	const bool sc = c->aabb.cone_angle == 0.f && c->aabb.max_cascade == 0; // one cascade, constant step: the specialised instances
 	const size_t march_lds = sc ? (size_t)(2 * COARSE_WORDS + 2 * a.n_blocks_lds) * sizeof(uint32_t) : 0;
-	if (c->knobs.march_narrow || n_rays >= c->knobs.march_narrow_from) {
+	if (c->knobs.march_narrow || large_batch(c, n_rays)) {
 		if (sc && c->knobs.march_skip && c->knobs.march_skip_narrow && a.lattice_ok) { // RNB_MARCH_SKIP_NARROW=1 (dropped, kept as an A/B knob): the thread-per-ray march minus the stretches that cannot hold a sample (kernels_ray.cuh: march_skip_narrow)
 			if (c->knobs.march_skip == 2) a.lattice_ok |= 2u;
 			hipLaunchKernelGGL(k_march_count_skip_narrow, dim3(blocks), dim3(128), march_lds + COARSE_WORDS * sizeof(uint32_t), s, a);
@@ -730,19 +749,12 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 	}
 	c->prof.mark(s, P_MARCH_COUNT);
 	if (wait_before_scans) HIP_TRY(hipStreamWaitEvent(s, wait_before_scans, 0)); // (launch_premarch: the previous step's second loss pass may still be reading what the scans and k_march_write overwrite)
-	const uint32_t n_scan_tiles = (n_rays + SCAN_TILE - 1) / SCAN_TILE;
-	if (n_scan_tiles <= 64) { // one launch, one workgroup per 4096-ray tile (k_scan_rays_chain)
+	{ // one launch, one workgroup per 4096-ray tile
 		ScanChainArgs q;
 		q.n = n_rays; q.max_samples = max_samples; q.k1 = a.k1; q.steps = c->ray_steps.p; q.base = c->ray_base.p; q.slot = c->ray_slot.p; q.base1 = c->ray_base1.p;
 		q.counters = c->counters.p; q.fwd_counts = c->fwd_counts.p; q.words = c->scan_words.p; q.words2 = c->scan_words.p + 2 * 64 * 4; q.ticket = ++c->scan_ticket; q.error = c->host_coarse_dev + 5;
-		hipLaunchKernelGGL(k_scan_rays_chain, dim3(n_scan_tiles), dim3(SCAN_WG), 0, s, q);
-	} else if (n_rays >= c->knobs.march_narrow_from) { // one workgroup per 4096-ray tile (<= 64 tiles) instead of one workgroup walking them
-		const uint32_t n_tiles = (n_rays + SCAN_TILE - 1) / SCAN_TILE;
-		hipLaunchKernelGGL(k_scan_rays_sums, dim3(n_tiles), dim3(SCAN_WG), 0, s, n_rays, c->ray_steps.p, c->scan_tiles.p);
-		hipLaunchKernelGGL(k_scan_rays_base, dim3(n_tiles), dim3(SCAN_WG), 0, s, n_rays, max_samples, a.k1, c->ray_steps.p, c->scan_tiles.p, c->ray_base.p, c->scan_tiles.p + 64, c->counters.p);
-		hipLaunchKernelGGL(k_scan_rays_slots, dim3(n_tiles), dim3(SCAN_WG), 0, s, n_rays, max_samples, a.k1, c->ray_steps.p, c->ray_base.p, c->scan_tiles.p + 64, c->ray_slot.p, c->ray_base1.p, c->counters.p, c->fwd_counts.p);
-	} else
-		hipLaunchKernelGGL(k_scan_rays, dim3(1), dim3(1024), 0, s, n_rays, max_samples, c->ray_steps.p, c->ray_base.p, c->ray_slot.p, c->counters.p, a.k1, c->ray_base1.p, c->fwd_counts.p);
+		hipLaunchKernelGGL(k_scan_rays_chain, dim3(scan_tiles_of(n_rays)), dim3(SCAN_WG), 0, s, q);
+	}
 	c->prof.mark(s, P_SCAN_RAYS);
 	if (wait_before_write) HIP_TRY(hipStreamWaitEvent(s, wait_before_write, 0)); // (rnb_ctx::tail_pending)
 	// A march generated ahead (rest_done) is written in two launches below 65 536 rays per step: what the first network evaluation reads (idx1, the heads' coordinates) in a first one,
@@ -752,7 +764,7 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 	for (uint32_t part = c->gen_split ? 1u : 0u; part <= (c->gen_split ? 2u : 0u); ++part) {
 		a.part = part;
 		const hipEvent_t ev = part == 1 ? done : nullptr; // otherwise the constants' launch carries the event
-		if (n_rays >= c->knobs.march_narrow_from) LAUNCH_EV((k_march_write<16, 256>), dim3((n_rays + 15) / 16), dim3(256), 0, s, ev, a);
+		if (large_batch(c, n_rays)) LAUNCH_EV((k_march_write<16, 256>), dim3((n_rays + 15) / 16), dim3(256), 0, s, ev, a);
 		else LAUNCH_EV((k_march_write<64, 256>), dim3((n_rays + 3) / 4), dim3(256), 0, s, ev, a);
 	}
 	LAUNCH_EV(k_ray_constants, dim3((n_rays + 63) / 64), dim3(64), 0, s, c->gen_split ? rest_done : done, a, c->ray_const.p); // one thread per kept ray
@@ -786,7 +798,7 @@ int compute_loss(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32_t n_rays_tot
 	c->pre.loss_cleared = false;
 	const uint32_t blocks = (n_rays + 3) / 4; // one wavefront per ray
 	// 16 lanes per ray (four rays per wavefront) from the batch size at which the march switches kernels: many short rays
-	const bool rows = n_rays >= c->knobs.march_narrow_from && !c->knobs.loss_wave_per_ray;
+	const bool rows = large_batch(c, n_rays) && !c->knobs.loss_wave_per_ray;
 	const uint32_t blocks_heads = rows ? (n_rays + LOSS1_WG / 16 - 1) / (LOSS1_WG / 16) : (n_rays + LOSS1_WG / 64 - 1) / (LOSS1_WG / 64);
 	auto launch_heads = [&]() {
 		if (rows) hipLaunchKernelGGL(k_loss_pass1_heads<16>, dim3(blocks_heads), dim3(LOSS1_WG), 0, s, a);
@@ -808,16 +820,12 @@ int compute_loss(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32_t n_rays_tot
 	c->prof.mark(s, P_LOSS_PASS1);
 	const bool flat = a.chain_rec && c->knobs.loss_flat;
 	// the offsets formed inside k_loss_pass2_rays: step 1000 (13 k rays, 4 tiles) 0.6065 -> 0.6015 ms/step; step 6000 (95 k rays, 24 tiles: 5.9 k workgroups polling) 0.6274 -> 0.6270: up to 8 tiles
-	if (flat && c->knobs.loss_scan_fused && (n_rays + SCAN_TILE - 1) / SCAN_TILE <= (c->knobs.loss_scan_fused_always ? 64u : 8u)) {
+	if (flat && c->knobs.loss_scan_fused && scan_tiles_of(n_rays) <= (c->knobs.loss_scan_fused_always ? SCAN_MAX_TILES : 8u)) {
 		a.scan_words = c->scan_words.p + 64 * 4; a.scan_ticket = ++c->scan_ticket; a.scan_error = c->host_coarse_dev + 6; a.scan_total = c->counters.p + 1;
-	} else if (n_rays >= c->knobs.march_narrow_from && (n_rays + SCAN_TILE - 1) / SCAN_TILE <= 64) {
-		hipLaunchKernelGGL(k_scan_compact_chain, dim3((n_rays + SCAN_TILE - 1) / SCAN_TILE), dim3(SCAN_WG), 0, s, n_rays, c->ncomp.p, c->cbase.p, c->counters.p,
+	} else if (large_batch(c, n_rays)) {
+		hipLaunchKernelGGL(k_scan_compact_chain, dim3(scan_tiles_of(n_rays)), dim3(SCAN_WG), 0, s, n_rays, c->ncomp.p, c->cbase.p, c->counters.p,
 		                   c->scan_words.p + 64 * 4, ++c->scan_ticket, c->host_coarse_dev + 6);
-	} else if (n_rays >= c->knobs.march_narrow_from) {
-		const uint32_t n_tiles = (n_rays + SCAN_TILE - 1) / SCAN_TILE;
-		hipLaunchKernelGGL(k_scan_compact_sums, dim3(n_tiles), dim3(SCAN_WG), 0, s, n_rays, c->ncomp.p, c->scan_tiles.p + 256);
-		hipLaunchKernelGGL(k_scan_compact_offsets, dim3(n_tiles), dim3(SCAN_WG), 0, s, n_rays, c->ncomp.p, c->scan_tiles.p + 256, c->cbase.p, c->counters.p);
-	} else
+	} else // small batches without the fused form (RNB_LOSS_SCAN_FUSED=0, RNB_LOSS_FLAT=0, RNB_LOSS_CHAIN_RECORDS=0): its comparator, one workgroup
 		hipLaunchKernelGGL(k_scan_compact, dim3(1), dim3(1024), 0, s, n_rays, c->ncomp.p, c->cbase.p, c->counters.p);
 	c->prof.mark(s, P_SCAN_COMPACT);
 	if (flat) { // at every batch size (step 1000, 12 k long rays: 0.6247 -> 0.6189 ms/step; step 2000: 0.6216 -> 0.6100; step 6000: 0.6526 -> 0.6367)
@@ -1010,7 +1018,7 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 		plan.wg_start[plan.n] = wg;
 		const uint32_t cap_rl = scatter_cap ? (uint32_t)c->n_cus * scatter_cap : wg;
 		// operands staged in LDS while the batch is few long rays (the regime of the A-B-C scatter order), loaded inside the walk from there on (profiles/r05_ab_scatter_rl_staged.txt)
-		const bool staged = c->cur_n_rays != 0 && c->cur_n_rays < c->knobs.march_narrow_from;
+		const bool staged = c->cur_n_rays != 0 && !large_batch(c, c->cur_n_rays);
 		if (fixed) {
 			LAUNCH_EVF(k_grid_scatter_quad_rl_fixed, dim3(std::min(wg, cap_rl)), dim3(256), 0, st, nullptr, sc_flags(), c->meta(), sa, e_c, plan);
 			narrow(st, done, e_c, l_fine);
@@ -1055,7 +1063,7 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 		// Order of the groups by batch shape (round 4, ms/step over 160 steps, one box, B-A1-A2-C / A1-A2-B-C / A-B-C): step 1000, 14 k rays: 0.6446 / 0.6473 / 0.6325;
 		// 1200, 18.5 k: 0.6435 / 0.6594 / 0.6394; 1400, 24 k: 0.6304 / 0.6324 / 0.6388; 1800, 41 k: 0.6132 / 0.6142 / 0.6161; 6000, 94 k: 0.6452 / 0.6482 / 0.6470
 		// (profiles/r04_sweep_scatter_order.txt): the fine levels first and in one launch while the batch is few long rays (the regime of the 16-lanes-per-ray march).
-		c->sc.order = (!c->sc.dp && c->cur_n_rays < c->knobs.march_narrow_from && !split) ? 2 : 0; // (albedo mode, step 1000: 0.763 with A-B-C vs 0.755 with B-A1-A2-C: its march is held behind the training kernels)
+		c->sc.order = (!c->sc.dp && !large_batch(c, c->cur_n_rays) && !split) ? 2 : 0; // (albedo mode, step 1000: 0.763 with A-B-C vs 0.755 with B-A1-A2-C: its march is held behind the training kernels)
 		if (c->sc.order == 0) { // B, A1, A2 (, C)
 			launch_b(s, c->ev_sc[0]);
 			launch_a(s, c->ev_sc[1], l_fine, a_mid);
@@ -1322,25 +1330,15 @@ int rnb_destroy(rnb_ctx* c) try {
 		if (hipMemcpy(h, c->march_stats.p, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[0])
 			fprintf(stderr, "k_march_count_skip: %llu wavefronts, %.2f loop iterations each; %llu rays: %.3f skipped at least once, %.3f ended early, %.5f start-overs per ray, %.3f rounds per ray looking for a re-entry cell\n",
 			        h[0], (double)h[1] / h[0], h[2], (double)h[3] / h[2], (double)h[6] / h[2], (double)h[4] / h[2], (double)h[5] / h[2]);
-		c->march_stats.free();
 	}
-	c->opt_rec.free(); c->params_fp32.free(); c->grads.free(); c->grads16.free(); c->grads_fixed.free(); c->adam_m.free(); c->adam_v.free(); c->params_fp16.free(); c->params_ema.free(); c->adam_steps.free(); c->adam_lr_table.free();
-	c->density_grid.free(); c->density_grid_tmp.free(); c->density_grid_tmp_alt.free(); c->density_mean.free(); c->mean_partial.free(); c->loss_sums.free(); c->bitfield.free(); c->coarse_bits.free(); c->coarse_count.free();
-	c->grid_sample_pos.free(); c->grid_sample_idx.free(); c->views.free(); c->pixels.free();
-	c->gs_sorted_pos.free(); c->gs_sorted_idx.free(); c->gs_stage_pos.free(); c->gs_stage_idx.free(); c->gs_hist.free(); c->gs_range.free(); c->gs_eval_pos.free(); c->gs_eval_idx.free();
-	c->ray_indices.free(); c->numsteps.free(); c->counters.free(); c->rays.free(); c->coords.free(); c->coords_compacted.free();
-	c->loss.free(); c->mlp_out.free(); c->chain_rec.free(); c->ray_grad.free(); c->ray_of.free(); c->slot_of.free(); c->wg_partial.free(); c->dloss_dout.free();
-	c->wimg_fwd.free(); c->wimg_fbs.free(); c->wimg_train.free(); c->wimg_rgb.free(); c->cin_eval.free(); c->dcin.free(); c->rgb_out_scratch.free(); c->src_slot.free(); c->ray_const.free(); c->ray_base1.free(); c->scan_words.free(); c->idx1.free(); c->idx2.free(); c->fwd_counts.free(); c->unfinished.free();
-	c->ray_setup.free(); c->ray_t.free(); c->ray_dunnorm.free(); c->ray_steps.free(); c->ray_base.free(); c->ray_slot.free(); c->ncomp.free(); c->cbase.free(); c->scan_tiles.free(); c->loss_partial.free(); c->ray_loss.free();
-	c->render_rays[0].free(); c->render_rays[1].free(); c->render_keep.free(); c->render_scan.free(); c->render_counts.free(); c->render_res.free(); c->render_coords.free(); c->render_out.free();
-	c->mc_table.free(); c->fm.free(); c->g12.free(); c->srec.free(); c->var_partial.free(); c->dw_partial.free();
 	c->prof.destroy();
 	if (c->s_march) { (void)hipStreamSynchronize(c->s_march); (void)hipStreamDestroy(c->s_march); }
 	for (hipStream_t st : {c->s_dw, c->s_adam}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
 	for (hipEvent_t e : {c->ev_loss, c->ev_march, c->ev_fb, c->ev_dw, c->ev_adam, c->ev_tail, c->ev_march_rest, c->ev_all, c->ev_grid, c->ev_gs, c->ev_sc[0], c->ev_sc[1], c->ev_sc[2]}) if (e) (void)hipEventDestroy(e);
-	if (c->host_rb) (void)hipHostFree(c->host_rb);
-	if (c->host_coarse) (void)hipHostFree(c->host_coarse);
-	delete c;
+	void *host_rb = c->host_rb, *host_coarse = c->host_coarse;
+	delete c; // the device buffers go with it (DevBuf); the first hipFree waits for the device, as it did in front of the two mapped host blocks before
+	if (host_rb) (void)hipHostFree(host_rb);
+	if (host_coarse) (void)hipHostFree(host_coarse);
 	return RNB_OK;
 } RNB_GUARD
 
@@ -1351,7 +1349,7 @@ int rnb_create(const rnb_config* cfg, rnb_ctx** out) try {
 	if (cfg->base_resolution < 2) return fail(RNB_ERR_INVALID, "base_resolution must be >= 2");
 	if (cfg->aabb_scale == 0 || (cfg->aabb_scale & (cfg->aabb_scale - 1)) != 0 || cfg->aabb_scale > 128) return fail(RNB_ERR_INVALID, "aabb_scale must be a power of two <= 128");
 	if (cfg->target_batch_size == 0 || cfg->target_batch_size % 128 != 0) return fail(RNB_ERR_INVALID, "target_batch_size must be a positive multiple of 128");
-	if (cfg->max_rays_per_batch == 0 || cfg->max_rays_per_batch > (1u << 18)) return fail(RNB_ERR_INVALID, "max_rays_per_batch must be in [1, 2^18]");
+	if (cfg->max_rays_per_batch == 0 || cfg->max_rays_per_batch > MAX_RAYS_PER_BATCH) return fail(RNB_ERR_INVALID, "max_rays_per_batch must be in [1, 2^18]");
 	if (cfg->world_size == 0 || cfg->rank >= cfg->world_size) return fail(RNB_ERR_INVALID, "bad rank/world_size");
 	if (cfg->accumulate > RNB_ACCUM_HALF) return fail(RNB_ERR_INVALID, "accumulate must be RNB_ACCUM_FP32 or RNB_ACCUM_HALF");
 	if (cfg->deterministic > 1) return fail(RNB_ERR_INVALID, "deterministic must be 0 or 1");
@@ -1412,7 +1410,7 @@ int rnb_create(const rnb_config* cfg, rnb_ctx** out) try {
 	ALLOC(c->coords, (size_t)B * 16 * 7); ALLOC(c->mlp_out, (size_t)B * 16 * 16); ALLOC(c->chain_rec, (size_t)B * 16 * CHAIN_REC_FLOATS); ALLOC(c->ray_grad, (size_t)maxr * 16); ALLOC(c->ray_of, B); ALLOC(c->slot_of, B); ALLOC(c->wg_partial, ((size_t)maxr + 15) / 16 * 3); ALLOC(c->dloss_dout, (size_t)B * 16); ALLOC(c->coords_compacted, (size_t)B * 7);
 	ALLOC(c->loss, (size_t)maxr * 3); c->ek_loss = c->loss.p + maxr; c->mask_loss = c->loss.p + (size_t)maxr * 2;
 	ALLOC(c->ray_setup, (size_t)maxr * 8); ALLOC(c->ray_t, (size_t)maxr * RNB_MAX_STEPS); ALLOC(c->ray_dunnorm, (size_t)maxr * 3); ALLOC(c->ray_steps, maxr); ALLOC(c->ray_base, maxr); ALLOC(c->ray_slot, maxr);
-	ALLOC(c->scan_tiles, 256 + 64); ALLOC(c->loss_partial, 64 * 3);
+	ALLOC(c->loss_partial, 64 * 3);
 	ALLOC(c->ncomp, maxr); ALLOC(c->cbase, maxr); ALLOC(c->ray_loss, maxr);
 	ALLOC(c->wimg_fwd, W_FWD_END); ALLOC(c->wimg_fbs, SWF_END); ALLOC(c->wimg_train, W_TRAIN_END); ALLOC(c->wimg_rgb, RW_END);
 	ALLOC(c->ray_const, (size_t)maxr * RAY_CONST_FLOATS); ALLOC(c->ray_base1, maxr); ALLOC(c->scan_words, 3 * 64 * 4); ALLOC(c->unfinished, maxr); ALLOC(c->fwd_counts, 4); ALLOC(c->idx1, (size_t)B * 16); ALLOC(c->idx2, (size_t)B * 16);
@@ -1787,172 +1785,6 @@ int rnb_forward_infer(rnb_ctx* c, void* stream, const float* coords, uint32_t n,
 	return launch_forward(c, as_stream(stream), coords, nullptr, n, reinterpret_cast<half_t*>(out), inference != 0);
 } RNB_GUARD
 
-// ---- mesh extraction (src/testbed_nerf.cu:4218-4269, src/marching_cubes.cu:276-430, 794-822) ----
-int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float lattice_min, float lattice_max, float* out, int inference) try {
-	if (!c || !res || !out) return fail(RNB_ERR_INVALID, "null argument");
-	if (!res[0] || !res[1] || !res[2]) return fail(RNB_ERR_INVALID, "empty lattice");
-	hipStream_t s = as_stream(stream);
-	const uint64_t n = (uint64_t)res[0] * res[1] * res[2];
-	const uint32_t batch = 1u << 22; // lattice points per network launch (the reference: 2^20 per call, same arithmetic per point)
-	float* pos = nullptr;
-	half_t* val = nullptr;
-	if (hipMalloc((void**)&pos, (size_t)batch * 12) != hipSuccess || hipMalloc((void**)&val, (size_t)batch * 2) != hipSuccess) {
-		if (pos) (void)hipFree(pos);
-		return fail(RNB_ERR_NOMEM, "hipMalloc failed for the lattice batch");
-	}
-	const float diag = c->aabb.mx - c->aabb.mn;
-	int rc = RNB_OK;
-	for (uint64_t off = 0; off < n && rc == RNB_OK; off += batch) {
-		const uint32_t nb = (uint32_t)std::min<uint64_t>(batch, n - off);
-		hipLaunchKernelGGL(k_lattice_positions, dim3((nb + 255) / 256), dim3(256), 0, s, off, nb, res[0], res[1], res[2], lattice_min, lattice_max - lattice_min, c->aabb.mn, diag, pos);
-		rc = launch_point_query(c, s, pos, nb, val, nullptr, nullptr, 0, inference != 0);
-		if (rc != RNB_OK) break;
-		hipLaunchKernelGGL(k_half_to_float, dim3((nb + 255) / 256), dim3(256), 0, s, val, out + off, nb);
-		if (hipGetLastError() != hipSuccess) rc = fail(RNB_ERR_DEVICE, "rnb_sdf_lattice: kernel launch failed");
-	}
-	hipError_t e = hipStreamSynchronize(s);
-	(void)hipFree(pos); (void)hipFree(val);
-	if (rc != RNB_OK) return rc;
-	if (e != hipSuccess) return fail(RNB_ERR_DEVICE, std::string("rnb_sdf_lattice: ") + hipGetErrorString(e));
-	return RNB_OK;
-} RNB_GUARD
-
-// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster) ----
-extern "C++" {
-namespace {
-// elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
-uint64_t scan_scratch_elems(uint64_t n) {
-	uint64_t total = 0;
-	do { n = (n + 1023) / 1024; total += n; } while (n > 1);
-	return total;
-}
-// in-place exclusive prefix sums of n counts (device), total to *total_out; `scratch` holds scan_scratch_elems(n) uint32 (allocated once per
-// call and shared by its scans)
-int scan_exclusive(uint32_t* data, uint64_t n, hipStream_t s, uint32_t* total_out, uint32_t* scratch) {
-	std::vector<uint32_t*> levels{data};
-	std::vector<uint64_t> sizes{n};
-	while (true) {
-		const uint64_t nb = (sizes.back() + 1023) / 1024;
-		uint32_t* sums = scratch;
-		scratch += nb;
-		hipLaunchKernelGGL(k_scan_blocks, dim3((uint32_t)nb), dim3(1024), 0, s, levels.back(), sizes.back(), sums);
-		levels.push_back(sums); sizes.push_back(nb);
-		if (nb == 1) break;
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(total_out, levels.back(), 4, hipMemcpyDeviceToHost, s));
-	// levels.back() holds one value (the total); every level below gets its block offsets added, top-down
-	for (size_t k = levels.size() - 1; k >= 2; --k) { /* levels[k-1] was scanned by the launch that produced levels[k]; add it to levels[k-2] */
-		hipLaunchKernelGGL(k_scan_add, dim3((uint32_t)sizes[k - 1]), dim3(1024), 0, s, levels[k - 2], sizes[k - 2], levels[k - 1]);
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipStreamSynchronize(s));
-	return RNB_OK;
-}
-// Phase one of a count / write kernel pair: the <false> instantiation leaves one count per workgroup in wg; they become the workgroups' exclusive offsets, their sum goes
-// to *total (synchronises). The write launch stays with the caller, who allocates for the total in between.
-template <typename K, typename... A>
-int count_and_scan(hipStream_t s, uint32_t n_wg, uint32_t* wg, uint32_t* scratch, uint32_t* total, K count_kernel, A... args) {
-	hipLaunchKernelGGL(count_kernel, dim3(n_wg), dim3(MC_WG), 0, s, args...);
-	HIP_TRY(hipGetLastError());
-	return scan_exclusive(wg, n_wg, s, total, scratch);
-}
-
-// The device memory of one mesh call: what is still held when the object goes out of scope is released; bytes held now and at the peak.
-struct MeshWorkspace {
-	std::vector<std::pair<void*, size_t>> held;
-	size_t cur = 0, peak = 0;
-	template <typename T>
-	bool alloc(T** p, size_t count) {
-		*p = nullptr;
-		const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-		if (hipMalloc((void**)p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-		held.emplace_back((void*)*p, bytes);
-		cur += bytes; peak = std::max(peak, cur);
-		return true;
-	}
-	template <typename T>
-	void release(T*& p) { // free now
-		for (auto& h : held) if (h.first == (void*)p && p) { (void)hipFree(h.first); cur -= h.second; h.first = nullptr; }
-		p = nullptr;
-	}
-	void* keep(void* p) { // the caller owns it from here on (it still counts as held)
-		for (auto& h : held) if (h.first == p) h.first = nullptr;
-		return p;
-	}
-	~MeshWorkspace() { for (auto& h : held) if (h.first) (void)hipFree(h.first); }
-};
-
-// What rnb_mesh_clean, rnb_mesh_simplify and rnb_mesh_distance (which has no output mesh and hands in one it discards) ask of their input mesh, said in the entry
-// point's name; *out is zeroed as soon as it is known not to be the input.
-int check_mesh_input(const char* name, const rnb_mesh* in, rnb_mesh* out) {
-	const std::string n(name);
-	if (in == out) return fail(RNB_ERR_INVALID, n + ": in and out must be different objects");
-	std::memset(out, 0, sizeof(*out));
-	if (in->n_indices % 3u) return fail(RNB_ERR_INVALID, n + ": n_indices is not a multiple of 3");
-	if ((in->n_verts && !in->verts) || (in->n_indices && !in->indices)) return fail(RNB_ERR_INVALID, n + ": null vertex or index buffer");
-	if (in->n_indices && in->n_verts == 0) return fail(RNB_ERR_INVALID, n + ": an index is out of range (the mesh has no vertices)");
-	return RNB_OK;
-}
-// The output mesh of a stage, held by the workspace: nvo vertices with the attributes asked for, nto triangles (a count of 0 still gets a buffer: MeshWorkspace::alloc).
-bool alloc_mesh(MeshWorkspace& ws, rnb_mesh* m, uint32_t nvo, uint32_t nto, bool has_colors, bool has_normals) {
-	std::memset(m, 0, sizeof(*m));
-	m->n_verts = nvo; m->n_indices = nto * 3u;
-	return ws.alloc(&m->verts, (size_t)nvo * 3) && ws.alloc(&m->indices, (size_t)nto * 3) && (!has_colors || ws.alloc(&m->colors, (size_t)nvo * 3)) && (!has_normals || ws.alloc(&m->normals, (size_t)nvo * 3));
-}
-// *out = m, whose buffers the caller owns from here on.
-void hand_over(MeshWorkspace& ws, const rnb_mesh& m, rnb_mesh* out) {
-	*out = m;
-	ws.keep(m.verts); ws.keep(m.indices); ws.keep(m.colors); ws.keep(m.normals);
-}
-} // namespace
-} // extern "C++"
-
-// the marching-cubes case table of host/mesh.hpp on the device, uploaded on first use
-static int ensure_mc_table(rnb_ctx* c) {
-	if (c->mc_table.p) return RNB_OK;
-	static const mesh::Tables T;
-	std::vector<McTable> h(1);
-	for (int m = 0; m < 256; ++m) {
-		int k = 0;
-		for (; T.tri[m][k] >= 0; ++k) h[0].tri[m][k] = T.tri[m][k];
-		h[0].n[m] = (uint8_t)k;
-		for (; k < 40; ++k) h[0].tri[m][k] = -1;
-	}
-	if (c->mc_table.alloc(1) != hipSuccess) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the case table");
-	HIP_TRY(hipMemcpy(c->mc_table.p, h.data(), sizeof(McTable), hipMemcpyHostToDevice));
-	return RNB_OK;
-}
-
-int rnb_marching_cubes(rnb_ctx* c, void* stream, const float* density, const uint32_t res[3], const float aabb_min[3], const float aabb_max[3], float thresh,
-                       float** verts_out, uint32_t** indices_out, uint32_t* n_verts, uint32_t* n_indices) try {
-	if (!c || !density || !res || !aabb_min || !aabb_max || !verts_out || !indices_out || !n_verts || !n_indices) return fail(RNB_ERR_INVALID, "null argument");
-	*verts_out = nullptr; *indices_out = nullptr; *n_verts = 0; *n_indices = 0;
-	const uint64_t res3 = (uint64_t)res[0] * res[1] * res[2];
-	if (res3 == 0 || res3 >= (1ull << 32)) return fail(RNB_ERR_INVALID, "lattice must hold 1 .. 2^32-1 points");
-	hipStream_t s = as_stream(stream);
-	if (int rc = ensure_mc_table(c); rc != RNB_OK) return rc;
-	McArgs a;
-	a.density = density; a.rx = res[0]; a.ry = res[1]; a.rz = res[2]; a.thresh = thresh;
-	for (int d = 0; d < 3; ++d) { a.sc[d] = (aabb_max[d] - aabb_min[d]) / (float)res[d]; a.mn[d] = aabb_min[d]; }
-	const uint64_t n_wg64 = (res3 + MC_WG - 1) / MC_WG;
-	const uint32_t n_wg = (uint32_t)n_wg64;
-	MeshWorkspace ws;
-	uint32_t *wg = nullptr, *scan_scratch = nullptr, *vidx = nullptr, *indices = nullptr;
-	float* verts = nullptr;
-	if (!ws.alloc(&wg, n_wg) || !ws.alloc(&scan_scratch, scan_scratch_elems(n_wg)) || !ws.alloc(&vidx, (size_t)res3 * 3)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the marching-cubes scratch (12 bytes per lattice point)");
-	uint32_t nv = 0, ni = 0;
-	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &nv, k_mc_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr); rc != RNB_OK) return rc;
-	if (nv && !ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the vertices");
-	hipLaunchKernelGGL(k_mc_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
-	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &ni, k_mc_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr); rc != RNB_OK) return rc;
-	if (ni && !ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the indices");
-	hipLaunchKernelGGL(k_mc_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
-	if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return fail(RNB_ERR_DEVICE, "rnb_marching_cubes: kernel failure");
-	*verts_out = (float*)ws.keep(verts); *indices_out = (uint32_t*)ws.keep(indices); *n_verts = nv; *n_indices = ni; // (null where the count is 0; the scratch goes with ws)
-	return RNB_OK;
-} RNB_GUARD
-
 int rnb_generate_training_samples(rnb_ctx* c, void* stream, uint32_t n_rays, uint32_t n_rays_total, uint32_t max_samples) try {
 	if (!c) return fail(RNB_ERR_INVALID, "null ctx");
 	discard_premarch(c);
@@ -2035,7 +1867,7 @@ static int step_front(rnb_ctx* c, hipStream_t s) {
 		n_rays_total = c->n_rays_total;
 		c->n_rays_total += n_rays * c->cfg.world_size;
 		// (Counters::prepare_for_training_steps, testbed_nerf.cu:3519-3530, zeroes the counters here; every one of them is written with a plain store by
-		// the scans of this step -- k_scan_rays*: [0] [2] [3], k_scan_compact*: [1] -- so the fill, a launch on the critical path of the update steps, is left out)
+		// the scans of this step -- k_scan_rays_chain: [0] [2] [3], the compaction scan (compute_loss): [1] -- so the fill, a launch on the critical path of the update steps, is left out)
 		rc = generate_training_samples(c, s, n_rays, n_rays_total, max_inference);
 		if (rc != RNB_OK) return rc;
 		c->cur_k1 = c->gen_k1;
@@ -2084,8 +1916,8 @@ static int launch_reduce_losses(rnb_ctx* c, hipStream_t s) {
 	if (c->loss_reduced) return RNB_OK; // k_loss_pass2_samples did it (compute_loss)
 	c->prof.mark(s, P_NONE);
 	// the 48-byte readback goes straight into the pinned host block (no copy kernel, no marker packet); ev_loss is the kernel's completion
-	const bool tiled = c->cur_n_rays >= c->knobs.march_narrow_from;
-	const uint32_t n_tiles = (c->cur_n_rays + SCAN_TILE - 1) / SCAN_TILE;
+	const bool tiled = large_batch(c, c->cur_n_rays);
+	const uint32_t n_tiles = scan_tiles_of(c->cur_n_rays);
 	if (tiled) hipLaunchKernelGGL(k_reduce_losses_tiles, dim3(n_tiles), dim3(1024), 0, s, c->cur_n_rays, c->counters.p, c->loss.p, c->ek_loss, c->mask_loss, c->loss_partial.p);
 	// Single GPU, overlapped schedule: no completion event (ev_loss carries a system-scope fence and has a waiter on the march's stream: ~5 us between this kernel
 	// and k_fwd_bwd, tools/probe_barriers.hip); the host polls the readback's sequence word instead (wait_loss_readback). Data parallel / serial: the event, as before.
@@ -2113,7 +1945,7 @@ static int launch_premarch(rnb_ctx* c) {
 	// k_fwd_bwd (0 of 1300 for the one-thread-per-ray kernel of the large batches). DESIGN.md section 6.
 	if (c->poll_loss()) { const int rc0 = wait_loss_readback(c, c->step_stream); if (rc0 != RNB_OK) return rc0; } // the host has SEEN the loss pass end: nothing to wait for on the device
 	else HIP_TRY(hipStreamWaitEvent(c->s_march, c->ev_loss, 0));
-	// No fill in front of the march: every step counter is written with a plain store by the scans (k_scan_rays*, k_scan_compact*), and the
+	// No fill in front of the march: every step counter is written with a plain store by the scans (k_scan_rays_chain and the compaction scan of compute_loss), and the
 	// loss rows are written for every kept ray by k_loss_pass2 (zeros for a ray without compacted samples) -- k_reduce_losses reads nothing
 	// else. (Round 2 queued a k_clear_step here: 62 us behind k_fwd_bwd_sdf's workgroups at the head of the march chain.)
 	// Albedo mode: always. Its two training kernels (k_rgb_fwd_bwd: one wavefront per SIMD with ~470 registers; k_fwd_bwd_sdf_full: two with 256) and the march
@@ -2407,763 +2239,8 @@ int rnb_gradient_part_wait(rnb_ctx* c, uint32_t part, void* stream) try {
 	if (early && c->sc.dp) HIP_TRY(hipStreamWaitEvent(as_stream(stream), c->ev_dw, 0)); // block 0 holds the MLPs' gradients (side stream)
 	return RNB_OK;
 } RNB_GUARD
-
-// ---- inference tracer (include/rnb_render.h; Testbed::NerfTracer, src/testbed_nerf.cu:2499-2770) ----
-uint32_t rnb_render_abi_version(void) { return RNB_RENDER_ABI_VERSION; }
-
-int rnb_render_default_options(rnb_render_options* opt) try {
-	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
-	std::memset(opt, 0, sizeof(*opt));
-	opt->abi_version = RNB_RENDER_ABI_VERSION;
-	opt->min_transmittance = 0.01f; // testbed.h:723
-	opt->near_distance = 0.2f;      // testbed_nerf.cu:48
-	opt->use_inference_params = 1;
-	opt->use_occupancy = 1;
-	opt->max_rays_in_flight = 0;
-	return RNB_OK;
-} RNB_GUARD
-
-int rnb_render(rnb_ctx* c, void* stream, const rnb_view* view, const rnb_render_options* opt, float* out, rnb_render_stats* stats) try {
-	if (!c || !view || !opt) return fail(RNB_ERR_INVALID, "rnb_render: null argument");
-	if (opt->abi_version != RNB_RENDER_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_render: options abi_version mismatch (expected RNB_RENDER_ABI_VERSION)");
-	if (!out) return fail(RNB_ERR_INVALID, "rnb_render: out_dev is null");
-	if (view->width == 0 || view->height == 0) return fail(RNB_ERR_INVALID, "rnb_render: empty view");
-	const uint64_t n_pix = (uint64_t)view->width * view->height;
-	if (n_pix > (1ull << 31)) return fail(RNB_ERR_INVALID, "rnb_render: more than 2^31 pixels");
-	if (!(opt->min_transmittance >= 0.f && opt->min_transmittance < 1.f)) return fail(RNB_ERR_INVALID, "rnb_render: min_transmittance must be in [0, 1)");
-	if (!(opt->near_distance >= 0.f) || !std::isfinite(opt->near_distance)) return fail(RNB_ERR_INVALID, "rnb_render: near_distance must be finite and >= 0");
-	if (!(view->focal_length[0] > 0.f && view->focal_length[1] > 0.f)) return fail(RNB_ERR_INVALID, "rnb_render: focal lengths must be positive");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
-
-	// tile size: a multiple of 64 (the write kernel's 16-byte stores start on a 4-pixel boundary), no larger than the image needs
-	uint32_t R = opt->max_rays_in_flight ? opt->max_rays_in_flight : (1u << 19);
-	R = std::max<uint32_t>(64u, R / 64u * 64u);
-	R = (uint32_t)std::min<uint64_t>(R, (n_pix + 63) / 64 * 64);
-	if (R > c->render_cap) {
-		c->render_rays[0].free(); c->render_rays[1].free(); c->render_keep.free(); c->render_scan.free(); c->render_res.free(); c->render_coords.free(); c->render_out.free();
-		c->render_cap = 0;
-		if (c->render_rays[0].alloc(R) != hipSuccess || c->render_rays[1].alloc(R) != hipSuccess || c->render_keep.alloc(R) != hipSuccess ||
-		    c->render_scan.alloc(scan_scratch_elems(R)) != hipSuccess || c->render_res.alloc((size_t)R * RENDER_RES_FLOATS) != hipSuccess ||
-		    c->render_coords.alloc((size_t)R * RENDER_MAX_N * 7) != hipSuccess || c->render_out.alloc((size_t)R * RENDER_MAX_N * 16) != hipSuccess) {
-			c->render_rays[0].free(); c->render_rays[1].free(); c->render_keep.free(); c->render_scan.free(); c->render_res.free(); c->render_coords.free(); c->render_out.free();
-			return fail(RNB_ERR_NOMEM, "rnb_render: hipMalloc failed for the render workspace (lower max_rays_in_flight)");
-		}
-		c->render_cap = R;
-	}
-	if (!c->render_counts.p && c->render_counts.alloc(4) != hipSuccess) return fail(RNB_ERR_NOMEM, "rnb_render: hipMalloc failed for the counters");
-	uint32_t* n_eval = c->render_counts.p;
-	uint32_t* n_hit = c->render_counts.p + 1;
-	unsigned long long* n_samples = reinterpret_cast<unsigned long long*>(c->render_counts.p + 2);
-	HIP_TRY(hipMemsetAsync(c->render_counts.p, 0, 16, s));
-
-	RenderArgs a;
-	std::memset(&a, 0, sizeof(a));
-	a.view.width = view->width; a.view.height = view->height;
-	a.view.focal[0] = view->focal_length[0]; a.view.focal[1] = view->focal_length[1];
-	a.view.principal[0] = view->principal_point[0]; a.view.principal[1] = view->principal_point[1];
-	for (int k = 0; k < 12; ++k) a.view.xform[k] = view->xform[k];
-	a.view.normal = nullptr; a.view.albedo = nullptr;
-	a.A = c->aabb;
-	a.bitfield = opt->use_occupancy ? c->bitfield.p : nullptr;
-	a.near_distance = opt->near_distance;
-	a.min_transmittance = opt->min_transmittance;
-	a.apply_no_albedo = c->cfg.apply_no_albedo;
-	a.fwd[0] = view->xform[2]; a.fwd[1] = view->xform[6]; a.fwd[2] = view->xform[10];
-	const bool inference = opt->use_inference_params != 0;
-	const bool vec = (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
-	uint32_t rounds = 0;
-	for (uint64_t p0 = 0; p0 < n_pix; p0 += R) {
-		const uint32_t nt = (uint32_t)std::min<uint64_t>(R, n_pix - p0);
-		a.p0 = (uint32_t)p0; a.nt = nt;
-		hipLaunchKernelGGL(k_render_init, dim3((nt + 255) / 256), dim3(256), 0, s, a, c->render_rays[0].p, c->render_keep.p, c->render_res.p);
-		HIP_TRY(hipGetLastError());
-		uint32_t cur = 0, n_cur = nt;
-		while (true) {
-			uint32_t n_alive = 0;
-			int rc = scan_exclusive(c->render_keep.p, n_cur, s, &n_alive, c->render_scan.p); // the round's one read (and synchronisation)
-			if (rc != RNB_OK) return rc;
-			if (n_alive == 0) break;
-			hipLaunchKernelGGL(k_render_compact, dim3((n_cur + 255) / 256), dim3(256), 0, s, n_cur, c->render_rays[cur].p, c->render_keep.p, n_alive, c->render_rays[cur ^ 1].p);
-			cur ^= 1;
-			// Samples per ray this round. The reference takes clamp(n_initialised / n_alive, 1, 8) (testbed_nerf.cu:2731): one sample per ray in the first round, and
-			// ~20 rounds for an 800 x 800 frame of a trained scene, each paying a read-back and seven launches. Here the round's budget is what the workspace holds,
-			// RENDER_MAX_N samples per ray of the tile, spread over the rays still alive (at most RENDER_ROUND_MAX each). The image does not depend on it.
-			const uint32_t n = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((uint64_t)RENDER_MAX_N * nt / n_alive, 1), RENDER_ROUND_MAX);
-			HIP_TRY(hipMemsetAsync(n_eval, 0, 4, s));
-			hipLaunchKernelGGL(k_render_march, dim3((n_alive + 255) / 256), dim3(256), 0, s, a, n_alive, n, c->render_rays[cur].p, c->render_coords.p, n_eval, n_samples);
-			HIP_TRY(hipGetLastError());
-			rc = launch_forward(c, s, c->render_coords.p, n_eval, n * n_alive, c->render_out.p, inference);
-			if (rc != RNB_OK) return rc;
-			hipLaunchKernelGGL(k_render_composite, dim3((n_alive + 255) / 256), dim3(256), 0, s, a, n_alive, c->render_rays[cur].p, c->render_coords.p, c->render_out.p,
-			                   c->render_keep.p, c->render_res.p, n_hit);
-			HIP_TRY(hipGetLastError());
-			n_cur = n_alive;
-			++rounds;
-		}
-		if (vec) hipLaunchKernelGGL(k_render_write<true>, dim3((nt / 4 + 1 + 255) / 256), dim3(256), 0, s, (uint32_t)p0, nt, c->render_res.p, out);
-		else hipLaunchKernelGGL(k_render_write<false>, dim3((nt + 255) / 256), dim3(256), 0, s, (uint32_t)p0, nt, c->render_res.p, out);
-		HIP_TRY(hipGetLastError());
-	}
-	uint32_t counts[4] = {0, 0, 0, 0};
-	HIP_TRY(hipMemcpyAsync(counts, c->render_counts.p, 16, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	if (stats) {
-		stats->n_rays = (uint32_t)n_pix;
-		stats->n_hit = counts[1];
-		stats->rounds = rounds;
-		stats->reserved = 0;
-		stats->n_samples = (uint64_t)counts[2] | ((uint64_t)counts[3] << 32);
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	}
-	return RNB_OK;
-} RNB_GUARD
-
-// ---- sparse mesh extraction (include/rnb_mesh.h) ----
-uint32_t rnb_mesh_abi_version(void) { return RNB_MESH_ABI_VERSION; }
-
-int rnb_mesh_default_options(rnb_mesh_options* opt) try {
-	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
-	std::memset(opt, 0, sizeof(*opt));
-	opt->abi_version = RNB_MESH_ABI_VERSION;
-	for (int k = 0; k < 3; ++k) { opt->res[k] = 256; opt->aabb_min[k] = 0.f; opt->aabb_max[k] = 1.f; }
-	opt->lattice_min = 0.f; opt->lattice_max = 1.f;
-	opt->thresh = 0.f;
-	opt->use_inference_params = 1;
-	opt->cull = RNB_MESH_CULL_OCCUPANCY;
-	return RNB_OK;
-} RNB_GUARD
-
-int rnb_mesh_free(rnb_ctx* c, rnb_mesh* m) try {
-	if (!c || !m) return fail(RNB_ERR_INVALID, "null argument");
-	if (m->verts) (void)hipFree(m->verts);
-	if (m->indices) (void)hipFree(m->indices);
-	if (m->colors) (void)hipFree(m->colors);
-	if (m->normals) (void)hipFree(m->normals);
-	std::memset(m, 0, sizeof(*m));
-	return RNB_OK;
-} RNB_GUARD
-
-constexpr uint32_t MESH_DEFAULT_BRICK = 16; // measured against 32 (tools/bench_mesh.py, profiles/mesh_sparse.md): fewer points evaluated around the surface
-int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_mesh* out, rnb_mesh_stats* stats) try {
-	if (!c || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: null argument");
-	std::memset(out, 0, sizeof(*out));
-	if (opt->abi_version != RNB_MESH_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: options abi_version mismatch (expected RNB_MESH_ABI_VERSION)");
-	for (int k = 0; k < 3; ++k) if (opt->res[k] == 0 || opt->res[k] > RNB_MESH_MAX_RES) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: res must be 1 .. 4096 per axis");
-	if (opt->cull != RNB_MESH_CULL_NONE && opt->cull != RNB_MESH_CULL_OCCUPANCY) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: unknown cull mode");
-	if (opt->attributes & ~(RNB_MESH_ATTR_COLORS | RNB_MESH_ATTR_NORMALS)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: unknown attribute bits");
-	const uint32_t B = opt->brick ? opt->brick : MESH_DEFAULT_BRICK;
-	if (B < 8 || B > 64 || (B & (B - 1))) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: brick must be a power of two, 8 .. 64 (0 = default)");
-	if (!std::isfinite(opt->lattice_min) || !std::isfinite(opt->lattice_max) || !std::isfinite(opt->thresh)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: lattice bounds and thresh must be finite");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
-	if (int rc = ensure_mc_table(c); rc != RNB_OK) return rc;
-
-	MeshWorkspace ws;
-	MsArgs a;
-	std::memset(&a, 0, sizeof(a));
-	a.lb = ilog2(B);
-	uint64_t n_bricks64 = 1;
-	for (int k = 0; k < 3; ++k) {
-		a.r[k] = opt->res[k]; a.nb[k] = (opt->res[k] + B - 1) / B; n_bricks64 *= a.nb[k];
-		a.sc[k] = (opt->aabb_max[k] - opt->aabb_min[k]) / (float)opt->res[k]; a.mn[k] = opt->aabb_min[k];
-	}
-	a.thresh = opt->thresh;
-	a.n_bricks = (uint32_t)n_bricks64; // at most (4096 / 8)^3 = 2^27
-	const uint32_t lb3 = 3 * a.lb;
-	const uint64_t brick_points = 1ull << lb3;
-	const bool inference = opt->use_inference_params != 0;
-
-	// 1. which bricks are kept, which are evaluated, and their slots
-	const uint32_t n_bwg = (a.n_bricks + MC_WG - 1) / MC_WG;
-	uint32_t *bwg = nullptr, *bscan = nullptr, *list = nullptr;
-	if (!ws.alloc(&a.word, a.n_bricks) || !ws.alloc(&bwg, n_bwg) || !ws.alloc(&bscan, scan_scratch_elems(n_bwg))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick words");
-	hipLaunchKernelGGL(k_ms_classify, dim3((a.n_bricks + 3) / 4), dim3(256), 0, s, a, (double)opt->lattice_min, (double)opt->lattice_max - (double)opt->lattice_min,
-	                   opt->cull == RNB_MESH_CULL_OCCUPANCY ? (const uint8_t*)c->bitfield.p : (const uint8_t*)nullptr);
-	uint32_t n_eval = 0;
-	int rc = count_and_scan(s, n_bwg, bwg, bscan, &n_eval, k_ms_mark<false>, a, bwg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-	if (rc != RNB_OK) return rc;
-	if (!ws.alloc(&list, n_eval)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick list");
-	a.list = list;
-	hipLaunchKernelGGL(k_ms_mark<true>, dim3(n_bwg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, bwg, list);
-	HIP_TRY(hipGetLastError());
-	uint64_t n_kept = 0;
-	{ // the kept count, for the statistics: the evaluated count is the scan's total
-		std::vector<uint32_t> h(a.n_bricks);
-		HIP_TRY(hipMemcpyAsync(h.data(), a.word, (size_t)a.n_bricks * 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		for (uint32_t w : h) n_kept += w & 1u;
-	}
-	ws.release(bwg); ws.release(bscan);
-	const uint64_t n_active_points = (uint64_t)n_eval * brick_points;
-	if (opt->max_active_points && n_active_points > opt->max_active_points)
-		return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: " + std::to_string(n_active_points) + " lattice points would be held at once (" + std::to_string(n_eval) + " bricks of " +
-		            std::to_string(B) + "^3), max_active_points is " + std::to_string(opt->max_active_points));
-	if (n_eval >= (1u << 30)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: more than 2^30 bricks to evaluate");
-
-	uint32_t n_act = 0, nv = 0, ni = 0;
-	float* verts = nullptr;
-	uint32_t* indices = nullptr;
-	if (n_eval) {
-		// 2. the lattice values of the evaluated bricks, through the point-query kernel of rnb_sdf_lattice
-		half_t* vals = nullptr;
-		float* pos = nullptr;
-		uint64_t per_launch = opt->max_points_in_flight ? opt->max_points_in_flight : (1u << 22);
-		const uint32_t slots_per_launch = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per_launch >> lb3, 1), n_eval);
-		if (!ws.alloc(&vals, n_active_points) || !ws.alloc(&pos, (size_t)slots_per_launch * brick_points * 3))
-			return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for " + std::to_string(n_active_points) + " lattice values (set max_active_points to fail before allocating, or cull)");
-		a.vals = vals;
-		const float diag = c->aabb.mx - c->aabb.mn;
-		for (uint32_t s0 = 0; s0 < n_eval; s0 += slots_per_launch) {
-			const uint32_t np = (uint32_t)(std::min<uint32_t>(slots_per_launch, n_eval - s0) * brick_points); // at most 2^22 or one brick (2^18)
-			hipLaunchKernelGGL(k_ms_positions, dim3((np + 255) / 256), dim3(256), 0, s, a, s0, np, opt->lattice_min, opt->lattice_max - opt->lattice_min, c->aabb.mn, diag, pos);
-			HIP_TRY(hipGetLastError());
-			rc = launch_point_query(c, s, pos, np, vals + (size_t)s0 * brick_points, nullptr, nullptr, 0, inference);
-			if (rc != RNB_OK) return rc;
-		}
-		// 3. which of them see both sides of the threshold; only those keep an edge table
-		uint32_t *act = nullptr, *aoff = nullptr, *ascan = nullptr, *alist = nullptr;
-		if (!ws.alloc(&act, n_eval) || !ws.alloc(&aoff, n_eval) || !ws.alloc(&ascan, scan_scratch_elems(n_eval))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick flags");
-		hipLaunchKernelGGL(k_ms_sign, dim3(n_eval), dim3(256), 0, s, a, act);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(aoff, act, (size_t)n_eval * 4, hipMemcpyDeviceToDevice, s));
-		rc = scan_exclusive(aoff, n_eval, s, &n_act, ascan);
-		if (rc != RNB_OK) return rc;
-		ws.release(pos); ws.release(ascan);
-		a.act = act; a.aoff = aoff;
-		if (n_act) {
-			if ((uint64_t)n_act << (lb3 - 8) >= (1ull << 31)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: too many bricks with a sign change for one launch");
-			const uint32_t n_wg = n_act << (lb3 - 8);
-			uint32_t *wg = nullptr, *wscan = nullptr, *vidx = nullptr;
-			if (!ws.alloc(&alist, n_act) || !ws.alloc(&wg, n_wg) || !ws.alloc(&wscan, scan_scratch_elems(n_wg)) || !ws.alloc(&vidx, (size_t)n_act * 3 * brick_points))
-				return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the edge tables of " + std::to_string(n_act) + " bricks");
-			a.alist = alist;
-			hipLaunchKernelGGL(k_ms_list, dim3((n_eval + 255) / 256), dim3(256), 0, s, n_eval, act, aoff, alist);
-			// 4. vertices, then triangles: count, scan, write (the dense path's scheme over the bricks' workgroups)
-			if ((rc = count_and_scan(s, n_wg, wg, wscan, &nv, k_ms_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
-			if (!ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
-			hipLaunchKernelGGL(k_ms_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
-			if ((rc = count_and_scan(s, n_wg, wg, wscan, &ni, k_ms_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr)) != RNB_OK) return rc;
-			if (!ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
-			hipLaunchKernelGGL(k_ms_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipStreamSynchronize(s));
-			ws.release(wg); ws.release(wscan); ws.release(vidx); ws.release(alist);
-		}
-		ws.release(vals); ws.release(act); ws.release(aoff);
-	}
-	ws.release(a.word); ws.release(list);
-	if (!verts && !ws.alloc(&verts, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
-	if (!indices && !ws.alloc(&indices, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
-
-	// 5. attributes: the full network at the vertices, in batches
-	float *colors = nullptr, *normals = nullptr;
-	if (opt->attributes) {
-		if ((opt->attributes & RNB_MESH_ATTR_COLORS) && !ws.alloc(&colors, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the colours");
-		if ((opt->attributes & RNB_MESH_ATTR_NORMALS) && !ws.alloc(&normals, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the normals");
-		const uint32_t batch = std::min<uint32_t>(1u << 20, std::max(nv, 1u));
-		float* coords = nullptr;
-		half_t* net = nullptr;
-		if (!ws.alloc(&coords, (size_t)batch * 7) || !ws.alloc(&net, (size_t)batch * 16)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the attribute batch");
-		const float diag = c->aabb.mx - c->aabb.mn;
-		for (uint32_t v0 = 0; v0 < nv; v0 += batch) {
-			const uint32_t nb = std::min(batch, nv - v0);
-			hipLaunchKernelGGL(k_ms_vertex_coords, dim3((nb + 255) / 256), dim3(256), 0, s, verts + (size_t)v0 * 3, nb, c->aabb.mn, diag, coords);
-			HIP_TRY(hipGetLastError());
-			rc = launch_forward(c, s, coords, nullptr, nb, net, inference);
-			if (rc != RNB_OK) return rc;
-			hipLaunchKernelGGL(k_ms_vertex_attr, dim3((nb + 255) / 256), dim3(256), 0, s, net, nb, colors ? colors + (size_t)v0 * 3 : nullptr, normals ? normals + (size_t)v0 * 3 : nullptr);
-			HIP_TRY(hipGetLastError());
-		}
-		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(coords); ws.release(net);
-	}
-	HIP_TRY(hipStreamSynchronize(s));
-	hand_over(ws, rnb_mesh{verts, indices, colors, normals, nv, ni}, out);
-	if (stats) {
-		std::memset(stats, 0, sizeof(*stats));
-		stats->n_bricks = a.n_bricks; stats->n_kept = n_kept; stats->n_evaluated = n_eval; stats->n_sign_change = n_act;
-		stats->n_points_evaluated = n_active_points;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	}
-	return RNB_OK;
-} RNB_GUARD
-
-// ---- mesh cleaning (include/rnb_mesh_clean.h) ----
-uint32_t rnb_mesh_clean_abi_version(void) { return RNB_MESH_CLEAN_ABI_VERSION; }
-
-int rnb_mesh_clean_default_options(rnb_mesh_clean_options* opt) try {
-	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
-	std::memset(opt, 0, sizeof(*opt));
-	opt->abi_version = RNB_MESH_CLEAN_ABI_VERSION;
-	opt->keep = RNB_MESH_KEEP_LARGEST;
-	opt->orient = RNB_MESH_ORIENT_OUTWARD;
-	return RNB_OK;
-} RNB_GUARD
-
-int rnb_mesh_clean_table_free(rnb_ctx* c, rnb_mesh_component* table) try {
-	if (!c) return fail(RNB_ERR_INVALID, "null argument");
-	if (table) (void)hipFree(table);
-	return RNB_OK;
-} RNB_GUARD
-
-int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_clean_options* opt, rnb_mesh* out, rnb_mesh_component** table_dev, rnb_mesh_clean_stats* stats) try {
-	if (table_dev) *table_dev = nullptr;
-	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: null argument");
-	if (int rc = check_mesh_input("rnb_mesh_clean", in, out); rc != RNB_OK) return rc;
-	const rnb_mesh m = *in;
-	if (opt->abi_version != RNB_MESH_CLEAN_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: options abi_version mismatch (expected RNB_MESH_CLEAN_ABI_VERSION)");
-	if (opt->keep != RNB_MESH_KEEP_ALL && opt->keep != RNB_MESH_KEEP_LARGEST) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown keep mode");
-	if (opt->orient != RNB_MESH_ORIENT_NONE && opt->orient != RNB_MESH_ORIENT_OUTWARD) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown orient mode");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
-
-	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
-	MeshWorkspace ws;
-	ClResult hres;
-	std::memset(&hres, 0, sizeof(hres));
-	hres.best = MESH_NONE;
-	uint32_t n_comp = 0, nvo = 0, nto = 0;
-	rnb_mesh_component* table = nullptr;
-	rnb_mesh o;
-	if (nt) {
-		const uint32_t g_v = (nv + CL_WG - 1) / CL_WG, g_t = (nt + CL_WG - 1) / CL_WG; // (nv >= 1: check_mesh_input)
-		uint32_t *parent = nullptr, *used = nullptr, *cid = nullptr, *scan = nullptr, *twg = nullptr, *cflags = nullptr;
-		ClResult* dres = nullptr;
-		if (!ws.alloc(&parent, nv) || !ws.alloc(&used, nv) || !ws.alloc(&cid, nv) || !ws.alloc(&twg, g_t) || !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) || !ws.alloc(&dres, 1))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
-		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-		// 1. every index is range-checked before any is used as an address
-		hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, CL_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & CL_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: an index is out of range (>= n_verts)");
-		// 2. labels: one hooking launch, one flattening launch; roots -> component ids in ascending label order
-		hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, parent);
-		hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
-		hipLaunchKernelGGL(k_cl_roots, dim3(g_v), dim3(CL_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, cid, nv);
-		HIP_TRY(hipGetLastError());
-		int rc = scan_exclusive(cid, nv, s, &n_comp, scan);
-		if (rc != RNB_OK) return rc;
-		if (!ws.alloc(&table, n_comp) || !ws.alloc(&cflags, n_comp)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the table of " + std::to_string(n_comp) + " components");
-		HIP_TRY(hipMemsetAsync(table, 0, std::max<size_t>(n_comp, 1) * sizeof(rnb_mesh_component), s));
-		hipLaunchKernelGGL(k_cl_relabel, dim3(g_v), dim3(CL_WG), 0, s, parent, (const uint32_t*)used, (const uint32_t*)cid, table, nv);
-		const uint32_t* comp = parent;
-		// 3. per-component sums, the selection
-		hipLaunchKernelGGL(k_cl_sums<true>, dim3(g_t), dim3(CL_WG), 0, s, (const float*)m.verts, (const uint32_t*)m.indices, nt, comp, table, dres);
-		hipLaunchKernelGGL(k_cl_sums<false>, dim3(g_v), dim3(CL_WG), 0, s, (const float*)nullptr, (const uint32_t*)nullptr, nv, comp, table, dres);
-		hipLaunchKernelGGL(k_cl_select, dim3(1), dim3(1024), 0, s, table, n_comp, opt->keep, opt->orient, cflags, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & CL_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: the area or volume term of a triangle is not finite or not below 2^18");
-		ws.release(used);
-		// 4. compaction: the new vertex numbering (cid's memory is reused), the kept triangles per workgroup
-		uint32_t* vmap = cid;
-		hipLaunchKernelGGL(k_cl_vflag, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, vmap, nv);
-		HIP_TRY(hipGetLastError());
-		rc = scan_exclusive(vmap, nv, s, &nvo, scan);
-		if (rc != RNB_OK) return rc;
-		if ((rc = count_and_scan(s, g_t, twg, scan, &nto, k_cl_tris<false>, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
-		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
-		hipLaunchKernelGGL(k_cl_verts, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, o.verts, o.colors, o.normals);
-		hipLaunchKernelGGL(k_cl_tris<true>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(s));
-		if (n_comp && hres.best < n_comp) { // the label of the selected component, for the statistics
-			uint32_t label = MESH_NONE;
-			HIP_TRY(hipMemcpy(&label, &table[hres.best].label, 4, hipMemcpyDeviceToHost));
-			hres.best = label;
-		} else hres.best = MESH_NONE;
-		ws.release(parent); ws.release(cid); ws.release(scan); ws.release(twg); ws.release(cflags); ws.release(dres);
-	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr) || (table_dev && !ws.alloc(&table, 1)))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
-	hand_over(ws, o, out);
-	if (table_dev) *table_dev = (rnb_mesh_component*)ws.keep(table);
-	if (stats) {
-		std::memset(stats, 0, sizeof(*stats));
-		stats->n_components = n_comp; stats->n_kept = hres.n_kept;
-		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
-		stats->largest_label = hres.best;
-		stats->hook_passes = nt ? 1u : 0u; stats->flatten_passes = nt ? 1u : 0u;
-		stats->area_q_in = hres.area_in; stats->area_q_out = hres.area_out;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	}
-	return RNB_OK;
-} RNB_GUARD
-
-// ---- mesh simplification (include/rnb_mesh_simplify.h) ----
-uint32_t rnb_mesh_simplify_abi_version(void) { return RNB_MESH_SIMPLIFY_ABI_VERSION; }
-
-int rnb_mesh_simplify_default_options(rnb_mesh_simplify_options* opt) try {
-	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
-	std::memset(opt, 0, sizeof(*opt));
-	opt->abi_version = RNB_MESH_SIMPLIFY_ABI_VERSION;
-	opt->cell = 1.0f / 256.0f;
-	opt->dims[0] = opt->dims[1] = opt->dims[2] = 256u;
-	opt->placement = RNB_MESH_PLACE_QUADRIC;
-	return RNB_OK;
-} RNB_GUARD
-
-int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_simplify_options* opt, rnb_mesh* out, rnb_mesh_simplify_stats* stats) try {
-	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: null argument");
-	if (int rc = check_mesh_input("rnb_mesh_simplify", in, out); rc != RNB_OK) return rc;
-	const rnb_mesh m = *in;
-	if (opt->abi_version != RNB_MESH_SIMPLIFY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: options abi_version mismatch (expected RNB_MESH_SIMPLIFY_ABI_VERSION)");
-	if (opt->placement != RNB_MESH_PLACE_QUADRIC && opt->placement != RNB_MESH_PLACE_MEAN) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: unknown placement");
-	if (!(opt->cell > 0.0f) || !std::isfinite(opt->cell)) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: cell must be finite and > 0");
-	uint64_t n_cells = 1;
-	for (int k = 0; k < 3; ++k) {
-		if (!std::isfinite(opt->origin[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: origin must be finite");
-		if (opt->dims[k] == 0 || opt->dims[k] > RNB_MESH_SIMPLIFY_MAX_DIM) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims must be 1 .. 4096 per axis");
-		n_cells *= opt->dims[k];
-	}
-	if (n_cells > RNB_MESH_SIMPLIFY_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims hold " + std::to_string(n_cells) + " cells, more than RNB_MESH_SIMPLIFY_MAX_CELLS (2^30)");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
-
-	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
-	MeshWorkspace ws;
-	SpResult hres;
-	std::memset(&hres, 0, sizeof(hres));
-	uint32_t n_cl = 0, nvo = 0, nto = 0;
-	rnb_mesh o;
-	if (nt) {
-		SpGrid g;
-		for (int k = 0; k < 3; ++k) { g.origin[k] = (double)opt->origin[k]; g.dims[k] = opt->dims[k]; }
-		g.cell = (double)opt->cell;
-		const uint32_t n_words = (uint32_t)((n_cells + 31u) / 32u);
-		const uint32_t g_v = (nv + SP_WG - 1) / SP_WG, g_t = (nt + SP_WG - 1) / SP_WG, g_w = (n_words + SP_WG - 1) / SP_WG;
-		uint32_t *used = nullptr, *vcl = nullptr, *bits = nullptr, *rank = nullptr, *scan = nullptr, *twg = nullptr, *ckey = nullptr, *cused = nullptr, *cmap = nullptr;
-		long long* sums = nullptr;
-		SpResult* dres = nullptr;
-		if (!ws.alloc(&used, nv) || !ws.alloc(&vcl, nv) || !ws.alloc(&bits, n_words) || !ws.alloc(&rank, n_words) || !ws.alloc(&twg, g_t) ||
-		    !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(std::max<uint64_t>(nv, n_words), g_t))) || !ws.alloc(&dres, 1))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(n_cells) + " cells");
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
-		HIP_TRY(hipMemsetAsync(bits, 0, (size_t)n_words * 4, s));
-		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-		// 1. every index is range-checked before any is used as an address; the occupied cells; cluster ids = ranks of the occupied keys
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, SP_BAD_INDEX);
-		hipLaunchKernelGGL(k_sp_cells, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)used, vcl, bits, dres);
-		hipLaunchKernelGGL(k_sp_popc, dim3(g_w), dim3(SP_WG), 0, s, (const uint32_t*)bits, rank, n_words);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		int rc = scan_exclusive(rank, n_words, s, &n_cl, scan); // (synchronises: hres has arrived)
-		if (rc != RNB_OK) return rc;
-		if (hres.flags & SP_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: an index is out of range (>= n_verts)");
-		if (hres.flags & SP_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a coordinate or attribute of a used vertex is not finite");
-		ws.release(used);
-		// 2. the sums of every cluster
-		if (!ws.alloc(&sums, (size_t)n_cl * SP_NSUM) || !ws.alloc(&ckey, n_cl) || !ws.alloc(&cused, n_cl) || !ws.alloc(&cmap, n_cl))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the records of " + std::to_string(n_cl) + " clusters");
-		HIP_TRY(hipMemsetAsync(sums, 0, std::max<size_t>(n_cl, 1) * SP_NSUM * sizeof(long long), s));
-		HIP_TRY(hipMemsetAsync(cused, 0, std::max<size_t>(n_cl, 1) * 4, s));
-		hipLaunchKernelGGL(k_sp_members, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)bits, (const uint32_t*)rank, vcl, ckey, sums, dres);
-		hipLaunchKernelGGL(k_sp_quadric, dim3(g_t), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, sums, dres);
-		// 3. the surviving triangles and the clusters they use, numbered by prefix sums (not count_and_scan: the count launch feeds two scans, the clusters' first)
-		hipLaunchKernelGGL(k_sp_tris<false>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, cused, (const uint32_t*)nullptr, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(cmap, cused, std::max<size_t>(n_cl, 1) * 4, hipMemcpyDeviceToDevice, s));
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		rc = scan_exclusive(cmap, n_cl, s, &nvo, scan);
-		if (rc != RNB_OK) return rc;
-		if (hres.flags & SP_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a term is not finite or not below 2^22 (a vertex or triangle too far from its cell, in cell units)");
-		rc = scan_exclusive(twg, g_t, s, &nto, scan);
-		if (rc != RNB_OK) return rc;
-		ws.release(bits); ws.release(rank);
-		// 4. the output: one solve per cluster, the triangles in input order
-		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
-		hipLaunchKernelGGL(k_sp_solve, dim3((n_cl + SP_WG - 1) / SP_WG), dim3(SP_WG), 0, s, g, opt->placement, n_cl, (const long long*)sums, (const uint32_t*)ckey, (const uint32_t*)cused, (const uint32_t*)cmap,
-		                   o.verts, o.colors, o.normals, dres);
-		hipLaunchKernelGGL(k_sp_tris<true>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, (uint32_t*)nullptr, (const uint32_t*)cmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(vcl); ws.release(scan); ws.release(twg); ws.release(sums); ws.release(ckey); ws.release(cused); ws.release(cmap); ws.release(dres);
-	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
-	hand_over(ws, o, out);
-	if (stats) {
-		std::memset(stats, 0, sizeof(*stats));
-		stats->n_verts_in = nv; stats->n_tris_in = nt; stats->n_clusters = n_cl; stats->n_verts_out = nvo; stats->n_tris_out = nto; stats->n_tris_collapsed = nt - nto;
-		stats->n_clamped = hres.n_clamped; stats->n_fallback = hres.n_fallback;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	}
-	return RNB_OK;
-} RNB_GUARD
-
-// ---- mesh-to-mesh distance (include/rnb_mesh_distance.h) ----
-uint32_t rnb_mesh_distance_abi_version(void) { return RNB_MESH_DISTANCE_ABI_VERSION; }
-
-int rnb_mesh_distance_default_options(rnb_mesh_distance_options* opt) try {
-	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
-	std::memset(opt, 0, sizeof(*opt));
-	opt->abi_version = RNB_MESH_DISTANCE_ABI_VERSION;
-	opt->level = 1u;
-	opt->unit = 1.0f / 1024.0f;
-	return RNB_OK;
-} RNB_GUARD
-
-int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_mesh* to, const rnb_mesh_distance_options* opt, float* vert_dist_dev, uint32_t* vert_nearest_dev,
-                      rnb_mesh_distance_stats* stats) try {
-	if (stats) std::memset(stats, 0, sizeof(*stats));
-	if (!c || !from || !to || !opt) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: null argument");
-	if (from == to) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: from and to must be different objects");
-	if (vert_dist_dev && (void*)vert_dist_dev == (void*)vert_nearest_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: vert_dist_dev and vert_nearest_dev must be different buffers");
-	if (opt->abi_version != RNB_MESH_DISTANCE_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: options abi_version mismatch (expected RNB_MESH_DISTANCE_ABI_VERSION)");
-	if (opt->level > RNB_MESH_DISTANCE_MAX_LEVEL) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: level must be 0 .. 3");
-	if (!(opt->unit > 0.0f) || !std::isfinite(opt->unit)) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: unit must be finite and > 0");
-	if (!(opt->max_distance >= 0.0f) || !std::isfinite(opt->max_distance)) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: max_distance must be finite and >= 0");
-	for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k)
-		if (!(opt->tau[k] >= 0.0f) || !std::isfinite(opt->tau[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a tau must be finite and >= 0");
-	if (opt->cells > RNB_MESH_DISTANCE_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: cells must be 0 .. 256");
-	{
-		rnb_mesh unused;
-		if (int rc = check_mesh_input("rnb_mesh_distance (from)", from, &unused); rc != RNB_OK) return rc;
-		if (int rc = check_mesh_input("rnb_mesh_distance (to)", to, &unused); rc != RNB_OK) return rc;
-	}
-	const rnb_mesh ma = *from, mb = *to;
-	const uint32_t nva = ma.n_verts, nta = ma.n_indices / 3u, nvb = mb.n_verts, ntb = mb.n_indices / 3u, nn = 1u << (2u * opt->level);
-	if ((uint64_t)nta * nn > 0xFFFFFFFFull) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: more than 2^32 - 1 samples (a lower level)");
-	if (nta && ntb == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
-
-	MeshWorkspace ws;
-	MdResult hres;
-	std::memset(&hres, 0, sizeof(hres));
-	for (int k = 0; k < 3; ++k) hres.bmin[k] = 0xFFFFFFFFu;
-	MdGrid g;
-	std::memset(&g, 0, sizeof(g));
-	uint32_t n_entries = 0;
-	float ms_grid = 0.0f;
-	int64_t sums[MD_NSUM] = {};
-	if (!nta) { // no sample: every vertex is unused
-		if (vert_dist_dev && nva) HIP_TRY(hipMemsetAsync(vert_dist_dev, 0, (size_t)nva * 4, s));
-		if (vert_nearest_dev && nva) HIP_TRY(hipMemsetAsync(vert_nearest_dev, 0xFF, (size_t)nva * 4, s));
-		HIP_TRY(hipStreamSynchronize(s));
-	} else {
-		const uint32_t g_va = (nva + MD_WG - 1) / MD_WG, g_ta = (nta + MD_WG - 1) / MD_WG, g_vb = (nvb + MD_WG - 1) / MD_WG, g_tb = (ntb + MD_WG - 1) / MD_WG; // (nva, nvb >= 1: check_mesh_input)
-		const MdMesh A{ma.verts, ma.indices, nva, nta}, B{mb.verts, mb.indices, nvb, ntb};
-		uint32_t *used_a = nullptr, *used_b = nullptr, *start = nullptr, *cursor = nullptr, *scan = nullptr, *entries = nullptr, *large = nullptr;
-		MdResult* dres = nullptr;
-		if (!ws.alloc(&used_a, nva) || !ws.alloc(&used_b, nvb) || !ws.alloc(&large, RNB_MESH_DISTANCE_MAX_LARGE) || !ws.alloc(&dres, 1))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the workspace of " + std::to_string(nva) + " and " + std::to_string(nvb) + " vertices");
-		HIP_TRY(hipMemsetAsync(used_a, 0, (size_t)nva * 4, s));
-		HIP_TRY(hipMemsetAsync(used_b, 0, (size_t)nvb * 4, s));
-		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-		// 1. every index of either mesh is range-checked before any is used as an address; used vertices, B's box, B's degenerate triangles
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_ta), dim3(MD_WG), 0, s, (const uint32_t*)ma.indices, nta, nva, used_a, &dres->flags, MD_BAD_INDEX_FROM);
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_tb), dim3(MD_WG), 0, s, (const uint32_t*)mb.indices, ntb, nvb, used_b, &dres->flags, MD_BAD_INDEX_TO);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MD_BAD_INDEX_FROM) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of from is out of range (>= n_verts)");
-		if (hres.flags & MD_BAD_INDEX_TO) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of to is out of range (>= n_verts)");
-		hipLaunchKernelGGL(k_md_verts<false>, dim3(g_va), dim3(MD_WG), 0, s, (const float*)ma.verts, nva, (const uint32_t*)used_a, dres);
-		hipLaunchKernelGGL(k_md_verts<true>, dim3(g_vb), dim3(MD_WG), 0, s, (const float*)mb.verts, nvb, (const uint32_t*)used_b, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MD_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a coordinate of a used vertex is not finite");
-		ws.release(used_b);
-		const auto t_grid = std::chrono::steady_clock::now();
-		hipLaunchKernelGGL(k_md_degenerate, dim3(g_tb), dim3(MD_WG), 0, s, B, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		const uint32_t m = ntb - hres.n_deg_to;
-		if (!m) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
-		// 2. the grid over B's box, the cell lists
-		double longest = 0.0;
-		for (int k = 0; k < 3; ++k) {
-			const auto value = [](uint32_t image) { const uint32_t u = (image & 0x80000000u) ? (image ^ 0x80000000u) : ~image; float f; std::memcpy(&f, &u, 4); return (double)f; };
-			g.lo[k] = value(hres.bmin[k]); g.hi[k] = value(hres.bmax[k]);
-			longest = std::max(longest, g.hi[k] - g.lo[k]);
-		}
-		uint32_t n_axis = opt->cells;
-		if (!n_axis) n_axis = (uint32_t)std::min<double>(std::max<double>(std::floor(std::sqrt((double)(m / 2u))), 1.0), (double)RNB_MESH_DISTANCE_MAX_CELLS);
-		g.cell = longest / (double)n_axis; // > 0: a non-degenerate triangle has an extent
-		uint64_t n_cells = 1;
-		for (int k = 0; k < 3; ++k) {
-			g.dims[k] = (uint32_t)std::min<double>((double)n_axis, std::floor((g.hi[k] - g.lo[k]) / g.cell) + 1.0);
-			n_cells *= g.dims[k];
-		}
-		if (!ws.alloc(&start, n_cells) || !ws.alloc(&cursor, n_cells) || !ws.alloc(&scan, scan_scratch_elems(n_cells)))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the lists of " + std::to_string(n_cells) + " cells");
-		HIP_TRY(hipMemsetAsync(start, 0, (size_t)n_cells * 4, s));
-		hipLaunchKernelGGL(k_md_register<false>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, start, (uint32_t*)nullptr, large, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		int rc = scan_exclusive(start, n_cells, s, &n_entries, scan); // (synchronises: hres has arrived)
-		if (rc != RNB_OK) return rc;
-		if (hres.n_large > RNB_MESH_DISTANCE_MAX_LARGE)
-			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_large) + " triangles of to overlap more than 2048 cells each, the large list holds 4096 (a coarser grid: fewer cells)");
-		if (hres.n_entries > RNB_MESH_DISTANCE_MAX_ENTRIES)
-			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_entries) + " cell entries, more than 2^31 (a coarser grid: fewer cells)");
-		if (!ws.alloc(&entries, n_entries)) return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for " + std::to_string(n_entries) + " cell entries");
-		HIP_TRY(hipMemcpyAsync(cursor, start, (size_t)n_cells * 4, hipMemcpyDeviceToDevice, s));
-		hipLaunchKernelGGL(k_md_register<true>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, cursor, entries, (uint32_t*)nullptr, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(s));
-		ms_grid = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_grid).count();
-		// 3. the queries: the vertices of A, then the sub-centroids of its triangles
-		MdQuery q;
-		std::memset(&q, 0, sizeof(q));
-		q.cap = (double)opt->max_distance; q.unit = (double)opt->unit; q.level = opt->level;
-		for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k) q.tau[k] = (double)opt->tau[k];
-		const MdSearch S{B, start, cursor, entries, large, hres.n_large};
-		const uint64_t n_threads = (uint64_t)nta * nn;
-		hipLaunchKernelGGL(k_md_query<true>, dim3(g_va), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)used_a, S, vert_dist_dev, vert_nearest_dev, dres);
-		hipLaunchKernelGGL(k_md_query<false>, dim3((uint32_t)((n_threads + MD_WG - 1) / MD_WG)), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)nullptr, S, (float*)nullptr, (uint32_t*)nullptr, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MD_BAD_TERM)
-			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a term is not finite or not below 2^12 (a larger unit, or a max_distance)");
-		for (int k = 0; k < MD_NSUM; ++k) { // the two words of a sum, joined in 128 bits
-			const unsigned __int128 total = ((unsigned __int128)hres.hi[k] << 32) + hres.lo[k];
-			if (total >> 63) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a sum reaches 2^15 (a larger unit, or a max_distance)");
-			sums[k] = (int64_t)total;
-		}
-		ws.release(used_a); ws.release(start); ws.release(cursor); ws.release(scan); ws.release(entries); ws.release(large); ws.release(dres);
-	}
-	if (stats) {
-		stats->n_verts_from_used = hres.n_used_from; stats->n_verts_to_used = hres.n_used_to; stats->n_tris_from = nta; stats->n_tris_to = ntb;
-		stats->n_degenerate_from = hres.n_deg_from; stats->n_degenerate_to = hres.n_deg_to; stats->n_verts_beyond = hres.n_verts_beyond; stats->n_large = hres.n_large;
-		stats->n_samples = hres.n_samples; stats->n_beyond = hres.n_beyond;
-		stats->sum_w = sums[0]; stats->sum_wd = sums[1]; stats->sum_wd2 = sums[2];
-		for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k) stats->sum_within[k] = sums[3 + k];
-		std::memcpy(&stats->max_distance, &hres.max_bits, 8);
-		for (int k = 0; k < 3; ++k) stats->dims[k] = g.dims[k];
-		stats->cell = g.cell;
-		stats->n_cell_entries = hres.n_entries; stats->n_pairs = hres.n_pairs;
-		stats->peak_workspace = ws.peak;
-		stats->ms_grid = ms_grid;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	}
-	return RNB_OK;
-} RNB_GUARD
-
-// ---- mesh rasteriser (include/rnb_mesh_raster.h) ----
-uint32_t rnb_mesh_raster_abi_version(void) { return RNB_MESH_RASTER_ABI_VERSION; }
-
-int rnb_mesh_raster_default_options(rnb_mesh_raster_options* opt) try {
-	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
-	std::memset(opt, 0, sizeof(*opt));
-	opt->abi_version = RNB_MESH_RASTER_ABI_VERSION;
-	opt->near = 1.0f / 1024.0f;
-	opt->cull = RNB_MESH_RASTER_CULL_NONE;
-	opt->normals = RNB_MESH_RASTER_NORMALS_FACE;
-	return RNB_OK;
-} RNB_GUARD
-
-int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, const rnb_mesh_raster_options* opt, float* out_dev, uint32_t* face_dev,
-                    rnb_mesh_raster_stats* stats) try {
-	if (stats) std::memset(stats, 0, sizeof(*stats));
-	if (!c || !mesh || !view || !opt || !out_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: null argument");
-	if ((void*)out_dev == (void*)face_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: out_dev and face_dev must be different buffers");
-	if (opt->abi_version != RNB_MESH_RASTER_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: options abi_version mismatch (expected RNB_MESH_RASTER_ABI_VERSION)");
-	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: near must be finite and > 0");
-	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
-	if (opt->normals > RNB_MESH_RASTER_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals must be RNB_MESH_RASTER_NORMALS_FACE or _VERTEX");
-	for (int k = 0; k < 2; ++k) {
-		if (!(view->focal_length[k] > 0.0f) || !std::isfinite(view->focal_length[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: a focal length must be finite and > 0");
-		if (!std::isfinite(view->principal_point[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: the principal point must be finite");
-	}
-	for (int k = 0; k < 12; ++k)
-		if (!std::isfinite(view->xform[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an entry of xform is not finite");
-	if (view->width == 0 || view->height == 0 || view->width > RNB_MESH_RASTER_MAX_SIZE || view->height > RNB_MESH_RASTER_MAX_SIZE)
-		return fail(RNB_ERR_INVALID, "rnb_mesh_raster: width and height must be 1 .. 16384");
-	{
-		rnb_mesh unused;
-		if (int rc = check_mesh_input("rnb_mesh_raster", mesh, &unused); rc != RNB_OK) return rc;
-	}
-	if (opt->normals == RNB_MESH_RASTER_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals = VERTEX needs a mesh with normals");
-	const rnb_mesh m = *mesh;
-	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, width = view->width, height = view->height, n_pix = width * height;
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
-
-	MrCamera cam;
-	std::memset(&cam, 0, sizeof(cam));
-	for (int r = 0; r < 3; ++r) {
-		cam.o[r] = (double)view->xform[4 * r + 3];
-		for (int k = 0; k < 3; ++k) cam.col[k][r] = (double)view->xform[4 * r + k];
-	}
-	cam.fx = (double)view->focal_length[0]; cam.fy = (double)view->focal_length[1];
-	cam.cxw = (double)view->principal_point[0] * (double)width; cam.cyh = (double)view->principal_point[1] * (double)height;
-	cam.near = (double)opt->near;
-	cam.w = width; cam.h = height; cam.cull = opt->cull; cam.normals = opt->normals;
-	const MrMesh M{m.verts, m.indices, m.colors, m.normals, nt};
-
-	MeshWorkspace ws;
-	MrResult hres;
-	std::memset(&hres, 0, sizeof(hres));
-	unsigned long long* keys = nullptr;
-	uint32_t *counts = nullptr, *used = nullptr, *list = nullptr;
-	MrResult* dres = nullptr;
-	if (!ws.alloc(&keys, n_pix) || !ws.alloc(&counts, n_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the workspace of " + std::to_string(n_pix) + " pixels and " + std::to_string(nv) + " vertices");
-	HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_pix * 8, s));
-	HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_pix * 4, s));
-	HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-	if (nt) {
-		const uint32_t g_t = (nt + MR_WG - 1) / MR_WG;
-		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MR_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, MR_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MR_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an index is out of range (>= n_verts)");
-		ws.release(used);
-		// 2. setup, classes, the small triangles filled; the large ones counted, then listed and filled by a wavefront each
-		hipLaunchKernelGGL(k_mr_bin<false>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, (uint32_t*)nullptr, 0u, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		const uint32_t n_large = hres.n_class[MR_LARGE];
-		if (n_large) {
-			if (!ws.alloc(&list, n_large)) return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the list of " + std::to_string(n_large) + " large triangles");
-			hipLaunchKernelGGL(k_mr_bin<true>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, list, n_large, dres);
-			hipLaunchKernelGGL(k_mr_fill_large, dim3((n_large + MR_WG / 64u - 1) / (MR_WG / 64u)), dim3(MR_WG), 0, s, cam, M, (const uint32_t*)list, n_large, keys, counts);
-			HIP_TRY(hipGetLastError());
-		}
-	}
-	// 3. one thread per pixel (an empty mesh: every key is still all ones, the image is zeros)
-	const uint32_t g_p = (n_pix + MR_WG - 1) / MR_WG;
-	if (((uintptr_t)out_dev & 15u) == 0)
-		hipLaunchKernelGGL(k_mr_resolve<true>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
-	else
-		hipLaunchKernelGGL(k_mr_resolve<false>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	ws.release(keys); ws.release(counts); ws.release(used); ws.release(list); ws.release(dres);
-	if (hres.n_unresolved) return fail(RNB_ERR_DEVICE, "rnb_mesh_raster: " + std::to_string(hres.n_unresolved) + " pixels whose winner the resolve pass does not find covering them (the fill and the resolve disagree: a defect of the library)");
-	if (stats) {
-		stats->n_tris = nt;
-		stats->n_behind = hres.n_class[MR_BEHIND]; stats->n_out_of_range = hres.n_class[MR_OUT_OF_RANGE]; stats->n_degenerate = hres.n_class[MR_DEGENERATE];
-		stats->n_culled = hres.n_class[MR_CULLED]; stats->n_offscreen = hres.n_class[MR_OFFSCREEN]; stats->n_small = hres.n_class[MR_SMALL]; stats->n_large = hres.n_class[MR_LARGE];
-		stats->n_covered = hres.n_covered; stats->n_back_pixels = hres.n_back_pixels; stats->n_fragments = hres.n_fragments;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-	}
-	return RNB_OK;
-} RNB_GUARD
-
 } // extern "C"
+
+// the drivers that stay off the training state, once each: the inference tracer, then the mesh stages
+#include "driver_render.hpp"
+#include "driver_mesh.hpp"
