@@ -486,6 +486,59 @@ MESH_RASTER_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_texture.h: a per-triangle UV atlas of a device mesh and the model's albedo, normal and position at its texels, a header of its own with its own version (the HIP library only) ----
+MESH_TEXTURE_ABI_VERSION = 1
+MESH_TEXTURE_MIN_SIZE, MESH_TEXTURE_MAX_SIZE, MESH_TEXTURE_MIN_BLOCK, MESH_TEXTURE_MAX_IN_FLIGHT = 4, 8192, 4, 1 << 22
+MESH_TEXTURE_ALBEDO, MESH_TEXTURE_NORMAL, MESH_TEXTURE_POSITION = 1, 2, 4
+MESH_TEXTURE_MAPS = dict(albedo=MESH_TEXTURE_ALBEDO, normal=MESH_TEXTURE_NORMAL, position=MESH_TEXTURE_POSITION)  # the result's fields, in the struct's order
+
+
+class MeshTextureOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("size", C.c_uint32),
+        ("block", C.c_uint32),
+        ("maps", C.c_uint32),
+        ("use_inference_params", C.c_uint32),
+        ("max_texels_in_flight", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshTexture(C.Structure):
+    _fields_ = [
+        ("uv", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("position", C.c_void_p),
+        ("size", C.c_uint32),
+        ("block", C.c_uint32),
+        ("blocks_per_row", C.c_uint32),
+        ("n_tris", C.c_uint32),
+    ]
+
+
+class MeshTextureStats(C.Structure):
+    _fields_ = [
+        ("n_texels", C.c_uint64),
+        ("peak_workspace", C.c_uint64),
+        ("n_batches", C.c_uint32),
+        ("ms", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+MESH_TEXTURE_PROTOTYPES = {
+    "mesh_texture_abi_version": (_u32, []),
+    "mesh_texture_default_options": (_i, [C.POINTER(MeshTextureOptions)]),
+    "mesh_texture_layout": (_i, [_u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "mesh_bake_texture": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshTextureOptions), C.POINTER(MeshTexture), C.POINTER(MeshTextureStats)]),
+    "mesh_texture_free": (_i, [_ctx, C.POINTER(MeshTexture)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -506,9 +559,10 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False):
+def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
-    mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h); only the HIP library exports those."""
+    mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
-                     + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ()))
+                     + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
+                     + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()))

@@ -46,7 +46,7 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True)
+        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -61,6 +61,8 @@ def load_library():
             raise RuntimeError("mesh-distance ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_raster_abi_version() != _abi.MESH_RASTER_ABI_VERSION:
             raise RuntimeError("mesh-raster ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_texture_abi_version() != _abi.MESH_TEXTURE_ABI_VERSION:
+            raise RuntimeError("mesh-texture ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -551,7 +553,7 @@ class Context:
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
-                     simplify=None, placement="quadric", error=False):
+                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",)):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -564,7 +566,9 @@ class Context:
         error=True (with simplify only): the distance between the mesh handed to the simplifier and the one it returned is measured on the device before anything is
         downloaded (rnb_mesh_distance in both directions, its default options; see mesh_distance) and returned under `simplify_error`: the dict of
         mesh_distance(input, output, symmetric=True), A = the simplifier's input (a simplification that leaves no triangle fails the call: there is nothing to measure against). With False (the default) nothing
-        of that runs and the result is as it was."""
+        of that runs and the result is as it was.
+        texture = S: the final mesh (after keep, orient and simplify), still on the device, gets a texture bake of S texels per side (rnb_mesh_bake_texture, see
+        bake_texture) with the maps of `texture_maps`, and the dict gains `texture`: the dict of DeviceMesh.bake_texture. With None (the default) nothing of that runs."""
         if error and simplify is None:
             raise ValueError("error=True needs simplify")
         grid = None if simplify is None else self.simplify_grid(aabb_min, aabb_max, simplify)
@@ -577,8 +581,12 @@ class Context:
                 chain.append(chain[-1].simplify(*grid, placement=placement, stream=stream))
                 if error:
                     simplify_error = chain[-2].distance_to(chain[-1], symmetric=True, stream=stream)
+            if texture is not None:
+                baked = chain[-1].bake_texture(texture, maps=texture_maps, inference=inference, stream=stream)
             out = chain[-1].download()
             out["stats"] = chain[0].stats
+            if texture is not None:
+                out["texture"] = baked
             if grid is not None and error:
                 out["simplify_error"] = simplify_error
             if keep is not None or orient is not None:
@@ -750,6 +758,46 @@ class Context:
                 per_view.append(e)
         k = max(len(per_view), 1)
         return dict(views=per_view, mean={key: sum(e[key] for e in per_view) / k for key in ("mean_angle_deg", "median_angle_deg", "mask_iou")})
+
+    def _texture_options(self, size, block, maps, inference, max_texels_in_flight):
+        if isinstance(maps, str):
+            maps = (maps,)
+        if not isinstance(maps, int):
+            unknown = [m for m in maps if m not in _abi.MESH_TEXTURE_MAPS]
+            if unknown:
+                raise ValueError("maps must be of 'albedo', 'normal' and 'position'")
+            maps = sum(_abi.MESH_TEXTURE_MAPS[m] for m in set(maps))
+        opt = _abi.MeshTextureOptions()
+        self._check(self.f.mesh_texture_default_options(C.byref(opt)))
+        opt.size, opt.block, opt.maps = int(size), int(block), int(maps)
+        opt.use_inference_params = int(bool(inference))
+        opt.max_texels_in_flight = int(max_texels_in_flight)
+        return opt
+
+    @staticmethod
+    def texture_layout(n_tris, size, block=0, fns=None):
+        """rnb_mesh_texture_layout (include/rnb_mesh_texture.h): the atlas bake_texture lays out for n_tris triangles in a texture of `size` texels per side, as a dict of
+        `block` (the block edge in texels; block=0 asks for the largest that holds the mesh), `blocks_per_row` and `n_blocks` (block k holds the triangles 2k and 2k + 1).
+        A mesh that does not fit raises RnbError with ERR_INVALID; its message ends in the smallest size that would. A host function: it needs no context and no GPU."""
+        f = fns or load_library()
+        b, bpr, nb = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        rc = f.mesh_texture_layout(int(n_tris), int(size), int(block), C.byref(b), C.byref(bpr), C.byref(nb))
+        if rc != 0:
+            raise RnbError(rc, f.last_error().decode(errors="replace"))
+        return dict(block=b.value, blocks_per_row=bpr.value, n_blocks=nb.value)
+
+    def bake_texture(self, verts, indices, size, block=0, maps=("albedo",), inference=True, max_texels_in_flight=0, stream=None):
+        """rnb_mesh_bake_texture (include/rnb_mesh_texture.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3]): a per-triangle UV atlas of `size` texels
+        per side -- two triangles to a square block of `block` texels (0: the largest that holds the mesh, see texture_layout), laid out so that a bilinear lookup inside
+        a triangle reads only that triangle's texels -- and the model sampled at every texel. Returns a dict: `uv` float32[nt,3,2] (U, V of the corners of every
+        triangle, in the order of its indices; V = 1 at the top row), one float32[S,S,4] per name in `maps` -- `albedo` (the logistic of the colour head), `normal` (the
+        normalised SDF gradient, zeros for a zero gradient), `position` (the texel's point on the triangle's plane) in channels 0-2, channel 3 = 1 on the texels of a
+        triangle, all zeros elsewhere; row 0 is the top row of an image file -- and `block`, `blocks_per_row`, `stats` (n_texels, n_batches, peak_workspace, ms).
+        inference: the EMA weights; max_texels_in_flight (0 = 2^20) bounds the workspace and does not change a bit. The texels along an edge two triangles share are
+        equal bit for bit in both; a corner texel holds what extract_mesh(colors=True, normals=True) gives the vertex. meshproc.save_obj_textured writes the result as
+        OBJ + MTL + PNG. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices) as m:
+            return m.bake_texture(size, block, maps, inference, max_texels_in_flight, stream)
 
     def upload(self, array):
         """numpy array -> library-side buffer (device_malloc + copy); release with device_free."""
@@ -985,4 +1033,22 @@ class DeviceMesh(_abi.Mesh):
         finally:
             for p in own:
                 c.device_free(p)
+        return out
+
+    def bake_texture(self, size, block=0, maps=("albedo",), inference=True, max_texels_in_flight=0, stream=None):
+        """rnb_mesh_bake_texture of this mesh: the dict of Context.bake_texture, which describes every argument and key. The device result is downloaded and released
+        before the call returns; nothing stays allocated if a step raises."""
+        c = self._live()
+        opt = c._texture_options(size, block, maps, inference, max_texels_in_flight)
+        tex, st = _abi.MeshTexture(), _abi.MeshTextureStats()
+        try:
+            c._check(c.f.mesh_bake_texture(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), C.byref(tex), C.byref(st)))
+            nt, n = tex.n_tris, tex.size * tex.size * 4
+            out = dict(uv=c.download(tex.uv, nt * 6, np.float32).reshape(nt, 3, 2) if nt else np.empty((0, 3, 2), np.float32))
+            for name in _abi.MESH_TEXTURE_MAPS:
+                if getattr(tex, name):
+                    out[name] = c.download(getattr(tex, name), n, np.float32).reshape(tex.size, tex.size, 4)
+            out.update(block=tex.block, blocks_per_row=tex.blocks_per_row, stats=st.as_dict())
+        finally:
+            c.f.mesh_texture_free(c._h, C.byref(tex))  # (whatever a failed call left: a zeroed struct releases nothing)
         return out

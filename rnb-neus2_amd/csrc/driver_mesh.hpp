@@ -1,5 +1,5 @@
 // driver_mesh.hpp -- rnb_sdf_lattice, what the mesh drivers share (scan_exclusive, count_and_scan, MeshWorkspace, check_mesh_input, alloc_mesh, hand_over,
-// ensure_mc_table), rnb_marching_cubes and the stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster.
+// ensure_mc_table), rnb_marching_cubes and the stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_bake_texture.
 // Needs, of rnb_neus2_hip.hip, which includes it: the context (aabb, bitfield, cfg, mc_table), as_stream, fail / HIP_TRY / RNB_GUARD, launch_point_query
 // and launch_forward.
 extern "C" {
@@ -34,7 +34,7 @@ int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float latti
 	return RNB_OK;
 } RNB_GUARD
 
-// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster) ----
+// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_bake_texture) ----
 extern "C++" {
 namespace {
 // elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
@@ -816,5 +816,136 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 	return RNB_OK;
 } RNB_GUARD
 
+// ---- texture baker (include/rnb_mesh_texture.h) ----
+uint32_t rnb_mesh_texture_abi_version(void) { return RNB_MESH_TEXTURE_ABI_VERSION; }
+
+int rnb_mesh_texture_default_options(rnb_mesh_texture_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_TEXTURE_ABI_VERSION;
+	opt->size = 1024u;
+	opt->maps = RNB_MESH_TEXTURE_ALBEDO;
+	opt->use_inference_params = 1;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_texture_layout(uint32_t n_tris, uint32_t size, uint32_t block, uint32_t* block_out, uint32_t* blocks_per_row_out, uint32_t* n_blocks_out) try {
+	if (block_out) *block_out = 0;
+	if (blocks_per_row_out) *blocks_per_row_out = 0;
+	if (n_blocks_out) *n_blocks_out = 0;
+	if (size < RNB_MESH_TEXTURE_MIN_SIZE || size > RNB_MESH_TEXTURE_MAX_SIZE) return fail(RNB_ERR_INVALID, "rnb_mesh_texture_layout: size must be 4 .. 8192");
+	const uint64_t n_blocks = ((uint64_t)n_tris + 1u) / 2u;
+	uint64_t m = (uint64_t)std::sqrt((double)n_blocks); // m = ceil(sqrt(n_blocks)): the blocks per row the mesh needs
+	while (m * m > n_blocks) --m;
+	while (m * m < n_blocks) ++m;
+	const auto smallest = [&](uint64_t b) { return ": the smallest size that would fit is " + std::to_string(std::max<uint64_t>(b * std::max<uint64_t>(m, 1), RNB_MESH_TEXTURE_MIN_SIZE)); };
+	uint32_t b = block;
+	if (block == 0) {
+		b = m ? (uint32_t)(size / m) : size;
+		if (b < RNB_MESH_TEXTURE_MIN_BLOCK)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_texture_layout: " + std::to_string(n_tris) + " triangles do not fit a texture of " + std::to_string(size) + " texels per side in blocks of 4" + smallest(RNB_MESH_TEXTURE_MIN_BLOCK));
+	} else {
+		if (block < RNB_MESH_TEXTURE_MIN_BLOCK) return fail(RNB_ERR_INVALID, "rnb_mesh_texture_layout: block must be 0 or at least 4" + smallest(RNB_MESH_TEXTURE_MIN_BLOCK));
+		if (block > size || (uint64_t)(size / block) < m)
+			return fail(RNB_ERR_INVALID, "rnb_mesh_texture_layout: " + std::to_string(n_tris) + " triangles do not fit a texture of " + std::to_string(size) + " texels per side in blocks of " + std::to_string(block) + smallest(block));
+	}
+	if (block_out) *block_out = b;
+	if (blocks_per_row_out) *blocks_per_row_out = size / b;
+	if (n_blocks_out) *n_blocks_out = (uint32_t)n_blocks;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_texture_free(rnb_ctx* c, rnb_mesh_texture* tex) try {
+	if (!c || !tex) return fail(RNB_ERR_INVALID, "null argument");
+	if (tex->uv) (void)hipFree(tex->uv);
+	if (tex->albedo) (void)hipFree(tex->albedo);
+	if (tex->normal) (void)hipFree(tex->normal);
+	if (tex->position) (void)hipFree(tex->position);
+	std::memset(tex, 0, sizeof(*tex));
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_bake_texture(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_mesh_texture_options* opt, rnb_mesh_texture* out, rnb_mesh_texture_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (out) std::memset(out, 0, sizeof(*out));
+	if (!c || !mesh || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: null argument");
+	if (opt->abi_version != RNB_MESH_TEXTURE_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: options abi_version mismatch (expected RNB_MESH_TEXTURE_ABI_VERSION)");
+	if (opt->size < RNB_MESH_TEXTURE_MIN_SIZE || opt->size > RNB_MESH_TEXTURE_MAX_SIZE) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: size must be 4 .. 8192");
+	if (opt->maps == 0 || (opt->maps & ~(RNB_MESH_TEXTURE_ALBEDO | RNB_MESH_TEXTURE_NORMAL | RNB_MESH_TEXTURE_POSITION)))
+		return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: maps must be a non-empty set of RNB_MESH_TEXTURE_ALBEDO, _NORMAL and _POSITION");
+	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: a reserved word of the options is not 0");
+	{
+		rnb_mesh unused;
+		if (int rc = check_mesh_input("rnb_mesh_bake_texture", mesh, &unused); rc != RNB_OK) return rc;
+	}
+	const rnb_mesh m = *mesh;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, S = opt->size;
+	MtAtlas A;
+	std::memset(&A, 0, sizeof(A));
+	uint32_t n_blocks = 0;
+	if (int rc = rnb_mesh_texture_layout(nt, S, opt->block, &A.block, &A.bpr, &n_blocks); rc != RNB_OK) return rc;
+	A.size = S; A.n_tris = nt;
+	A.n_texels = n_blocks * A.block * A.block; // at most S * S = 2^26
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
+
+	MeshWorkspace ws;
+	const size_t n_pix = (size_t)S * S;
+	const bool network = (opt->maps & (RNB_MESH_TEXTURE_ALBEDO | RNB_MESH_TEXTURE_NORMAL)) != 0;
+	float* uv = nullptr;
+	f4* map[3] = {nullptr, nullptr, nullptr}; // albedo, normal, position
+	if (!ws.alloc(&uv, (size_t)nt * 6)) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for the UVs of " + std::to_string(nt) + " triangles");
+	for (int k = 0; k < 3; ++k)
+		if (opt->maps & (1u << k)) {
+			if (!ws.alloc(&map[k], n_pix)) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for a map of " + std::to_string(S) + "^2 texels");
+			HIP_TRY(hipMemsetAsync(map[k], 0, n_pix * sizeof(f4), s));
+		}
+	uint32_t n_batches = 0;
+	if (nt) {
+		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
+		uint32_t *used = nullptr, *dflags = nullptr, hflags = 0;
+		if (!ws.alloc(&used, nv) || !ws.alloc(&dflags, 1)) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemsetAsync(dflags, 0, 4, s));
+		hipLaunchKernelGGL(k_mesh_validate, dim3((nt + MT_WG - 1) / MT_WG), dim3(MT_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, dflags, MT_BAD_INDEX);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hflags, dflags, 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hflags & MT_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: an index is out of range (>= n_verts)");
+		ws.release(used); ws.release(dflags);
+		// 2. the texels, in batches: positions, the corners' UVs and network inputs, the network, the maps
+		const uint32_t per_launch = std::min<uint32_t>(opt->max_texels_in_flight ? opt->max_texels_in_flight : (1u << 20), RNB_MESH_TEXTURE_MAX_IN_FLIGHT);
+		const uint32_t batch = std::min(per_launch, A.n_texels);
+		float* coords = nullptr;
+		half_t* net = nullptr;
+		if (network && (!ws.alloc(&coords, (size_t)batch * 7) || !ws.alloc(&net, (size_t)batch * 16))) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for a batch of " + std::to_string(batch) + " texels");
+		const float diag = c->aabb.mx - c->aabb.mn;
+		const bool inference = opt->use_inference_params != 0;
+		for (uint32_t w0 = 0; w0 < A.n_texels; w0 += batch) {
+			const uint32_t nb = std::min(batch, A.n_texels - w0);
+			hipLaunchKernelGGL(k_mt_texels, dim3((nb + MT_WG - 1) / MT_WG), dim3(MT_WG), 0, s, A, (const float*)m.verts, (const uint32_t*)m.indices, w0, nb, c->aabb.mn, diag, uv, map[2], coords);
+			HIP_TRY(hipGetLastError());
+			if (!network) continue;
+			if (int rc = launch_forward(c, s, coords, nullptr, nb, net, inference); rc != RNB_OK) return rc;
+			hipLaunchKernelGGL(k_mt_maps, dim3((nb + MT_WG - 1) / MT_WG), dim3(MT_WG), 0, s, A, (const half_t*)net, w0, nb, map[0], map[1]);
+			HIP_TRY(hipGetLastError());
+			++n_batches;
+		}
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(coords); ws.release(net);
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	out->uv = (float*)ws.keep(uv);
+	out->albedo = (float*)ws.keep(map[0]); out->normal = (float*)ws.keep(map[1]); out->position = (float*)ws.keep(map[2]);
+	out->size = S; out->block = A.block; out->blocks_per_row = A.bpr; out->n_tris = nt;
+	if (stats) {
+		stats->n_texels = network ? A.n_texels : 0u;
+		stats->n_batches = n_batches;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
 
 } // extern "C"

@@ -12,6 +12,7 @@
 #include "kernels_mesh_simplify.cuh"
 #include "kernels_mesh_distance.cuh"
 #include "kernels_mesh_raster.cuh"
+#include "kernels_mesh_texture.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>

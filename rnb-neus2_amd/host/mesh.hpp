@@ -80,4 +80,68 @@ inline void save_obj(const std::string& path, const Mesh& m, float nerf_scale, c
 	std::fclose(f);
 }
 
+// The atlas and the maps of rnb_mesh_bake_texture (include/rnb_mesh_texture.h) on the host: uv float[nt][3][2], albedo / normal float[size][size][4] or empty.
+struct Texture {
+	std::vector<float> uv, albedo, normal;
+	uint32_t size = 0;
+};
+// png16::save, handed in by the caller (this header is also read where zlib is not).
+using PngSave = void (*)(const std::string& path, const void* data, uint32_t w, uint32_t h, int channels, int depth, int level);
+
+// save_obj with a texture: `path` = X.obj gets three `vt` records per triangle and `f a/t/n` faces, X.mtl names the images, X_albedo.png (8-bit RGB,
+// floor(255 * clip(c) + 0.5), the values as they are, like the vertex colours) and X_normal.png (16-bit RGB of n * 0.5 + 0.5) are written for the maps the texture has.
+// The same position transform and the same face reversal rule as save_obj; corner `q` of triangle t names vt 3 t + q + 1, and keeps it when the face is reversed.
+inline void save_obj_textured(const std::string& path, const Mesh& m, const Texture& tex, PngSave save_png, float nerf_scale, const float nerf_offset[3], float n2w_s, const float n2w_t[3],
+                              bool invert_normals = true) {
+	const size_t dot = path.rfind('.'), slash = path.find_last_of('/');
+	const std::string stem = (dot != std::string::npos && (slash == std::string::npos || dot > slash)) ? path.substr(0, dot) : path;
+	const std::string base = slash == std::string::npos ? stem : stem.substr(slash + 1);
+	const size_t n_pix = (size_t)tex.size * tex.size;
+	if (tex.uv.size() != m.indices.size() * 2) throw std::runtime_error("save_obj_textured: the atlas does not belong to the mesh");
+	if ((!tex.albedo.empty() && tex.albedo.size() != n_pix * 4) || (!tex.normal.empty() && tex.normal.size() != n_pix * 4)) throw std::runtime_error("save_obj_textured: a map of the wrong size");
+	auto unit = [](double x) { return x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x); };
+	if (!tex.albedo.empty()) {
+		std::vector<uint8_t> img(n_pix * 3);
+		for (size_t p = 0; p < n_pix; ++p)
+			for (int k = 0; k < 3; ++k) img[p * 3 + k] = (uint8_t)std::floor(255.0 * unit((double)tex.albedo[p * 4 + k]) + 0.5);
+		save_png(stem + "_albedo.png", img.data(), tex.size, tex.size, 3, 8, 1);
+	}
+	if (!tex.normal.empty()) {
+		std::vector<uint16_t> img(n_pix * 3);
+		for (size_t p = 0; p < n_pix; ++p)
+			for (int k = 0; k < 3; ++k) img[p * 3 + k] = (uint16_t)std::floor(65535.0 * unit((double)tex.normal[p * 4 + k] * 0.5 + 0.5) + 0.5);
+		save_png(stem + "_normal.png", img.data(), tex.size, tex.size, 3, 16, 1);
+	}
+	FILE* f = std::fopen((stem + ".mtl").c_str(), "wb");
+	if (!f) throw std::runtime_error("cannot write " + stem + ".mtl");
+	std::fprintf(f, "newmtl baked\nKa 1.000 1.000 1.000\nKd 1.000 1.000 1.000\nKs 0.000 0.000 0.000\nillum 1\n");
+	if (!tex.albedo.empty()) std::fprintf(f, "map_Kd %s_albedo.png\n", base.c_str());
+	if (!tex.normal.empty()) std::fprintf(f, "norm %s_normal.png\n", base.c_str());
+	std::fclose(f);
+	f = std::fopen(path.c_str(), "wb");
+	if (!f) throw std::runtime_error("cannot write " + path);
+	std::fprintf(f, "mtllib %s.mtl\n", base.c_str());
+	for (size_t i = 0; i < m.verts.size(); ++i) {
+		const Vec3 v = m.verts[i];
+		const float p[3] = {n2w_s * ((v.x - nerf_offset[0]) / nerf_scale) + n2w_t[0], n2w_s * ((v.y - nerf_offset[1]) / nerf_scale) + n2w_t[1], n2w_s * ((v.z - nerf_offset[2]) / nerf_scale) + n2w_t[2]};
+		const Vec3 c = i < m.colors.size() ? m.colors[i] : Vec3{1.f, 1.f, 1.f};
+		auto cl = [](float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); };
+		std::fprintf(f, "v %0.5f %0.5f %0.5f %0.3f %0.3f %0.3f\n", p[0], p[1], p[2], cl(c.x), cl(c.y), cl(c.z));
+	}
+	for (size_t i = 0; i + 1 < tex.uv.size(); i += 2) std::fprintf(f, "vt %.9g %.9g\n", tex.uv[i], tex.uv[i + 1]);
+	for (const Vec3& n0 : m.normals) {
+		Vec3 n = {n2w_s * n0.x, n2w_s * n0.y, n2w_s * n0.z};
+		const float l = std::sqrt(n.x * n.x + n.y * n.y + n.z * n.z);
+		if (l > 0.f) { n.x /= l; n.y /= l; n.z /= l; }
+		std::fprintf(f, "vn %0.5f %0.5f %0.5f\n", n.x, n.y, n.z);
+	}
+	std::fprintf(f, "usemtl baked\n");
+	for (size_t i = 0; i + 2 < m.indices.size(); i += 3) {
+		const size_t qa = invert_normals ? 0 : 2, qc = invert_normals ? 2 : 0;
+		const uint32_t a = m.indices[i + qa] + 1, b = m.indices[i + 1] + 1, c = m.indices[i + qc] + 1;
+		std::fprintf(f, "f %u/%zu/%u %u/%zu/%u %u/%zu/%u\n", a, i + qa + 1, a, b, i + 2, b, c, i + qc + 1, c);
+	}
+	std::fclose(f);
+}
+
 } // namespace mesh

@@ -4,6 +4,7 @@
 //
 //   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
 //        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean] [--report-error]] [--report-views [--views-out FILE]]
+//        [--texture S [--texture-maps albedo[,normal]]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -17,6 +18,9 @@
 // With --report-views the final mesh, still on the device and in the frame of the loaded views (before save_obj's scale and shift), is rasterised into every camera of the
 // scene (rnb_mesh_raster, include/rnb_mesh_raster.h, default options) and compared with the input normal maps by view_metrics.hpp, as build/render compares the model's
 // render: one line per view, the means, and <out>.views.json (or --views-out FILE) with the fields of render_metrics.json plus n_back_pixels and odd_count_pixels per view.
+// With --texture S the mesh as finally written (after --keep, --orient and --simplify), still on the device, gets a texture bake (rnb_mesh_bake_texture,
+// include/rnb_mesh_texture.h): a per-triangle atlas of S x S texels and the model's albedo (and, with --texture-maps albedo,normal, its SDF-gradient normal) at every
+// texel. The output is then FILE.obj with vt records (mesh::save_obj_textured), FILE.mtl, FILE_albedo.png and FILE_normal.png.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -24,6 +28,7 @@
 #include "../../include/rnb_mesh_simplify.h"
 #include "../../include/rnb_mesh_distance.h"
 #include "../../include/rnb_mesh_raster.h"
+#include "../../include/rnb_mesh_texture.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -63,6 +68,8 @@ const Flag FLAGS[] = {
 	{"report-error", nullptr, "--simplify only (takes no value). Measure the distance between the mesh before and after the simplification, both directions, and print it."},
 	{"report-views", nullptr, "(takes no value). Rasterise the final mesh into every camera of the scene and compare it with the input normal maps: normal angle and mask IoU per view."},
 	{"views-out", "FILE", "--report-views only. Where the per-view report is written (default: the output mesh's path + .views.json)."},
+	{"texture", "S", "Bake a texture of S x S texels (4 .. 8192) for the final mesh on the device: FILE.obj gets vt records, FILE.mtl and FILE_albedo.png are written beside it."},
+	{"texture-maps", "LIST", "--texture only. The maps to bake, separated by commas: albedo (default), normal (the SDF gradient, object space, FILE_normal.png)."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -171,6 +178,7 @@ int main(int argc, char** argv) {
 	uint32_t keep = RNB_MESH_KEEP_ALL, orient = RNB_MESH_ORIENT_NONE; // with one of the two flags given, the other one leaves its part alone
 	uint32_t simplify = 0, placement = RNB_MESH_PLACE_QUADRIC;           // 0: no simplification
 	bool report_error = false, want_views = false;
+	uint32_t texture = 0, texture_maps = RNB_MESH_TEXTURE_ALBEDO; // 0: no texture
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -213,6 +221,21 @@ int main(int argc, char** argv) {
 		}
 		if (a.count("report-views")) want_views = true;
 		if (a.count("views-out") && !want_views) throw ParseError("Argument 'views-out' is only used with --report-views");
+		if (a.count("texture")) {
+			texture = parse_u32("texture", a["texture"]);
+			if (texture < RNB_MESH_TEXTURE_MIN_SIZE || texture > RNB_MESH_TEXTURE_MAX_SIZE) throw ParseError("Argument 'texture' must be 4 .. 8192");
+		}
+		if (a.count("texture-maps")) {
+			if (!texture) throw ParseError("Argument 'texture-maps' is only used with --texture");
+			texture_maps = 0;
+			const std::string list = a["texture-maps"] + ",";
+			for (size_t p = 0, q; (q = list.find(',', p)) != std::string::npos; p = q + 1) {
+				const std::string name = list.substr(p, q - p);
+				if (name == "albedo") texture_maps |= RNB_MESH_TEXTURE_ALBEDO;
+				else if (name == "normal") texture_maps |= RNB_MESH_TEXTURE_NORMAL;
+				else throw ParseError("Argument 'texture-maps' must be a list of albedo and normal");
+			}
+		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
 		print_help(std::cerr, argv[0]);
@@ -224,8 +247,10 @@ int main(int argc, char** argv) {
 
 	rnb_ctx* ctx = nullptr;
 	rnb_mesh dm, cm;
+	rnb_mesh_texture dt;
 	std::memset(&dm, 0, sizeof(dm));
 	std::memset(&cm, 0, sizeof(cm));
+	std::memset(&dt, 0, sizeof(dt));
 	try {
 		const Dataset ds = load_dataset(scene);
 		const snapshot::Data sd = snapshot::read(snap_path);
@@ -293,6 +318,24 @@ int main(int argc, char** argv) {
 		// --report-views: made here, while the mesh is on the device and in the frame of the loaded views; printed and written after the mesh's own lines, below
 		std::string views_report, views_json;
 		if (want_views) report_views(ctx, ds, dm, snap_path, views_report, views_json);
+		// --texture: the mesh as it will be written, while it is on the device
+		mesh::Texture tex;
+		rnb_mesh_texture_stats ts;
+		if (texture) {
+			rnb_mesh_texture_options to;
+			RNB_CHECK(rnb_mesh_texture_default_options(&to));
+			to.size = texture; to.maps = texture_maps;
+			RNB_CHECK(rnb_mesh_bake_texture(ctx, nullptr, &dm, &to, &dt, &ts));
+			tex.size = dt.size;
+			tex.uv.resize((size_t)dt.n_tris * 6);
+			if (dt.n_tris) RNB_CHECK(rnb_memcpy(ctx, tex.uv.data(), dt.uv, (uint64_t)tex.uv.size() * 4, RNB_D2H));
+			const uint64_t n_map = (uint64_t)dt.size * dt.size * 4;
+			if (dt.albedo) { tex.albedo.resize(n_map); RNB_CHECK(rnb_memcpy(ctx, tex.albedo.data(), dt.albedo, n_map * 4, RNB_D2H)); }
+			if (dt.normal) { tex.normal.resize(n_map); RNB_CHECK(rnb_memcpy(ctx, tex.normal.data(), dt.normal, n_map * 4, RNB_D2H)); }
+			std::printf("texture: %u^2 texels, blocks of %u (%u per row) for %u triangles, %llu texels through the network in %u batches, peak workspace %.1f MB, %.1f ms\n", dt.size, dt.block,
+			            dt.blocks_per_row, dt.n_tris, (unsigned long long)ts.n_texels, ts.n_batches, (double)ts.peak_workspace / 1e6, ts.ms);
+			RNB_CHECK(rnb_mesh_texture_free(ctx, &dt));
+		}
 		mesh::Mesh m;
 		m.verts.resize(dm.n_verts); m.colors.resize(dm.n_verts); m.indices.resize(dm.n_indices);
 		if (dm.n_verts) {
@@ -333,11 +376,13 @@ int main(int argc, char** argv) {
 		// --orient outward speaks of the file: the device turned every kept component counter-clockwise seen from outside, and the faces are written as they are
 		// (without it, the scene's from_na flag decides whether save_obj reverses them, as in the testbed). save_obj maps positions by a uniform scale and a shift,
 		// which keeps the winding as long as the scales are positive (scale > 0 and n2w_s > 0, as every scene the loader accepts has them).
-		mesh::save_obj(a["out"], m, ds.scale, ds.offset, ds.n2w_s, ds.n2w_t, (clean && orient == RNB_MESH_ORIENT_OUTWARD) ? true : ds.from_na);
+		const bool as_they_are = (clean && orient == RNB_MESH_ORIENT_OUTWARD) ? true : ds.from_na;
+		if (texture) mesh::save_obj_textured(a["out"], m, tex, png16::save, ds.scale, ds.offset, ds.n2w_s, ds.n2w_t, as_they_are);
+		else mesh::save_obj(a["out"], m, ds.scale, ds.offset, ds.n2w_s, ds.n2w_t, as_they_are);
 		rnb_destroy(ctx);
 	} catch (const std::exception& e) {
 		std::fprintf(stderr, "Uncaught exception: %s\n", e.what());
-		if (ctx) { rnb_mesh_free(ctx, &dm); rnb_mesh_free(ctx, &cm); rnb_destroy(ctx); }
+		if (ctx) { rnb_mesh_free(ctx, &dm); rnb_mesh_free(ctx, &cm); rnb_mesh_texture_free(ctx, &dt); rnb_destroy(ctx); }
 		return 1;
 	}
 	return 0;

@@ -125,3 +125,54 @@ def save_obj(path, mesh):
             f.write("vn %.8f %.8f %.8f\n" % (q[0], q[1], q[2]))
         for a, b, c in mesh.faces + 1:
             f.write("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c))
+
+
+def texture_albedo_u8(albedo):
+    """The albedo PNG's samples: uint8 RGB, floor(255 * clip(c, 0, 1) + 0.5) of channels 0-2, the values as they are (no colour-space transform), like the vertex colours."""
+    c = np.clip(np.asarray(albedo, np.float32)[..., :3].astype(np.float64), 0.0, 1.0)
+    return np.floor(255.0 * c + 0.5).astype(np.uint8)
+
+
+def texture_normal_u16(normal):
+    """The normal PNG's samples: uint16 RGB, floor(65535 * clip(n * 0.5 + 0.5, 0, 1) + 0.5) of channels 0-2: an object-space normal map (a texel without a triangle is mid-grey)."""
+    c = np.clip(np.asarray(normal, np.float32)[..., :3].astype(np.float64) * 0.5 + 0.5, 0.0, 1.0)
+    return np.floor(65535.0 * c + 0.5).astype(np.uint16)
+
+
+def save_obj_textured(path, mesh, uv, maps):
+    """A mesh with the atlas of Context.bake_texture: `path` = X.obj gets `vt` records (three per triangle, in the order of `uv` float32[nt, 3, 2]) and `f a/t/n` faces
+    whose corner `corner` of triangle t names vt 3 t + corner + 1; X.mtl names the images; X_albedo.png (8-bit RGB, texture_albedo_u8) and X_normal.png (16-bit RGB,
+    texture_normal_u16) are written for the maps of those names in `maps` (name -> float32[S, S, 4], row 0 = the top row); other entries are ignored. The PNGs go through hostlib.png_write."""
+    import os
+    from . import hostlib
+
+    uv = np.asarray(uv, np.float32).reshape(-1, 3, 2)
+    if len(uv) != len(mesh.faces):
+        raise ValueError("uv must have one row of three corners per triangle")
+    stem = os.path.splitext(str(path))[0]
+    base = os.path.basename(stem)
+    images = {}
+    if maps.get("albedo") is not None:
+        images["albedo"] = base + "_albedo.png"
+        hostlib.png_write(stem + "_albedo.png", texture_albedo_u8(maps["albedo"]))
+    if maps.get("normal") is not None:
+        images["normal"] = base + "_normal.png"
+        hostlib.png_write(stem + "_normal.png", texture_normal_u16(maps["normal"]))
+    with open(stem + ".mtl", "w") as f:
+        f.write("newmtl baked\nKa 1.000 1.000 1.000\nKd 1.000 1.000 1.000\nKs 0.000 0.000 0.000\nillum 1\n")
+        if "albedo" in images:
+            f.write("map_Kd %s\n" % images["albedo"])
+        if "normal" in images:
+            f.write("norm %s\n" % images["normal"])
+    n = mesh.vertex_normals()
+    with open(path, "w") as f:
+        f.write("mtllib %s.mtl\n" % base)
+        for v in mesh.vertices:
+            f.write("v %.8f %.8f %.8f\n" % (v[0], v[1], v[2]))
+        for q in uv.reshape(-1, 2):
+            f.write("vt %.9g %.9g\n" % (q[0], q[1]))
+        for q in n:
+            f.write("vn %.8f %.8f %.8f\n" % (q[0], q[1], q[2]))
+        f.write("usemtl baked\n")
+        for t, (a, b, c) in enumerate(mesh.faces + 1):
+            f.write("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % (a, 3 * t + 1, a, b, 3 * t + 2, b, c, 3 * t + 3, c))

@@ -38,6 +38,7 @@ _SPEC = """
 --mesh-exe          | str   |        | --device-postprocess only: the mesh executable (default: build/mesh beside the testbed)
 --simplify          | int   |        | --device-postprocess only: simplify the final mesh on the GPU by vertex clustering on N^3 cells over the scene box (build/mesh --simplify N)
 --report-views      | flag  |        | --device-postprocess only: rasterise the final mesh into every input view and write its normal angle and mask IoU per view (build/mesh --report-views)
+--texture           | int   |        | --device-postprocess only: bake an albedo texture of S x S texels for the final mesh on the GPU; mesh.mtl and mesh_albedo.png beside mesh.obj (build/mesh --texture S)
 """
 
 
@@ -66,7 +67,7 @@ def pipeline_kwargs(ns):
     """argparse namespace -> keywords of rnb_neus2_amd.pipeline.run_full_pipeline."""
     renamed = {"input": "input_path", "testbed": "testbed_path", "output": "output_dir", "supernormal": "super_normal", "l1": "use_l1",
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
-    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views")}
+    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
@@ -75,6 +76,8 @@ def pipeline_kwargs(ns):
             kw["simplify"] = ns.simplify
         if ns.report_views:
             kw["report_views"] = True
+        if ns.texture is not None:
+            kw["texture"] = ns.texture
     return kw
 
 
@@ -87,6 +90,10 @@ def main(argv=None):
         parser.error("--simplify is only used with --device-postprocess")
     if ns.report_views and not ns.device_postprocess:
         parser.error("--report-views is only used with --device-postprocess")
+    if ns.texture is not None and not ns.device_postprocess:
+        parser.error("--texture is only used with --device-postprocess")
+    if ns.texture is not None and not 4 <= ns.texture <= 8192:
+        parser.error("--texture must be 4 .. 8192")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
         parser.error("--simplify must be 1 .. 1024")
     np.random.seed(ns.seed)
