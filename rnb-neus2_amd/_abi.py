@@ -539,6 +539,111 @@ MESH_TEXTURE_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_visibility.h: what a set of cameras sees of a device mesh, per triangle, and the mesh without the rest; a header of its own with its own version (the HIP library only) ----
+MESH_VISIBILITY_ABI_VERSION = 1
+MESH_VISIBILITY_NONE, MESH_VISIBILITY_MAX_RINGS = 0xFFFFFFFF, 64
+MESH_VISIBILITY_UNIT_COMPONENT, MESH_VISIBILITY_UNIT_FACE = 0, 1
+
+
+class MeshVisibilityView(C.Structure):
+    _fields_ = [
+        ("view", View),
+        ("mask_dev", C.c_void_p),
+        ("mask_width", C.c_uint32),
+        ("mask_height", C.c_uint32),
+    ]
+
+
+class MeshVisibilityOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("near", C.c_float),
+        ("cull", C.c_uint32),
+        ("min_pixels", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshFaceVisibility(C.Structure):
+    _fields_ = [
+        ("n_drawn", C.c_uint32),
+        ("n_seen", C.c_uint32),
+        ("n_off_mask", C.c_uint32),
+        ("best_view", C.c_uint32),
+        ("best_pixels", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_pixels_won", C.c_uint64),
+        ("n_pixels_covered", C.c_uint64),
+    ]
+
+
+# one record of rnb_mesh_face_visibility as a numpy structured dtype (40 bytes)
+MESH_FACE_VISIBILITY_DTYPE = [("n_drawn", "<u4"), ("n_seen", "<u4"), ("n_off_mask", "<u4"), ("best_view", "<u4"), ("best_pixels", "<u4"), ("reserved", "<u4"),
+                              ("n_pixels_won", "<u8"), ("n_pixels_covered", "<u8")]
+
+
+class MeshVisibilityStats(C.Structure):
+    _fields_ = [
+        ("n_tris", C.c_uint32),
+        ("n_views", C.c_uint32),
+        ("n_behind", C.c_uint64),
+        ("n_out_of_range", C.c_uint64),
+        ("n_degenerate", C.c_uint64),
+        ("n_culled", C.c_uint64),
+        ("n_offscreen", C.c_uint64),
+        ("n_small", C.c_uint64),
+        ("n_large", C.c_uint64),
+        ("n_pixels", C.c_uint64),
+        ("n_faces_seen", C.c_uint32),
+        ("n_faces_off_mask", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+class MeshVisibilitySelectOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("unit", C.c_uint32),
+        ("min_views_seen", C.c_uint32),
+        ("max_views_off_mask", C.c_uint32),
+        ("rings", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+class MeshVisibilitySelectStats(C.Structure):
+    _fields_ = [
+        ("n_verts_in", C.c_uint32),
+        ("n_verts_out", C.c_uint32),
+        ("n_tris_in", C.c_uint32),
+        ("n_tris_out", C.c_uint32),
+        ("n_seeds", C.c_uint32),
+        ("n_candidates", C.c_uint32),
+        ("n_components", C.c_uint32),
+        ("n_components_kept", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_VISIBILITY_PROTOTYPES = {
+    "mesh_visibility_abi_version": (_u32, []),
+    "mesh_visibility_default_options": (_i, [C.POINTER(MeshVisibilityOptions)]),
+    "mesh_visibility_select_default_options": (_i, [C.POINTER(MeshVisibilitySelectOptions)]),
+    "mesh_visibility": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshVisibilityView), _u32, C.POINTER(MeshVisibilityOptions), C.c_void_p, C.POINTER(MeshVisibilityStats)]),
+    "mesh_visibility_select": (_i, [_ctx, _stream, C.POINTER(Mesh), C.c_void_p, C.POINTER(MeshVisibilitySelectOptions), C.POINTER(Mesh), C.c_void_p, C.POINTER(MeshVisibilitySelectStats)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -559,10 +664,12 @@ class Functions:
             raise ImportError("library %s lacks symbols: %s" % (getattr(lib, "_name", lib), ", ".join(missing)))
 
 
-def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False):
+def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
+            mesh_visibility=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
-    mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h); only the HIP library exports those."""
+    mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
+    mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
-                     + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()))
+                     + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ()))

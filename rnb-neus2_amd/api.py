@@ -46,7 +46,8 @@ def load_library():
                 "%s not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()'). "
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True)
+        _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
+                              mesh_visibility=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -63,6 +64,8 @@ def load_library():
             raise RuntimeError("mesh-raster ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_texture_abi_version() != _abi.MESH_TEXTURE_ABI_VERSION:
             raise RuntimeError("mesh-texture ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_visibility_abi_version() != _abi.MESH_VISIBILITY_ABI_VERSION:
+            raise RuntimeError("mesh-visibility ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -553,7 +556,7 @@ class Context:
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
-                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",)):
+                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -568,7 +571,12 @@ class Context:
         mesh_distance(input, output, symmetric=True), A = the simplifier's input (a simplification that leaves no triangle fails the call: there is nothing to measure against). With False (the default) nothing
         of that runs and the result is as it was.
         texture = S: the final mesh (after keep, orient and simplify), still on the device, gets a texture bake of S texels per side (rnb_mesh_bake_texture, see
-        bake_texture) with the maps of `texture_maps`, and the dict gains `texture`: the dict of DeviceMesh.bake_texture. With None (the default) nothing of that runs."""
+        bake_texture) with the maps of `texture_maps`, and the dict gains `texture`: the dict of DeviceMesh.bake_texture. With None (the default) nothing of that runs.
+        seen_by = views: after keep / orient and before simplify, still on the device, what none of these cameras sees is removed (DeviceMesh.cull_unseen with its
+        defaults: whole components, see cull_unseen_mesh; seen_masks = one mask or None per view), and the dict gains `seen_stats` (the select stats) and
+        `visibility_stats`. With None (the default) nothing of that runs and the calls made are exactly those made without it."""
+        if seen_masks is not None and seen_by is None:
+            raise ValueError("seen_masks needs seen_by")
         if error and simplify is None:
             raise ValueError("error=True needs simplify")
         grid = None if simplify is None else self.simplify_grid(aabb_min, aabb_max, simplify)
@@ -577,6 +585,9 @@ class Context:
         try:  # device to device: the extracted mesh never visits the host
             if keep is not None or orient is not None:
                 chain.append(chain[-1].clean("all" if keep is None else keep, "none" if orient is None else orient, stream=stream))
+            if seen_by is not None:
+                culled, seen = chain[-1].cull_unseen(seen_by, seen_masks, stream=stream, report=True)
+                chain.append(culled)
             if grid is not None:
                 chain.append(chain[-1].simplify(*grid, placement=placement, stream=stream))
                 if error:
@@ -589,6 +600,8 @@ class Context:
                 out["texture"] = baked
             if grid is not None and error:
                 out["simplify_error"] = simplify_error
+            if seen_by is not None:
+                out["seen_stats"], out["visibility_stats"] = seen["select"], seen["visibility"]
             if keep is not None or orient is not None:
                 out["clean_stats"] = chain[1].stats
             if grid is not None:
@@ -758,6 +771,82 @@ class Context:
                 per_view.append(e)
         k = max(len(per_view), 1)
         return dict(views=per_view, mean={key: sum(e[key] for e in per_view) / k for key in ("mean_angle_deg", "median_angle_deg", "mask_iou")})
+
+    def _visibility_options(self, near, cull, min_pixels):
+        culls = {"none": _abi.MESH_RASTER_CULL_NONE, "back": _abi.MESH_RASTER_CULL_BACK, "front": _abi.MESH_RASTER_CULL_FRONT}
+        if cull not in culls:
+            raise ValueError("cull must be 'none', 'back' or 'front'")
+        if int(min_pixels) < 1:
+            raise ValueError("min_pixels must be at least 1")
+        opt = _abi.MeshVisibilityOptions()
+        self._check(self.f.mesh_visibility_default_options(C.byref(opt)))
+        opt.near, opt.cull, opt.min_pixels = float(near), culls[cull], int(min_pixels)
+        return opt
+
+    @staticmethod
+    def _visibility_views(views, masks, supersample):
+        """The host array of rnb_mesh_visibility_view for `views` (each through scaled_view(view, supersample) when that is not 1), the masks not yet attached."""
+        views = list(views)
+        if not views:
+            raise ValueError("at least one view")
+        if masks is not None and len(masks) != len(views):
+            raise ValueError("one mask (or None) per view")
+        for mk in masks or ():
+            if mk is not None and (np.ndim(mk) != 2 or 0 in np.shape(mk)):
+                raise ValueError("a mask must be a non-empty 2-D array")
+        k = int(supersample)
+        if k != supersample or k < 1:
+            raise ValueError("supersample must be a positive integer")
+        if k != 1:
+            views = [scaled_view(v, k) for v in views]
+        if any(max(int(v["width"]), int(v["height"])) > _abi.MESH_RASTER_MAX_SIZE for v in views):
+            raise ValueError("a view times supersample exceeds %d pixels per side" % _abi.MESH_RASTER_MAX_SIZE)
+        arr = (_abi.MeshVisibilityView * len(views))()
+        for e, v in zip(arr, views):
+            e.view = _view_struct(v)
+        return arr
+
+    def _visibility_select_options(self, unit, min_views, max_off_mask, rings):
+        units = {"component": _abi.MESH_VISIBILITY_UNIT_COMPONENT, "face": _abi.MESH_VISIBILITY_UNIT_FACE, "faces": _abi.MESH_VISIBILITY_UNIT_FACE}
+        if unit not in units:
+            raise ValueError("unit must be 'component' or 'face'")
+        if not 0 <= int(rings) <= _abi.MESH_VISIBILITY_MAX_RINGS:
+            raise ValueError("rings must be 0 .. %d" % _abi.MESH_VISIBILITY_MAX_RINGS)
+        if int(min_views) < 0 or (max_off_mask is not None and int(max_off_mask) < 0):
+            raise ValueError("min_views and max_off_mask must not be negative")
+        opt = _abi.MeshVisibilitySelectOptions()
+        self._check(self.f.mesh_visibility_select_default_options(C.byref(opt)))
+        opt.unit, opt.min_views_seen, opt.rings = units[unit], int(min_views), int(rings)
+        opt.max_views_off_mask = 0xFFFFFFFF if max_off_mask is None else min(int(max_off_mask), 0xFFFFFFFF)
+        return opt
+
+    def mesh_visibility(self, verts, indices, views, masks=None, near=2.0 ** -10, cull="none", min_pixels=1, supersample=1, stream=None):
+        """rnb_mesh_visibility (include/rnb_mesh_visibility.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3]) and a list of cameras (view dicts as
+        rasterize_mesh takes one): what the cameras see, per triangle, counted on the device over all views in one call. Returns (records, stats): `records` a numpy
+        structured array, one per triangle in the mesh's order, of n_drawn (views that draw it), n_seen (views in which it wins at least min_pixels pixels: the
+        rasteriser's winner of a pixel, the nearest triangle over its centre), n_off_mask (views in which less than half of the pixel centres it covers are on the
+        mask), best_view (the view in which it wins the most pixels, 0xFFFFFFFF if none), best_pixels, n_pixels_won, n_pixels_covered; `stats` the dict of
+        rnb_mesh_visibility_stats (the rasteriser's class counts summed over the views, n_faces_seen, n_faces_off_mask, n_pixels, peak_workspace, ms).
+        masks: None, or per view None or a 2-D array, non-zero = object, of any resolution (a view pixel reads the mask pixel whose area holds its centre). near, cull: as
+        rasterize_mesh. supersample=k: every view goes through scaled_view(view, k), the masks stay as given. All integers: bit-reproducible. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices) as m:
+            return m.visibility(views, masks, near, cull, min_pixels, supersample, stream=stream)
+
+    def cull_unseen_mesh(self, verts, indices, views, masks=None, colors=None, normals=None, unit="component", min_views=1, max_off_mask=None, rings=1, near=2.0 ** -10, cull="none",
+                         min_pixels=1, supersample=1, stream=None):
+        """A host mesh without what the cameras do not see: rnb_mesh_visibility, then rnb_mesh_visibility_select (include/rnb_mesh_visibility.h). A triangle is a
+        candidate if it lies off the mask in at most max_off_mask views (None: the masks carve nothing) and a seed if it is a candidate that at least min_views views
+        see. unit="component" (the default): the connected components are those of clean_mesh, and the candidates of every component that holds a seed are kept -- a
+        cavity shell inside the object goes, closed surfaces stay closed, a second object any camera saw stays. unit="face": the seeds and, `rings` times, every candidate
+        that shares a vertex with a kept triangle; a side of a closed surface that no camera saw becomes a hole. Returns a dict of numpy arrays like clean_mesh (verts,
+        indices, colors / normals when given, in the input's order), `kept` uint32[n_triangles] (1 for a kept triangle of the input), `stats` (the select stats) and
+        `visibility_stats`. The other arguments are those of mesh_visibility. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            culled, rep = m.cull_unseen(views, masks, unit, min_views, max_off_mask, rings, near, cull, min_pixels, supersample, stream, report=True)
+        with culled:
+            out = culled.download()
+            out.update(kept=rep["kept"], stats=rep["select"], visibility_stats=rep["visibility"])
+        return out
 
     def _texture_options(self, size, block, maps, inference, max_texels_in_flight):
         if isinstance(maps, str):
@@ -1034,6 +1123,70 @@ class DeviceMesh(_abi.Mesh):
             for p in own:
                 c.device_free(p)
         return out
+
+    def visibility(self, views, masks=None, near=2.0 ** -10, cull="none", min_pixels=1, supersample=1, on_device=False, stream=None):
+        """rnb_mesh_visibility of this mesh in all of `views` at once: (records, stats), described by Context.mesh_visibility. on_device=True: the records stay on the
+        device and `records` is the pointer to n_triangles records of 40 bytes, which the caller releases with Context.device_free."""
+        c = self._live()
+        opt, varr = c._visibility_options(near, cull, min_pixels), c._visibility_views(views, masks, supersample)
+        st = _abi.MeshVisibilityStats()
+        nt, own, faces = self.n_triangles, [], None
+        rec = np.dtype(_abi.MESH_FACE_VISIBILITY_DTYPE)
+        try:
+            for k, mk in enumerate(masks or ()):
+                if mk is not None:
+                    a = np.ascontiguousarray(np.asarray(mk) != 0, dtype=np.uint8)
+                    varr[k].mask_height, varr[k].mask_width = a.shape
+                    own.append(c.upload(a) if a.size else c.device_malloc(4))
+                    varr[k].mask_dev = own[-1]
+            faces = c.device_malloc(max(nt, 1) * rec.itemsize)
+            c._check(c.f.mesh_visibility(c._h, _stream_handle(stream), C.byref(self), varr, len(varr), C.byref(opt), faces, C.byref(st)))
+            if on_device:
+                out, faces = faces, None
+            else:
+                out = c.download(faces, nt, rec) if nt else np.empty(0, rec)
+        finally:
+            for p in own + ([faces] if faces else []):
+                c.device_free(p)
+        return out, st.as_dict()
+
+    def select_seen(self, records_ptr, unit="component", min_views=1, max_off_mask=None, rings=1, kept=False, stream=None):
+        """rnb_mesh_visibility_select on the records visibility(on_device=True) left on the device -> the DeviceMesh of what is kept; its `stats` are the select stats, with
+        kept=True also `kept`: uint32[n_triangles], 1 for a kept triangle of this mesh. The arguments are those of Context.cull_unseen_mesh."""
+        c = self._live()
+        opt, st = c._visibility_select_options(unit, min_views, max_off_mask, rings), _abi.MeshVisibilitySelectStats()
+        nt, flags = self.n_triangles, None
+        try:
+            if kept:
+                flags = c.device_malloc(max(nt, 1) * 4)
+            out = _returned_mesh(c, st, lambda m: c.f.mesh_visibility_select(c._h, _stream_handle(stream), C.byref(self), records_ptr, C.byref(opt), m, flags, C.byref(st)))
+            if kept:
+                try:
+                    out._stats["kept"] = c.download(flags, nt, np.uint32) if nt else np.empty(0, np.uint32)
+                except BaseException:
+                    out.free()
+                    raise
+        finally:
+            if flags:
+                c.device_free(flags)
+        return out
+
+    def cull_unseen(self, views, masks=None, unit="component", min_views=1, max_off_mask=None, rings=1, near=2.0 ** -10, cull="none", min_pixels=1, supersample=1, stream=None,
+                    report=False):
+        """This mesh without what the cameras do not see: visibility, then select_seen, the records released whether or not a stage fails -> the DeviceMesh of what is kept
+        (its `stats`: the select stats). report=True: (mesh, dict(visibility=the statistics of the measurement, select=those of the selection, kept=uint32[n_triangles])).
+        The arguments are those of Context.cull_unseen_mesh."""
+        c = self._live()
+        c._visibility_select_options(unit, min_views, max_off_mask, rings)  # a bad argument fails before anything is measured
+        records, vis = self.visibility(views, masks, near, cull, min_pixels, supersample, on_device=True, stream=stream)
+        try:
+            out = self.select_seen(records, unit, min_views, max_off_mask, rings, kept=report, stream=stream)
+        finally:
+            c.device_free(records)
+        if not report:
+            return out
+        sel = dict(out.stats)
+        return out, dict(visibility=vis, select=sel, kept=sel.pop("kept"))
 
     def bake_texture(self, size, block=0, maps=("albedo",), inference=True, max_texels_in_flight=0, stream=None):
         """rnb_mesh_bake_texture of this mesh: the dict of Context.bake_texture, which describes every argument and key. The device result is downloaded and released

@@ -1,5 +1,6 @@
 // driver_mesh.hpp -- rnb_sdf_lattice, what the mesh drivers share (scan_exclusive, count_and_scan, MeshWorkspace, check_mesh_input, alloc_mesh, hand_over,
-// ensure_mc_table), rnb_marching_cubes and the stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_bake_texture.
+// ensure_mc_table), rnb_marching_cubes and the stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_visibility,
+// rnb_mesh_visibility_select, rnb_mesh_bake_texture.
 // Needs, of rnb_neus2_hip.hip, which includes it: the context (aabb, bitfield, cfg, mc_table), as_stream, fail / HIP_TRY / RNB_GUARD, launch_point_query
 // and launch_forward.
 extern "C" {
@@ -34,7 +35,7 @@ int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float latti
 	return RNB_OK;
 } RNB_GUARD
 
-// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_bake_texture) ----
+// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_visibility, rnb_mesh_bake_texture) ----
 extern "C++" {
 namespace {
 // elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
@@ -720,6 +721,62 @@ int rnb_mesh_raster_default_options(rnb_mesh_raster_options* opt) try {
 	return RNB_OK;
 } RNB_GUARD
 
+extern "C++" {
+namespace {
+// What rnb_mesh_raster and rnb_mesh_visibility ask of a camera, said in the entry point's name.
+int check_raster_view(const char* name, const rnb_view* view) {
+	const std::string n(name);
+	for (int k = 0; k < 2; ++k) {
+		if (!(view->focal_length[k] > 0.0f) || !std::isfinite(view->focal_length[k])) return fail(RNB_ERR_INVALID, n + ": a focal length must be finite and > 0");
+		if (!std::isfinite(view->principal_point[k])) return fail(RNB_ERR_INVALID, n + ": the principal point must be finite");
+	}
+	for (int k = 0; k < 12; ++k)
+		if (!std::isfinite(view->xform[k])) return fail(RNB_ERR_INVALID, n + ": an entry of xform is not finite");
+	if (view->width == 0 || view->height == 0 || view->width > RNB_MESH_RASTER_MAX_SIZE || view->height > RNB_MESH_RASTER_MAX_SIZE)
+		return fail(RNB_ERR_INVALID, n + ": width and height must be 1 .. 16384");
+	return RNB_OK;
+}
+MrCamera raster_camera(const rnb_view* view, float near, uint32_t cull, uint32_t normals) {
+	MrCamera cam;
+	std::memset(&cam, 0, sizeof(cam));
+	for (int r = 0; r < 3; ++r) {
+		cam.o[r] = (double)view->xform[4 * r + 3];
+		for (int k = 0; k < 3; ++k) cam.col[k][r] = (double)view->xform[4 * r + k];
+	}
+	cam.fx = (double)view->focal_length[0]; cam.fy = (double)view->focal_length[1];
+	cam.cxw = (double)view->principal_point[0] * (double)view->width; cam.cyh = (double)view->principal_point[1] * (double)view->height;
+	cam.near = (double)near;
+	cam.w = view->width; cam.h = view->height; cam.cull = cull; cam.normals = normals;
+	return cam;
+}
+// The fill of one view, for the rasteriser (VIS = false, an empty tally) and the visibility stage (VIS = true): setup, classes, the small triangles filled; the large
+// ones counted, then listed and filled by a wavefront each. keys are all ones, counts and *dres zero on entry (and for VIS the tally's words); *hres is *dres after
+// the first pass (synchronises). The list grows when a view needs a longer one and is the caller's to release. M.nt >= 1, the indices are range-checked.
+template <bool VIS>
+int raster_fill(const char* name, MeshWorkspace& ws, hipStream_t s, const MrCamera& cam, const MrMesh& M, unsigned long long* keys, uint32_t* counts, MrResult* dres, MrResult* hres,
+                uint32_t** list, uint32_t* list_cap, const MrTally& tally) {
+	const uint32_t g_t = (M.nt + MR_WG - 1) / MR_WG;
+	hipLaunchKernelGGL((k_mr_bin<false, VIS>), dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, (uint32_t*)nullptr, 0u, dres, tally);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(hres, dres, sizeof(*hres), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	const uint32_t n_large = hres->n_class[MR_LARGE];
+	if (n_large) {
+		if (n_large > *list_cap) {
+			ws.release(*list);
+			*list_cap = 0;
+			if (!ws.alloc(list, n_large)) return fail(RNB_ERR_NOMEM, std::string(name) + ": hipMalloc failed for the list of " + std::to_string(n_large) + " large triangles");
+			*list_cap = n_large;
+		}
+		hipLaunchKernelGGL((k_mr_bin<true, VIS>), dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, *list, n_large, dres, tally);
+		hipLaunchKernelGGL(k_mr_fill_large<VIS>, dim3((n_large + MR_WG / 64u - 1) / (MR_WG / 64u)), dim3(MR_WG), 0, s, cam, M, (const uint32_t*)*list, n_large, keys, counts, tally);
+		HIP_TRY(hipGetLastError());
+	}
+	return RNB_OK;
+}
+} // namespace
+} // extern "C++"
+
 int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, const rnb_mesh_raster_options* opt, float* out_dev, uint32_t* face_dev,
                     rnb_mesh_raster_stats* stats) try {
 	if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -729,14 +786,7 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: near must be finite and > 0");
 	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
 	if (opt->normals > RNB_MESH_RASTER_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals must be RNB_MESH_RASTER_NORMALS_FACE or _VERTEX");
-	for (int k = 0; k < 2; ++k) {
-		if (!(view->focal_length[k] > 0.0f) || !std::isfinite(view->focal_length[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: a focal length must be finite and > 0");
-		if (!std::isfinite(view->principal_point[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: the principal point must be finite");
-	}
-	for (int k = 0; k < 12; ++k)
-		if (!std::isfinite(view->xform[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an entry of xform is not finite");
-	if (view->width == 0 || view->height == 0 || view->width > RNB_MESH_RASTER_MAX_SIZE || view->height > RNB_MESH_RASTER_MAX_SIZE)
-		return fail(RNB_ERR_INVALID, "rnb_mesh_raster: width and height must be 1 .. 16384");
+	if (int rc = check_raster_view("rnb_mesh_raster", view); rc != RNB_OK) return rc;
 	{
 		rnb_mesh unused;
 		if (int rc = check_mesh_input("rnb_mesh_raster", mesh, &unused); rc != RNB_OK) return rc;
@@ -748,16 +798,7 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 	hipStream_t s = as_stream(stream);
 	join_tail_host(c);
 
-	MrCamera cam;
-	std::memset(&cam, 0, sizeof(cam));
-	for (int r = 0; r < 3; ++r) {
-		cam.o[r] = (double)view->xform[4 * r + 3];
-		for (int k = 0; k < 3; ++k) cam.col[k][r] = (double)view->xform[4 * r + k];
-	}
-	cam.fx = (double)view->focal_length[0]; cam.fy = (double)view->focal_length[1];
-	cam.cxw = (double)view->principal_point[0] * (double)width; cam.cyh = (double)view->principal_point[1] * (double)height;
-	cam.near = (double)opt->near;
-	cam.w = width; cam.h = height; cam.cull = opt->cull; cam.normals = opt->normals;
+	const MrCamera cam = raster_camera(view, opt->near, opt->cull, opt->normals);
 	const MrMesh M{m.verts, m.indices, m.colors, m.normals, nt};
 
 	MeshWorkspace ws;
@@ -782,17 +823,8 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 		if (hres.flags & MR_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an index is out of range (>= n_verts)");
 		ws.release(used);
 		// 2. setup, classes, the small triangles filled; the large ones counted, then listed and filled by a wavefront each
-		hipLaunchKernelGGL(k_mr_bin<false>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, (uint32_t*)nullptr, 0u, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		const uint32_t n_large = hres.n_class[MR_LARGE];
-		if (n_large) {
-			if (!ws.alloc(&list, n_large)) return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the list of " + std::to_string(n_large) + " large triangles");
-			hipLaunchKernelGGL(k_mr_bin<true>, dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, list, n_large, dres);
-			hipLaunchKernelGGL(k_mr_fill_large, dim3((n_large + MR_WG / 64u - 1) / (MR_WG / 64u)), dim3(MR_WG), 0, s, cam, M, (const uint32_t*)list, n_large, keys, counts);
-			HIP_TRY(hipGetLastError());
-		}
+		uint32_t list_cap = 0;
+		if (int rc = raster_fill<false>("rnb_mesh_raster", ws, s, cam, M, keys, counts, dres, &hres, &list, &list_cap, MrTally{}); rc != RNB_OK) return rc;
 	}
 	// 3. one thread per pixel (an empty mesh: every key is still all ones, the image is zeros)
 	const uint32_t g_p = (n_pix + MR_WG - 1) / MR_WG;
@@ -810,6 +842,199 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 		stats->n_behind = hres.n_class[MR_BEHIND]; stats->n_out_of_range = hres.n_class[MR_OUT_OF_RANGE]; stats->n_degenerate = hres.n_class[MR_DEGENERATE];
 		stats->n_culled = hres.n_class[MR_CULLED]; stats->n_offscreen = hres.n_class[MR_OFFSCREEN]; stats->n_small = hres.n_class[MR_SMALL]; stats->n_large = hres.n_class[MR_LARGE];
 		stats->n_covered = hres.n_covered; stats->n_back_pixels = hres.n_back_pixels; stats->n_fragments = hres.n_fragments;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- visibility (include/rnb_mesh_visibility.h) ----
+uint32_t rnb_mesh_visibility_abi_version(void) { return RNB_MESH_VISIBILITY_ABI_VERSION; }
+
+int rnb_mesh_visibility_default_options(rnb_mesh_visibility_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_VISIBILITY_ABI_VERSION;
+	opt->near = 1.0f / 1024.0f;
+	opt->cull = RNB_MESH_RASTER_CULL_NONE;
+	opt->min_pixels = 1u;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_visibility_select_default_options(rnb_mesh_visibility_select_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_VISIBILITY_ABI_VERSION;
+	opt->unit = RNB_MESH_VISIBILITY_UNIT_COMPONENT;
+	opt->min_views_seen = 1u;
+	opt->max_views_off_mask = 0xFFFFFFFFu;
+	opt->rings = 1u;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_visibility(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_mesh_visibility_view* views, uint32_t n_views, const rnb_mesh_visibility_options* opt,
+                        rnb_mesh_face_visibility* faces_dev, rnb_mesh_visibility_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !mesh || !views || !opt || !faces_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: null argument");
+	if (n_views == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: n_views must be at least 1");
+	if (opt->abi_version != RNB_MESH_VISIBILITY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: options abi_version mismatch (expected RNB_MESH_VISIBILITY_ABI_VERSION)");
+	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: near must be finite and > 0");
+	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
+	if (opt->min_pixels == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: min_pixels must be at least 1");
+	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: a reserved word of the options is not 0");
+	uint32_t max_pix = 0;
+	uint64_t n_pixels = 0;
+	for (uint32_t v = 0; v < n_views; ++v) {
+		if (int rc = check_raster_view("rnb_mesh_visibility", &views[v].view); rc != RNB_OK) return rc;
+		if (views[v].mask_dev && (views[v].mask_width == 0 || views[v].mask_height == 0)) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: view " + std::to_string(v) + " has a mask of size 0");
+		const uint32_t n = views[v].view.width * views[v].view.height; // at most 2^28
+		max_pix = std::max(max_pix, n);
+		n_pixels += n;
+	}
+	{
+		rnb_mesh unused;
+		if (int rc = check_mesh_input("rnb_mesh_visibility", mesh, &unused); rc != RNB_OK) return rc;
+	}
+	const rnb_mesh m = *mesh;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	MeshWorkspace ws;
+	uint64_t n_class[MR_NCLASS] = {};
+	MvResult hv;
+	std::memset(&hv, 0, sizeof(hv));
+	if (nt) {
+		const MrMesh M{m.verts, m.indices, nullptr, nullptr, nt};
+		const uint32_t g_t = (nt + MV_WG - 1) / MV_WG;
+		unsigned long long* keys = nullptr;
+		uint32_t *counts = nullptr, *used = nullptr, *list = nullptr, *words = nullptr, list_cap = 0;
+		MrResult* dres = nullptr;
+		MvResult* dv = nullptr;
+		if (!ws.alloc(&keys, max_pix) || !ws.alloc(&counts, max_pix) || !ws.alloc(&words, (size_t)nt * 3) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1) || !ws.alloc(&dv, 1))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility: hipMalloc failed for the workspace of " + std::to_string(max_pix) + " pixels, " + std::to_string(nt) + " triangles and " + std::to_string(nv) + " vertices");
+		uint32_t *cov = words, *on = words + nt, *won = words + 2 * (size_t)nt;
+		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemsetAsync(words, 0, (size_t)nt * 12, s));
+		HIP_TRY(hipMemcpyAsync(dv, &hv, sizeof(hv), hipMemcpyHostToDevice, s));
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MV_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dv->flags, MV_BAD_INDEX);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hv.flags & MV_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: an index is out of range (>= n_verts)");
+		ws.release(used);
+		// 2. view by view: the rasteriser's fill, the winners tallied, the three words of every triangle folded into its record
+		for (uint32_t v = 0; v < n_views; ++v) {
+			const rnb_mesh_visibility_view& V = views[v];
+			const uint32_t n_pix = V.view.width * V.view.height;
+			const MrCamera cam = raster_camera(&V.view, opt->near, opt->cull, RNB_MESH_RASTER_NORMALS_FACE);
+			const MrTally tally{V.mask_dev, V.mask_width, V.mask_height, cov, on};
+			MrResult hres;
+			std::memset(&hres, 0, sizeof(hres));
+			HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_pix * 8, s));
+			HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_pix * 4, s));
+			HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+			if (int rc = raster_fill<true>("rnb_mesh_visibility", ws, s, cam, M, keys, counts, dres, &hres, &list, &list_cap, tally); rc != RNB_OK) return rc;
+			for (uint32_t k = 0; k < MR_NCLASS; ++k) n_class[k] += hres.n_class[k];
+			hipLaunchKernelGGL(k_mv_tally, dim3((n_pix + MV_WG - 1) / MV_WG), dim3(MV_WG), 0, s, V.view.width, V.view.height, nt, tally, (const unsigned long long*)keys, won);
+			hipLaunchKernelGGL(k_mv_fold, dim3(g_t), dim3(MV_WG), 0, s, nt, v, v == 0 ? 1u : 0u, v + 1 == n_views ? 1u : 0u, V.mask_dev ? 1u : 0u, opt->min_pixels, cov, on, won, faces_dev, dv);
+			HIP_TRY(hipGetLastError());
+		}
+		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(keys); ws.release(counts); ws.release(words); ws.release(list); ws.release(dres); ws.release(dv);
+	}
+	if (stats) {
+		stats->n_tris = nt; stats->n_views = n_views;
+		stats->n_behind = n_class[MR_BEHIND]; stats->n_out_of_range = n_class[MR_OUT_OF_RANGE]; stats->n_degenerate = n_class[MR_DEGENERATE]; stats->n_culled = n_class[MR_CULLED];
+		stats->n_offscreen = n_class[MR_OFFSCREEN]; stats->n_small = n_class[MR_SMALL]; stats->n_large = n_class[MR_LARGE];
+		stats->n_pixels = n_pixels;
+		stats->n_faces_seen = hv.n_faces_seen; stats->n_faces_off_mask = hv.n_faces_off_mask;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_visibility_select(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_face_visibility* faces_dev, const rnb_mesh_visibility_select_options* opt, rnb_mesh* out,
+                               uint32_t* kept_dev, rnb_mesh_visibility_select_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_visibility_select", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_VISIBILITY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: options abi_version mismatch (expected RNB_MESH_VISIBILITY_ABI_VERSION)");
+	if (opt->unit != RNB_MESH_VISIBILITY_UNIT_COMPONENT && opt->unit != RNB_MESH_VISIBILITY_UNIT_FACE) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: unknown unit");
+	if (opt->rings > RNB_MESH_VISIBILITY_MAX_RINGS) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: rings must be 0 .. 64");
+	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: a reserved word of the options is not 0");
+	if (m.n_indices && !faces_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: faces_dev is null");
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	MeshWorkspace ws;
+	MvResult hv;
+	std::memset(&hv, 0, sizeof(hv));
+	uint32_t nvo = 0, nto = 0;
+	rnb_mesh o;
+	if (nt) {
+		const uint32_t g_v = (nv + MV_WG - 1) / MV_WG, g_t = (nt + MV_WG - 1) / MV_WG; // (nv >= 1: check_mesh_input)
+		const uint32_t* idx = m.indices;
+		uint32_t *used = nullptr, *flag = nullptr, *vmark = nullptr, *parent = nullptr, *vmap = nullptr, *scan = nullptr, *twg = nullptr;
+		MvResult* dv = nullptr;
+		if (!ws.alloc(&used, nv) || !ws.alloc(&flag, nt) || !ws.alloc(&vmark, nv) || !ws.alloc(&vmap, nv) || !ws.alloc(&twg, g_t) || !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) ||
+		    !ws.alloc(&dv, 1) || (opt->unit == RNB_MESH_VISIBILITY_UNIT_COMPONENT && !ws.alloc(&parent, nv)))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility_select: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(nt) + " triangles");
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemsetAsync(vmark, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemcpyAsync(dv, &hv, sizeof(hv), hipMemcpyHostToDevice, s));
+		// 1. every index is range-checked before any is used as an address
+		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, nv, used, &dv->flags, MV_BAD_INDEX);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hv.flags & MV_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: an index is out of range (>= n_verts)");
+		// 2. candidates and seeds; the kept triangles
+		hipLaunchKernelGGL(k_mv_flags, dim3(g_t), dim3(MV_WG), 0, s, faces_dev, nt, opt->min_views_seen, opt->max_views_off_mask, flag, dv);
+		if (opt->unit == RNB_MESH_VISIBILITY_UNIT_FACE) {
+			hipLaunchKernelGGL(k_mv_seeds_kept, dim3(g_t), dim3(MV_WG), 0, s, flag, nt);
+			for (uint32_t r = 0; r < opt->rings; ++r) { // (the marks of the earlier rings stay: their triangles are still marked)
+				hipLaunchKernelGGL(k_mv_ring_mark, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, vmark);
+				hipLaunchKernelGGL(k_mv_ring_grow, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, flag, (const uint32_t*)vmark);
+			}
+		} else { // the cleaner's labels: the root of a component is its smallest vertex
+			hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
+			hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(CL_WG), 0, s, idx, nt, parent);
+			hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
+			hipLaunchKernelGGL(k_mv_comp_seed, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, (const uint32_t*)parent, vmark);
+			hipLaunchKernelGGL(k_mv_comp_keep, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, flag, (const uint32_t*)parent, (const uint32_t*)vmark);
+			hipLaunchKernelGGL(k_mv_comp_count, dim3(g_v), dim3(MV_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, (const uint32_t*)vmark, nv, dv);
+		}
+		HIP_TRY(hipGetLastError());
+		// 3. compaction: the kept vertices numbered (used's memory holds their flags), the kept triangles per workgroup
+		uint32_t* vkeep = used;
+		HIP_TRY(hipMemsetAsync(vkeep, 0, (size_t)nv * 4, s));
+		hipLaunchKernelGGL(k_mv_vflag, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, vkeep, kept_dev);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(vmap, vkeep, (size_t)nv * 4, hipMemcpyDeviceToDevice, s));
+		int rc = scan_exclusive(vmap, nv, s, &nvo, scan);
+		if (rc != RNB_OK) return rc;
+		if ((rc = count_and_scan(s, g_t, twg, scan, &nto, k_mv_tris<false>, idx, nt, (const uint32_t*)flag, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
+		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility_select: hipMalloc failed for the output mesh");
+		hipLaunchKernelGGL(k_mv_verts, dim3(g_v), dim3(MV_WG), 0, s, (const uint32_t*)vkeep, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, o.verts, o.colors, o.normals);
+		hipLaunchKernelGGL(k_mv_tris<true>, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(used); ws.release(flag); ws.release(vmark); ws.release(parent); ws.release(vmap); ws.release(scan); ws.release(twg); ws.release(dv);
+	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility_select: hipMalloc failed for the output mesh");
+	hand_over(ws, o, out);
+	if (stats) {
+		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
+		stats->n_seeds = hv.n_seeds; stats->n_candidates = hv.n_candidates; stats->n_components = hv.n_components; stats->n_components_kept = hv.n_components_kept;
 		stats->peak_workspace = ws.peak;
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}

@@ -1,12 +1,14 @@
 // kernels_mesh_raster.cuh — the mesh rasteriser of include/rnb_mesh_raster.h (rnb_mesh_raster): an indexed device mesh into one camera's depth, normal, colour, coverage
 // and face maps.
 //   (k_mesh_validate of mesh_common.cuh comes first: nothing is dereferenced through an index before that kernel has passed)
-//   k_mr_bin<LIST>     one thread per triangle: rules 1-4 up to the pixel box. LIST = false: the triangle is counted in its class, and one whose box holds at most
+//   k_mr_bin<LIST, VIS> one thread per triangle: rules 1-4 up to the pixel box. LIST = false: the triangle is counted in its class, and one whose box holds at most
 //                      RNB_MESH_RASTER_SMALL_PIXELS pixels is filled by this thread. LIST = true (launched only when the first pass counted large triangles, with a list of
 //                      exactly that length): the large triangles' indices into the list, in any order
 //   k_mr_fill_large    one wavefront per large triangle, 64 pixels of its (clamped) box per step: a screen-filling triangle costs no thread more than a few pixels per step
 //   k_mr_resolve<VEC>  one thread per pixel: the winner's weights, depth, colour and normal again by the same formulas; the nine channels through LDS, so that with VEC
 //                      (the image 16-byte aligned) a workgroup's 256 pixels leave as 16-byte stores
+// VIS (k_mr_bin, k_mr_fill_large): the fill as the visibility stage runs it (kernels_mesh_visibility.cuh) -- the same code, and beside the keys and counts every drawn
+// triangle's covered and on-mask pixel counts (MrTally). The rasteriser launches VIS = false.
 // Per covered (triangle, pixel) one 64-bit atomic minimum on the key and one 32-bit atomic add on the count, results unused (the no-return forms). A minimum and a sum of
 // integers: nothing that leaves the call depends on the schedule, the launch shape or which path filled a triangle. Operation for operation what
 // tests/mesh_raster_reference.py computes (this file is compiled with -ffp-contract=off; the pragma says so once more where it matters). Vector loads, stores and atomics only.
@@ -131,20 +133,41 @@ __device__ __forceinline__ double mr_depth(const MrTri& T, const long long w[3],
 	const double iz = (l[0] * T.r[0] + l[1] * T.r[1]) + l[2] * T.r[2];
 	return 1.0 / iz;
 }
-// One (triangle, pixel): the two atomics if the pixel is covered. (i, j) is inside the image: the box was clamped.
-__device__ __forceinline__ void mr_fragment(const MrTri& T, const uint32_t t, const uint32_t width, const int i, const int j, unsigned long long* __restrict__ keys, uint32_t* __restrict__ counts) {
-	long long w[3];
-	if (!mr_cover(T, i, j, w)) return;
-	double l[3];
-	const float z = (float)mr_depth(T, w, l);
-	const size_t p = (size_t)j * width + (size_t)i;
-	(void)atomicMin(&keys[p], ((unsigned long long)__float_as_uint(z) << 32) | t);
-	(void)atomicAdd(&counts[p], 1u);
+// What the visibility stage (kernels_mesh_visibility.cuh) has the fill write beside the image's keys and counts: per triangle the pixel centres it covers (bit 31:
+// the triangle is drawn) and those of them that are on the view's mask. Written by whoever fills the triangle, without atomics. The rasteriser itself (VIS = false)
+// hands in an empty one and compiles to what it was.
+struct MrTally {
+	const uint8_t* mask; // uint8[mh][mw], or null: every pixel is on the mask
+	uint32_t mw, mh;
+	uint32_t* cov; // [nt], zero on entry
+	uint32_t* on;  // [nt], zero on entry
+};
+constexpr uint32_t MR_DRAWN = 0x80000000u; // bit of MrTally::cov (a count is at most 2^28)
+// The mask pixel whose area holds the centre of pixel (i, j) of a w x h view (include/rnb_mesh_visibility.h): non-zero, or no mask.
+__device__ __forceinline__ bool mr_on_mask(const MrTally& y, const uint32_t w, const uint32_t h, const uint32_t i, const uint32_t j) {
+	if (!y.mask) return true;
+	const uint32_t mi = min(y.mw - 1u, (uint32_t)(((2ull * i + 1ull) * y.mw) / (2ull * w))), mj = min(y.mh - 1u, (uint32_t)(((2ull * j + 1ull) * y.mh) / (2ull * h)));
+	return y.mask[(size_t)mj * y.mw + mi] != 0;
 }
 
-template <bool LIST>
+// One (triangle, pixel): the two atomics if the pixel is covered. (i, j) is inside the image: the box was clamped. Returns 0 if the pixel is not covered, else 1, and
+// with VIS 3 if it is also on the mask.
+template <bool VIS>
+__device__ __forceinline__ uint32_t mr_fragment(const MrTri& T, const uint32_t t, const MrCamera& cam, const MrTally& y, const int i, const int j, unsigned long long* __restrict__ keys,
+                                                uint32_t* __restrict__ counts) {
+	long long w[3];
+	if (!mr_cover(T, i, j, w)) return 0u;
+	double l[3];
+	const float z = (float)mr_depth(T, w, l);
+	const size_t p = (size_t)j * cam.w + (size_t)i;
+	(void)atomicMin(&keys[p], ((unsigned long long)__float_as_uint(z) << 32) | t);
+	(void)atomicAdd(&counts[p], 1u);
+	return (VIS && mr_on_mask(y, cam.w, cam.h, (uint32_t)i, (uint32_t)j)) ? 3u : 1u;
+}
+
+template <bool LIST, bool VIS>
 __global__ __launch_bounds__(MR_WG) void k_mr_bin(const MrCamera cam, const MrMesh m, unsigned long long* __restrict__ keys, uint32_t* __restrict__ counts, uint32_t* __restrict__ list,
-                                                  const uint32_t list_len, MrResult* __restrict__ res) {
+                                                  const uint32_t list_len, MrResult* __restrict__ res, const MrTally y) {
 	const uint32_t t = blockIdx.x * MR_WG + threadIdx.x;
 	MrTri T;
 	const uint32_t cls = t < m.nt ? mr_setup(cam, m, t, &T) : (uint32_t)MR_NCLASS;
@@ -162,12 +185,18 @@ __global__ __launch_bounds__(MR_WG) void k_mr_bin(const MrCamera cam, const MrMe
 		if (mask && lane == (uint32_t)(__ffsll((unsigned long long)mask) - 1)) (void)atomicAdd(&res->n_class[k], (uint32_t)__popcll(mask));
 	}
 	if (cls != MR_SMALL) return;
+	uint32_t n_cov = 0u, n_on = 0u;
 	for (int j = T.j0; j <= T.j1; ++j)
-		for (int i = T.i0; i <= T.i1; ++i) mr_fragment(T, t, cam.w, i, j, keys, counts);
+		for (int i = T.i0; i <= T.i1; ++i) {
+			const uint32_t f = mr_fragment<VIS>(T, t, cam, y, i, j, keys, counts);
+			if (VIS) { n_cov += f & 1u; n_on += f >> 1; }
+		}
+	if (VIS) { y.cov[t] = MR_DRAWN | n_cov; y.on[t] = n_on; }
 }
 
+template <bool VIS>
 __global__ __launch_bounds__(MR_WG) void k_mr_fill_large(const MrCamera cam, const MrMesh m, const uint32_t* __restrict__ list, const uint32_t list_len, unsigned long long* __restrict__ keys,
-                                                         uint32_t* __restrict__ counts) {
+                                                         uint32_t* __restrict__ counts, const MrTally y) {
 	const uint32_t entry = blockIdx.x * (MR_WG / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
 	if (entry >= list_len) return;
 	const uint32_t t = list[entry];
@@ -175,7 +204,15 @@ __global__ __launch_bounds__(MR_WG) void k_mr_fill_large(const MrCamera cam, con
 	MrTri T;
 	if (mr_setup(cam, m, t, &T) != MR_LARGE) return; // (never; every lane of the wavefront computes the same)
 	const uint32_t bw = (uint32_t)(T.i1 - T.i0 + 1), n = bw * (uint32_t)(T.j1 - T.j0 + 1); // at most 2^28 pixels
-	for (uint32_t q = lane; q < n; q += 64u) mr_fragment(T, t, cam.w, T.i0 + (int)(q % bw), T.j0 + (int)(q / bw), keys, counts);
+	uint32_t n_cov = 0u, n_on = 0u;
+	for (uint32_t q = lane; q < n; q += 64u) {
+		const uint32_t f = mr_fragment<VIS>(T, t, cam, y, T.i0 + (int)(q % bw), T.j0 + (int)(q / bw), keys, counts);
+		if (VIS) { n_cov += f & 1u; n_on += f >> 1; }
+	}
+	if (VIS) { // (the whole wavefront is here: the returns above are uniform over it)
+		n_cov = wave_sum(n_cov); n_on = wave_sum(n_on);
+		if (lane == 0u) { y.cov[t] = MR_DRAWN | n_cov; y.on[t] = n_on; }
+	}
 }
 
 template <bool VEC>

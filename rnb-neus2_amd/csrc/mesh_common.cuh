@@ -1,5 +1,5 @@
-// mesh_common.cuh — what the mesh stages share (kernels_mesh.cuh, kernels_mesh_sparse.cuh, kernels_mesh_clean.cuh, kernels_mesh_simplify.cuh); the only header they
-// include from each other:
+// mesh_common.cuh — what the mesh stages share (kernels_mesh.cuh, kernels_mesh_sparse.cuh, kernels_mesh_clean.cuh, kernels_mesh_simplify.cuh, ...); the only header they
+// include from each other (but for kernels_mesh_visibility.cuh, which runs the rasteriser's fill and the cleaner's components and includes both):
 //   k_scan_blocks / k_scan_add, wg_exclusive_256   the prefix sums that number every vertex, triangle, brick and cluster (the driver's scan_exclusive; the count / write kernel pairs)
 //   k_mesh_validate                                every index of a triangle list range-checked before any is used as an address, used[v] marked
 //   wave_sum, wave_group_next                      the sums of the lanes of a wavefront that hold the same key, group by group

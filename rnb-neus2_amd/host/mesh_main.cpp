@@ -5,12 +5,17 @@
 //   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
 //        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean] [--report-error]] [--report-views [--views-out FILE]]
 //        [--texture S [--texture-maps albedo[,normal]]]
+//        [--keep-seen component|faces [--seen-min-views N] [--seen-rings R] [--seen-masks [--seen-max-off N]] [--seen-supersample K]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
 // With --keep and / or --orient the device mesh goes through rnb_mesh_clean (include/rnb_mesh_clean.h) before it is downloaded: connected components, the largest one
 // kept, triangles turned outward -- the pipeline's post-processing without the round trip through an OBJ. Without them nothing of that is called; with only one of
 // them the other part is left alone (--keep alone does not turn anything, --orient alone keeps every component), as Context.extract_mesh(keep=, orient=) does.
+// With --keep-seen the (cleaned) device mesh loses what no camera of the scene sees (rnb_mesh_visibility and rnb_mesh_visibility_select, include/rnb_mesh_visibility.h):
+// whole connected components (component: a cavity shell inside the object goes, closed surfaces stay closed) or single triangles grown by --seen-rings rings (faces: a
+// side no camera saw becomes a hole). With --seen-masks the alpha of the input normal maps are the masks, and --seen-max-off N also drops what lies off them in more
+// than N views. It comes after --keep / --orient and before --simplify, as Context.extract_mesh(seen_by=) places it.
 // With --simplify N the (cleaned) device mesh then goes through rnb_mesh_simplify (include/rnb_mesh_simplify.h): vertex clustering on N^3 cells over the scene's box
 // (origin aabb_min, cell = (aabb_max - aabb_min) / N), the representative of a cell placed by --placement (quadric by default). Ring normals are those of the simplified mesh.
 // With --report-error the distance between the simplifier's input and its output is measured on the device in both directions (rnb_mesh_distance,
@@ -29,6 +34,7 @@
 #include "../../include/rnb_mesh_distance.h"
 #include "../../include/rnb_mesh_raster.h"
 #include "../../include/rnb_mesh_texture.h"
+#include "../../include/rnb_mesh_visibility.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -69,6 +75,12 @@ const Flag FLAGS[] = {
 	{"report-views", nullptr, "(takes no value). Rasterise the final mesh into every camera of the scene and compare it with the input normal maps: normal angle and mask IoU per view."},
 	{"views-out", "FILE", "--report-views only. Where the per-view report is written (default: the output mesh's path + .views.json)."},
 	{"texture", "S", "Bake a texture of S x S texels (4 .. 8192) for the final mesh on the device: FILE.obj gets vt records, FILE.mtl and FILE_albedo.png are written beside it."},
+	{"keep-seen", "MODE", "Drop what no camera of the scene sees, on the device, after the cleaning. component: whole connected components; faces: triangle by triangle (a side nobody saw becomes a hole)."},
+	{"seen-min-views", "N", "--keep-seen only. A triangle counts as seen if at least N views see it (default 1)."},
+	{"seen-rings", "R", "--keep-seen faces only. Grow the seen triangles by R rings of neighbours that share a vertex (0 .. 64, default 1)."},
+	{"seen-masks", nullptr, "--keep-seen only (takes no value). Use the alpha of the input normal maps as masks: a pixel off the mask sees nothing."},
+	{"seen-max-off", "N", "--seen-masks only. Also drop what lies off the mask in more than N views (default: the masks carve nothing)."},
+	{"seen-supersample", "K", "--keep-seen only. Measure in views of K times the resolution (default 1); the masks stay as they are."},
 	{"texture-maps", "LIST", "--texture only. The maps to bake, separated by commas: albedo (default), normal (the SDF gradient, object space, FILE_normal.png)."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -169,6 +181,60 @@ void report_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& mesh, const s
 	             num(s_mean / k) + ", \"median_angle_deg\": " + num(s_median / k) + ", \"mask_iou\": " + num(s_iou / k) + ", \"frame_ms\": " + num(s_ms / k) + "}\n}\n";
 }
 
+// --keep-seen: *dm without what the cameras of the scene do not see, in *out. `report`: the two lines to print.
+struct SeenOptions { uint32_t unit = RNB_MESH_VISIBILITY_UNIT_COMPONENT, min_views = 1, rings = 1, max_off = 0xFFFFFFFFu, supersample = 1; bool masks = false; };
+void keep_seen(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& dm, const SeenOptions& so, rnb_mesh* out, std::string& report) {
+	std::vector<rnb_mesh_visibility_view> views(ds.views.size());
+	std::vector<void*> held;
+	rnb_mesh_face_visibility* faces = nullptr;
+	rnb_mesh_visibility_stats vs;
+	rnb_mesh_visibility_select_stats ss;
+	try {
+		for (size_t vi = 0; vi < ds.views.size(); ++vi) {
+			rnb_mesh_visibility_view& V = views[vi];
+			std::memset(&V, 0, sizeof(V));
+			V.view = ds.views[vi];
+			const uint64_t w = (uint64_t)V.view.width * so.supersample, h = (uint64_t)V.view.height * so.supersample; // api.scaled_view(view, K) for a whole K
+			if (w > RNB_MESH_RASTER_MAX_SIZE || h > RNB_MESH_RASTER_MAX_SIZE) throw std::runtime_error("--seen-supersample: view " + std::to_string(vi) + " would exceed 16384 pixels per side");
+			V.view.focal_length[0] = (float)((double)V.view.focal_length[0] * (double)w / (double)V.view.width);
+			V.view.focal_length[1] = (float)((double)V.view.focal_length[1] * (double)h / (double)V.view.height);
+			V.view.width = (uint32_t)w; V.view.height = (uint32_t)h;
+			if (so.masks) {
+				const png16::Image& in = ds.normals[vi];
+				std::vector<uint8_t> m((size_t)in.width * in.height);
+				for (size_t p = 0; p < m.size(); ++p) m[p] = in.rgba[4 * p + 3] > 0 ? 1 : 0; // the input mask of view_metrics.hpp
+				if (m.empty()) throw std::runtime_error("--seen-masks: the normal map of view " + std::to_string(vi) + " is empty");
+				void* d = nullptr;
+				RNB_CHECK(rnb_device_malloc(ctx, m.size(), &d));
+				held.push_back(d);
+				RNB_CHECK(rnb_memcpy(ctx, d, m.data(), m.size(), RNB_H2D));
+				V.mask_dev = (const uint8_t*)d; V.mask_width = in.width; V.mask_height = in.height;
+			}
+		}
+		RNB_CHECK(rnb_device_malloc(ctx, std::max<uint64_t>(dm.n_indices / 3u, 1) * sizeof(rnb_mesh_face_visibility), (void**)&faces));
+		held.push_back(faces);
+		rnb_mesh_visibility_options vo;
+		RNB_CHECK(rnb_mesh_visibility_default_options(&vo));
+		RNB_CHECK(rnb_mesh_visibility(ctx, nullptr, &dm, views.data(), (uint32_t)views.size(), &vo, faces, &vs));
+		rnb_mesh_visibility_select_options lo;
+		RNB_CHECK(rnb_mesh_visibility_select_default_options(&lo));
+		lo.unit = so.unit; lo.min_views_seen = so.min_views; lo.max_views_off_mask = so.max_off; lo.rings = so.rings;
+		RNB_CHECK(rnb_mesh_visibility_select(ctx, nullptr, &dm, faces, &lo, out, nullptr, &ss));
+	} catch (...) {
+		for (void* p : held) rnb_device_free(ctx, p);
+		throw;
+	}
+	for (void* p : held) RNB_CHECK(rnb_device_free(ctx, p));
+	char line[320];
+	std::snprintf(line, sizeof(line), "seen: %u views, %llu pixels, %u of %u triangles seen, %u off the mask, peak workspace %.1f MB, %.1f ms\n", vs.n_views, (unsigned long long)vs.n_pixels,
+	              vs.n_faces_seen, vs.n_tris, vs.n_faces_off_mask, (double)vs.peak_workspace / 1e6, vs.ms);
+	report += line;
+	std::snprintf(line, sizeof(line), "keep-seen %s: %u seeds, %u candidates, %u components of which %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n",
+	              so.unit == RNB_MESH_VISIBILITY_UNIT_FACE ? "faces" : "component", ss.n_seeds, ss.n_candidates, ss.n_components, ss.n_components_kept, ss.n_tris_in, ss.n_tris_out, ss.n_verts_in,
+	              ss.n_verts_out, ss.ms);
+	report += line;
+}
+
 } // namespace
 
 int main(int argc, char** argv) {
@@ -179,6 +245,8 @@ int main(int argc, char** argv) {
 	uint32_t simplify = 0, placement = RNB_MESH_PLACE_QUADRIC;           // 0: no simplification
 	bool report_error = false, want_views = false;
 	uint32_t texture = 0, texture_maps = RNB_MESH_TEXTURE_ALBEDO; // 0: no texture
+	bool want_seen = false;
+	SeenOptions seen;
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -221,6 +289,28 @@ int main(int argc, char** argv) {
 		}
 		if (a.count("report-views")) want_views = true;
 		if (a.count("views-out") && !want_views) throw ParseError("Argument 'views-out' is only used with --report-views");
+		if (a.count("keep-seen")) {
+			want_seen = true;
+			if (a["keep-seen"] == "faces") seen.unit = RNB_MESH_VISIBILITY_UNIT_FACE;
+			else if (a["keep-seen"] != "component") throw ParseError("Argument 'keep-seen' must be component or faces");
+		}
+		for (const char* sub : {"seen-min-views", "seen-rings", "seen-masks", "seen-max-off", "seen-supersample"})
+			if (a.count(sub) && !want_seen) throw ParseError(std::string("Argument '") + sub + "' is only used with --keep-seen");
+		if (a.count("seen-min-views")) seen.min_views = parse_u32("seen-min-views", a["seen-min-views"]);
+		if (a.count("seen-rings")) {
+			if (seen.unit != RNB_MESH_VISIBILITY_UNIT_FACE) throw ParseError("Argument 'seen-rings' is only used with --keep-seen faces");
+			seen.rings = parse_u32("seen-rings", a["seen-rings"]);
+			if (seen.rings > RNB_MESH_VISIBILITY_MAX_RINGS) throw ParseError("Argument 'seen-rings' must be 0 .. 64");
+		}
+		if (a.count("seen-masks")) seen.masks = true;
+		if (a.count("seen-max-off")) {
+			if (!seen.masks) throw ParseError("Argument 'seen-max-off' is only used with --seen-masks");
+			seen.max_off = parse_u32("seen-max-off", a["seen-max-off"]);
+		}
+		if (a.count("seen-supersample")) {
+			seen.supersample = parse_u32("seen-supersample", a["seen-supersample"]);
+			if (seen.supersample == 0 || seen.supersample > RNB_MESH_RASTER_MAX_SIZE) throw ParseError("Argument 'seen-supersample' must be 1 .. 16384");
+		}
 		if (a.count("texture")) {
 			texture = parse_u32("texture", a["texture"]);
 			if (texture < RNB_MESH_TEXTURE_MIN_SIZE || texture > RNB_MESH_TEXTURE_MAX_SIZE) throw ParseError("Argument 'texture' must be 4 .. 8192");
@@ -294,6 +384,13 @@ int main(int argc, char** argv) {
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		}
+		std::string seen_report;
+		if (want_seen) { // device to device, after the cleaning and before the simplification
+			keep_seen(ctx, ds, dm, seen, &cm, seen_report);
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+		}
 		rnb_mesh_simplify_stats ss;
 		rnb_mesh_distance_stats es[2];
 		double error_unit = 0.0;
@@ -353,6 +450,7 @@ int main(int argc, char** argv) {
 		            100.0 * (double)st.n_points_evaluated / ((double)res * res * res), (unsigned long long)st.n_sign_change, (double)st.peak_workspace / 1e6, st.ms);
 		if (clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
 		                       cs.n_verts_in, cs.n_verts_out, cs.ms);
+		if (want_seen) std::fputs(seen_report.c_str(), stdout);
 		if (simplify) std::printf("simplify: %u clusters, %u -> %u triangles (%u collapsed), %u -> %u vertices, %u clamped, %u at the mean, %.1f ms\n", ss.n_clusters, ss.n_tris_in,
 		                          ss.n_tris_out, ss.n_tris_collapsed, ss.n_verts_in, ss.n_verts_out, ss.n_clamped, ss.n_fallback, ss.ms);
 		if (report_error) {

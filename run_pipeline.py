@@ -39,6 +39,12 @@ _SPEC = """
 --simplify          | int   |        | --device-postprocess only: simplify the final mesh on the GPU by vertex clustering on N^3 cells over the scene box (build/mesh --simplify N)
 --report-views      | flag  |        | --device-postprocess only: rasterise the final mesh into every input view and write its normal angle and mask IoU per view (build/mesh --report-views)
 --texture           | int   |        | --device-postprocess only: bake an albedo texture of S x S texels for the final mesh on the GPU; mesh.mtl and mesh_albedo.png beside mesh.obj (build/mesh --texture S)
+--keep-seen         | str   |        | --device-postprocess only: drop what no input view sees from the final mesh on the GPU, component (whole connected components) or faces (build/mesh --keep-seen)
+--seen-min-views    | int   |        | --keep-seen only: a triangle counts as seen if at least N views see it
+--seen-rings        | int   |        | --keep-seen faces only: grow the seen triangles by R rings of neighbours
+--seen-masks        | flag  |        | --keep-seen only: the alpha of the input normal maps are the masks
+--seen-max-off      | int   |        | --seen-masks only: also drop what lies off the mask in more than N views
+--seen-supersample  | int   |        | --keep-seen only: measure at K times the views' resolution
 """
 
 
@@ -67,7 +73,8 @@ def pipeline_kwargs(ns):
     """argparse namespace -> keywords of rnb_neus2_amd.pipeline.run_full_pipeline."""
     renamed = {"input": "input_path", "testbed": "testbed_path", "output": "output_dir", "supernormal": "super_normal", "l1": "use_l1",
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
-    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture")}
+    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "keep_seen", "seen_min_views",
+                                                                                "seen_rings", "seen_masks", "seen_max_off", "seen_supersample")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
@@ -78,6 +85,9 @@ def pipeline_kwargs(ns):
             kw["report_views"] = True
         if ns.texture is not None:
             kw["texture"] = ns.texture
+        if ns.keep_seen:
+            ks = dict(unit=ns.keep_seen, min_views=ns.seen_min_views, rings=ns.seen_rings, masks=ns.seen_masks or None, max_off=ns.seen_max_off, supersample=ns.seen_supersample)
+            kw["keep_seen"] = {k: v for k, v in ks.items() if v is not None}
     return kw
 
 
@@ -94,6 +104,17 @@ def main(argv=None):
         parser.error("--texture is only used with --device-postprocess")
     if ns.texture is not None and not 4 <= ns.texture <= 8192:
         parser.error("--texture must be 4 .. 8192")
+    if ns.keep_seen and not ns.device_postprocess:
+        parser.error("--keep-seen is only used with --device-postprocess")
+    if ns.keep_seen and ns.keep_seen not in ("component", "faces"):
+        parser.error("--keep-seen must be component or faces")
+    for name in ("seen_min_views", "seen_rings", "seen_masks", "seen_max_off", "seen_supersample"):
+        if getattr(ns, name) not in (None, False) and not ns.keep_seen:
+            parser.error("--%s is only used with --keep-seen" % name.replace("_", "-"))
+    if ns.seen_rings is not None and ns.keep_seen != "faces":
+        parser.error("--seen-rings is only used with --keep-seen faces")
+    if ns.seen_max_off is not None and not ns.seen_masks:
+        parser.error("--seen-max-off is only used with --seen-masks")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
         parser.error("--simplify must be 1 .. 1024")
     np.random.seed(ns.seed)
