@@ -644,6 +644,78 @@ MESH_VISIBILITY_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_project.h: the texels of the baker's atlas coloured from calibrated images (project, test occlusion, blend); a header of its own with its own version (the HIP library only) ----
+MESH_PROJECT_ABI_VERSION = 1
+MESH_PROJECT_NONE, MESH_PROJECT_MAX_WEIGHT_POWER = 0xFFFFFFFF, 8
+MESH_PROJECT_FORMAT_F32, MESH_PROJECT_FORMAT_U16, MESH_PROJECT_FORMAT_U8 = 0, 1, 2
+MESH_PROJECT_MODE_BLEND, MESH_PROJECT_MODE_BEST = 0, 1
+MESH_PROJECT_NORMALS_FACE, MESH_PROJECT_NORMALS_VERTEX = 0, 1
+MESH_PROJECT_FORMATS = {"float32": MESH_PROJECT_FORMAT_F32, "uint16": MESH_PROJECT_FORMAT_U16, "uint8": MESH_PROJECT_FORMAT_U8}  # by numpy dtype name
+
+
+class MeshProjectView(C.Structure):
+    _fields_ = [
+        ("view", View),
+        ("image_dev", C.c_void_p),
+        ("image_width", C.c_uint32),
+        ("image_height", C.c_uint32),
+        ("format", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class MeshProjectOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("size", C.c_uint32),
+        ("block", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("normals", C.c_uint32),
+        ("weight_power", C.c_uint32),
+        ("min_cos", C.c_float),
+        ("depth_tolerance", C.c_float),
+        ("near", C.c_float),
+        ("cull", C.c_uint32),
+        ("fallback_dev", C.c_void_p),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshProjection(C.Structure):
+    _fields_ = [
+        ("uv", C.c_void_p),
+        ("color", C.c_void_p),
+        ("info", C.c_void_p),
+        ("size", C.c_uint32),
+        ("block", C.c_uint32),
+        ("blocks_per_row", C.c_uint32),
+        ("n_tris", C.c_uint32),
+    ]
+
+
+class MeshProjectStats(C.Structure):
+    _fields_ = [
+        ("n_texels", C.c_uint64),
+        ("n_textured", C.c_uint64),
+        ("n_pairs_tested", C.c_uint64),
+        ("n_occluded", C.c_uint64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_PROJECT_PROTOTYPES = {
+    "mesh_project_abi_version": (_u32, []),
+    "mesh_project_default_options": (_i, [C.POINTER(MeshProjectOptions)]),
+    "mesh_project_views": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshProjectView), _u32, C.POINTER(MeshProjectOptions), C.POINTER(MeshProjection), C.POINTER(MeshProjectStats)]),
+    "mesh_projection_free": (_i, [_ctx, C.POINTER(MeshProjection)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -665,11 +737,13 @@ class Functions:
 
 
 def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
-            mesh_visibility=False):
+            mesh_visibility=False, mesh_project=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
     mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
-    mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h); only the HIP library exports those."""
+    mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h); only the HIP library
+    exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
-                     + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ()))
+                     + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ())
+                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()))

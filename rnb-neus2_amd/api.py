@@ -47,7 +47,7 @@ def load_library():
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
-                              mesh_visibility=True)
+                              mesh_visibility=True, mesh_project=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -66,6 +66,8 @@ def load_library():
             raise RuntimeError("mesh-texture ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_visibility_abi_version() != _abi.MESH_VISIBILITY_ABI_VERSION:
             raise RuntimeError("mesh-visibility ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_project_abi_version() != _abi.MESH_PROJECT_ABI_VERSION:
+            raise RuntimeError("mesh-project ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -556,7 +558,7 @@ class Context:
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
-                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None):
+                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -574,7 +576,15 @@ class Context:
         bake_texture) with the maps of `texture_maps`, and the dict gains `texture`: the dict of DeviceMesh.bake_texture. With None (the default) nothing of that runs.
         seen_by = views: after keep / orient and before simplify, still on the device, what none of these cameras sees is removed (DeviceMesh.cull_unseen with its
         defaults: whole components, see cull_unseen_mesh; seen_masks = one mask or None per view), and the dict gains `seen_stats` (the select stats) and
-        `visibility_stats`. With None (the default) nothing of that runs and the calls made are exactly those made without it."""
+        `visibility_stats`. With None (the default) nothing of that runs and the calls made are exactly those made without it.
+        texture_from = (views, images) (with texture = S only): the texture is not baked from the model but projected from these images (rnb_mesh_project_views, see
+        project_views, its defaults; the mesh's vertex normals weight the views when normals=True), with the model's albedo as the fallback of the texels no view
+        reaches, and `texture` is the dict of DeviceMesh.project_views (`color` where a bake has `albedo`; texture_maps does not apply). With None (the default) nothing
+        of that runs."""
+        if texture_from is not None and texture is None:
+            raise ValueError("texture_from needs texture")
+        if texture_from is not None and len(texture_from) != 2:
+            raise ValueError("texture_from must be (views, images)")
         if seen_masks is not None and seen_by is None:
             raise ValueError("seen_masks needs seen_by")
         if error and simplify is None:
@@ -592,7 +602,9 @@ class Context:
                 chain.append(chain[-1].simplify(*grid, placement=placement, stream=stream))
                 if error:
                     simplify_error = chain[-2].distance_to(chain[-1], symmetric=True, stream=stream)
-            if texture is not None:
+            if texture is not None and texture_from is not None:
+                baked = chain[-1].project_views(texture_from[0], texture_from[1], texture, fallback="model", inference=inference, stream=stream)
+            elif texture is not None:
                 baked = chain[-1].bake_texture(texture, maps=texture_maps, inference=inference, stream=stream)
             out = chain[-1].download()
             out["stats"] = chain[0].stats
@@ -887,6 +899,74 @@ class Context:
         OBJ + MTL + PNG. Leaves the training state as it was."""
         with self.upload_mesh(verts, indices) as m:
             return m.bake_texture(size, block, maps, inference, max_texels_in_flight, stream)
+
+    def _project_options(self, size, block, mode, normals, weight_power, min_cos, depth_tolerance, near, cull):
+        modes = {"blend": _abi.MESH_PROJECT_MODE_BLEND, "best": _abi.MESH_PROJECT_MODE_BEST}
+        kinds = {"face": _abi.MESH_PROJECT_NORMALS_FACE, "vertex": _abi.MESH_PROJECT_NORMALS_VERTEX}
+        culls = {"none": _abi.MESH_RASTER_CULL_NONE, "back": _abi.MESH_RASTER_CULL_BACK, "front": _abi.MESH_RASTER_CULL_FRONT}
+        if mode not in modes:
+            raise ValueError("mode must be 'blend' or 'best'")
+        if normals not in kinds:
+            raise ValueError("normals must be None, 'face' or 'vertex'")
+        if cull not in culls:
+            raise ValueError("cull must be 'none', 'back' or 'front'")
+        if int(weight_power) != weight_power or not 0 <= int(weight_power) <= _abi.MESH_PROJECT_MAX_WEIGHT_POWER:
+            raise ValueError("weight_power must be an integer 0 .. %d" % _abi.MESH_PROJECT_MAX_WEIGHT_POWER)
+        if not 0.0 <= float(min_cos) < 1.0:
+            raise ValueError("min_cos must be in [0, 1)")
+        if not (float(depth_tolerance) >= 0.0 and math.isfinite(float(depth_tolerance))):
+            raise ValueError("depth_tolerance must be finite and not negative")
+        opt = _abi.MeshProjectOptions()
+        self._check(self.f.mesh_project_default_options(C.byref(opt)))
+        opt.size, opt.block, opt.mode, opt.normals, opt.weight_power = int(size), int(block), modes[mode], kinds[normals], int(weight_power)
+        opt.min_cos, opt.depth_tolerance, opt.near, opt.cull = float(min_cos), float(depth_tolerance), float(near), culls[cull]
+        return opt
+
+    @staticmethod
+    def _project_views(views, images):
+        """The host array of rnb_mesh_project_view for `views` and, per view, its image as a contiguous [h, w, 4] array of float32, uint16 or uint8 (a 3-channel image gets
+        alpha 1: 1.0, 65535 or 255), not yet uploaded."""
+        views, images = list(views), list(images)
+        if not views:
+            raise ValueError("at least one view")
+        if len(images) != len(views):
+            raise ValueError("one image per view")
+        arrays = []
+        for im in images:
+            a = np.asarray(im)
+            if a.dtype.name not in _abi.MESH_PROJECT_FORMATS:
+                raise ValueError("an image must be of dtype float32, uint16 or uint8")
+            if a.ndim != 3 or a.shape[2] not in (3, 4) or 0 in a.shape:
+                raise ValueError("an image must be a non-empty [h, w, 4] (or [h, w, 3]) array")
+            if a.shape[2] == 3:
+                one = 1.0 if a.dtype == np.float32 else np.iinfo(a.dtype).max
+                a = np.concatenate([a, np.full(a.shape[:2] + (1,), one, a.dtype)], axis=2)
+            arrays.append(np.ascontiguousarray(a))
+        if any(max(int(v["width"]), int(v["height"])) > _abi.MESH_RASTER_MAX_SIZE for v in views):
+            raise ValueError("a view exceeds %d pixels per side" % _abi.MESH_RASTER_MAX_SIZE)
+        arr = (_abi.MeshProjectView * len(views))()
+        for e, v, a in zip(arr, views, arrays):
+            e.view = _view_struct(v)
+            e.image_height, e.image_width, e.format = a.shape[0], a.shape[1], _abi.MESH_PROJECT_FORMATS[a.dtype.name]
+        return arr, arrays
+
+    def project_views(self, verts, indices, views, images, normals=None, size=1024, block=0, mode="blend", shading=None, weight_power=2, min_cos=0.1, depth_tolerance=2.0 ** -8,
+                      near=2.0 ** -10, cull="none", fallback=None, inference=True, stream=None):
+        """rnb_mesh_project_views (include/rnb_mesh_project.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3], optional per-vertex `normals`): the atlas of
+        bake_texture (same `size` and `block`, the same `uv`, bit for bit) with every texel coloured from the input images -- projected into each camera of `views` (view
+        dicts as rasterize_mesh takes one), skipped where the view looks at it at a flatter angle than min_cos or where the mesh itself is in front of it by more than the
+        relative depth_tolerance (the rasteriser's nearest surface of the pixel that holds the projection), sampled bilinearly with alpha as the mask, and blended with
+        the weight cos^weight_power * alpha (mode="blend") or taken from the view of the greatest such weight (mode="best").
+        images: one per view, numpy [h, w, 4] (or [h, w, 3]: alpha 1) of dtype float32, uint16 (x / 65535) or uint8 (x / 255), of any resolution, row 0 on top; the values
+        are blended as stored. shading: "face" or "vertex" -- which normal weights a view; None: "vertex" when normals are given, else "face".
+        fallback: None, "model" (the model's albedo baked with the same size and block, see bake_texture; `inference` picks its weights) or a float32 [S, S, 4] array:
+        what an owned texel no view contributes to gets; without one it is (0, 0, 0, 1).
+        Returns a dict: `uv` float32[nt,3,2], `color` float32[S,S,4] (alpha 1 on the texels of a triangle, zeros elsewhere), `info` uint32[S,S,2] (the number of
+        contributing views and the best view, 0xFFFFFFFF if none), `block`, `blocks_per_row` and `stats` (n_texels, n_textured, n_pairs_tested, n_occluded,
+        peak_workspace, ms). Reads nothing of the model (but for fallback="model"): any mesh, any calibrated images. Bit-reproducible. meshproc.save_obj_textured
+        writes `color` as the albedo map. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, normals=normals) as m:
+            return m.project_views(views, images, size, block, mode, shading, weight_power, min_cos, depth_tolerance, near, cull, fallback, inference, stream)
 
     def upload(self, array):
         """numpy array -> library-side buffer (device_malloc + copy); release with device_free."""
@@ -1204,4 +1284,46 @@ class DeviceMesh(_abi.Mesh):
             out.update(block=tex.block, blocks_per_row=tex.blocks_per_row, stats=st.as_dict())
         finally:
             c.f.mesh_texture_free(c._h, C.byref(tex))  # (whatever a failed call left: a zeroed struct releases nothing)
+        return out
+
+    def project_views(self, views, images, size=1024, block=0, mode="blend", normals=None, weight_power=2, min_cos=0.1, depth_tolerance=2.0 ** -8, near=2.0 ** -10, cull="none",
+                      fallback=None, inference=True, stream=None):
+        """rnb_mesh_project_views of this mesh: the dict of Context.project_views, which describes every argument and key (normals: its `shading`; None means the vertex
+        normals when the mesh has them, else the face normals). Every image is uploaded once; the images, the fallback and the device result are released before the call
+        returns, whether or not a step raises."""
+        c = self._live()
+        if normals is None:
+            normals = "vertex" if self.has_normals else "face"
+        opt = c._project_options(size, block, mode, normals, weight_power, min_cos, depth_tolerance, near, cull)
+        if normals == "vertex" and not self.has_normals:
+            raise ValueError("normals='vertex' needs a mesh with normals")
+        varr, arrays = c._project_views(views, images)
+        fb = None
+        if fallback is not None and not (isinstance(fallback, str) and fallback == "model"):
+            fb = np.ascontiguousarray(fallback, dtype=np.float32)
+            if fb.shape != (int(size), int(size), 4):
+                raise ValueError("fallback must be None, 'model' or a float32 array [size, size, 4]")
+        own, proj, tex, st = [], _abi.MeshProjection(), _abi.MeshTexture(), _abi.MeshProjectStats()
+        try:
+            for e, a in zip(varr, arrays):
+                own.append(c.upload(a))
+                e.image_dev = own[-1]
+            if fb is not None:
+                own.append(c.upload(fb))
+                opt.fallback_dev = own[-1]
+            elif fallback is not None:
+                topt = c._texture_options(size, block, ("albedo",), inference, 0)
+                c._check(c.f.mesh_bake_texture(c._h, _stream_handle(stream), C.byref(self), C.byref(topt), C.byref(tex), None))
+                opt.fallback_dev = tex.albedo
+            c._check(c.f.mesh_project_views(c._h, _stream_handle(stream), C.byref(self), varr, len(varr), C.byref(opt), C.byref(proj), C.byref(st)))
+            nt, n = proj.n_tris, proj.size * proj.size
+            out = dict(uv=c.download(proj.uv, nt * 6, np.float32).reshape(nt, 3, 2) if nt else np.empty((0, 3, 2), np.float32),
+                       color=c.download(proj.color, n * 4, np.float32).reshape(proj.size, proj.size, 4),
+                       info=c.download(proj.info, n * 2, np.uint32).reshape(proj.size, proj.size, 2),
+                       block=proj.block, blocks_per_row=proj.blocks_per_row, stats=st.as_dict())
+        finally:
+            c.f.mesh_projection_free(c._h, C.byref(proj))  # (whatever a failed call left: a zeroed struct releases nothing)
+            c.f.mesh_texture_free(c._h, C.byref(tex))
+            for p in own:
+                c.device_free(p)
         return out

@@ -1,6 +1,6 @@
 // driver_mesh.hpp -- rnb_sdf_lattice, what the mesh drivers share (scan_exclusive, count_and_scan, MeshWorkspace, check_mesh_input, alloc_mesh, hand_over,
 // ensure_mc_table), rnb_marching_cubes and the stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_visibility,
-// rnb_mesh_visibility_select, rnb_mesh_bake_texture.
+// rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views.
 // Needs, of rnb_neus2_hip.hip, which includes it: the context (aabb, bitfield, cfg, mc_table), as_stream, fail / HIP_TRY / RNB_GUARD, launch_point_query
 // and launch_forward.
 extern "C" {
@@ -1167,6 +1167,166 @@ int rnb_mesh_bake_texture(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const 
 	if (stats) {
 		stats->n_texels = network ? A.n_texels : 0u;
 		stats->n_batches = n_batches;
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- view projection (include/rnb_mesh_project.h) ----
+uint32_t rnb_mesh_project_abi_version(void) { return RNB_MESH_PROJECT_ABI_VERSION; }
+
+int rnb_mesh_project_default_options(rnb_mesh_project_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_PROJECT_ABI_VERSION;
+	opt->size = 1024u;
+	opt->mode = RNB_MESH_PROJECT_MODE_BLEND;
+	opt->normals = RNB_MESH_PROJECT_NORMALS_FACE;
+	opt->weight_power = 2u;
+	opt->min_cos = 0.1f;
+	opt->depth_tolerance = 1.0f / 256.0f;
+	opt->near = 1.0f / 1024.0f;
+	opt->cull = RNB_MESH_RASTER_CULL_NONE;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_projection_free(rnb_ctx* c, rnb_mesh_projection* out) try {
+	if (!c || !out) return fail(RNB_ERR_INVALID, "null argument");
+	if (out->uv) (void)hipFree(out->uv);
+	if (out->color) (void)hipFree(out->color);
+	if (out->info) (void)hipFree(out->info);
+	std::memset(out, 0, sizeof(*out));
+	return RNB_OK;
+} RNB_GUARD
+
+extern "C++" {
+namespace {
+constexpr bool MP_FILL_TALLIES = false; // the projection reads the keys of the fill and none of the visibility stage's tallies
+template <int FMT>
+void launch_mp_accumulate(hipStream_t s, const MrCamera& cam, const MpState& st, const unsigned long long* keys, const MpImage& img, const MpParams& P, MpResult* dres) {
+	hipLaunchKernelGGL(k_mp_accumulate<FMT>, dim3((st.n + MP_WG - 1) / MP_WG), dim3(MP_WG), 0, s, cam, st, keys, img, P, dres);
+}
+} // namespace
+} // extern "C++"
+
+int rnb_mesh_project_views(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_mesh_project_view* views, uint32_t n_views, const rnb_mesh_project_options* opt,
+                           rnb_mesh_projection* out, rnb_mesh_project_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (out) std::memset(out, 0, sizeof(*out));
+	if (!c || !mesh || !views || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: null argument");
+	if (n_views == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: n_views must be at least 1");
+	if (opt->abi_version != RNB_MESH_PROJECT_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: options abi_version mismatch (expected RNB_MESH_PROJECT_ABI_VERSION)");
+	if (opt->size < RNB_MESH_TEXTURE_MIN_SIZE || opt->size > RNB_MESH_TEXTURE_MAX_SIZE) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: size must be 4 .. 8192");
+	if (opt->mode > RNB_MESH_PROJECT_MODE_BEST) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: mode must be RNB_MESH_PROJECT_MODE_BLEND or _BEST");
+	if (opt->normals > RNB_MESH_PROJECT_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: normals must be RNB_MESH_PROJECT_NORMALS_FACE or _VERTEX");
+	if (opt->weight_power > RNB_MESH_PROJECT_MAX_WEIGHT_POWER) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: weight_power must be 0 .. 8");
+	if (!(opt->min_cos >= 0.0f && opt->min_cos < 1.0f)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: min_cos must be in [0, 1)");
+	if (!(opt->depth_tolerance >= 0.0f) || !std::isfinite(opt->depth_tolerance)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: depth_tolerance must be finite and >= 0");
+	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: near must be finite and > 0");
+	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: cull must be 0 (none), 1 (back) or 2 (front)");
+	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: a reserved word of the options is not 0");
+	if (opt->fallback_dev && ((uintptr_t)opt->fallback_dev & 15u)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: fallback_dev is not aligned to 16 bytes");
+	uint32_t max_pix = 0;
+	for (uint32_t v = 0; v < n_views; ++v) {
+		const rnb_mesh_project_view& V = views[v];
+		const std::string who = "rnb_mesh_project_views: view " + std::to_string(v);
+		if (int rc = check_raster_view("rnb_mesh_project_views", &V.view); rc != RNB_OK) return rc;
+		if (!V.image_dev) return fail(RNB_ERR_INVALID, who + " has a null image");
+		if (V.image_width == 0 || V.image_height == 0) return fail(RNB_ERR_INVALID, who + " has an image of size 0");
+		if (V.format > RNB_MESH_PROJECT_FORMAT_U8) return fail(RNB_ERR_INVALID, who + " has an unknown format");
+		if ((uintptr_t)V.image_dev & (V.format == RNB_MESH_PROJECT_FORMAT_F32 ? 15u : V.format == RNB_MESH_PROJECT_FORMAT_U16 ? 7u : 3u)) return fail(RNB_ERR_INVALID, who + " has an image that is not aligned to one pixel");
+		if (V.reserved) return fail(RNB_ERR_INVALID, who + " has a reserved word that is not 0");
+		max_pix = std::max(max_pix, V.view.width * V.view.height); // at most 2^28
+	}
+	{
+		rnb_mesh unused;
+		if (int rc = check_mesh_input("rnb_mesh_project_views", mesh, &unused); rc != RNB_OK) return rc;
+	}
+	if (opt->normals == RNB_MESH_PROJECT_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: normals = VERTEX needs a mesh with normals");
+	const rnb_mesh m = *mesh;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, S = opt->size;
+	MtAtlas A;
+	std::memset(&A, 0, sizeof(A));
+	uint32_t n_blocks = 0;
+	if (int rc = rnb_mesh_texture_layout(nt, S, opt->block, &A.block, &A.bpr, &n_blocks); rc != RNB_OK) return rc;
+	A.size = S; A.n_tris = nt;
+	A.n_texels = n_blocks * A.block * A.block; // at most S * S = 2^26
+	const auto t_begin = std::chrono::steady_clock::now();
+	hipStream_t s = as_stream(stream);
+	join_tail_host(c);
+
+	MeshWorkspace ws;
+	const size_t n_pix = (size_t)S * S, n = A.n_texels;
+	float* uv = nullptr;
+	f4* color = nullptr;
+	mp_u2* info = nullptr;
+	MpResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	if (!ws.alloc(&uv, (size_t)nt * 6) || !ws.alloc(&color, n_pix) || !ws.alloc(&info, n_pix))
+		return fail(RNB_ERR_NOMEM, "rnb_mesh_project_views: hipMalloc failed for the maps of " + std::to_string(S) + "^2 texels and the UVs of " + std::to_string(nt) + " triangles");
+	HIP_TRY(hipMemsetAsync(color, 0, n_pix * sizeof(f4), s));
+	HIP_TRY(hipMemsetAsync(info, 0, n_pix * sizeof(mp_u2), s));
+	if (nt) {
+		const MrMesh M{m.verts, m.indices, nullptr, nullptr, nt};
+		unsigned long long* keys = nullptr;
+		uint32_t *counts = nullptr, *used = nullptr, *list = nullptr, list_cap = 0;
+		MrResult* dfill = nullptr;
+		MpResult* dres = nullptr;
+		MpState st;
+		std::memset(&st, 0, sizeof(st));
+		st.n = A.n_texels;
+		if (!ws.alloc(&keys, max_pix) || !ws.alloc(&counts, max_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dfill, 1) || !ws.alloc(&dres, 1) || !ws.alloc(&st.p, 3 * n) || !ws.alloc(&st.nrm, 3 * n) ||
+		    !ws.alloc(&st.acc, 4 * n) || !ws.alloc(&st.w_best, n) || !ws.alloc(&st.count, n) || !ws.alloc(&st.best, n))
+			return fail(RNB_ERR_NOMEM, "rnb_mesh_project_views: hipMalloc failed for the workspace of " + std::to_string(max_pix) + " pixels, " + std::to_string(n) + " texels and " + std::to_string(nv) + " vertices");
+		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		hipLaunchKernelGGL(k_mesh_validate, dim3((nt + MP_WG - 1) / MP_WG), dim3(MP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, MP_BAD_INDEX);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MP_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: an index is out of range (>= n_verts)");
+		ws.release(used);
+		// 2. p and N of every texel, the accumulators cleared
+		const uint32_t g_w = (A.n_texels + MP_WG - 1) / MP_WG;
+		hipLaunchKernelGGL(k_mp_setup, dim3(g_w), dim3(MP_WG), 0, s, A, (const float*)m.verts, (const uint32_t*)m.indices, (const float*)m.normals, opt->normals, st);
+		HIP_TRY(hipGetLastError());
+		// 3. view by view: the rasteriser's fill, then every texel against its keys and its image
+		MpParams P;
+		std::memset(&P, 0, sizeof(P));
+		P.min_cos = (double)opt->min_cos; P.slack = 1.0 + (double)opt->depth_tolerance;
+		P.power = opt->weight_power; P.mode = opt->mode;
+		for (uint32_t v = 0; v < n_views; ++v) {
+			const rnb_mesh_project_view& V = views[v];
+			const uint32_t n_view_pix = V.view.width * V.view.height;
+			const MrCamera cam = raster_camera(&V.view, opt->near, opt->cull, RNB_MESH_RASTER_NORMALS_FACE);
+			MrResult hfill;
+			std::memset(&hfill, 0, sizeof(hfill));
+			HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_view_pix * 8, s));
+			HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_view_pix * 4, s));
+			HIP_TRY(hipMemcpyAsync(dfill, &hfill, sizeof(hfill), hipMemcpyHostToDevice, s));
+			if (int rc = raster_fill<MP_FILL_TALLIES>("rnb_mesh_project_views", ws, s, cam, M, keys, counts, dfill, &hfill, &list, &list_cap, MrTally{}); rc != RNB_OK) return rc;
+			const MpImage img{V.image_dev, V.image_width, V.image_height};
+			P.view = v;
+			if (V.format == RNB_MESH_PROJECT_FORMAT_F32) launch_mp_accumulate<RNB_MESH_PROJECT_FORMAT_F32>(s, cam, st, keys, img, P, dres);
+			else if (V.format == RNB_MESH_PROJECT_FORMAT_U16) launch_mp_accumulate<RNB_MESH_PROJECT_FORMAT_U16>(s, cam, st, keys, img, P, dres);
+			else launch_mp_accumulate<RNB_MESH_PROJECT_FORMAT_U8>(s, cam, st, keys, img, P, dres);
+			HIP_TRY(hipGetLastError());
+		}
+		// 4. the result
+		hipLaunchKernelGGL(k_mp_finish, dim3(g_w), dim3(MP_WG), 0, s, A, st, (const f4*)opt->fallback_dev, uv, color, info, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		ws.release(keys); ws.release(counts); ws.release(list); ws.release(dfill); ws.release(dres);
+		ws.release(st.p); ws.release(st.nrm); ws.release(st.acc); ws.release(st.w_best); ws.release(st.count); ws.release(st.best);
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	out->uv = (float*)ws.keep(uv); out->color = (float*)ws.keep(color); out->info = (uint32_t*)ws.keep(info);
+	out->size = S; out->block = A.block; out->blocks_per_row = A.bpr; out->n_tris = nt;
+	if (stats) {
+		stats->n_texels = hres.n_texels; stats->n_textured = hres.n_textured; stats->n_pairs_tested = hres.n_tested; stats->n_occluded = hres.n_occluded;
 		stats->peak_workspace = ws.peak;
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}

@@ -37,6 +37,28 @@ __device__ __forceinline__ bool mt_texel(const MtAtlas& A, const uint32_t w, MtT
 	return t.tri < A.n_tris;
 }
 
+// The position of an owned texel, the header's formula, and (i0, i1, i2) its triangle's vertices (range-checked by k_mesh_validate). Shared with the view projection
+// (kernels_mesh_project.cuh), whose texels are these.
+__device__ __forceinline__ void mt_position(const MtAtlas& A, const MtTexel& t, const float* __restrict__ verts, const uint32_t* __restrict__ idx, float v[3], uint32_t& i0, uint32_t& i1, uint32_t& i2) {
+#pragma clang fp contract(off)
+	i0 = idx[3 * (size_t)t.tri]; i1 = idx[3 * (size_t)t.tri + 1]; i2 = idx[3 * (size_t)t.tri + 2];
+	const double a0 = (double)t.a0, a1 = (double)t.a1, a2 = (double)t.a2, n = (double)((int)A.block - 3);
+#pragma unroll
+	for (int k = 0; k < 3; ++k)
+		v[k] = (float)(((a0 * (double)verts[3 * (size_t)i0 + k] + a1 * (double)verts[3 * (size_t)i1 + k]) + a2 * (double)verts[3 * (size_t)i2 + k]) / n);
+}
+// Which corner of its triangle an owned texel is (one weight n, the others 0: they add up to n), or -1; and the corner's (U, V) by the layout's formula.
+__device__ __forceinline__ int mt_corner(const MtAtlas& A, const MtTexel& t) {
+	const int nn = (int)A.block - 3;
+	return (t.a1 == 0 && t.a2 == 0) ? 0 : ((t.a1 == nn && t.a2 == 0) ? 1 : ((t.a1 == 0 && t.a2 == nn) ? 2 : -1));
+}
+__device__ __forceinline__ void mt_corner_uv(const MtAtlas& A, const MtTexel& t, const int corner, float* __restrict__ uv) {
+#pragma clang fp contract(off)
+	float* o = uv + ((size_t)t.tri * 3 + (size_t)corner) * 2;
+	o[0] = (float)(((double)t.x + 0.5) / (double)A.size);
+	o[1] = (float)(1.0 - ((double)t.y + 0.5) / (double)A.size);
+}
+
 // Texels w0 .. w0 + nb - 1. uv: float[n_tris][3][2], written by the three corner texels of every triangle. position (or null): the position map. coords (or null): the network input of the batch, 7 floats per texel; a texel without a triangle gets
 // the input of the point (0, 0, 0), so that the batch stays dense (its output is not used).
 __global__ __launch_bounds__(MT_WG) void k_mt_texels(const MtAtlas A, const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t w0, const uint32_t nb,
@@ -47,18 +69,11 @@ __global__ __launch_bounds__(MT_WG) void k_mt_texels(const MtAtlas A, const floa
 	MtTexel t;
 	float v[3] = {0.f, 0.f, 0.f};
 	if (mt_texel(A, w0 + q, t)) {
-		const uint32_t i0 = idx[3 * (size_t)t.tri], i1 = idx[3 * (size_t)t.tri + 1], i2 = idx[3 * (size_t)t.tri + 2]; // (range-checked by k_mesh_validate)
-		const double a0 = (double)t.a0, a1 = (double)t.a1, a2 = (double)t.a2, n = (double)((int)A.block - 3);
-#pragma unroll
-		for (int k = 0; k < 3; ++k)
-			v[k] = (float)(((a0 * (double)verts[3 * (size_t)i0 + k] + a1 * (double)verts[3 * (size_t)i1 + k]) + a2 * (double)verts[3 * (size_t)i2 + k]) / n);
+		uint32_t i0, i1, i2;
+		mt_position(A, t, verts, idx, v, i0, i1, i2);
 		if (position) position[(size_t)t.y * A.size + t.x] = f4{v[0], v[1], v[2], 1.0f};
-		const int nn = (int)A.block - 3, corner = (t.a1 == 0 && t.a2 == 0) ? 0 : ((t.a1 == nn && t.a2 == 0) ? 1 : ((t.a1 == 0 && t.a2 == nn) ? 2 : -1)); // (one weight n, the others 0: they add up to n)
-		if (corner >= 0) {
-			float* o = uv + ((size_t)t.tri * 3 + (size_t)corner) * 2;
-			o[0] = (float)(((double)t.x + 0.5) / (double)A.size);
-			o[1] = (float)(1.0 - ((double)t.y + 0.5) / (double)A.size);
-		}
+		const int corner = mt_corner(A, t);
+		if (corner >= 0) mt_corner_uv(A, t, corner, uv);
 	}
 	if (!coords) return;
 	// k_ms_vertex_coords, expression for expression, for a position inside the scene's box: a corner texel gets the network input of its vertex

@@ -4,7 +4,7 @@
 //
 //   mesh --snapshot PATH --scene DIR --out FILE.obj [--resolution R] [--cull none|occupancy] [--brick N] [--normals ring|gradient]
 //        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean] [--report-error]] [--report-views [--views-out FILE]]
-//        [--texture S [--texture-maps albedo[,normal]]]
+//        [--texture S [--texture-maps albedo[,normal]] [--texture-from views [--texture-mode blend|best] [--texture-depth-tolerance T] [--texture-min-cos C]]]
 //        [--keep-seen component|faces [--seen-min-views N] [--seen-rings R] [--seen-masks [--seen-max-off N]] [--seen-supersample K]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
@@ -26,6 +26,9 @@
 // With --texture S the mesh as finally written (after --keep, --orient and --simplify), still on the device, gets a texture bake (rnb_mesh_bake_texture,
 // include/rnb_mesh_texture.h): a per-triangle atlas of S x S texels and the model's albedo (and, with --texture-maps albedo,normal, its SDF-gradient normal) at every
 // texel. The output is then FILE.obj with vt records (mesh::save_obj_textured), FILE.mtl, FILE_albedo.png and FILE_normal.png.
+// With --texture-from views the albedo map is not the model's but the scene's own albedo maps projected onto the mesh (rnb_mesh_project_views, include/rnb_mesh_project.h):
+// the images as the loader read them (16 bit, their alpha the mask, the stored values as they are -- the scale the model's albedo and FILE_albedo.png have), every
+// camera of the scene, the model's baked albedo as the fallback of the texels no view reaches. The atlas is the same one: the vt records do not change.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -35,6 +38,7 @@
 #include "../../include/rnb_mesh_raster.h"
 #include "../../include/rnb_mesh_texture.h"
 #include "../../include/rnb_mesh_visibility.h"
+#include "../../include/rnb_mesh_project.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -82,6 +86,10 @@ const Flag FLAGS[] = {
 	{"seen-max-off", "N", "--seen-masks only. Also drop what lies off the mask in more than N views (default: the masks carve nothing)."},
 	{"seen-supersample", "K", "--keep-seen only. Measure in views of K times the resolution (default 1); the masks stay as they are."},
 	{"texture-maps", "LIST", "--texture only. The maps to bake, separated by commas: albedo (default), normal (the SDF gradient, object space, FILE_normal.png)."},
+	{"texture-from", "SOURCE", "--texture only. views: the albedo map is projected from the scene's albedo maps through its cameras; the model's albedo fills what no view reaches."},
+	{"texture-mode", "MODE", "--texture-from only. blend (default): the views weighted by cos^2 * alpha; best: the view of the greatest weight alone."},
+	{"texture-depth-tolerance", "T", "--texture-from only. Relative depth slack of the occlusion test (>= 0, default 0.00390625)."},
+	{"texture-min-cos", "C", "--texture-from only. A view that looks at the surface at a cosine of at most C is skipped ([0, 1), default 0.1)."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -124,6 +132,13 @@ uint32_t parse_u32(const std::string& k, const std::string& s) {
 	const unsigned long long v = std::strtoull(s.c_str(), &e, 10);
 	if (s.empty() || *e || s[0] == '-' || v > 0xffffffffull) throw ParseError("Argument '" + k + "' received invalid value type '" + s + "'");
 	return (uint32_t)v;
+}
+
+float parse_float(const std::string& k, const std::string& s) {
+	char* e = nullptr;
+	const float v = std::strtof(s.c_str(), &e);
+	if (s.empty() || *e || !std::isfinite(v)) throw ParseError("Argument '" + k + "' received invalid value type '" + s + "'");
+	return v;
 }
 
 #define RNB_CHECK(expr)                                                                          \
@@ -235,6 +250,51 @@ void keep_seen(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& dm, const SeenOp
 	report += line;
 }
 
+// --texture-from views: the scene's albedo maps projected onto *dm in the atlas of the bake `dt`, whose albedo is the fallback. `color`: the map, float[S][S][4].
+struct ProjectOptions { uint32_t mode = RNB_MESH_PROJECT_MODE_BLEND; float depth_tolerance = 1.0f / 256.0f, min_cos = 0.1f; bool tolerance_given = false, min_cos_given = false; };
+void project_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& dm, const rnb_mesh_texture& dt, const ProjectOptions& po, std::vector<float>& color, std::string& report) {
+	std::vector<rnb_mesh_project_view> views(ds.views.size());
+	std::vector<void*> held;
+	rnb_mesh_projection pr;
+	rnb_mesh_project_stats ps;
+	std::memset(&pr, 0, sizeof(pr));
+	try {
+		for (size_t vi = 0; vi < ds.views.size(); ++vi) {
+			const png16::Image& in = ds.albedos[vi];
+			if (in.rgba.empty()) throw std::runtime_error("--texture-from: the albedo map of view " + std::to_string(vi) + " is empty");
+			void* d = nullptr;
+			RNB_CHECK(rnb_device_malloc(ctx, in.rgba.size() * 2, &d));
+			held.push_back(d);
+			RNB_CHECK(rnb_memcpy(ctx, d, in.rgba.data(), in.rgba.size() * 2, RNB_H2D));
+			rnb_mesh_project_view& V = views[vi];
+			std::memset(&V, 0, sizeof(V));
+			V.view = ds.views[vi];
+			V.image_dev = d; V.image_width = in.width; V.image_height = in.height; V.format = RNB_MESH_PROJECT_FORMAT_U16;
+		}
+		rnb_mesh_project_options o;
+		RNB_CHECK(rnb_mesh_project_default_options(&o));
+		o.size = dt.size; o.block = dt.block; o.mode = po.mode;
+		o.normals = dm.normals ? RNB_MESH_PROJECT_NORMALS_VERTEX : RNB_MESH_PROJECT_NORMALS_FACE;
+		if (po.tolerance_given) o.depth_tolerance = po.depth_tolerance;
+		if (po.min_cos_given) o.min_cos = po.min_cos;
+		o.fallback_dev = dt.albedo;
+		RNB_CHECK(rnb_mesh_project_views(ctx, nullptr, &dm, views.data(), (uint32_t)views.size(), &o, &pr, &ps));
+		color.resize((size_t)pr.size * pr.size * 4);
+		RNB_CHECK(rnb_memcpy(ctx, color.data(), pr.color, (uint64_t)color.size() * 4, RNB_D2H));
+	} catch (...) {
+		rnb_mesh_projection_free(ctx, &pr);
+		for (void* p : held) rnb_device_free(ctx, p);
+		throw;
+	}
+	RNB_CHECK(rnb_mesh_projection_free(ctx, &pr));
+	for (void* p : held) RNB_CHECK(rnb_device_free(ctx, p));
+	char line[320];
+	std::snprintf(line, sizeof(line), "texture from %zu views (%s): %llu of %llu texels textured, %llu pairs tested of which %llu occluded, peak workspace %.1f MB, %.1f ms\n", ds.views.size(),
+	              po.mode == RNB_MESH_PROJECT_MODE_BEST ? "best" : "blend", (unsigned long long)ps.n_textured, (unsigned long long)ps.n_texels, (unsigned long long)ps.n_pairs_tested,
+	              (unsigned long long)ps.n_occluded, (double)ps.peak_workspace / 1e6, ps.ms);
+	report += line;
+}
+
 } // namespace
 
 int main(int argc, char** argv) {
@@ -245,8 +305,9 @@ int main(int argc, char** argv) {
 	uint32_t simplify = 0, placement = RNB_MESH_PLACE_QUADRIC;           // 0: no simplification
 	bool report_error = false, want_views = false;
 	uint32_t texture = 0, texture_maps = RNB_MESH_TEXTURE_ALBEDO; // 0: no texture
-	bool want_seen = false;
+	bool want_seen = false, texture_from = false;
 	SeenOptions seen;
+	ProjectOptions project;
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -325,6 +386,27 @@ int main(int argc, char** argv) {
 				else if (name == "normal") texture_maps |= RNB_MESH_TEXTURE_NORMAL;
 				else throw ParseError("Argument 'texture-maps' must be a list of albedo and normal");
 			}
+		}
+		if (a.count("texture-from")) {
+			if (!texture) throw ParseError("Argument 'texture-from' is only used with --texture");
+			if (a["texture-from"] != "views") throw ParseError("Argument 'texture-from' must be views");
+			texture_from = true;
+		}
+		for (const char* sub : {"texture-mode", "texture-depth-tolerance", "texture-min-cos"})
+			if (a.count(sub) && !texture_from) throw ParseError(std::string("Argument '") + sub + "' is only used with --texture-from");
+		if (a.count("texture-mode")) {
+			if (a["texture-mode"] == "best") project.mode = RNB_MESH_PROJECT_MODE_BEST;
+			else if (a["texture-mode"] != "blend") throw ParseError("Argument 'texture-mode' must be blend or best");
+		}
+		if (a.count("texture-depth-tolerance")) {
+			project.depth_tolerance = parse_float("texture-depth-tolerance", a["texture-depth-tolerance"]);
+			project.tolerance_given = true;
+			if (!(project.depth_tolerance >= 0.0f)) throw ParseError("Argument 'texture-depth-tolerance' must not be negative");
+		}
+		if (a.count("texture-min-cos")) {
+			project.min_cos = parse_float("texture-min-cos", a["texture-min-cos"]);
+			project.min_cos_given = true;
+			if (!(project.min_cos >= 0.0f && project.min_cos < 1.0f)) throw ParseError("Argument 'texture-min-cos' must be in [0, 1)");
 		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
@@ -421,7 +503,7 @@ int main(int argc, char** argv) {
 		if (texture) {
 			rnb_mesh_texture_options to;
 			RNB_CHECK(rnb_mesh_texture_default_options(&to));
-			to.size = texture; to.maps = texture_maps;
+			to.size = texture; to.maps = texture_maps | (texture_from ? RNB_MESH_TEXTURE_ALBEDO : 0u); // the model's albedo is the projection's fallback
 			RNB_CHECK(rnb_mesh_bake_texture(ctx, nullptr, &dm, &to, &dt, &ts));
 			tex.size = dt.size;
 			tex.uv.resize((size_t)dt.n_tris * 6);
@@ -431,6 +513,11 @@ int main(int argc, char** argv) {
 			if (dt.normal) { tex.normal.resize(n_map); RNB_CHECK(rnb_memcpy(ctx, tex.normal.data(), dt.normal, n_map * 4, RNB_D2H)); }
 			std::printf("texture: %u^2 texels, blocks of %u (%u per row) for %u triangles, %llu texels through the network in %u batches, peak workspace %.1f MB, %.1f ms\n", dt.size, dt.block,
 			            dt.blocks_per_row, dt.n_tris, (unsigned long long)ts.n_texels, ts.n_batches, (double)ts.peak_workspace / 1e6, ts.ms);
+			if (texture_from) { // the same atlas: the albedo map becomes the projection of the scene's albedo maps
+				std::string line;
+				project_views(ctx, ds, dm, dt, project, tex.albedo, line);
+				std::fputs(line.c_str(), stdout);
+			}
 			RNB_CHECK(rnb_mesh_texture_free(ctx, &dt));
 		}
 		mesh::Mesh m;

@@ -168,7 +168,7 @@ def postprocess_mesh(data_dir, output_mesh_path, logger=None):
     shutil.rmtree(os.path.join(data_dir, "output"), ignore_errors=True)
 
 
-def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None):
+def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None, texture_from=None):
     """The last stage on the device: one `build/mesh` process that extracts the mesh of the stage-2 snapshot (plan_two_stage passes --save-snapshot) at `resolution`,
     keeps the largest connected component and turns it outward (include/rnb_mesh_clean.h), and writes `output_mesh_path`. Pure; the snapshot named here is the first
     of snapshot_candidates, run_device_postprocess replaces it by the one that exists. simplify = N: the cleaned mesh is then simplified on N^3 cells over the
@@ -178,7 +178,12 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
     build/mesh --texture S writes <out> with vt records, the .mtl and the _albedo.png beside it); None (the default) plans the command without it.
     keep_seen = "component" or "faces", or a dict(unit=..., min_views=N, rings=R, masks=True, max_off=N, supersample=K) of which only `unit` is needed: what no camera of
     the scene sees is dropped on the device after the cleaning and before the simplification (include/rnb_mesh_visibility.h, build/mesh --keep-seen ... and its
-    --seen-* flags); None (the default) plans the command without it."""
+    --seen-* flags); None (the default) plans the command without it. texture_from = "views" (with texture only): the texture is projected from the scene's albedo maps
+    through their cameras (include/rnb_mesh_project.h, build/mesh --texture-from views), the model's albedo where no view reaches; None (the default) plans the command without it."""
+    if texture_from is not None and texture is None:
+        raise ValueError("texture_from needs texture")
+    if texture_from not in (None, "views"):
+        raise ValueError("texture_from must be 'views'")
     argv = [str(mesh_exe), "--snapshot", snapshot_candidates(data_dir, max_steps)[0], "--scene", str(data_dir), "--out", str(output_mesh_path),
             "--resolution", str(resolution), "--keep", "largest", "--orient", "outward"]
     if simplify is not None:
@@ -187,6 +192,8 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
         argv += ["--report-views"]
     if texture is not None:
         argv += ["--texture", str(int(texture))]
+    if texture_from is not None:
+        argv += ["--texture-from", texture_from]
     if keep_seen is not None:
         argv += keep_seen_flags(keep_seen)
     return argv
@@ -220,10 +227,12 @@ def default_mesh_exe(testbed_path):
     return os.path.join(os.path.dirname(os.path.abspath(testbed_path)), "mesh")
 
 
-def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None, simplify=None, report_views=False, texture=None, keep_seen=None):
+def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None, simplify=None, report_views=False, texture=None, keep_seen=None,
+                           texture_from=None):
     """postprocess_mesh's job without the OBJ round trip: runs plan_device_postprocess' command, then drops the training output directory as postprocess_mesh does."""
     logger = logger or SimpleLogger()
-    cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=simplify, report_views=report_views, texture=texture, keep_seen=keep_seen)
+    cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=simplify, report_views=report_views, texture=texture, keep_seen=keep_seen,
+                                  texture_from=texture_from)
     found = [p for p in snapshot_candidates(data_dir, max_steps) if os.path.exists(p)]
     if not found:
         raise RuntimeError("Snapshot not found after {} iterations".format(max_steps))
@@ -245,14 +254,17 @@ def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, me
 def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mesh_resolution=1024, scaling_mode="auto", sphere_scale=1.0, margin_px=20,
                       warmup_ratio=0.1, mask_weight=1.0, super_normal=False, use_l1=False, use_rgb_plus=True, has_albedo=False,
                       albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None, device_postprocess=False, mesh_exe=None, simplify=None, report_views=False, texture=None,
-                      keep_seen=None):
+                      keep_seen=None, texture_from=None):
     """load -> prepare (<output_dir>/prepared_data) -> train (two-stage, or warm-up + albedo scaling + two-stage when
     `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
     device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh;
     simplify = N (with device_postprocess only): that step also simplifies the mesh on N^3 cells (build/mesh --simplify N);
     report_views (with device_postprocess only): that step also writes <output_dir>/mesh.obj.views.json, the mesh's normal angle and mask IoU per input view;
     texture = S (with device_postprocess only): that step also bakes an albedo texture of S x S texels: mesh.obj gets vt records, mesh.mtl and mesh_albedo.png beside it;
-    keep_seen (with device_postprocess only): that step also drops what no camera sees (plan_device_postprocess describes the value; build/mesh --keep-seen)."""
+    keep_seen (with device_postprocess only): that step also drops what no camera sees (plan_device_postprocess describes the value; build/mesh --keep-seen);
+    texture_from = "views" (with texture only): the texture is projected from the input albedo maps instead of baked from the model (build/mesh --texture-from views)."""
+    if texture_from is not None and texture is None:
+        raise ValueError("texture_from needs texture")
     if keep_seen is not None and not device_postprocess:
         raise ValueError("keep_seen needs device_postprocess")
     if simplify is not None and not device_postprocess:
@@ -278,7 +290,7 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     output_mesh = os.path.join(output_dir, "mesh.obj")
     if device_postprocess:
         run_device_postprocess(data_dir, max_steps, mesh_resolution, output_mesh, mesh_exe or default_mesh_exe(testbed_path), logger, simplify=simplify, report_views=report_views, texture=texture,
-                               keep_seen=keep_seen)
+                               keep_seen=keep_seen, texture_from=texture_from)
     else:
         postprocess_mesh(data_dir, output_mesh, logger)
     logger.info("=== Pipeline complete ===")

@@ -39,6 +39,7 @@ _SPEC = """
 --simplify          | int   |        | --device-postprocess only: simplify the final mesh on the GPU by vertex clustering on N^3 cells over the scene box (build/mesh --simplify N)
 --report-views      | flag  |        | --device-postprocess only: rasterise the final mesh into every input view and write its normal angle and mask IoU per view (build/mesh --report-views)
 --texture           | int   |        | --device-postprocess only: bake an albedo texture of S x S texels for the final mesh on the GPU; mesh.mtl and mesh_albedo.png beside mesh.obj (build/mesh --texture S)
+--texture-from      | str   |        | --texture only: views = the texture is projected from the input albedo maps through their cameras, the model's albedo where no view reaches (build/mesh --texture-from views)
 --keep-seen         | str   |        | --device-postprocess only: drop what no input view sees from the final mesh on the GPU, component (whole connected components) or faces (build/mesh --keep-seen)
 --seen-min-views    | int   |        | --keep-seen only: a triangle counts as seen if at least N views see it
 --seen-rings        | int   |        | --keep-seen faces only: grow the seen triangles by R rings of neighbours
@@ -73,7 +74,7 @@ def pipeline_kwargs(ns):
     """argparse namespace -> keywords of rnb_neus2_amd.pipeline.run_full_pipeline."""
     renamed = {"input": "input_path", "testbed": "testbed_path", "output": "output_dir", "supernormal": "super_normal", "l1": "use_l1",
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
-    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "keep_seen", "seen_min_views",
+    kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "texture_from", "keep_seen", "seen_min_views",
                                                                                 "seen_rings", "seen_masks", "seen_max_off", "seen_supersample")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
@@ -85,6 +86,8 @@ def pipeline_kwargs(ns):
             kw["report_views"] = True
         if ns.texture is not None:
             kw["texture"] = ns.texture
+        if ns.texture_from:
+            kw["texture_from"] = ns.texture_from
         if ns.keep_seen:
             ks = dict(unit=ns.keep_seen, min_views=ns.seen_min_views, rings=ns.seen_rings, masks=ns.seen_masks or None, max_off=ns.seen_max_off, supersample=ns.seen_supersample)
             kw["keep_seen"] = {k: v for k, v in ks.items() if v is not None}
@@ -104,6 +107,10 @@ def main(argv=None):
         parser.error("--texture is only used with --device-postprocess")
     if ns.texture is not None and not 4 <= ns.texture <= 8192:
         parser.error("--texture must be 4 .. 8192")
+    if ns.texture_from and ns.texture is None:
+        parser.error("--texture-from is only used with --texture")
+    if ns.texture_from and ns.texture_from != "views":
+        parser.error("--texture-from must be views")
     if ns.keep_seen and not ns.device_postprocess:
         parser.error("--keep-seen is only used with --device-postprocess")
     if ns.keep_seen and ns.keep_seen not in ("component", "faces"):
