@@ -716,6 +716,53 @@ MESH_PROJECT_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_draw.h: a device mesh with a texture atlas into one camera, in the rasteriser's channel layout; a header of its own with its own version (the HIP library only) ----
+MESH_DRAW_ABI_VERSION = 1
+MESH_DRAW_FILTER_NEAREST, MESH_DRAW_FILTER_BILINEAR = 0, 1
+
+
+class MeshDrawTexture(C.Structure):
+    _fields_ = [
+        ("uv_dev", C.c_void_p),
+        ("color_dev", C.c_void_p),
+        ("normal_dev", C.c_void_p),
+        ("size", C.c_uint32),
+        ("n_tris", C.c_uint32),
+    ]
+
+
+class MeshDrawOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("near", C.c_float),
+        ("cull", C.c_uint32),
+        ("normals", C.c_uint32),
+        ("filter", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshDrawStats(C.Structure):
+    _fields_ = [
+        ("raster", MeshRasterStats),
+        ("n_bad_uv", C.c_uint32),
+        ("n_normal_fallback", C.c_uint32),
+        ("n_unowned_taps", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        """The rasteriser's fields flat, as DeviceMesh.rasterize returns them, and the three counts of the draw."""
+        return dict(self.raster.as_dict(), n_bad_uv=self.n_bad_uv, n_normal_fallback=self.n_normal_fallback, n_unowned_taps=self.n_unowned_taps)
+
+
+MESH_DRAW_PROTOTYPES = {
+    "mesh_draw_abi_version": (_u32, []),
+    "mesh_draw_default_options": (_i, [C.POINTER(MeshDrawOptions)]),
+    "mesh_draw_textured": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshDrawTexture), C.POINTER(View), C.POINTER(MeshDrawOptions), C.c_void_p, C.c_void_p, C.POINTER(MeshDrawStats)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -737,13 +784,13 @@ class Functions:
 
 
 def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
-            mesh_visibility=False, mesh_project=False):
+            mesh_visibility=False, mesh_project=False, mesh_draw=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
     mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
-    mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h); only the HIP library
-    exports those."""
+    mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h),
+    mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
                      + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ())
-                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()))
+                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()))

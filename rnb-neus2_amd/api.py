@@ -47,7 +47,7 @@ def load_library():
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
-                              mesh_visibility=True, mesh_project=True)
+                              mesh_visibility=True, mesh_project=True, mesh_draw=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -68,6 +68,8 @@ def load_library():
             raise RuntimeError("mesh-visibility ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_project_abi_version() != _abi.MESH_PROJECT_ABI_VERSION:
             raise RuntimeError("mesh-project ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_draw_abi_version() != _abi.MESH_DRAW_ABI_VERSION:
+            raise RuntimeError("mesh-draw ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -148,6 +150,35 @@ def view_normal_metrics(image, view, normal_map):
         k = a.size
         median = float(a[k // 2]) if k % 2 else float(0.5 * (a[k // 2 - 1] + a[k // 2]))
     return dict(mean_angle_deg=mean, median_angle_deg=median, mask_iou=(inter / uni if uni else 1.0), pixels_compared=int(angles.size))
+
+
+def view_albedo_metrics(image, view, albedo_map):
+    """One view's comparison of a [H,W,9] image (colour in channels 3-5, coverage or opacity in 6) with the scene's input albedo map (uint16 or uint8 [h,w,4], read as
+    x / 65535 or x / 255; alpha = mask), by the definitions of host/view_metrics.hpp with the masks and the choice of input pixel of view_normal_metrics: over the pixels
+    where both masks hold, in row-major order and in double, e = image - input per channel, the sums of (|e_0| + |e_1|) + |e_2| and of (e_0^2 + e_1^2) + e_2^2. Returns a
+    dict of albedo_mae (the first sum / 3n), albedo_rmse (sqrt(mse), mse = the second sum / 3n), albedo_psnr_db = 10 log10(1 / mse) (values in [0, 1]; inf for mse 0) and
+    pixels_compared (n; all three numbers are 0 when it is 0). `view` is not read: the images are compared pixel by pixel."""
+    img = np.asarray(image, dtype=np.float32)
+    h, w = img.shape[:2]
+    t = np.asarray(albedo_map)
+    if t.dtype not in (np.uint16, np.uint8) or t.ndim != 3 or t.shape[2] != 4:
+        raise ValueError("albedo_map must be uint16 or uint8 [h, w, 4]")
+    scale = 65535.0 if t.dtype == np.uint16 else 255.0
+    ih, iw = t.shape[:2]
+    mask = img[..., 6] > np.float32(0.5)
+    ix = np.minimum(iw - 1, ((np.arange(w, dtype=np.float64) + 0.5) * iw / w).astype(np.int64))
+    iy = np.minimum(ih - 1, ((np.arange(h, dtype=np.float64) + 0.5) * ih / h).astype(np.int64))
+    t = t[iy][:, ix]
+    both = mask & (t[..., 3] > 0)
+    n = int(both.sum())
+    if n == 0:
+        return dict(albedo_mae=0.0, albedo_rmse=0.0, albedo_psnr_db=0.0, pixels_compared=0)
+    e = img[both][:, 3:6].astype(np.float64) - t[both][:, :3].astype(np.float64) / scale
+    a = np.abs(e)
+    sum_abs = float(np.cumsum((a[:, 0] + a[:, 1]) + a[:, 2])[-1])  # one after the other, in pixel order, as the header does
+    sum_sq = float(np.cumsum((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2])[-1])
+    mse = sum_sq / (3.0 * n)
+    return dict(albedo_mae=sum_abs / (3.0 * n), albedo_rmse=math.sqrt(mse), albedo_psnr_db=(10.0 * math.log10(1.0 / mse) if mse > 0 else math.inf), pixels_compared=n)
 
 
 def scaled_view(view, factor):
@@ -765,24 +796,60 @@ class Context:
         with self.upload_mesh(verts, indices, colors, normals) as m:
             return m.rasterize(view, near, cull, shading, faces, stream)
 
-    def mesh_view_metrics(self, verts, indices, views, normal_maps, normals=None, near=2.0 ** -10, cull="none", shading="face", stream=None):
+    def _draw_options(self, near, cull, shading, filter):
+        ro = self._raster_options(near, cull, shading)
+        filters = {"nearest": _abi.MESH_DRAW_FILTER_NEAREST, "bilinear": _abi.MESH_DRAW_FILTER_BILINEAR}
+        if filter not in filters:
+            raise ValueError("filter must be 'nearest' or 'bilinear'")
+        opt = _abi.MeshDrawOptions()
+        self._check(self.f.mesh_draw_default_options(C.byref(opt)))
+        opt.near, opt.cull, opt.normals, opt.filter = ro.near, ro.cull, ro.normals, filters[filter]
+        return opt
+
+    def draw_textured_mesh(self, verts, indices, view, uv, color=None, normal=None, normals=None, colors=None, near=2.0 ** -10, cull="none", shading="face", filter="bilinear",
+                           faces=False, stream=None):
+        """rnb_mesh_draw_textured (include/rnb_mesh_draw.h) on a host mesh and one camera: DeviceMesh.draw_textured, which describes every argument and key, on an upload of
+        (verts, indices, colors, normals) that is released before the call returns."""
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            return m.draw_textured(view, uv, color, normal, near, cull, shading, filter, faces, stream)
+
+    def mesh_view_metrics(self, verts, indices, views, normal_maps, normals=None, near=2.0 ** -10, cull="none", shading="face", stream=None, texture=None, albedo_maps=None):
         """The mesh's counterpart of build/render's render_metrics.json: the mesh rasterised into every view of `views` (rasterize_mesh) and compared with that view's
         input normal map (`normal_maps`: uint16 [h,w,4] each) by view_normal_metrics. Returns dict(views=[one dict per view: mean_angle_deg, median_angle_deg, mask_iou,
-        pixels_compared, n_back_pixels, odd_count_pixels (pixels an odd number of triangles cover: 0 for a closed mesh), ms], mean={the means of the first three})."""
+        pixels_compared, n_back_pixels, odd_count_pixels (pixels an odd number of triangles cover: 0 for a closed mesh), ms], mean={the means of the first three}).
+        texture=dict(uv=, color=, normal=) (color or normal may be missing or None): every view is drawn with DeviceMesh.draw_textured instead, the texture uploaded once,
+        so the normal numbers describe the normal-mapped surface. albedo_maps (one uint16 or uint8 [h,w,4] per view; needs a texture with a colour map): the per-view dict
+        also carries albedo_mae, albedo_rmse and albedo_psnr_db of view_albedo_metrics, and `mean` their means. With neither the call is what it was."""
         if len(views) != len(normal_maps):
             raise ValueError("one normal map per view")
         self._raster_options(near, cull, shading)  # a bad argument fails before anything is uploaded, and with no view at all
         if shading == "vertex" and normals is None:
             raise ValueError("shading='vertex' needs normals")
-        per_view = []
+        if albedo_maps is not None and (texture is None or texture.get("color") is None):
+            raise ValueError("albedo_maps need a texture with a colour map")
+        if albedo_maps is not None and len(albedo_maps) != len(views):
+            raise ValueError("one albedo map per view")
+        per_view, keys, own = [], ["mean_angle_deg", "median_angle_deg", "mask_iou"], []
         with self.upload_mesh(verts, indices, None, normals) as m:
-            for view, nm in zip(views, normal_maps):
-                r = m.rasterize(view, near, cull, shading, stream=stream)
-                e = view_normal_metrics(r["image"], view, nm)
-                e.update(n_back_pixels=r["n_back_pixels"], odd_count_pixels=int((r["image"][..., 8].astype(np.int64) & 1).sum()), ms=r["ms"])
-                per_view.append(e)
+            try:
+                if texture is not None:
+                    opt = self._draw_options(near, cull, shading, "bilinear")
+                    tex = m._upload_texture(texture["uv"], texture.get("color"), texture.get("normal"), own)
+                for k, (view, nm) in enumerate(zip(views, normal_maps)):
+                    r = m.rasterize(view, near, cull, shading, stream=stream) if texture is None else m._draw(tex, view, opt, False, stream, None)
+                    e = view_normal_metrics(r["image"], view, nm)
+                    if albedo_maps is not None:
+                        a = view_albedo_metrics(r["image"], view, albedo_maps[k])
+                        e.update(albedo_mae=a["albedo_mae"], albedo_rmse=a["albedo_rmse"], albedo_psnr_db=a["albedo_psnr_db"])
+                    e.update(n_back_pixels=r["n_back_pixels"], odd_count_pixels=int((r["image"][..., 8].astype(np.int64) & 1).sum()), ms=r["ms"])
+                    per_view.append(e)
+            finally:
+                for p in own:
+                    self.device_free(p)
+        if albedo_maps is not None:
+            keys += ["albedo_mae", "albedo_rmse", "albedo_psnr_db"]
         k = max(len(per_view), 1)
-        return dict(views=per_view, mean={key: sum(e[key] for e in per_view) / k for key in ("mean_angle_deg", "median_angle_deg", "mask_iou")})
+        return dict(views=per_view, mean={key: sum(e[key] for e in per_view) / k for key in keys})
 
     def _visibility_options(self, near, cull, min_pixels):
         culls = {"none": _abi.MESH_RASTER_CULL_NONE, "back": _abi.MESH_RASTER_CULL_BACK, "front": _abi.MESH_RASTER_CULL_FRONT}
@@ -1203,6 +1270,76 @@ class DeviceMesh(_abi.Mesh):
             for p in own:
                 c.device_free(p)
         return out
+
+    def _texture_arrays(self, uv, color, normal):
+        """The host arrays of a texture checked against this mesh: (uv float32[n_triangles,3,2], color, normal float32[S,S,4] or None, S)."""
+        if color is None and normal is None:
+            raise ValueError("a colour map, a normal map or both must be given")
+        uv = np.ascontiguousarray(uv, dtype=np.float32)
+        if uv.size != self.n_triangles * 6:
+            raise ValueError("uv must hold 3 x 2 floats per triangle (%d triangles, %d floats)" % (self.n_triangles, uv.size))
+        maps = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (color, normal)]
+        shapes = {a.shape for a in maps if a is not None}
+        shape = next(iter(shapes))
+        if len(shapes) != 1 or len(shape) != 3 or shape[0] != shape[1] or shape[2] != 4 or shape[0] < 1:
+            raise ValueError("color and normal must be float32 arrays [S, S, 4] of one size")
+        return uv, maps[0], maps[1], shape[0]
+
+    def _upload_texture(self, uv, color, normal, own):
+        """rnb_mesh_draw_texture of the arrays of _texture_arrays, each uploaded once; the device buffers are appended to `own`, which the caller releases."""
+        c = self._live()
+        uv, color, normal, size = self._texture_arrays(uv, color, normal)
+        tex = _abi.MeshDrawTexture()
+        tex.size, tex.n_tris = size, self.n_triangles
+        for field, a in (("uv_dev", uv), ("color_dev", color), ("normal_dev", normal)):
+            if a is not None and a.size:
+                own.append(c.upload(a))
+                setattr(tex, field, own[-1])
+        return tex
+
+    def _draw(self, tex, view, opt, faces, stream, out_ptr):
+        """rnb_mesh_draw_textured with a texture that is on the device: the dict of draw_textured."""
+        c = self._live()
+        h, w = int(view["height"]), int(view["width"])
+        n = h * w
+        st = _abi.MeshDrawStats()
+        img, fac, own = out_ptr, None, []
+        try:
+            if img is None:
+                img = c.device_malloc(max(n, 1) * _abi.MESH_RASTER_CHANNELS * 4)
+                own.append(img)
+            if faces:
+                fac = c.device_malloc(max(n, 1) * 4)
+                own.append(fac)
+            c._check(c.f.mesh_draw_textured(c._h, _stream_handle(stream), C.byref(self), C.byref(tex), C.byref(_view_struct(view)), C.byref(opt), img, fac, C.byref(st)))
+            out = st.as_dict()
+            if out_ptr is None:
+                out["image"] = c.download(img, n * _abi.MESH_RASTER_CHANNELS, np.float32).reshape(h, w, _abi.MESH_RASTER_CHANNELS)
+            if faces:
+                out["faces"] = c.download(fac, n, np.uint32).reshape(h, w)
+        finally:
+            for p in own:
+                c.device_free(p)
+        return out
+
+    def draw_textured(self, view, uv, color=None, normal=None, near=2.0 ** -10, cull="none", shading="face", filter="bilinear", faces=False, stream=None, out_ptr=None):
+        """rnb_mesh_draw_textured (include/rnb_mesh_draw.h) of this mesh into one camera: the dict of rasterize (`image` float32 [H,W,9], with faces=True `faces`, the
+        fields of rnb_mesh_raster_stats) and n_bad_uv, n_normal_fallback, n_unowned_taps. uv float32[n_triangles,3,2], color and normal float32[S,S,4] (one of the two
+        may be None) are host arrays, such as the `uv` / `albedo` / `color` / `normal` entries of bake_texture or project_views: channels 3-5 of the image are the colour
+        map's texels under the pixels (the mesh's own colours without one), channels 0-2 the normal map's, normalised (the normal `shading` selects without one, and
+        where the map holds no direction); channels 6-8 and `faces` are those of rasterize. filter: "bilinear" or "nearest". The arrays are uploaded once and released
+        whether or not a step raises. out_ptr: as in rasterize. Bit-reproducible. Leaves the training state as it was."""
+        c = self._live()
+        opt = c._draw_options(near, cull, shading, filter)
+        if shading == "vertex" and not self.has_normals:
+            raise ValueError("shading='vertex' needs normals")
+        own = []
+        try:
+            tex = self._upload_texture(uv, color, normal, own)
+            return self._draw(tex, view, opt, faces, stream, out_ptr)
+        finally:
+            for p in own:
+                c.device_free(p)
 
     def visibility(self, views, masks=None, near=2.0 ** -10, cull="none", min_pixels=1, supersample=1, on_device=False, stream=None):
         """rnb_mesh_visibility of this mesh in all of `views` at once: (records, stats), described by Context.mesh_visibility. on_device=True: the records stay on the

@@ -774,31 +774,48 @@ int raster_fill(const char* name, MeshWorkspace& ws, hipStream_t s, const MrCame
 	}
 	return RNB_OK;
 }
-} // namespace
-} // extern "C++"
-
-int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, const rnb_mesh_raster_options* opt, float* out_dev, uint32_t* face_dev,
-                    rnb_mesh_raster_stats* stats) try {
-	if (stats) std::memset(stats, 0, sizeof(*stats));
-	if (!c || !mesh || !view || !opt || !out_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: null argument");
-	if ((void*)out_dev == (void*)face_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: out_dev and face_dev must be different buffers");
-	if (opt->abi_version != RNB_MESH_RASTER_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: options abi_version mismatch (expected RNB_MESH_RASTER_ABI_VERSION)");
-	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: near must be finite and > 0");
-	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
-	if (opt->normals > RNB_MESH_RASTER_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals must be RNB_MESH_RASTER_NORMALS_FACE or _VERTEX");
-	if (int rc = check_raster_view("rnb_mesh_raster", view); rc != RNB_OK) return rc;
+// What rnb_mesh_raster and rnb_mesh_draw_textured ask of near, cull, normals, the camera and the mesh, said in the entry point's name.
+int check_raster_call(const char* name, float near, uint32_t cull, uint32_t normals, const rnb_view* view, const rnb_mesh* mesh) {
+	const std::string n(name);
+	if (!(near > 0.0f) || !std::isfinite(near)) return fail(RNB_ERR_INVALID, n + ": near must be finite and > 0");
+	if (cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, n + ": cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
+	if (normals > RNB_MESH_RASTER_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, n + ": normals must be RNB_MESH_RASTER_NORMALS_FACE or _VERTEX");
+	if (int rc = check_raster_view(name, view); rc != RNB_OK) return rc;
 	{
 		rnb_mesh unused;
-		if (int rc = check_mesh_input("rnb_mesh_raster", mesh, &unused); rc != RNB_OK) return rc;
+		if (int rc = check_mesh_input(name, mesh, &unused); rc != RNB_OK) return rc;
 	}
-	if (opt->normals == RNB_MESH_RASTER_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: normals = VERTEX needs a mesh with normals");
+	if (normals == RNB_MESH_RASTER_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, n + ": normals = VERTEX needs a mesh with normals");
+	return RNB_OK;
+}
+// The textured resolve of include/rnb_mesh_draw.h: the instantiation the filter, the maps given and the image's alignment select.
+template <int FILTER, bool COLOR, bool NORMAL>
+void launch_md_resolve(uint32_t g_p, hipStream_t s, const MrCamera& cam, const MrMesh& M, const DrawTexture& tex, const unsigned long long* keys, const uint32_t* counts, float* out_dev, uint32_t* face_dev,
+                       MrResult* dres, DrawResult* ddraw) {
+	if (((uintptr_t)out_dev & 15u) == 0)
+		hipLaunchKernelGGL((k_md_resolve<FILTER, COLOR, NORMAL, true>), dim3(g_p), dim3(MR_WG), 0, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
+	else
+		hipLaunchKernelGGL((k_md_resolve<FILTER, COLOR, NORMAL, false>), dim3(g_p), dim3(MR_WG), 0, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
+}
+template <int FILTER>
+void launch_md_resolve(uint32_t g_p, hipStream_t s, const MrCamera& cam, const MrMesh& M, const DrawTexture& tex, const unsigned long long* keys, const uint32_t* counts, float* out_dev, uint32_t* face_dev,
+                       MrResult* dres, DrawResult* ddraw) {
+	if (tex.color && tex.normal) launch_md_resolve<FILTER, true, true>(g_p, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
+	else if (tex.color) launch_md_resolve<FILTER, true, false>(g_p, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
+	else launch_md_resolve<FILTER, false, true>(g_p, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
+}
+// One view of a mesh, for rnb_mesh_raster (tex null) and rnb_mesh_draw_textured (tex, filter, *drawn): the range check, the fill and the resolve of whichever of the two,
+// on arguments the caller has checked. *stats (may be null) is zero on entry.
+int raster_image(const char* name, rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, float near, uint32_t cull, uint32_t normals, const DrawTexture* tex, uint32_t filter,
+                 float* out_dev, uint32_t* face_dev, rnb_mesh_raster_stats* stats, DrawResult* drawn) {
+	const std::string nm(name);
 	const rnb_mesh m = *mesh;
 	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, width = view->width, height = view->height, n_pix = width * height;
 	const auto t_begin = std::chrono::steady_clock::now();
 	hipStream_t s = as_stream(stream);
 	join_tail_host(c);
 
-	const MrCamera cam = raster_camera(view, opt->near, opt->cull, opt->normals);
+	const MrCamera cam = raster_camera(view, near, cull, normals);
 	const MrMesh M{m.verts, m.indices, m.colors, m.normals, nt};
 
 	MeshWorkspace ws;
@@ -807,11 +824,13 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 	unsigned long long* keys = nullptr;
 	uint32_t *counts = nullptr, *used = nullptr, *list = nullptr;
 	MrResult* dres = nullptr;
-	if (!ws.alloc(&keys, n_pix) || !ws.alloc(&counts, n_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_raster: hipMalloc failed for the workspace of " + std::to_string(n_pix) + " pixels and " + std::to_string(nv) + " vertices");
+	DrawResult* ddraw = nullptr;
+	if (!ws.alloc(&keys, n_pix) || !ws.alloc(&counts, n_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1) || (tex && !ws.alloc(&ddraw, 1)))
+		return fail(RNB_ERR_NOMEM, nm + ": hipMalloc failed for the workspace of " + std::to_string(n_pix) + " pixels and " + std::to_string(nv) + " vertices");
 	HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_pix * 8, s));
 	HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_pix * 4, s));
 	HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+	if (tex) HIP_TRY(hipMemsetAsync(ddraw, 0, sizeof(DrawResult), s));
 	if (nt) {
 		const uint32_t g_t = (nt + MR_WG - 1) / MR_WG;
 		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
@@ -820,23 +839,28 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MR_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: an index is out of range (>= n_verts)");
+		if (hres.flags & MR_BAD_INDEX) return fail(RNB_ERR_INVALID, nm + ": an index is out of range (>= n_verts)");
 		ws.release(used);
-		// 2. setup, classes, the small triangles filled; the large ones counted, then listed and filled by a wavefront each
+		// 2. setup, classes, the small triangles filled; the large ones counted, then listed and filled by a wavefront each (the fill is the rasteriser's for both callers,
+		//    and names the rasteriser if its list cannot be allocated)
 		uint32_t list_cap = 0;
 		if (int rc = raster_fill<false>("rnb_mesh_raster", ws, s, cam, M, keys, counts, dres, &hres, &list, &list_cap, MrTally{}); rc != RNB_OK) return rc;
 	}
 	// 3. one thread per pixel (an empty mesh: every key is still all ones, the image is zeros)
 	const uint32_t g_p = (n_pix + MR_WG - 1) / MR_WG;
-	if (((uintptr_t)out_dev & 15u) == 0)
+	if (tex) {
+		if (filter == RNB_MESH_DRAW_FILTER_NEAREST) launch_md_resolve<RNB_MESH_DRAW_FILTER_NEAREST>(g_p, s, cam, M, *tex, keys, counts, out_dev, face_dev, dres, ddraw);
+		else launch_md_resolve<RNB_MESH_DRAW_FILTER_BILINEAR>(g_p, s, cam, M, *tex, keys, counts, out_dev, face_dev, dres, ddraw);
+	} else if (((uintptr_t)out_dev & 15u) == 0)
 		hipLaunchKernelGGL(k_mr_resolve<true>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
 	else
 		hipLaunchKernelGGL(k_mr_resolve<false>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+	if (tex) HIP_TRY(hipMemcpyAsync(drawn, ddraw, sizeof(DrawResult), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	ws.release(keys); ws.release(counts); ws.release(used); ws.release(list); ws.release(dres);
-	if (hres.n_unresolved) return fail(RNB_ERR_DEVICE, "rnb_mesh_raster: " + std::to_string(hres.n_unresolved) + " pixels whose winner the resolve pass does not find covering them (the fill and the resolve disagree: a defect of the library)");
+	ws.release(keys); ws.release(counts); ws.release(used); ws.release(list); ws.release(dres); ws.release(ddraw);
+	if (hres.n_unresolved) return fail(RNB_ERR_DEVICE, nm + ": " + std::to_string(hres.n_unresolved) + " pixels whose winner the resolve pass does not find covering them (the fill and the resolve disagree: a defect of the library)");
 	if (stats) {
 		stats->n_tris = nt;
 		stats->n_behind = hres.n_class[MR_BEHIND]; stats->n_out_of_range = hres.n_class[MR_OUT_OF_RANGE]; stats->n_degenerate = hres.n_class[MR_DEGENERATE];
@@ -846,6 +870,55 @@ int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_vi
 		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
 	}
 	return RNB_OK;
+}
+} // namespace
+} // extern "C++"
+
+int rnb_mesh_raster(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, const rnb_mesh_raster_options* opt, float* out_dev, uint32_t* face_dev,
+                    rnb_mesh_raster_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !mesh || !view || !opt || !out_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: null argument");
+	if ((void*)out_dev == (void*)face_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: out_dev and face_dev must be different buffers");
+	if (opt->abi_version != RNB_MESH_RASTER_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_raster: options abi_version mismatch (expected RNB_MESH_RASTER_ABI_VERSION)");
+	if (int rc = check_raster_call("rnb_mesh_raster", opt->near, opt->cull, opt->normals, view, mesh); rc != RNB_OK) return rc;
+	return raster_image("rnb_mesh_raster", c, stream, mesh, view, opt->near, opt->cull, opt->normals, nullptr, 0u, out_dev, face_dev, stats, nullptr);
+} RNB_GUARD
+
+// ---- textured draw (include/rnb_mesh_draw.h) ----
+uint32_t rnb_mesh_draw_abi_version(void) { return RNB_MESH_DRAW_ABI_VERSION; }
+
+int rnb_mesh_draw_default_options(rnb_mesh_draw_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_DRAW_ABI_VERSION;
+	opt->near = 1.0f / 1024.0f;
+	opt->cull = RNB_MESH_RASTER_CULL_NONE;
+	opt->normals = RNB_MESH_RASTER_NORMALS_FACE;
+	opt->filter = RNB_MESH_DRAW_FILTER_BILINEAR;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_draw_textured(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_mesh_draw_texture* tex, const rnb_view* view, const rnb_mesh_draw_options* opt, float* out_dev,
+                           uint32_t* face_dev, rnb_mesh_draw_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !mesh || !tex || !view || !opt || !out_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: null argument");
+	if ((void*)out_dev == (void*)face_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: out_dev and face_dev must be different buffers");
+	if (opt->abi_version != RNB_MESH_DRAW_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: options abi_version mismatch (expected RNB_MESH_DRAW_ABI_VERSION)");
+	if (opt->filter > RNB_MESH_DRAW_FILTER_BILINEAR) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: filter must be RNB_MESH_DRAW_FILTER_NEAREST or _BILINEAR");
+	for (uint32_t r : opt->reserved)
+		if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: a reserved word of the options is not 0");
+	if (int rc = check_raster_call("rnb_mesh_draw_textured", opt->near, opt->cull, opt->normals, view, mesh); rc != RNB_OK) return rc;
+	if (!tex->color_dev && !tex->normal_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: no map (color_dev and normal_dev are both null)");
+	if (((uintptr_t)tex->color_dev | (uintptr_t)tex->normal_dev) & 15u) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: a map is not aligned to 16 bytes");
+	if (tex->size == 0 || tex->size > RNB_MESH_TEXTURE_MAX_SIZE) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: size must be 1 .. " + std::to_string(RNB_MESH_TEXTURE_MAX_SIZE));
+	if (tex->n_tris != mesh->n_indices / 3u) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: the texture is of " + std::to_string(tex->n_tris) + " triangles, the mesh has " + std::to_string(mesh->n_indices / 3u));
+	if (tex->n_tris && !tex->uv_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: uv_dev is null");
+	const DrawTexture T{tex->uv_dev, tex->color_dev, tex->normal_dev, tex->size};
+	DrawResult drawn;
+	std::memset(&drawn, 0, sizeof(drawn));
+	const int rc = raster_image("rnb_mesh_draw_textured", c, stream, mesh, view, opt->near, opt->cull, opt->normals, &T, opt->filter, out_dev, face_dev, stats ? &stats->raster : nullptr, &drawn);
+	if (stats && rc == RNB_OK) { stats->n_bad_uv = drawn.n_bad_uv; stats->n_normal_fallback = drawn.n_fallback; stats->n_unowned_taps = drawn.n_unowned; }
+	return rc;
 } RNB_GUARD
 
 // ---- visibility (include/rnb_mesh_visibility.h) ----

@@ -29,6 +29,10 @@
 // With --texture-from views the albedo map is not the model's but the scene's own albedo maps projected onto the mesh (rnb_mesh_project_views, include/rnb_mesh_project.h):
 // the images as the loader read them (16 bit, their alpha the mask, the stored values as they are -- the scale the model's albedo and FILE_albedo.png have), every
 // camera of the scene, the model's baked albedo as the fallback of the texels no view reaches. The atlas is the same one: the vt records do not change.
+// With --texture and --report-views together the textured mesh, with the maps about to be written, is also drawn into every camera (rnb_mesh_draw_textured,
+// include/rnb_mesh_draw.h): per view and in the means textured_mean_angle_deg and textured_median_angle_deg (when a normal map was baked: the normal-mapped surface
+// against the input normal maps) and albedo_mae, albedo_rmse, albedo_psnr_db (when there is a colour map and the scene has albedo maps), with every digit of a double.
+// A PSNR that is not finite (the drawn colours equal the input's: mse 0), per view or in the means, is written as null (view_metrics::num_full).
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -37,6 +41,7 @@
 #include "../../include/rnb_mesh_distance.h"
 #include "../../include/rnb_mesh_raster.h"
 #include "../../include/rnb_mesh_texture.h"
+#include "../../include/rnb_mesh_draw.h"
 #include "../../include/rnb_mesh_visibility.h"
 #include "../../include/rnb_mesh_project.h"
 #include "dataset.hpp"
@@ -148,14 +153,22 @@ float parse_float(const std::string& k, const std::string& s) {
 	} while (0)
 
 // --report-views: the device mesh rasterised into every camera of the scene and compared with the input normal maps (view_metrics.hpp, as build/render compares the
-// model's render). `report`: one line per view and the means, to print; `json`: the text of <out>.views.json.
-void report_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& mesh, const std::string& snap_path, std::string& report, std::string& json) {
+// model's render). `report`: one line per view and the means, to print; `json`: the text of <out>.views.json. With `tex` (--texture: the maps about to be written, on the
+// device) every view is also drawn with the texture (rnb_mesh_draw_textured, include/rnb_mesh_draw.h): the normal angle of the normal-mapped surface when a normal map was
+// baked, the albedo error against the scene's albedo maps when there is a colour map and the scene has albedo maps. Without `tex` both texts are what they were.
+void report_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& mesh, const rnb_mesh_draw_texture* tex, const std::string& snap_path, std::string& report, std::string& json) {
 	using view_metrics::num;
+	using view_metrics::num_full;
 	rnb_mesh_raster_options ropt;
 	RNB_CHECK(rnb_mesh_raster_default_options(&ropt));
+	rnb_mesh_draw_options dopt;
+	RNB_CHECK(rnb_mesh_draw_default_options(&dopt));
+	bool with_albedo = tex && tex->color_dev && ds.albedos.size() == ds.views.size();
+	for (size_t vi = 0; with_albedo && vi < ds.albedos.size(); ++vi) with_albedo = !ds.albedos[vi].rgba.empty();
+	const bool with_normal = tex && tex->normal_dev;
 	float* img_dev = nullptr;
 	size_t cap = 0;
-	double s_mean = 0, s_median = 0, s_iou = 0, s_ms = 0;
+	double s_mean = 0, s_median = 0, s_iou = 0, s_ms = 0, s_tmean = 0, s_tmedian = 0, s_mae = 0, s_rmse = 0, s_psnr = 0, s_dms = 0;
 	char line[256];
 	try {
 		for (uint32_t vi = 0; vi < ds.views.size(); ++vi) {
@@ -179,10 +192,36 @@ void report_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& mesh, const s
 			std::snprintf(line, sizeof(line), "view %u: %ux%u, mesh normal angle mean %.3f median %.3f deg, mask IoU %.4f, %u back-facing and %llu odd-count pixels, %.2f ms\n", vi, v.width,
 			              v.height, vm.mean_angle_deg, vm.median_angle_deg, vm.mask_iou, rs.n_back_pixels, (unsigned long long)odd, rs.ms);
 			report += line;
+			std::string extra;
+			if (with_normal || with_albedo) { // the textured mesh in the same camera
+				rnb_mesh_draw_stats dst;
+				RNB_CHECK(rnb_mesh_draw_textured(ctx, nullptr, &mesh, tex, &v, &dopt, img_dev, nullptr, &dst));
+				RNB_CHECK(rnb_memcpy(ctx, img.data(), img_dev, img.size() * 4, RNB_D2H));
+				s_dms += dst.raster.ms;
+				report += "  textured:";
+				if (with_normal) {
+					const view_metrics::Result tm = view_metrics::compare(img.data(), RNB_MESH_RASTER_CHANNELS, v.width, v.height, v.xform, in.rgba.data(), in.width, in.height);
+					s_tmean += tm.mean_angle_deg; s_tmedian += tm.median_angle_deg;
+					extra += ", \"textured_mean_angle_deg\": " + num_full(tm.mean_angle_deg) + ", \"textured_median_angle_deg\": " + num_full(tm.median_angle_deg);
+					std::snprintf(line, sizeof(line), " normal angle mean %.3f median %.3f deg,", tm.mean_angle_deg, tm.median_angle_deg);
+					report += line;
+				}
+				if (with_albedo) {
+					const png16::Image& al = ds.albedos[vi];
+					const view_metrics::AlbedoResult ar = view_metrics::compare_albedo(img.data(), RNB_MESH_RASTER_CHANNELS, v.width, v.height, al.rgba.data(), al.width, al.height);
+					s_mae += ar.mae; s_rmse += ar.rmse; s_psnr += ar.psnr_db;
+					extra += ", \"albedo_mae\": " + num_full(ar.mae) + ", \"albedo_rmse\": " + num_full(ar.rmse) + ", \"albedo_psnr_db\": " + num_full(ar.psnr_db);
+					std::snprintf(line, sizeof(line), " albedo mae %.5f rmse %.5f psnr %.2f dB,", ar.mae, ar.rmse, ar.psnr_db);
+					report += line;
+				}
+				extra += ", \"textured_frame_ms\": " + num(dst.raster.ms);
+				std::snprintf(line, sizeof(line), " %.2f ms\n", dst.raster.ms);
+				report += line;
+			}
 			if (!json.empty()) json += ",\n";
 			json += "    {\"view\": " + std::to_string(vi) + ", \"width\": " + std::to_string(v.width) + ", \"height\": " + std::to_string(v.height) + ", " +
 			              view_metrics::json_fields(vm) + ", \"n_back_pixels\": " + std::to_string(rs.n_back_pixels) + ", \"odd_count_pixels\": " + std::to_string(odd) +
-			              ", \"frame_ms\": " + num(rs.ms) + "}";
+			              ", \"frame_ms\": " + num(rs.ms) + extra + "}";
 		}
 	} catch (...) {
 		if (img_dev) rnb_device_free(ctx, img_dev);
@@ -192,8 +231,25 @@ void report_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& mesh, const s
 	const double k = ds.views.empty() ? 1.0 : (double)ds.views.size();
 	std::snprintf(line, sizeof(line), "views: %zu, mesh normal angle mean %.3f median %.3f deg, mask IoU %.4f, %.2f ms per view\n", ds.views.size(), s_mean / k, s_median / k, s_iou / k, s_ms / k);
 	report += line;
+	std::string extra;
+	if (with_normal || with_albedo) {
+		report += "views textured:";
+		if (with_normal) {
+			extra += ", \"textured_mean_angle_deg\": " + num_full(s_tmean / k) + ", \"textured_median_angle_deg\": " + num_full(s_tmedian / k);
+			std::snprintf(line, sizeof(line), " normal angle mean %.3f median %.3f deg,", s_tmean / k, s_tmedian / k);
+			report += line;
+		}
+		if (with_albedo) {
+			extra += ", \"albedo_mae\": " + num_full(s_mae / k) + ", \"albedo_rmse\": " + num_full(s_rmse / k) + ", \"albedo_psnr_db\": " + num_full(s_psnr / k);
+			std::snprintf(line, sizeof(line), " albedo mae %.5f rmse %.5f psnr %.2f dB,", s_mae / k, s_rmse / k, s_psnr / k);
+			report += line;
+		}
+		extra += ", \"textured_frame_ms\": " + num(s_dms / k);
+		std::snprintf(line, sizeof(line), " %.2f ms per view\n", s_dms / k);
+		report += line;
+	}
 	json = "{\n  \"snapshot\": \"" + snap_path + "\",\n  \"n_triangles\": " + std::to_string(mesh.n_indices / 3u) + ",\n  \"views\": [\n" + json + "\n  ],\n  \"mean\": {\"mean_angle_deg\": " +
-	             num(s_mean / k) + ", \"median_angle_deg\": " + num(s_median / k) + ", \"mask_iou\": " + num(s_iou / k) + ", \"frame_ms\": " + num(s_ms / k) + "}\n}\n";
+	             num(s_mean / k) + ", \"median_angle_deg\": " + num(s_median / k) + ", \"mask_iou\": " + num(s_iou / k) + ", \"frame_ms\": " + num(s_ms / k) + extra + "}\n}\n";
 }
 
 // --keep-seen: *dm without what the cameras of the scene do not see, in *out. `report`: the two lines to print.
@@ -496,7 +552,7 @@ int main(int argc, char** argv) {
 		}
 		// --report-views: made here, while the mesh is on the device and in the frame of the loaded views; printed and written after the mesh's own lines, below
 		std::string views_report, views_json;
-		if (want_views) report_views(ctx, ds, dm, snap_path, views_report, views_json);
+		if (want_views && !texture) report_views(ctx, ds, dm, nullptr, snap_path, views_report, views_json);
 		// --texture: the mesh as it will be written, while it is on the device
 		mesh::Texture tex;
 		rnb_mesh_texture_stats ts;
@@ -517,6 +573,13 @@ int main(int argc, char** argv) {
 				std::string line;
 				project_views(ctx, ds, dm, dt, project, tex.albedo, line);
 				std::fputs(line.c_str(), stdout);
+			}
+			if (want_views) { // the maps about to be written, drawn into every camera: the model's bake, or the projected colour (uploaded again: the projection was released)
+				rnb_mesh_draw_texture vt;
+				std::memset(&vt, 0, sizeof(vt));
+				vt.uv_dev = dt.uv; vt.color_dev = dt.albedo; vt.normal_dev = dt.normal; vt.size = dt.size; vt.n_tris = dt.n_tris;
+				if (texture_from && dt.albedo) RNB_CHECK(rnb_memcpy(ctx, dt.albedo, tex.albedo.data(), n_map * 4, RNB_H2D));
+				report_views(ctx, ds, dm, (vt.color_dev || vt.normal_dev) ? &vt : nullptr, snap_path, views_report, views_json);
 			}
 			RNB_CHECK(rnb_mesh_texture_free(ctx, &dt));
 		}

@@ -89,6 +89,48 @@ inline Result compare(const float* img, uint32_t channels, uint32_t width, uint3
 	return acc.finish();
 }
 
+// A number of the JSON reports with every digit a double has (what is compared with the Python side's sums, not read by eye). What is not finite is written as
+// null: albedo_psnr_db of a view whose drawn colours equal the input's is infinite (mse 0), and so is a mean over views that holds such a view -- the Python side returns
+// inf for both. null never stands for a bad result; a reader takes it as "no error to measure".
+inline std::string num_full(double v) {
+	if (!std::isfinite(v)) return "null";
+	char b[64];
+	std::snprintf(b, sizeof(b), "%.17g", v);
+	return b;
+}
+
+// One view's comparison of the image's colour (channels 3-5) with a scene's input albedo map (uint16 RGBA, read as x / 65535; alpha = mask), and what
+// rnb_neus2_amd.api.view_albedo_metrics repeats in numpy: the masks and the input pixel of Accumulator::add; over the pixels where both masks hold, in row-major order,
+// e = image - input per channel, the sums of (|e_0| + |e_1|) + |e_2| and of (e_0^2 + e_1^2) + e_2^2; mae = the first / 3n, mse = the second / 3n, rmse = sqrt(mse),
+// psnr_db = 10 log10(1 / mse) (infinite for mse 0: num_full writes null); all zeros when n is 0.
+struct AlbedoResult {
+	double mae = 0, rmse = 0, psnr_db = 0;
+	size_t pixels_compared = 0;
+};
+inline AlbedoResult compare_albedo(const float* img, uint32_t channels, uint32_t width, uint32_t height, const uint16_t* in_rgba, uint32_t in_width, uint32_t in_height) {
+	AlbedoResult r;
+	double sum_abs = 0, sum_sq = 0;
+	for (uint32_t y = 0; y < height; ++y)
+		for (uint32_t x = 0; x < width; ++x) {
+			const float* c = img + ((size_t)y * width + x) * channels;
+			const uint32_t ix = std::min(in_width - 1, (uint32_t)(((double)x + 0.5) * in_width / width));
+			const uint32_t iy = std::min(in_height - 1, (uint32_t)(((double)y + 0.5) * in_height / height));
+			const uint16_t* t = in_rgba + ((size_t)iy * in_width + ix) * 4;
+			if (!(c[6] > 0.5f) || !(t[3] > 0)) continue;
+			const double e0 = (double)c[3] - t[0] / 65535.0, e1 = (double)c[4] - t[1] / 65535.0, e2 = (double)c[5] - t[2] / 65535.0;
+			sum_abs += (std::fabs(e0) + std::fabs(e1)) + std::fabs(e2);
+			sum_sq += (e0 * e0 + e1 * e1) + e2 * e2;
+			++r.pixels_compared;
+		}
+	if (r.pixels_compared) {
+		const double n3 = 3.0 * (double)r.pixels_compared, mse = sum_sq / n3;
+		r.mae = sum_abs / n3;
+		r.rmse = std::sqrt(mse);
+		r.psnr_db = 10.0 * std::log10(1.0 / mse);
+	}
+	return r;
+}
+
 // The fields a view's entry of the JSON reports share: "mean_angle_deg": ..., "median_angle_deg": ..., "mask_iou": ..., "pixels_compared": ...
 inline std::string json_fields(const Result& r) {
 	return "\"mean_angle_deg\": " + num(r.mean_angle_deg) + ", \"median_angle_deg\": " + num(r.median_angle_deg) + ", \"mask_iou\": " + num(r.mask_iou) +

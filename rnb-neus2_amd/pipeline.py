@@ -259,7 +259,8 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
     device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh;
     simplify = N (with device_postprocess only): that step also simplifies the mesh on N^3 cells (build/mesh --simplify N);
-    report_views (with device_postprocess only): that step also writes <output_dir>/mesh.obj.views.json, the mesh's normal angle and mask IoU per input view;
+    report_views (with device_postprocess only): that step also writes <output_dir>/mesh.obj.views.json, the mesh's normal angle and mask IoU per input view (with texture as well:
+    the textured mesh's, textured_* and albedo_* of include/rnb_mesh_draw.h, whose lines build/mesh prints and this function logs with the others);
     texture = S (with device_postprocess only): that step also bakes an albedo texture of S x S texels: mesh.obj gets vt records, mesh.mtl and mesh_albedo.png beside it;
     keep_seen (with device_postprocess only): that step also drops what no camera sees (plan_device_postprocess describes the value; build/mesh --keep-seen);
     texture_from = "views" (with texture only): the texture is projected from the input albedo maps instead of baked from the model (build/mesh --texture-from views)."""
