@@ -1,8 +1,16 @@
-// driver_mesh.hpp -- rnb_sdf_lattice, what the mesh drivers share (scan_exclusive, count_and_scan, MeshWorkspace, check_mesh_input, alloc_mesh, hand_over,
-// ensure_mc_table), rnb_marching_cubes and the stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_visibility,
-// rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views.
-// Needs, of rnb_neus2_hip.hip, which includes it: the context (aabb, bitfield, cfg, mc_table), as_stream, fail / HIP_TRY / RNB_GUARD, launch_point_query
-// and launch_forward.
+// driver_mesh.hpp -- rnb_sdf_lattice, rnb_marching_cubes and the mesh stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster,
+// rnb_mesh_draw_textured, rnb_mesh_visibility, rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views. What they share:
+//   scan_exclusive, count_and_scan                  the prefix sums behind every numbering, and the count half of a count / write kernel pair
+//   MeshWorkspace, alloc_mesh, hand_over            the device memory of one call and the mesh it returns
+//   check_mesh_input, check_reserved, free_device   the argument checks every stage makes; the *_free functions
+//   MeshCall                                        one call of a stage: its name in every failure, stream, workspace and time; the index check (check_indices)
+//                                                   and the compaction of a mesh to its kept part (compact)
+//   ensure_mc_table                                 the marching-cubes case table on the device
+//   check_near_cull, check_raster_view, check_raster_call, raster_camera, raster_clear, raster_fill, raster_image, launch_md_resolve
+//                                                   the rasteriser's checks, camera and fill, for the draw, the visibility stage and the projection too
+//   make_atlas, launch_mp_accumulate                the atlas of the baker and the projection; the projection's accumulate launch per image format
+// Needs, of rnb_neus2_hip.hip, which includes it: the context (aabb, bitfield, cfg, mc_table), as_stream, join_tail_host, fail / HIP_TRY / RNB_GUARD,
+// launch_point_query and launch_forward.
 extern "C" {
 
 // ---- mesh extraction (src/testbed_nerf.cu:4218-4269, src/marching_cubes.cu:276-430, 794-822) ----
@@ -35,7 +43,7 @@ int rnb_sdf_lattice(rnb_ctx* c, void* stream, const uint32_t res[3], float latti
 	return RNB_OK;
 } RNB_GUARD
 
-// ---- what the drivers of the mesh stages share (rnb_marching_cubes, rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster, rnb_mesh_visibility, rnb_mesh_bake_texture) ----
+// ---- what the drivers of the mesh stages share ----
 extern "C++" {
 namespace {
 // elements of block-sum scratch scan_exclusive needs for n counts: sum over the levels of ceil(n / 1024^k)
@@ -67,11 +75,13 @@ int scan_exclusive(uint32_t* data, uint64_t n, hipStream_t s, uint32_t* total_ou
 	HIP_TRY(hipStreamSynchronize(s));
 	return RNB_OK;
 }
+// workgroups of MESH_WG threads for one thread per item
+uint32_t groups(uint64_t n) { return (uint32_t)((n + MESH_WG - 1) / MESH_WG); }
 // Phase one of a count / write kernel pair: the <false> instantiation leaves one count per workgroup in wg; they become the workgroups' exclusive offsets, their sum goes
 // to *total (synchronises). The write launch stays with the caller, who allocates for the total in between.
 template <typename K, typename... A>
 int count_and_scan(hipStream_t s, uint32_t n_wg, uint32_t* wg, uint32_t* scratch, uint32_t* total, K count_kernel, A... args) {
-	hipLaunchKernelGGL(count_kernel, dim3(n_wg), dim3(MC_WG), 0, s, args...);
+	hipLaunchKernelGGL(count_kernel, dim3(n_wg), dim3(MESH_WG), 0, s, args...);
 	HIP_TRY(hipGetLastError());
 	return scan_exclusive(wg, n_wg, s, total, scratch);
 }
@@ -89,10 +99,11 @@ struct MeshWorkspace {
 		cur += bytes; peak = std::max(peak, cur);
 		return true;
 	}
-	template <typename T>
-	void release(T*& p) { // free now
+	template <typename T, typename... U>
+	void release(T*& p, U*&... more) { // free now
 		for (auto& h : held) if (h.first == (void*)p && p) { (void)hipFree(h.first); cur -= h.second; h.first = nullptr; }
 		p = nullptr;
+		if constexpr (sizeof...(more) > 0) release(more...);
 	}
 	void* keep(void* p) { // the caller owns it from here on (it still counts as held)
 		for (auto& h : held) if (h.first == p) h.first = nullptr;
@@ -101,12 +112,14 @@ struct MeshWorkspace {
 	~MeshWorkspace() { for (auto& h : held) if (h.first) (void)hipFree(h.first); }
 };
 
-// What rnb_mesh_clean, rnb_mesh_simplify and rnb_mesh_distance (which has no output mesh and hands in one it discards) ask of their input mesh, said in the entry
-// point's name; *out is zeroed as soon as it is known not to be the input.
-int check_mesh_input(const char* name, const rnb_mesh* in, rnb_mesh* out) {
+// What every stage asks of its input mesh, said in the entry point's name; *out (null for a stage that returns no mesh) is zeroed as soon as it is known not to be
+// the input.
+int check_mesh_input(const char* name, const rnb_mesh* in, rnb_mesh* out = nullptr) {
 	const std::string n(name);
-	if (in == out) return fail(RNB_ERR_INVALID, n + ": in and out must be different objects");
-	std::memset(out, 0, sizeof(*out));
+	if (out) {
+		if (in == out) return fail(RNB_ERR_INVALID, n + ": in and out must be different objects");
+		std::memset(out, 0, sizeof(*out));
+	}
 	if (in->n_indices % 3u) return fail(RNB_ERR_INVALID, n + ": n_indices is not a multiple of 3");
 	if ((in->n_verts && !in->verts) || (in->n_indices && !in->indices)) return fail(RNB_ERR_INVALID, n + ": null vertex or index buffer");
 	if (in->n_indices && in->n_verts == 0) return fail(RNB_ERR_INVALID, n + ": an index is out of range (the mesh has no vertices)");
@@ -123,6 +136,83 @@ void hand_over(MeshWorkspace& ws, const rnb_mesh& m, rnb_mesh* out) {
 	*out = m;
 	ws.keep(m.verts); ws.keep(m.indices); ws.keep(m.colors); ws.keep(m.normals);
 }
+// The reserved words of an options struct must be 0.
+template <size_t N>
+int check_reserved(const char* name, const uint32_t (&reserved)[N]) {
+	for (uint32_t r : reserved)
+		if (r) return fail(RNB_ERR_INVALID, std::string(name) + ": a reserved word of the options is not 0");
+	return RNB_OK;
+}
+// The *_free functions: the device buffers of a result released, the struct zeroed.
+template <typename S>
+void free_device(S* obj, std::initializer_list<void*> buffers) {
+	for (void* p : buffers) if (p) (void)hipFree(p);
+	std::memset(obj, 0, sizeof(*obj));
+}
+
+// One call of a mesh stage, constructed from the entry point's name once its arguments have passed their checks: the start of the time the statistics report, the
+// stream (the side stream's tail joined: its optimizer launch writes the weights the network evaluations read), the workspace; failures said in the entry point's
+// name; and what the stages do alike on the device.
+struct MeshCall {
+	const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+	const std::string name;
+	const hipStream_t s;
+	MeshWorkspace ws;
+	MeshCall(const char* name_, rnb_ctx* c, void* stream) : name(name_), s(as_stream(stream)) { join_tail_host(c); }
+	int invalid(const std::string& text) const { return fail(RNB_ERR_INVALID, name + ": " + text); }
+	int nomem(const std::string& text) const { return fail(RNB_ERR_NOMEM, name + ": " + text); }
+	int device(const std::string& text) const { return fail(RNB_ERR_DEVICE, name + ": " + text); }
+	template <typename S>
+	void finish(S* stats) const {
+		stats->peak_workspace = ws.peak;
+		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+	}
+
+	// The index check: every index of m is range-checked before any is used as an address (m has a triangle, so n_verts >= 1: check_mesh_input). used[] is
+	// cleared and gets a 1 per corner; `bit` is set in the caller's flag word *dflags (device, zero) if an index is >= n_verts. In three parts, for the stages that
+	// check two meshes, or read more than the flag, under one synchronise: the launch,
+	int check_indices_launch(const rnb_mesh& m, uint32_t* used, uint32_t* dflags, uint32_t bit = MESH_BAD_INDEX) const {
+		const uint32_t nt = m.n_indices / 3u;
+		HIP_TRY(hipMemsetAsync(used, 0, (size_t)m.n_verts * 4, s));
+		hipLaunchKernelGGL(k_mesh_validate, dim3(groups(nt)), dim3(MESH_WG), 0, s, (const uint32_t*)m.indices, nt, m.n_verts, used, dflags, bit);
+		HIP_TRY(hipGetLastError());
+		return RNB_OK;
+	}
+	// the flag word read back (synchronises),
+	int read_flags(const uint32_t* dflags, uint32_t* hflags) const {
+		HIP_TRY(hipMemcpyAsync(hflags, dflags, 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		return RNB_OK;
+	}
+	// the failure (of: "of from ", "of to " where a stage takes two meshes);
+	int bad_index(const char* of = "") const { return invalid(std::string("an index ") + of + "is out of range (>= n_verts)"); }
+	// and all three, for a stage that checks one mesh under a synchronise of its own.
+	int check_indices(const rnb_mesh& m, uint32_t* used, uint32_t* dflags) const {
+		uint32_t hflags = 0;
+		if (int rc = check_indices_launch(m, used, dflags); rc != RNB_OK) return rc;
+		if (int rc = read_flags(dflags, &hflags); rc != RNB_OK) return rc;
+		return (hflags & MESH_BAD_INDEX) ? bad_index() : RNB_OK;
+	}
+
+	// An output mesh shaped like m (its attributes), held by the workspace.
+	int alloc_like(const rnb_mesh& m, rnb_mesh* o, uint32_t nvo, uint32_t nto) {
+		return alloc_mesh(ws, o, nvo, nto, m.colors != nullptr, m.normals != nullptr) ? RNB_OK : nomem("hipMalloc failed for the output mesh");
+	}
+	// The stable compaction of m to what `keep` keeps (ClKeep, MvKeep; k_compact_verts and k_compact_tris of mesh_common.cuh), as the new mesh *o: vmap holds a 1 per
+	// kept vertex on entry and the new numbering on return, twg takes one count per workgroup of triangles, scan is the scratch of scan_exclusive for both.
+	// The launches are issued; the caller synchronises.
+	template <typename KEEP>
+	int compact(const rnb_mesh& m, const KEEP& keep, uint32_t* vmap, uint32_t* twg, uint32_t* scan, rnb_mesh* o, uint32_t* nvo, uint32_t* nto) {
+		const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, g_v = groups(nv), g_t = groups(nt);
+		if (int rc = scan_exclusive(vmap, nv, s, nvo, scan); rc != RNB_OK) return rc;
+		if (int rc = count_and_scan(s, g_t, twg, scan, nto, k_compact_tris<false, KEEP>, (const uint32_t*)m.indices, nt, keep, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr); rc != RNB_OK) return rc;
+		if (int rc = alloc_like(m, o, *nvo, *nto); rc != RNB_OK) return rc;
+		hipLaunchKernelGGL(k_compact_verts<KEEP>, dim3(g_v), dim3(MESH_WG), 0, s, keep, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, o->verts, o->colors, o->normals);
+		hipLaunchKernelGGL((k_compact_tris<true, KEEP>), dim3(g_t), dim3(MESH_WG), 0, s, (const uint32_t*)m.indices, nt, keep, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, o->indices);
+		HIP_TRY(hipGetLastError());
+		return RNB_OK;
+	}
+};
 } // namespace
 } // extern "C++"
 
@@ -153,8 +243,7 @@ int rnb_marching_cubes(rnb_ctx* c, void* stream, const float* density, const uin
 	McArgs a;
 	a.density = density; a.rx = res[0]; a.ry = res[1]; a.rz = res[2]; a.thresh = thresh;
 	for (int d = 0; d < 3; ++d) { a.sc[d] = (aabb_max[d] - aabb_min[d]) / (float)res[d]; a.mn[d] = aabb_min[d]; }
-	const uint64_t n_wg64 = (res3 + MC_WG - 1) / MC_WG;
-	const uint32_t n_wg = (uint32_t)n_wg64;
+	const uint32_t n_wg = groups(res3);
 	MeshWorkspace ws;
 	uint32_t *wg = nullptr, *scan_scratch = nullptr, *vidx = nullptr, *indices = nullptr;
 	float* verts = nullptr;
@@ -162,10 +251,10 @@ int rnb_marching_cubes(rnb_ctx* c, void* stream, const float* density, const uin
 	uint32_t nv = 0, ni = 0;
 	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &nv, k_mc_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr); rc != RNB_OK) return rc;
 	if (nv && !ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the vertices");
-	hipLaunchKernelGGL(k_mc_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
+	hipLaunchKernelGGL(k_mc_verts<true>, dim3(n_wg), dim3(MESH_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
 	if (int rc = count_and_scan(s, n_wg, wg, scan_scratch, &ni, k_mc_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr); rc != RNB_OK) return rc;
 	if (ni && !ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "hipMalloc failed for the indices");
-	hipLaunchKernelGGL(k_mc_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
+	hipLaunchKernelGGL(k_mc_faces<true>, dim3(n_wg), dim3(MESH_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
 	if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return fail(RNB_ERR_DEVICE, "rnb_marching_cubes: kernel failure");
 	*verts_out = (float*)ws.keep(verts); *indices_out = (uint32_t*)ws.keep(indices); *n_verts = nv; *n_indices = ni; // (null where the count is 0; the scratch goes with ws)
 	return RNB_OK;
@@ -188,11 +277,7 @@ int rnb_mesh_default_options(rnb_mesh_options* opt) try {
 
 int rnb_mesh_free(rnb_ctx* c, rnb_mesh* m) try {
 	if (!c || !m) return fail(RNB_ERR_INVALID, "null argument");
-	if (m->verts) (void)hipFree(m->verts);
-	if (m->indices) (void)hipFree(m->indices);
-	if (m->colors) (void)hipFree(m->colors);
-	if (m->normals) (void)hipFree(m->normals);
-	std::memset(m, 0, sizeof(*m));
+	free_device(m, {m->verts, m->indices, m->colors, m->normals});
 	return RNB_OK;
 } RNB_GUARD
 
@@ -207,12 +292,10 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 	const uint32_t B = opt->brick ? opt->brick : MESH_DEFAULT_BRICK;
 	if (B < 8 || B > 64 || (B & (B - 1))) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: brick must be a power of two, 8 .. 64 (0 = default)");
 	if (!std::isfinite(opt->lattice_min) || !std::isfinite(opt->lattice_max) || !std::isfinite(opt->thresh)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: lattice bounds and thresh must be finite");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
+	MeshCall call("rnb_extract_mesh", c, stream);
+	const hipStream_t s = call.s;
 	if (int rc = ensure_mc_table(c); rc != RNB_OK) return rc;
 
-	MeshWorkspace ws;
 	MsArgs a;
 	std::memset(&a, 0, sizeof(a));
 	a.lb = ilog2(B);
@@ -228,17 +311,17 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 	const bool inference = opt->use_inference_params != 0;
 
 	// 1. which bricks are kept, which are evaluated, and their slots
-	const uint32_t n_bwg = (a.n_bricks + MC_WG - 1) / MC_WG;
+	const uint32_t n_bwg = groups(a.n_bricks);
 	uint32_t *bwg = nullptr, *bscan = nullptr, *list = nullptr;
-	if (!ws.alloc(&a.word, a.n_bricks) || !ws.alloc(&bwg, n_bwg) || !ws.alloc(&bscan, scan_scratch_elems(n_bwg))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick words");
+	if (!call.ws.alloc(&a.word, a.n_bricks) || !call.ws.alloc(&bwg, n_bwg) || !call.ws.alloc(&bscan, scan_scratch_elems(n_bwg))) return call.nomem("hipMalloc failed for the brick words");
 	hipLaunchKernelGGL(k_ms_classify, dim3((a.n_bricks + 3) / 4), dim3(256), 0, s, a, (double)opt->lattice_min, (double)opt->lattice_max - (double)opt->lattice_min,
 	                   opt->cull == RNB_MESH_CULL_OCCUPANCY ? (const uint8_t*)c->bitfield.p : (const uint8_t*)nullptr);
 	uint32_t n_eval = 0;
 	int rc = count_and_scan(s, n_bwg, bwg, bscan, &n_eval, k_ms_mark<false>, a, bwg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
 	if (rc != RNB_OK) return rc;
-	if (!ws.alloc(&list, n_eval)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick list");
+	if (!call.ws.alloc(&list, n_eval)) return call.nomem("hipMalloc failed for the brick list");
 	a.list = list;
-	hipLaunchKernelGGL(k_ms_mark<true>, dim3(n_bwg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, bwg, list);
+	hipLaunchKernelGGL(k_ms_mark<true>, dim3(n_bwg), dim3(MESH_WG), 0, s, a, (uint32_t*)nullptr, bwg, list);
 	HIP_TRY(hipGetLastError());
 	uint64_t n_kept = 0;
 	{ // the kept count, for the statistics: the evaluated count is the scan's total
@@ -247,12 +330,12 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 		HIP_TRY(hipStreamSynchronize(s));
 		for (uint32_t w : h) n_kept += w & 1u;
 	}
-	ws.release(bwg); ws.release(bscan);
+	call.ws.release(bwg, bscan);
 	const uint64_t n_active_points = (uint64_t)n_eval * brick_points;
 	if (opt->max_active_points && n_active_points > opt->max_active_points)
-		return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: " + std::to_string(n_active_points) + " lattice points would be held at once (" + std::to_string(n_eval) + " bricks of " +
+		return call.nomem(std::to_string(n_active_points) + " lattice points would be held at once (" + std::to_string(n_eval) + " bricks of " +
 		            std::to_string(B) + "^3), max_active_points is " + std::to_string(opt->max_active_points));
-	if (n_eval >= (1u << 30)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: more than 2^30 bricks to evaluate");
+	if (n_eval >= (1u << 30)) return call.invalid("more than 2^30 bricks to evaluate");
 
 	uint32_t n_act = 0, nv = 0, ni = 0;
 	float* verts = nullptr;
@@ -263,8 +346,8 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 		float* pos = nullptr;
 		uint64_t per_launch = opt->max_points_in_flight ? opt->max_points_in_flight : (1u << 22);
 		const uint32_t slots_per_launch = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(per_launch >> lb3, 1), n_eval);
-		if (!ws.alloc(&vals, n_active_points) || !ws.alloc(&pos, (size_t)slots_per_launch * brick_points * 3))
-			return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for " + std::to_string(n_active_points) + " lattice values (set max_active_points to fail before allocating, or cull)");
+		if (!call.ws.alloc(&vals, n_active_points) || !call.ws.alloc(&pos, (size_t)slots_per_launch * brick_points * 3))
+			return call.nomem("hipMalloc failed for " + std::to_string(n_active_points) + " lattice values (set max_active_points to fail before allocating, or cull)");
 		a.vals = vals;
 		const float diag = c->aabb.mx - c->aabb.mn;
 		for (uint32_t s0 = 0; s0 < n_eval; s0 += slots_per_launch) {
@@ -276,48 +359,48 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 		}
 		// 3. which of them see both sides of the threshold; only those keep an edge table
 		uint32_t *act = nullptr, *aoff = nullptr, *ascan = nullptr, *alist = nullptr;
-		if (!ws.alloc(&act, n_eval) || !ws.alloc(&aoff, n_eval) || !ws.alloc(&ascan, scan_scratch_elems(n_eval))) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the brick flags");
+		if (!call.ws.alloc(&act, n_eval) || !call.ws.alloc(&aoff, n_eval) || !call.ws.alloc(&ascan, scan_scratch_elems(n_eval))) return call.nomem("hipMalloc failed for the brick flags");
 		hipLaunchKernelGGL(k_ms_sign, dim3(n_eval), dim3(256), 0, s, a, act);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(aoff, act, (size_t)n_eval * 4, hipMemcpyDeviceToDevice, s));
 		rc = scan_exclusive(aoff, n_eval, s, &n_act, ascan);
 		if (rc != RNB_OK) return rc;
-		ws.release(pos); ws.release(ascan);
+		call.ws.release(pos, ascan);
 		a.act = act; a.aoff = aoff;
 		if (n_act) {
-			if ((uint64_t)n_act << (lb3 - 8) >= (1ull << 31)) return fail(RNB_ERR_INVALID, "rnb_extract_mesh: too many bricks with a sign change for one launch");
+			if ((uint64_t)n_act << (lb3 - 8) >= (1ull << 31)) return call.invalid("too many bricks with a sign change for one launch");
 			const uint32_t n_wg = n_act << (lb3 - 8);
 			uint32_t *wg = nullptr, *wscan = nullptr, *vidx = nullptr;
-			if (!ws.alloc(&alist, n_act) || !ws.alloc(&wg, n_wg) || !ws.alloc(&wscan, scan_scratch_elems(n_wg)) || !ws.alloc(&vidx, (size_t)n_act * 3 * brick_points))
-				return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the edge tables of " + std::to_string(n_act) + " bricks");
+			if (!call.ws.alloc(&alist, n_act) || !call.ws.alloc(&wg, n_wg) || !call.ws.alloc(&wscan, scan_scratch_elems(n_wg)) || !call.ws.alloc(&vidx, (size_t)n_act * 3 * brick_points))
+				return call.nomem("hipMalloc failed for the edge tables of " + std::to_string(n_act) + " bricks");
 			a.alist = alist;
 			hipLaunchKernelGGL(k_ms_list, dim3((n_eval + 255) / 256), dim3(256), 0, s, n_eval, act, aoff, alist);
 			// 4. vertices, then triangles: count, scan, write (the dense path's scheme over the bricks' workgroups)
 			if ((rc = count_and_scan(s, n_wg, wg, wscan, &nv, k_ms_verts<false>, a, wg, (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
-			if (!ws.alloc(&verts, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
-			hipLaunchKernelGGL(k_ms_verts<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
+			if (!call.ws.alloc(&verts, (size_t)nv * 3)) return call.nomem("hipMalloc failed for the vertices");
+			hipLaunchKernelGGL(k_ms_verts<true>, dim3(n_wg), dim3(MESH_WG), 0, s, a, (uint32_t*)nullptr, wg, verts, vidx);
 			if ((rc = count_and_scan(s, n_wg, wg, wscan, &ni, k_ms_faces<false>, a, (const McTable*)c->mc_table.p, wg, (const uint32_t*)nullptr, (const uint32_t*)vidx, (uint32_t*)nullptr)) != RNB_OK) return rc;
-			if (!ws.alloc(&indices, (size_t)ni)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
-			hipLaunchKernelGGL(k_ms_faces<true>, dim3(n_wg), dim3(MC_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
+			if (!call.ws.alloc(&indices, (size_t)ni)) return call.nomem("hipMalloc failed for the indices");
+			hipLaunchKernelGGL(k_ms_faces<true>, dim3(n_wg), dim3(MESH_WG), 0, s, a, c->mc_table.p, (uint32_t*)nullptr, wg, (const uint32_t*)vidx, indices);
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipStreamSynchronize(s));
-			ws.release(wg); ws.release(wscan); ws.release(vidx); ws.release(alist);
+			call.ws.release(wg, wscan, vidx, alist);
 		}
-		ws.release(vals); ws.release(act); ws.release(aoff);
+		call.ws.release(vals, act, aoff);
 	}
-	ws.release(a.word); ws.release(list);
-	if (!verts && !ws.alloc(&verts, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the vertices");
-	if (!indices && !ws.alloc(&indices, 1)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the indices");
+	call.ws.release(a.word, list);
+	if (!verts && !call.ws.alloc(&verts, 1)) return call.nomem("hipMalloc failed for the vertices");
+	if (!indices && !call.ws.alloc(&indices, 1)) return call.nomem("hipMalloc failed for the indices");
 
 	// 5. attributes: the full network at the vertices, in batches
 	float *colors = nullptr, *normals = nullptr;
 	if (opt->attributes) {
-		if ((opt->attributes & RNB_MESH_ATTR_COLORS) && !ws.alloc(&colors, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the colours");
-		if ((opt->attributes & RNB_MESH_ATTR_NORMALS) && !ws.alloc(&normals, (size_t)nv * 3)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the normals");
+		if ((opt->attributes & RNB_MESH_ATTR_COLORS) && !call.ws.alloc(&colors, (size_t)nv * 3)) return call.nomem("hipMalloc failed for the colours");
+		if ((opt->attributes & RNB_MESH_ATTR_NORMALS) && !call.ws.alloc(&normals, (size_t)nv * 3)) return call.nomem("hipMalloc failed for the normals");
 		const uint32_t batch = std::min<uint32_t>(1u << 20, std::max(nv, 1u));
 		float* coords = nullptr;
 		half_t* net = nullptr;
-		if (!ws.alloc(&coords, (size_t)batch * 7) || !ws.alloc(&net, (size_t)batch * 16)) return fail(RNB_ERR_NOMEM, "rnb_extract_mesh: hipMalloc failed for the attribute batch");
+		if (!call.ws.alloc(&coords, (size_t)batch * 7) || !call.ws.alloc(&net, (size_t)batch * 16)) return call.nomem("hipMalloc failed for the attribute batch");
 		const float diag = c->aabb.mx - c->aabb.mn;
 		for (uint32_t v0 = 0; v0 < nv; v0 += batch) {
 			const uint32_t nb = std::min(batch, nv - v0);
@@ -329,16 +412,15 @@ int rnb_extract_mesh(rnb_ctx* c, void* stream, const rnb_mesh_options* opt, rnb_
 			HIP_TRY(hipGetLastError());
 		}
 		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(coords); ws.release(net);
+		call.ws.release(coords, net);
 	}
 	HIP_TRY(hipStreamSynchronize(s));
-	hand_over(ws, rnb_mesh{verts, indices, colors, normals, nv, ni}, out);
+	hand_over(call.ws, rnb_mesh{verts, indices, colors, normals, nv, ni}, out);
 	if (stats) {
 		std::memset(stats, 0, sizeof(*stats));
 		stats->n_bricks = a.n_bricks; stats->n_kept = n_kept; stats->n_evaluated = n_eval; stats->n_sign_change = n_act;
 		stats->n_points_evaluated = n_active_points;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD
@@ -369,12 +451,10 @@ int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_
 	if (opt->abi_version != RNB_MESH_CLEAN_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: options abi_version mismatch (expected RNB_MESH_CLEAN_ABI_VERSION)");
 	if (opt->keep != RNB_MESH_KEEP_ALL && opt->keep != RNB_MESH_KEEP_LARGEST) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown keep mode");
 	if (opt->orient != RNB_MESH_ORIENT_NONE && opt->orient != RNB_MESH_ORIENT_OUTWARD) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: unknown orient mode");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
+	MeshCall call("rnb_mesh_clean", c, stream);
+	const hipStream_t s = call.s;
 
 	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
-	MeshWorkspace ws;
 	ClResult hres;
 	std::memset(&hres, 0, sizeof(hres));
 	hres.best = MESH_NONE;
@@ -382,62 +462,51 @@ int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_
 	rnb_mesh_component* table = nullptr;
 	rnb_mesh o;
 	if (nt) {
-		const uint32_t g_v = (nv + CL_WG - 1) / CL_WG, g_t = (nt + CL_WG - 1) / CL_WG; // (nv >= 1: check_mesh_input)
+		const uint32_t g_v = groups(nv), g_t = groups(nt);
 		uint32_t *parent = nullptr, *used = nullptr, *cid = nullptr, *scan = nullptr, *twg = nullptr, *cflags = nullptr;
 		ClResult* dres = nullptr;
-		if (!ws.alloc(&parent, nv) || !ws.alloc(&used, nv) || !ws.alloc(&cid, nv) || !ws.alloc(&twg, g_t) || !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) || !ws.alloc(&dres, 1))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		if (!call.ws.alloc(&parent, nv) || !call.ws.alloc(&used, nv) || !call.ws.alloc(&cid, nv) || !call.ws.alloc(&twg, g_t) || !call.ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) || !call.ws.alloc(&dres, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
 		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
 		// 1. every index is range-checked before any is used as an address
-		hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, CL_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & CL_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: an index is out of range (>= n_verts)");
+		hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(MESH_WG), 0, s, parent, nv);
+		if (int rc = call.check_indices(m, used, &dres->flags); rc != RNB_OK) return rc;
 		// 2. labels: one hooking launch, one flattening launch; roots -> component ids in ascending label order
-		hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, parent);
-		hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
-		hipLaunchKernelGGL(k_cl_roots, dim3(g_v), dim3(CL_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, cid, nv);
+		hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(MESH_WG), 0, s, (const uint32_t*)m.indices, nt, parent);
+		hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(MESH_WG), 0, s, parent, nv);
+		hipLaunchKernelGGL(k_cl_roots, dim3(g_v), dim3(MESH_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, cid, nv);
 		HIP_TRY(hipGetLastError());
 		int rc = scan_exclusive(cid, nv, s, &n_comp, scan);
 		if (rc != RNB_OK) return rc;
-		if (!ws.alloc(&table, n_comp) || !ws.alloc(&cflags, n_comp)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the table of " + std::to_string(n_comp) + " components");
+		if (!call.ws.alloc(&table, n_comp) || !call.ws.alloc(&cflags, n_comp)) return call.nomem("hipMalloc failed for the table of " + std::to_string(n_comp) + " components");
 		HIP_TRY(hipMemsetAsync(table, 0, std::max<size_t>(n_comp, 1) * sizeof(rnb_mesh_component), s));
-		hipLaunchKernelGGL(k_cl_relabel, dim3(g_v), dim3(CL_WG), 0, s, parent, (const uint32_t*)used, (const uint32_t*)cid, table, nv);
+		hipLaunchKernelGGL(k_cl_relabel, dim3(g_v), dim3(MESH_WG), 0, s, parent, (const uint32_t*)used, (const uint32_t*)cid, table, nv);
 		const uint32_t* comp = parent;
 		// 3. per-component sums, the selection
-		hipLaunchKernelGGL(k_cl_sums<true>, dim3(g_t), dim3(CL_WG), 0, s, (const float*)m.verts, (const uint32_t*)m.indices, nt, comp, table, dres);
-		hipLaunchKernelGGL(k_cl_sums<false>, dim3(g_v), dim3(CL_WG), 0, s, (const float*)nullptr, (const uint32_t*)nullptr, nv, comp, table, dres);
+		hipLaunchKernelGGL(k_cl_sums<true>, dim3(g_t), dim3(MESH_WG), 0, s, (const float*)m.verts, (const uint32_t*)m.indices, nt, comp, table, dres);
+		hipLaunchKernelGGL(k_cl_sums<false>, dim3(g_v), dim3(MESH_WG), 0, s, (const float*)nullptr, (const uint32_t*)nullptr, nv, comp, table, dres);
 		hipLaunchKernelGGL(k_cl_select, dim3(1), dim3(1024), 0, s, table, n_comp, opt->keep, opt->orient, cflags, dres);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & CL_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_clean: the area or volume term of a triangle is not finite or not below 2^18");
-		ws.release(used);
+		if (hres.flags & CL_BAD_TERM) return call.invalid("the area or volume term of a triangle is not finite or not below 2^18");
+		call.ws.release(used);
 		// 4. compaction: the new vertex numbering (cid's memory is reused), the kept triangles per workgroup
 		uint32_t* vmap = cid;
-		hipLaunchKernelGGL(k_cl_vflag, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, vmap, nv);
+		hipLaunchKernelGGL(k_cl_vflag, dim3(g_v), dim3(MESH_WG), 0, s, comp, (const uint32_t*)cflags, vmap, nv);
 		HIP_TRY(hipGetLastError());
-		rc = scan_exclusive(vmap, nv, s, &nvo, scan);
-		if (rc != RNB_OK) return rc;
-		if ((rc = count_and_scan(s, g_t, twg, scan, &nto, k_cl_tris<false>, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
-		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
-		hipLaunchKernelGGL(k_cl_verts, dim3(g_v), dim3(CL_WG), 0, s, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, o.verts, o.colors, o.normals);
-		hipLaunchKernelGGL(k_cl_tris<true>, dim3(g_t), dim3(CL_WG), 0, s, (const uint32_t*)m.indices, nt, comp, (const uint32_t*)cflags, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
-		HIP_TRY(hipGetLastError());
+		if ((rc = call.compact(m, ClKeep{comp, cflags}, vmap, twg, scan, &o, &nvo, &nto)) != RNB_OK) return rc;
 		HIP_TRY(hipStreamSynchronize(s));
 		if (n_comp && hres.best < n_comp) { // the label of the selected component, for the statistics
 			uint32_t label = MESH_NONE;
 			HIP_TRY(hipMemcpy(&label, &table[hres.best].label, 4, hipMemcpyDeviceToHost));
 			hres.best = label;
 		} else hres.best = MESH_NONE;
-		ws.release(parent); ws.release(cid); ws.release(scan); ws.release(twg); ws.release(cflags); ws.release(dres);
-	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr) || (table_dev && !ws.alloc(&table, 1)))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_clean: hipMalloc failed for the output mesh");
-	hand_over(ws, o, out);
-	if (table_dev) *table_dev = (rnb_mesh_component*)ws.keep(table);
+		call.ws.release(parent, cid, scan, twg, cflags, dres);
+	} else if (!alloc_mesh(call.ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr) || (table_dev && !call.ws.alloc(&table, 1)))
+		return call.nomem("hipMalloc failed for the output mesh");
+	hand_over(call.ws, o, out);
+	if (table_dev) *table_dev = (rnb_mesh_component*)call.ws.keep(table);
 	if (stats) {
 		std::memset(stats, 0, sizeof(*stats));
 		stats->n_components = n_comp; stats->n_kept = hres.n_kept;
@@ -445,8 +514,7 @@ int rnb_mesh_clean(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_
 		stats->largest_label = hres.best;
 		stats->hook_passes = nt ? 1u : 0u; stats->flatten_passes = nt ? 1u : 0u;
 		stats->area_q_in = hres.area_in; stats->area_q_out = hres.area_out;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD
@@ -478,12 +546,10 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 		n_cells *= opt->dims[k];
 	}
 	if (n_cells > RNB_MESH_SIMPLIFY_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: dims hold " + std::to_string(n_cells) + " cells, more than RNB_MESH_SIMPLIFY_MAX_CELLS (2^30)");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
+	MeshCall call("rnb_mesh_simplify", c, stream);
+	const hipStream_t s = call.s;
 
 	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
-	MeshWorkspace ws;
 	SpResult hres;
 	std::memset(&hres, 0, sizeof(hres));
 	uint32_t n_cl = 0, nvo = 0, nto = 0;
@@ -493,63 +559,62 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 		for (int k = 0; k < 3; ++k) { g.origin[k] = (double)opt->origin[k]; g.dims[k] = opt->dims[k]; }
 		g.cell = (double)opt->cell;
 		const uint32_t n_words = (uint32_t)((n_cells + 31u) / 32u);
-		const uint32_t g_v = (nv + SP_WG - 1) / SP_WG, g_t = (nt + SP_WG - 1) / SP_WG, g_w = (n_words + SP_WG - 1) / SP_WG;
+		const uint32_t g_v = groups(nv), g_t = groups(nt), g_w = groups(n_words);
 		uint32_t *used = nullptr, *vcl = nullptr, *bits = nullptr, *rank = nullptr, *scan = nullptr, *twg = nullptr, *ckey = nullptr, *cused = nullptr, *cmap = nullptr;
 		long long* sums = nullptr;
 		SpResult* dres = nullptr;
-		if (!ws.alloc(&used, nv) || !ws.alloc(&vcl, nv) || !ws.alloc(&bits, n_words) || !ws.alloc(&rank, n_words) || !ws.alloc(&twg, g_t) ||
-		    !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(std::max<uint64_t>(nv, n_words), g_t))) || !ws.alloc(&dres, 1))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(n_cells) + " cells");
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		if (!call.ws.alloc(&used, nv) || !call.ws.alloc(&vcl, nv) || !call.ws.alloc(&bits, n_words) || !call.ws.alloc(&rank, n_words) || !call.ws.alloc(&twg, g_t) ||
+		    !call.ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(std::max<uint64_t>(nv, n_words), g_t))) || !call.ws.alloc(&dres, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(n_cells) + " cells");
 		HIP_TRY(hipMemsetAsync(bits, 0, (size_t)n_words * 4, s));
 		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-		// 1. every index is range-checked before any is used as an address; the occupied cells; cluster ids = ranks of the occupied keys
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, SP_BAD_INDEX);
-		hipLaunchKernelGGL(k_sp_cells, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)used, vcl, bits, dres);
-		hipLaunchKernelGGL(k_sp_popc, dim3(g_w), dim3(SP_WG), 0, s, (const uint32_t*)bits, rank, n_words);
+		// 1. every index is range-checked before any is used as an address (the flag arrives with the result below: no synchronise of its own); the occupied cells;
+		//    cluster ids = ranks of the occupied keys
+		if (int rc = call.check_indices_launch(m, used, &dres->flags); rc != RNB_OK) return rc;
+		hipLaunchKernelGGL(k_sp_cells, dim3(g_v), dim3(MESH_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)used, vcl, bits, dres);
+		hipLaunchKernelGGL(k_sp_popc, dim3(g_w), dim3(MESH_WG), 0, s, (const uint32_t*)bits, rank, n_words);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		int rc = scan_exclusive(rank, n_words, s, &n_cl, scan); // (synchronises: hres has arrived)
 		if (rc != RNB_OK) return rc;
-		if (hres.flags & SP_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: an index is out of range (>= n_verts)");
-		if (hres.flags & SP_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a coordinate or attribute of a used vertex is not finite");
-		ws.release(used);
+		if (hres.flags & MESH_BAD_INDEX) return call.bad_index();
+		if (hres.flags & SP_BAD_VALUE) return call.invalid("a coordinate or attribute of a used vertex is not finite");
+		call.ws.release(used);
 		// 2. the sums of every cluster
-		if (!ws.alloc(&sums, (size_t)n_cl * SP_NSUM) || !ws.alloc(&ckey, n_cl) || !ws.alloc(&cused, n_cl) || !ws.alloc(&cmap, n_cl))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the records of " + std::to_string(n_cl) + " clusters");
+		if (!call.ws.alloc(&sums, (size_t)n_cl * SP_NSUM) || !call.ws.alloc(&ckey, n_cl) || !call.ws.alloc(&cused, n_cl) || !call.ws.alloc(&cmap, n_cl))
+			return call.nomem("hipMalloc failed for the records of " + std::to_string(n_cl) + " clusters");
 		HIP_TRY(hipMemsetAsync(sums, 0, std::max<size_t>(n_cl, 1) * SP_NSUM * sizeof(long long), s));
 		HIP_TRY(hipMemsetAsync(cused, 0, std::max<size_t>(n_cl, 1) * 4, s));
-		hipLaunchKernelGGL(k_sp_members, dim3(g_v), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)bits, (const uint32_t*)rank, vcl, ckey, sums, dres);
-		hipLaunchKernelGGL(k_sp_quadric, dim3(g_t), dim3(SP_WG), 0, s, g, (const float*)m.verts, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, sums, dres);
+		hipLaunchKernelGGL(k_sp_members, dim3(g_v), dim3(MESH_WG), 0, s, g, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, nv, (const uint32_t*)bits, (const uint32_t*)rank, vcl, ckey, sums, dres);
+		hipLaunchKernelGGL(k_sp_quadric, dim3(g_t), dim3(MESH_WG), 0, s, g, (const float*)m.verts, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, sums, dres);
 		// 3. the surviving triangles and the clusters they use, numbered by prefix sums (not count_and_scan: the count launch feeds two scans, the clusters' first)
-		hipLaunchKernelGGL(k_sp_tris<false>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, cused, (const uint32_t*)nullptr, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+		hipLaunchKernelGGL(k_sp_tris<false>, dim3(g_t), dim3(MESH_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, cused, (const uint32_t*)nullptr, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(cmap, cused, std::max<size_t>(n_cl, 1) * 4, hipMemcpyDeviceToDevice, s));
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		rc = scan_exclusive(cmap, n_cl, s, &nvo, scan);
 		if (rc != RNB_OK) return rc;
-		if (hres.flags & SP_BAD_TERM) return fail(RNB_ERR_INVALID, "rnb_mesh_simplify: a term is not finite or not below 2^22 (a vertex or triangle too far from its cell, in cell units)");
+		if (hres.flags & SP_BAD_TERM) return call.invalid("a term is not finite or not below 2^22 (a vertex or triangle too far from its cell, in cell units)");
 		rc = scan_exclusive(twg, g_t, s, &nto, scan);
 		if (rc != RNB_OK) return rc;
-		ws.release(bits); ws.release(rank);
+		call.ws.release(bits, rank);
 		// 4. the output: one solve per cluster, the triangles in input order
-		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
-		hipLaunchKernelGGL(k_sp_solve, dim3((n_cl + SP_WG - 1) / SP_WG), dim3(SP_WG), 0, s, g, opt->placement, n_cl, (const long long*)sums, (const uint32_t*)ckey, (const uint32_t*)cused, (const uint32_t*)cmap,
+		if ((rc = call.alloc_like(m, &o, nvo, nto)) != RNB_OK) return rc;
+		hipLaunchKernelGGL(k_sp_solve, dim3(groups(n_cl)), dim3(MESH_WG), 0, s, g, opt->placement, n_cl, (const long long*)sums, (const uint32_t*)ckey, (const uint32_t*)cused, (const uint32_t*)cmap,
 		                   o.verts, o.colors, o.normals, dres);
-		hipLaunchKernelGGL(k_sp_tris<true>, dim3(g_t), dim3(SP_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, (uint32_t*)nullptr, (const uint32_t*)cmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
+		hipLaunchKernelGGL(k_sp_tris<true>, dim3(g_t), dim3(MESH_WG), 0, s, (const uint32_t*)m.indices, nt, (const uint32_t*)vcl, (uint32_t*)nullptr, (const uint32_t*)cmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(vcl); ws.release(scan); ws.release(twg); ws.release(sums); ws.release(ckey); ws.release(cused); ws.release(cmap); ws.release(dres);
-	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_simplify: hipMalloc failed for the output mesh");
-	hand_over(ws, o, out);
+		call.ws.release(vcl, scan, twg, sums, ckey, cused, cmap, dres);
+	} else if (int rc = call.alloc_like(m, &o, 0, 0); rc != RNB_OK)
+		return rc;
+	hand_over(call.ws, o, out);
 	if (stats) {
 		std::memset(stats, 0, sizeof(*stats));
 		stats->n_verts_in = nv; stats->n_tris_in = nt; stats->n_clusters = n_cl; stats->n_verts_out = nvo; stats->n_tris_out = nto; stats->n_tris_collapsed = nt - nto;
 		stats->n_clamped = hres.n_clamped; stats->n_fallback = hres.n_fallback;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD
@@ -579,20 +644,15 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 	for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k)
 		if (!(opt->tau[k] >= 0.0f) || !std::isfinite(opt->tau[k])) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a tau must be finite and >= 0");
 	if (opt->cells > RNB_MESH_DISTANCE_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: cells must be 0 .. 256");
-	{
-		rnb_mesh unused;
-		if (int rc = check_mesh_input("rnb_mesh_distance (from)", from, &unused); rc != RNB_OK) return rc;
-		if (int rc = check_mesh_input("rnb_mesh_distance (to)", to, &unused); rc != RNB_OK) return rc;
-	}
+	if (int rc = check_mesh_input("rnb_mesh_distance (from)", from); rc != RNB_OK) return rc;
+	if (int rc = check_mesh_input("rnb_mesh_distance (to)", to); rc != RNB_OK) return rc;
 	const rnb_mesh ma = *from, mb = *to;
 	const uint32_t nva = ma.n_verts, nta = ma.n_indices / 3u, nvb = mb.n_verts, ntb = mb.n_indices / 3u, nn = 1u << (2u * opt->level);
 	if ((uint64_t)nta * nn > 0xFFFFFFFFull) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: more than 2^32 - 1 samples (a lower level)");
 	if (nta && ntb == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
+	MeshCall call("rnb_mesh_distance", c, stream);
+	const hipStream_t s = call.s;
 
-	MeshWorkspace ws;
 	MdResult hres;
 	std::memset(&hres, 0, sizeof(hres));
 	for (int k = 0; k < 3; ++k) hres.bmin[k] = 0xFFFFFFFFu;
@@ -606,37 +666,33 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 		if (vert_nearest_dev && nva) HIP_TRY(hipMemsetAsync(vert_nearest_dev, 0xFF, (size_t)nva * 4, s));
 		HIP_TRY(hipStreamSynchronize(s));
 	} else {
-		const uint32_t g_va = (nva + MD_WG - 1) / MD_WG, g_ta = (nta + MD_WG - 1) / MD_WG, g_vb = (nvb + MD_WG - 1) / MD_WG, g_tb = (ntb + MD_WG - 1) / MD_WG; // (nva, nvb >= 1: check_mesh_input)
+		const uint32_t g_va = groups(nva), g_vb = groups(nvb), g_tb = groups(ntb);
 		const MdMesh A{ma.verts, ma.indices, nva, nta}, B{mb.verts, mb.indices, nvb, ntb};
 		uint32_t *used_a = nullptr, *used_b = nullptr, *start = nullptr, *cursor = nullptr, *scan = nullptr, *entries = nullptr, *large = nullptr;
 		MdResult* dres = nullptr;
-		if (!ws.alloc(&used_a, nva) || !ws.alloc(&used_b, nvb) || !ws.alloc(&large, RNB_MESH_DISTANCE_MAX_LARGE) || !ws.alloc(&dres, 1))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the workspace of " + std::to_string(nva) + " and " + std::to_string(nvb) + " vertices");
-		HIP_TRY(hipMemsetAsync(used_a, 0, (size_t)nva * 4, s));
-		HIP_TRY(hipMemsetAsync(used_b, 0, (size_t)nvb * 4, s));
+		if (!call.ws.alloc(&used_a, nva) || !call.ws.alloc(&used_b, nvb) || !call.ws.alloc(&large, RNB_MESH_DISTANCE_MAX_LARGE) || !call.ws.alloc(&dres, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nva) + " and " + std::to_string(nvb) + " vertices");
 		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-		// 1. every index of either mesh is range-checked before any is used as an address; used vertices, B's box, B's degenerate triangles
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_ta), dim3(MD_WG), 0, s, (const uint32_t*)ma.indices, nta, nva, used_a, &dres->flags, MD_BAD_INDEX_FROM);
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_tb), dim3(MD_WG), 0, s, (const uint32_t*)mb.indices, ntb, nvb, used_b, &dres->flags, MD_BAD_INDEX_TO);
+		// 1. every index of either mesh is range-checked before any is used as an address (both under one synchronise); used vertices, B's box, B's degenerate triangles
+		if (int rc = call.check_indices_launch(ma, used_a, &dres->flags); rc != RNB_OK) return rc;
+		if (int rc = call.check_indices_launch(mb, used_b, &dres->flags, MD_BAD_INDEX_TO); rc != RNB_OK) return rc;
+		if (int rc = call.read_flags(&dres->flags, &hres.flags); rc != RNB_OK) return rc;
+		if (hres.flags & MESH_BAD_INDEX) return call.bad_index("of from ");
+		if (hres.flags & MD_BAD_INDEX_TO) return call.bad_index("of to ");
+		hipLaunchKernelGGL(k_md_verts<false>, dim3(g_va), dim3(MESH_WG), 0, s, (const float*)ma.verts, nva, (const uint32_t*)used_a, dres);
+		hipLaunchKernelGGL(k_md_verts<true>, dim3(g_vb), dim3(MESH_WG), 0, s, (const float*)mb.verts, nvb, (const uint32_t*)used_b, dres);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MD_BAD_INDEX_FROM) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of from is out of range (>= n_verts)");
-		if (hres.flags & MD_BAD_INDEX_TO) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: an index of to is out of range (>= n_verts)");
-		hipLaunchKernelGGL(k_md_verts<false>, dim3(g_va), dim3(MD_WG), 0, s, (const float*)ma.verts, nva, (const uint32_t*)used_a, dres);
-		hipLaunchKernelGGL(k_md_verts<true>, dim3(g_vb), dim3(MD_WG), 0, s, (const float*)mb.verts, nvb, (const uint32_t*)used_b, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MD_BAD_VALUE) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a coordinate of a used vertex is not finite");
-		ws.release(used_b);
+		if (hres.flags & MD_BAD_VALUE) return call.invalid("a coordinate of a used vertex is not finite");
+		call.ws.release(used_b);
 		const auto t_grid = std::chrono::steady_clock::now();
-		hipLaunchKernelGGL(k_md_degenerate, dim3(g_tb), dim3(MD_WG), 0, s, B, dres);
+		hipLaunchKernelGGL(k_md_degenerate, dim3(g_tb), dim3(MESH_WG), 0, s, B, dres);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		const uint32_t m = ntb - hres.n_deg_to;
-		if (!m) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: to has no non-degenerate triangle");
+		if (!m) return call.invalid("to has no non-degenerate triangle");
 		// 2. the grid over B's box, the cell lists
 		double longest = 0.0;
 		for (int k = 0; k < 3; ++k) {
@@ -652,21 +708,21 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 			g.dims[k] = (uint32_t)std::min<double>((double)n_axis, std::floor((g.hi[k] - g.lo[k]) / g.cell) + 1.0);
 			n_cells *= g.dims[k];
 		}
-		if (!ws.alloc(&start, n_cells) || !ws.alloc(&cursor, n_cells) || !ws.alloc(&scan, scan_scratch_elems(n_cells)))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for the lists of " + std::to_string(n_cells) + " cells");
+		if (!call.ws.alloc(&start, n_cells) || !call.ws.alloc(&cursor, n_cells) || !call.ws.alloc(&scan, scan_scratch_elems(n_cells)))
+			return call.nomem("hipMalloc failed for the lists of " + std::to_string(n_cells) + " cells");
 		HIP_TRY(hipMemsetAsync(start, 0, (size_t)n_cells * 4, s));
-		hipLaunchKernelGGL(k_md_register<false>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, start, (uint32_t*)nullptr, large, dres);
+		hipLaunchKernelGGL(k_md_register<false>, dim3(g_tb), dim3(MESH_WG), 0, s, g, B, start, (uint32_t*)nullptr, large, dres);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		int rc = scan_exclusive(start, n_cells, s, &n_entries, scan); // (synchronises: hres has arrived)
 		if (rc != RNB_OK) return rc;
 		if (hres.n_large > RNB_MESH_DISTANCE_MAX_LARGE)
-			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_large) + " triangles of to overlap more than 2048 cells each, the large list holds 4096 (a coarser grid: fewer cells)");
+			return call.invalid(std::to_string(hres.n_large) + " triangles of to overlap more than 2048 cells each, the large list holds 4096 (a coarser grid: fewer cells)");
 		if (hres.n_entries > RNB_MESH_DISTANCE_MAX_ENTRIES)
-			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: " + std::to_string(hres.n_entries) + " cell entries, more than 2^31 (a coarser grid: fewer cells)");
-		if (!ws.alloc(&entries, n_entries)) return fail(RNB_ERR_NOMEM, "rnb_mesh_distance: hipMalloc failed for " + std::to_string(n_entries) + " cell entries");
+			return call.invalid(std::to_string(hres.n_entries) + " cell entries, more than 2^31 (a coarser grid: fewer cells)");
+		if (!call.ws.alloc(&entries, n_entries)) return call.nomem("hipMalloc failed for " + std::to_string(n_entries) + " cell entries");
 		HIP_TRY(hipMemcpyAsync(cursor, start, (size_t)n_cells * 4, hipMemcpyDeviceToDevice, s));
-		hipLaunchKernelGGL(k_md_register<true>, dim3(g_tb), dim3(MD_WG), 0, s, g, B, cursor, entries, (uint32_t*)nullptr, dres);
+		hipLaunchKernelGGL(k_md_register<true>, dim3(g_tb), dim3(MESH_WG), 0, s, g, B, cursor, entries, (uint32_t*)nullptr, dres);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipStreamSynchronize(s));
 		ms_grid = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_grid).count();
@@ -677,19 +733,19 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 		for (int k = 0; k < RNB_MESH_DISTANCE_MAX_TAUS; ++k) q.tau[k] = (double)opt->tau[k];
 		const MdSearch S{B, start, cursor, entries, large, hres.n_large};
 		const uint64_t n_threads = (uint64_t)nta * nn;
-		hipLaunchKernelGGL(k_md_query<true>, dim3(g_va), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)used_a, S, vert_dist_dev, vert_nearest_dev, dres);
-		hipLaunchKernelGGL(k_md_query<false>, dim3((uint32_t)((n_threads + MD_WG - 1) / MD_WG)), dim3(MD_WG), 0, s, g, q, A, (const uint32_t*)nullptr, S, (float*)nullptr, (uint32_t*)nullptr, dres);
+		hipLaunchKernelGGL(k_md_query<true>, dim3(g_va), dim3(MESH_WG), 0, s, g, q, A, (const uint32_t*)used_a, S, vert_dist_dev, vert_nearest_dev, dres);
+		hipLaunchKernelGGL(k_md_query<false>, dim3(groups(n_threads)), dim3(MESH_WG), 0, s, g, q, A, (const uint32_t*)nullptr, S, (float*)nullptr, (uint32_t*)nullptr, dres);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		if (hres.flags & MD_BAD_TERM)
-			return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a term is not finite or not below 2^12 (a larger unit, or a max_distance)");
+			return call.invalid("a term is not finite or not below 2^12 (a larger unit, or a max_distance)");
 		for (int k = 0; k < MD_NSUM; ++k) { // the two words of a sum, joined in 128 bits
 			const unsigned __int128 total = ((unsigned __int128)hres.hi[k] << 32) + hres.lo[k];
-			if (total >> 63) return fail(RNB_ERR_INVALID, "rnb_mesh_distance: a sum reaches 2^15 (a larger unit, or a max_distance)");
+			if (total >> 63) return call.invalid("a sum reaches 2^15 (a larger unit, or a max_distance)");
 			sums[k] = (int64_t)total;
 		}
-		ws.release(used_a); ws.release(start); ws.release(cursor); ws.release(scan); ws.release(entries); ws.release(large); ws.release(dres);
+		call.ws.release(used_a, start, cursor, scan, entries, large, dres);
 	}
 	if (stats) {
 		stats->n_verts_from_used = hres.n_used_from; stats->n_verts_to_used = hres.n_used_to; stats->n_tris_from = nta; stats->n_tris_to = ntb;
@@ -701,9 +757,8 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 		for (int k = 0; k < 3; ++k) stats->dims[k] = g.dims[k];
 		stats->cell = g.cell;
 		stats->n_cell_entries = hres.n_entries; stats->n_pairs = hres.n_pairs;
-		stats->peak_workspace = ws.peak;
 		stats->ms_grid = ms_grid;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD
@@ -723,7 +778,13 @@ int rnb_mesh_raster_default_options(rnb_mesh_raster_options* opt) try {
 
 extern "C++" {
 namespace {
-// What rnb_mesh_raster and rnb_mesh_visibility ask of a camera, said in the entry point's name.
+// What the rasteriser, the draw, the visibility stage and the projection ask of near and cull, and of a camera, said in the entry point's name.
+int check_near_cull(const char* name, float near, uint32_t cull) {
+	const std::string n(name);
+	if (!(near > 0.0f) || !std::isfinite(near)) return fail(RNB_ERR_INVALID, n + ": near must be finite and > 0");
+	if (cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, n + ": cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
+	return RNB_OK;
+}
 int check_raster_view(const char* name, const rnb_view* view) {
 	const std::string n(name);
 	for (int k = 0; k < 2; ++k) {
@@ -749,27 +810,38 @@ MrCamera raster_camera(const rnb_view* view, float near, uint32_t cull, uint32_t
 	cam.w = view->width; cam.h = view->height; cam.cull = cull; cam.normals = normals;
 	return cam;
 }
+// What the fill of a view starts from: the keys of its pixels all ones, their counts zero, *dres and *hres zero.
+int raster_clear(hipStream_t s, const MrCamera& cam, unsigned long long* keys, uint32_t* counts, MrResult* dres, MrResult* hres) {
+	const size_t n_pix = (size_t)cam.w * cam.h;
+	std::memset(hres, 0, sizeof(*hres));
+	HIP_TRY(hipMemsetAsync(keys, 0xFF, n_pix * 8, s));
+	HIP_TRY(hipMemsetAsync(counts, 0, n_pix * 4, s));
+	HIP_TRY(hipMemcpyAsync(dres, hres, sizeof(*hres), hipMemcpyHostToDevice, s));
+	return RNB_OK;
+}
 // The fill of one view, for the rasteriser (VIS = false, an empty tally) and the visibility stage (VIS = true): setup, classes, the small triangles filled; the large
-// ones counted, then listed and filled by a wavefront each. keys are all ones, counts and *dres zero on entry (and for VIS the tally's words); *hres is *dres after
-// the first pass (synchronises). The list grows when a view needs a longer one and is the caller's to release. M.nt >= 1, the indices are range-checked.
+// ones counted, then listed and filled by a wavefront each. On entry the state of raster_clear (and for VIS the tally's words zero); *hres is *dres after the first
+// pass (synchronises). The list grows when a view needs a longer one and is the caller's to release; `name` is who is named if it cannot be allocated. M.nt >= 1, the
+// indices are range-checked.
 template <bool VIS>
-int raster_fill(const char* name, MeshWorkspace& ws, hipStream_t s, const MrCamera& cam, const MrMesh& M, unsigned long long* keys, uint32_t* counts, MrResult* dres, MrResult* hres,
-                uint32_t** list, uint32_t* list_cap, const MrTally& tally) {
-	const uint32_t g_t = (M.nt + MR_WG - 1) / MR_WG;
-	hipLaunchKernelGGL((k_mr_bin<false, VIS>), dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, (uint32_t*)nullptr, 0u, dres, tally);
+int raster_fill(const char* name, MeshCall& call, const MrCamera& cam, const MrMesh& M, unsigned long long* keys, uint32_t* counts, MrResult* dres, MrResult* hres, uint32_t** list,
+                uint32_t* list_cap, const MrTally& tally) {
+	const hipStream_t s = call.s;
+	const uint32_t g_t = groups(M.nt);
+	hipLaunchKernelGGL((k_mr_bin<false, VIS>), dim3(g_t), dim3(MESH_WG), 0, s, cam, M, keys, counts, (uint32_t*)nullptr, 0u, dres, tally);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(hres, dres, sizeof(*hres), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	const uint32_t n_large = hres->n_class[MR_LARGE];
 	if (n_large) {
 		if (n_large > *list_cap) {
-			ws.release(*list);
+			call.ws.release(*list);
 			*list_cap = 0;
-			if (!ws.alloc(list, n_large)) return fail(RNB_ERR_NOMEM, std::string(name) + ": hipMalloc failed for the list of " + std::to_string(n_large) + " large triangles");
+			if (!call.ws.alloc(list, n_large)) return fail(RNB_ERR_NOMEM, std::string(name) + ": hipMalloc failed for the list of " + std::to_string(n_large) + " large triangles");
 			*list_cap = n_large;
 		}
-		hipLaunchKernelGGL((k_mr_bin<true, VIS>), dim3(g_t), dim3(MR_WG), 0, s, cam, M, keys, counts, *list, n_large, dres, tally);
-		hipLaunchKernelGGL(k_mr_fill_large<VIS>, dim3((n_large + MR_WG / 64u - 1) / (MR_WG / 64u)), dim3(MR_WG), 0, s, cam, M, (const uint32_t*)*list, n_large, keys, counts, tally);
+		hipLaunchKernelGGL((k_mr_bin<true, VIS>), dim3(g_t), dim3(MESH_WG), 0, s, cam, M, keys, counts, *list, n_large, dres, tally);
+		hipLaunchKernelGGL(k_mr_fill_large<VIS>, dim3((n_large + MESH_WG / 64u - 1) / (MESH_WG / 64u)), dim3(MESH_WG), 0, s, cam, M, (const uint32_t*)*list, n_large, keys, counts, tally);
 		HIP_TRY(hipGetLastError());
 	}
 	return RNB_OK;
@@ -777,14 +849,10 @@ int raster_fill(const char* name, MeshWorkspace& ws, hipStream_t s, const MrCame
 // What rnb_mesh_raster and rnb_mesh_draw_textured ask of near, cull, normals, the camera and the mesh, said in the entry point's name.
 int check_raster_call(const char* name, float near, uint32_t cull, uint32_t normals, const rnb_view* view, const rnb_mesh* mesh) {
 	const std::string n(name);
-	if (!(near > 0.0f) || !std::isfinite(near)) return fail(RNB_ERR_INVALID, n + ": near must be finite and > 0");
-	if (cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, n + ": cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
+	if (int rc = check_near_cull(name, near, cull); rc != RNB_OK) return rc;
 	if (normals > RNB_MESH_RASTER_NORMALS_VERTEX) return fail(RNB_ERR_INVALID, n + ": normals must be RNB_MESH_RASTER_NORMALS_FACE or _VERTEX");
 	if (int rc = check_raster_view(name, view); rc != RNB_OK) return rc;
-	{
-		rnb_mesh unused;
-		if (int rc = check_mesh_input(name, mesh, &unused); rc != RNB_OK) return rc;
-	}
+	if (int rc = check_mesh_input(name, mesh); rc != RNB_OK) return rc;
 	if (normals == RNB_MESH_RASTER_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, n + ": normals = VERTEX needs a mesh with normals");
 	return RNB_OK;
 }
@@ -793,9 +861,9 @@ template <int FILTER, bool COLOR, bool NORMAL>
 void launch_md_resolve(uint32_t g_p, hipStream_t s, const MrCamera& cam, const MrMesh& M, const DrawTexture& tex, const unsigned long long* keys, const uint32_t* counts, float* out_dev, uint32_t* face_dev,
                        MrResult* dres, DrawResult* ddraw) {
 	if (((uintptr_t)out_dev & 15u) == 0)
-		hipLaunchKernelGGL((k_md_resolve<FILTER, COLOR, NORMAL, true>), dim3(g_p), dim3(MR_WG), 0, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
+		hipLaunchKernelGGL((k_md_resolve<FILTER, COLOR, NORMAL, true>), dim3(g_p), dim3(MESH_WG), 0, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
 	else
-		hipLaunchKernelGGL((k_md_resolve<FILTER, COLOR, NORMAL, false>), dim3(g_p), dim3(MR_WG), 0, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
+		hipLaunchKernelGGL((k_md_resolve<FILTER, COLOR, NORMAL, false>), dim3(g_p), dim3(MESH_WG), 0, s, cam, M, tex, keys, counts, out_dev, face_dev, dres, ddraw);
 }
 template <int FILTER>
 void launch_md_resolve(uint32_t g_p, hipStream_t s, const MrCamera& cam, const MrMesh& M, const DrawTexture& tex, const unsigned long long* keys, const uint32_t* counts, float* out_dev, uint32_t* face_dev,
@@ -808,66 +876,53 @@ void launch_md_resolve(uint32_t g_p, hipStream_t s, const MrCamera& cam, const M
 // on arguments the caller has checked. *stats (may be null) is zero on entry.
 int raster_image(const char* name, rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_view* view, float near, uint32_t cull, uint32_t normals, const DrawTexture* tex, uint32_t filter,
                  float* out_dev, uint32_t* face_dev, rnb_mesh_raster_stats* stats, DrawResult* drawn) {
-	const std::string nm(name);
 	const rnb_mesh m = *mesh;
-	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, width = view->width, height = view->height, n_pix = width * height;
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, n_pix = view->width * view->height;
+	MeshCall call(name, c, stream);
+	const hipStream_t s = call.s;
 
 	const MrCamera cam = raster_camera(view, near, cull, normals);
 	const MrMesh M{m.verts, m.indices, m.colors, m.normals, nt};
 
-	MeshWorkspace ws;
 	MrResult hres;
-	std::memset(&hres, 0, sizeof(hres));
 	unsigned long long* keys = nullptr;
 	uint32_t *counts = nullptr, *used = nullptr, *list = nullptr;
 	MrResult* dres = nullptr;
 	DrawResult* ddraw = nullptr;
-	if (!ws.alloc(&keys, n_pix) || !ws.alloc(&counts, n_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1) || (tex && !ws.alloc(&ddraw, 1)))
-		return fail(RNB_ERR_NOMEM, nm + ": hipMalloc failed for the workspace of " + std::to_string(n_pix) + " pixels and " + std::to_string(nv) + " vertices");
-	HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_pix * 8, s));
-	HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_pix * 4, s));
-	HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+	if (!call.ws.alloc(&keys, n_pix) || !call.ws.alloc(&counts, n_pix) || !call.ws.alloc(&used, nv) || !call.ws.alloc(&dres, 1) || (tex && !call.ws.alloc(&ddraw, 1)))
+		return call.nomem("hipMalloc failed for the workspace of " + std::to_string(n_pix) + " pixels and " + std::to_string(nv) + " vertices");
+	if (int rc = raster_clear(s, cam, keys, counts, dres, &hres); rc != RNB_OK) return rc;
 	if (tex) HIP_TRY(hipMemsetAsync(ddraw, 0, sizeof(DrawResult), s));
 	if (nt) {
-		const uint32_t g_t = (nt + MR_WG - 1) / MR_WG;
-		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MR_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, MR_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MR_BAD_INDEX) return fail(RNB_ERR_INVALID, nm + ": an index is out of range (>= n_verts)");
-		ws.release(used);
+		// 1. every index is range-checked before any is used as an address
+		if (int rc = call.check_indices(m, used, &dres->flags); rc != RNB_OK) return rc;
+		call.ws.release(used);
 		// 2. setup, classes, the small triangles filled; the large ones counted, then listed and filled by a wavefront each (the fill is the rasteriser's for both callers,
 		//    and names the rasteriser if its list cannot be allocated)
 		uint32_t list_cap = 0;
-		if (int rc = raster_fill<false>("rnb_mesh_raster", ws, s, cam, M, keys, counts, dres, &hres, &list, &list_cap, MrTally{}); rc != RNB_OK) return rc;
+		if (int rc = raster_fill<false>("rnb_mesh_raster", call, cam, M, keys, counts, dres, &hres, &list, &list_cap, MrTally{}); rc != RNB_OK) return rc;
 	}
 	// 3. one thread per pixel (an empty mesh: every key is still all ones, the image is zeros)
-	const uint32_t g_p = (n_pix + MR_WG - 1) / MR_WG;
+	const uint32_t g_p = groups(n_pix);
 	if (tex) {
 		if (filter == RNB_MESH_DRAW_FILTER_NEAREST) launch_md_resolve<RNB_MESH_DRAW_FILTER_NEAREST>(g_p, s, cam, M, *tex, keys, counts, out_dev, face_dev, dres, ddraw);
 		else launch_md_resolve<RNB_MESH_DRAW_FILTER_BILINEAR>(g_p, s, cam, M, *tex, keys, counts, out_dev, face_dev, dres, ddraw);
 	} else if (((uintptr_t)out_dev & 15u) == 0)
-		hipLaunchKernelGGL(k_mr_resolve<true>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
+		hipLaunchKernelGGL(k_mr_resolve<true>, dim3(g_p), dim3(MESH_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
 	else
-		hipLaunchKernelGGL(k_mr_resolve<false>, dim3(g_p), dim3(MR_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
+		hipLaunchKernelGGL(k_mr_resolve<false>, dim3(g_p), dim3(MESH_WG), 0, s, cam, M, (const unsigned long long*)keys, (const uint32_t*)counts, out_dev, face_dev, dres);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 	if (tex) HIP_TRY(hipMemcpyAsync(drawn, ddraw, sizeof(DrawResult), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	ws.release(keys); ws.release(counts); ws.release(used); ws.release(list); ws.release(dres); ws.release(ddraw);
-	if (hres.n_unresolved) return fail(RNB_ERR_DEVICE, nm + ": " + std::to_string(hres.n_unresolved) + " pixels whose winner the resolve pass does not find covering them (the fill and the resolve disagree: a defect of the library)");
+	call.ws.release(keys, counts, used, list, dres, ddraw);
+	if (hres.n_unresolved) return call.device(std::to_string(hres.n_unresolved) + " pixels whose winner the resolve pass does not find covering them (the fill and the resolve disagree: a defect of the library)");
 	if (stats) {
 		stats->n_tris = nt;
 		stats->n_behind = hres.n_class[MR_BEHIND]; stats->n_out_of_range = hres.n_class[MR_OUT_OF_RANGE]; stats->n_degenerate = hres.n_class[MR_DEGENERATE];
 		stats->n_culled = hres.n_class[MR_CULLED]; stats->n_offscreen = hres.n_class[MR_OFFSCREEN]; stats->n_small = hres.n_class[MR_SMALL]; stats->n_large = hres.n_class[MR_LARGE];
 		stats->n_covered = hres.n_covered; stats->n_back_pixels = hres.n_back_pixels; stats->n_fragments = hres.n_fragments;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 }
@@ -905,8 +960,7 @@ int rnb_mesh_draw_textured(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const
 	if ((void*)out_dev == (void*)face_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: out_dev and face_dev must be different buffers");
 	if (opt->abi_version != RNB_MESH_DRAW_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: options abi_version mismatch (expected RNB_MESH_DRAW_ABI_VERSION)");
 	if (opt->filter > RNB_MESH_DRAW_FILTER_BILINEAR) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: filter must be RNB_MESH_DRAW_FILTER_NEAREST or _BILINEAR");
-	for (uint32_t r : opt->reserved)
-		if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: a reserved word of the options is not 0");
+	if (int rc = check_reserved("rnb_mesh_draw_textured", opt->reserved); rc != RNB_OK) return rc;
 	if (int rc = check_raster_call("rnb_mesh_draw_textured", opt->near, opt->cull, opt->normals, view, mesh); rc != RNB_OK) return rc;
 	if (!tex->color_dev && !tex->normal_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: no map (color_dev and normal_dev are both null)");
 	if (((uintptr_t)tex->color_dev | (uintptr_t)tex->normal_dev) & 15u) return fail(RNB_ERR_INVALID, "rnb_mesh_draw_textured: a map is not aligned to 16 bytes");
@@ -951,10 +1005,9 @@ int rnb_mesh_visibility(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rn
 	if (!c || !mesh || !views || !opt || !faces_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: null argument");
 	if (n_views == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: n_views must be at least 1");
 	if (opt->abi_version != RNB_MESH_VISIBILITY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: options abi_version mismatch (expected RNB_MESH_VISIBILITY_ABI_VERSION)");
-	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: near must be finite and > 0");
-	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: cull must be RNB_MESH_RASTER_CULL_NONE, _BACK or _FRONT");
+	if (int rc = check_near_cull("rnb_mesh_visibility", opt->near, opt->cull); rc != RNB_OK) return rc;
 	if (opt->min_pixels == 0) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: min_pixels must be at least 1");
-	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: a reserved word of the options is not 0");
+	if (int rc = check_reserved("rnb_mesh_visibility", opt->reserved); rc != RNB_OK) return rc;
 	uint32_t max_pix = 0;
 	uint64_t n_pixels = 0;
 	for (uint32_t v = 0; v < n_views; ++v) {
@@ -964,40 +1017,30 @@ int rnb_mesh_visibility(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rn
 		max_pix = std::max(max_pix, n);
 		n_pixels += n;
 	}
-	{
-		rnb_mesh unused;
-		if (int rc = check_mesh_input("rnb_mesh_visibility", mesh, &unused); rc != RNB_OK) return rc;
-	}
+	if (int rc = check_mesh_input("rnb_mesh_visibility", mesh); rc != RNB_OK) return rc;
 	const rnb_mesh m = *mesh;
 	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
+	MeshCall call("rnb_mesh_visibility", c, stream);
+	const hipStream_t s = call.s;
 
-	MeshWorkspace ws;
 	uint64_t n_class[MR_NCLASS] = {};
 	MvResult hv;
 	std::memset(&hv, 0, sizeof(hv));
 	if (nt) {
 		const MrMesh M{m.verts, m.indices, nullptr, nullptr, nt};
-		const uint32_t g_t = (nt + MV_WG - 1) / MV_WG;
+		const uint32_t g_t = groups(nt);
 		unsigned long long* keys = nullptr;
 		uint32_t *counts = nullptr, *used = nullptr, *list = nullptr, *words = nullptr, list_cap = 0;
 		MrResult* dres = nullptr;
 		MvResult* dv = nullptr;
-		if (!ws.alloc(&keys, max_pix) || !ws.alloc(&counts, max_pix) || !ws.alloc(&words, (size_t)nt * 3) || !ws.alloc(&used, nv) || !ws.alloc(&dres, 1) || !ws.alloc(&dv, 1))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility: hipMalloc failed for the workspace of " + std::to_string(max_pix) + " pixels, " + std::to_string(nt) + " triangles and " + std::to_string(nv) + " vertices");
+		if (!call.ws.alloc(&keys, max_pix) || !call.ws.alloc(&counts, max_pix) || !call.ws.alloc(&words, (size_t)nt * 3) || !call.ws.alloc(&used, nv) || !call.ws.alloc(&dres, 1) || !call.ws.alloc(&dv, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(max_pix) + " pixels, " + std::to_string(nt) + " triangles and " + std::to_string(nv) + " vertices");
 		uint32_t *cov = words, *on = words + nt, *won = words + 2 * (size_t)nt;
-		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		// 1. every index is range-checked before any is used as an address
 		HIP_TRY(hipMemsetAsync(words, 0, (size_t)nt * 12, s));
 		HIP_TRY(hipMemcpyAsync(dv, &hv, sizeof(hv), hipMemcpyHostToDevice, s));
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MV_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dv->flags, MV_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hv.flags & MV_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility: an index is out of range (>= n_verts)");
-		ws.release(used);
+		if (int rc = call.check_indices(m, used, &dv->flags); rc != RNB_OK) return rc;
+		call.ws.release(used);
 		// 2. view by view: the rasteriser's fill, the winners tallied, the three words of every triangle folded into its record
 		for (uint32_t v = 0; v < n_views; ++v) {
 			const rnb_mesh_visibility_view& V = views[v];
@@ -1005,19 +1048,16 @@ int rnb_mesh_visibility(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rn
 			const MrCamera cam = raster_camera(&V.view, opt->near, opt->cull, RNB_MESH_RASTER_NORMALS_FACE);
 			const MrTally tally{V.mask_dev, V.mask_width, V.mask_height, cov, on};
 			MrResult hres;
-			std::memset(&hres, 0, sizeof(hres));
-			HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_pix * 8, s));
-			HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_pix * 4, s));
-			HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-			if (int rc = raster_fill<true>("rnb_mesh_visibility", ws, s, cam, M, keys, counts, dres, &hres, &list, &list_cap, tally); rc != RNB_OK) return rc;
+			if (int rc = raster_clear(s, cam, keys, counts, dres, &hres); rc != RNB_OK) return rc;
+			if (int rc = raster_fill<true>("rnb_mesh_visibility", call, cam, M, keys, counts, dres, &hres, &list, &list_cap, tally); rc != RNB_OK) return rc;
 			for (uint32_t k = 0; k < MR_NCLASS; ++k) n_class[k] += hres.n_class[k];
-			hipLaunchKernelGGL(k_mv_tally, dim3((n_pix + MV_WG - 1) / MV_WG), dim3(MV_WG), 0, s, V.view.width, V.view.height, nt, tally, (const unsigned long long*)keys, won);
-			hipLaunchKernelGGL(k_mv_fold, dim3(g_t), dim3(MV_WG), 0, s, nt, v, v == 0 ? 1u : 0u, v + 1 == n_views ? 1u : 0u, V.mask_dev ? 1u : 0u, opt->min_pixels, cov, on, won, faces_dev, dv);
+			hipLaunchKernelGGL(k_mv_tally, dim3(groups(n_pix)), dim3(MESH_WG), 0, s, V.view.width, V.view.height, nt, tally, (const unsigned long long*)keys, won);
+			hipLaunchKernelGGL(k_mv_fold, dim3(g_t), dim3(MESH_WG), 0, s, nt, v, v == 0 ? 1u : 0u, v + 1 == n_views ? 1u : 0u, V.mask_dev ? 1u : 0u, opt->min_pixels, cov, on, won, faces_dev, dv);
 			HIP_TRY(hipGetLastError());
 		}
 		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(keys); ws.release(counts); ws.release(words); ws.release(list); ws.release(dres); ws.release(dv);
+		call.ws.release(keys, counts, words, list, dres, dv);
 	}
 	if (stats) {
 		stats->n_tris = nt; stats->n_views = n_views;
@@ -1025,8 +1065,7 @@ int rnb_mesh_visibility(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rn
 		stats->n_offscreen = n_class[MR_OFFSCREEN]; stats->n_small = n_class[MR_SMALL]; stats->n_large = n_class[MR_LARGE];
 		stats->n_pixels = n_pixels;
 		stats->n_faces_seen = hv.n_faces_seen; stats->n_faces_off_mask = hv.n_faces_off_mask;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD
@@ -1040,76 +1079,62 @@ int rnb_mesh_visibility_select(rnb_ctx* c, void* stream, const rnb_mesh* in, con
 	if (opt->abi_version != RNB_MESH_VISIBILITY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: options abi_version mismatch (expected RNB_MESH_VISIBILITY_ABI_VERSION)");
 	if (opt->unit != RNB_MESH_VISIBILITY_UNIT_COMPONENT && opt->unit != RNB_MESH_VISIBILITY_UNIT_FACE) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: unknown unit");
 	if (opt->rings > RNB_MESH_VISIBILITY_MAX_RINGS) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: rings must be 0 .. 64");
-	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: a reserved word of the options is not 0");
+	if (int rc = check_reserved("rnb_mesh_visibility_select", opt->reserved); rc != RNB_OK) return rc;
 	if (m.n_indices && !faces_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: faces_dev is null");
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
+	MeshCall call("rnb_mesh_visibility_select", c, stream);
+	const hipStream_t s = call.s;
 
 	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
-	MeshWorkspace ws;
 	MvResult hv;
 	std::memset(&hv, 0, sizeof(hv));
 	uint32_t nvo = 0, nto = 0;
 	rnb_mesh o;
 	if (nt) {
-		const uint32_t g_v = (nv + MV_WG - 1) / MV_WG, g_t = (nt + MV_WG - 1) / MV_WG; // (nv >= 1: check_mesh_input)
+		const uint32_t g_v = groups(nv), g_t = groups(nt);
 		const uint32_t* idx = m.indices;
 		uint32_t *used = nullptr, *flag = nullptr, *vmark = nullptr, *parent = nullptr, *vmap = nullptr, *scan = nullptr, *twg = nullptr;
 		MvResult* dv = nullptr;
-		if (!ws.alloc(&used, nv) || !ws.alloc(&flag, nt) || !ws.alloc(&vmark, nv) || !ws.alloc(&vmap, nv) || !ws.alloc(&twg, g_t) || !ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) ||
-		    !ws.alloc(&dv, 1) || (opt->unit == RNB_MESH_VISIBILITY_UNIT_COMPONENT && !ws.alloc(&parent, nv)))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility_select: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(nt) + " triangles");
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		if (!call.ws.alloc(&used, nv) || !call.ws.alloc(&flag, nt) || !call.ws.alloc(&vmark, nv) || !call.ws.alloc(&vmap, nv) || !call.ws.alloc(&twg, g_t) || !call.ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) ||
+		    !call.ws.alloc(&dv, 1) || (opt->unit == RNB_MESH_VISIBILITY_UNIT_COMPONENT && !call.ws.alloc(&parent, nv)))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(nt) + " triangles");
 		HIP_TRY(hipMemsetAsync(vmark, 0, (size_t)nv * 4, s));
 		HIP_TRY(hipMemcpyAsync(dv, &hv, sizeof(hv), hipMemcpyHostToDevice, s));
 		// 1. every index is range-checked before any is used as an address
-		hipLaunchKernelGGL(k_mesh_validate, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, nv, used, &dv->flags, MV_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hv.flags & MV_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_visibility_select: an index is out of range (>= n_verts)");
+		if (int rc = call.check_indices(m, used, &dv->flags); rc != RNB_OK) return rc;
 		// 2. candidates and seeds; the kept triangles
-		hipLaunchKernelGGL(k_mv_flags, dim3(g_t), dim3(MV_WG), 0, s, faces_dev, nt, opt->min_views_seen, opt->max_views_off_mask, flag, dv);
+		hipLaunchKernelGGL(k_mv_flags, dim3(g_t), dim3(MESH_WG), 0, s, faces_dev, nt, opt->min_views_seen, opt->max_views_off_mask, flag, dv);
 		if (opt->unit == RNB_MESH_VISIBILITY_UNIT_FACE) {
-			hipLaunchKernelGGL(k_mv_seeds_kept, dim3(g_t), dim3(MV_WG), 0, s, flag, nt);
+			hipLaunchKernelGGL(k_mv_seeds_kept, dim3(g_t), dim3(MESH_WG), 0, s, flag, nt);
 			for (uint32_t r = 0; r < opt->rings; ++r) { // (the marks of the earlier rings stay: their triangles are still marked)
-				hipLaunchKernelGGL(k_mv_ring_mark, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, vmark);
-				hipLaunchKernelGGL(k_mv_ring_grow, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, flag, (const uint32_t*)vmark);
+				hipLaunchKernelGGL(k_mv_ring_mark, dim3(g_t), dim3(MESH_WG), 0, s, idx, nt, (const uint32_t*)flag, vmark);
+				hipLaunchKernelGGL(k_mv_ring_grow, dim3(g_t), dim3(MESH_WG), 0, s, idx, nt, flag, (const uint32_t*)vmark);
 			}
 		} else { // the cleaner's labels: the root of a component is its smallest vertex
-			hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
-			hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(CL_WG), 0, s, idx, nt, parent);
-			hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(CL_WG), 0, s, parent, nv);
-			hipLaunchKernelGGL(k_mv_comp_seed, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, (const uint32_t*)parent, vmark);
-			hipLaunchKernelGGL(k_mv_comp_keep, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, flag, (const uint32_t*)parent, (const uint32_t*)vmark);
-			hipLaunchKernelGGL(k_mv_comp_count, dim3(g_v), dim3(MV_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, (const uint32_t*)vmark, nv, dv);
+			hipLaunchKernelGGL(k_cl_init, dim3(g_v), dim3(MESH_WG), 0, s, parent, nv);
+			hipLaunchKernelGGL(k_cl_hook, dim3(g_t), dim3(MESH_WG), 0, s, idx, nt, parent);
+			hipLaunchKernelGGL(k_cl_flatten, dim3(g_v), dim3(MESH_WG), 0, s, parent, nv);
+			hipLaunchKernelGGL(k_mv_comp_seed, dim3(g_t), dim3(MESH_WG), 0, s, idx, nt, (const uint32_t*)flag, (const uint32_t*)parent, vmark);
+			hipLaunchKernelGGL(k_mv_comp_keep, dim3(g_t), dim3(MESH_WG), 0, s, idx, nt, flag, (const uint32_t*)parent, (const uint32_t*)vmark);
+			hipLaunchKernelGGL(k_mv_comp_count, dim3(g_v), dim3(MESH_WG), 0, s, (const uint32_t*)parent, (const uint32_t*)used, (const uint32_t*)vmark, nv, dv);
 		}
 		HIP_TRY(hipGetLastError());
 		// 3. compaction: the kept vertices numbered (used's memory holds their flags), the kept triangles per workgroup
 		uint32_t* vkeep = used;
 		HIP_TRY(hipMemsetAsync(vkeep, 0, (size_t)nv * 4, s));
-		hipLaunchKernelGGL(k_mv_vflag, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, vkeep, kept_dev);
+		hipLaunchKernelGGL(k_mv_vflag, dim3(g_t), dim3(MESH_WG), 0, s, idx, nt, (const uint32_t*)flag, vkeep, kept_dev);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(vmap, vkeep, (size_t)nv * 4, hipMemcpyDeviceToDevice, s));
-		int rc = scan_exclusive(vmap, nv, s, &nvo, scan);
-		if (rc != RNB_OK) return rc;
-		if ((rc = count_and_scan(s, g_t, twg, scan, &nto, k_mv_tris<false>, idx, nt, (const uint32_t*)flag, (const uint32_t*)vmap, twg, (const uint32_t*)nullptr, (uint32_t*)nullptr)) != RNB_OK) return rc;
-		if (!alloc_mesh(ws, &o, nvo, nto, m.colors != nullptr, m.normals != nullptr)) return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility_select: hipMalloc failed for the output mesh");
-		hipLaunchKernelGGL(k_mv_verts, dim3(g_v), dim3(MV_WG), 0, s, (const uint32_t*)vkeep, (const uint32_t*)vmap, nv, (const float*)m.verts, (const float*)m.colors, (const float*)m.normals, o.verts, o.colors, o.normals);
-		hipLaunchKernelGGL(k_mv_tris<true>, dim3(g_t), dim3(MV_WG), 0, s, idx, nt, (const uint32_t*)flag, (const uint32_t*)vmap, (uint32_t*)nullptr, (const uint32_t*)twg, o.indices);
-		HIP_TRY(hipGetLastError());
+		if (int rc = call.compact(m, MvKeep{flag, vkeep}, vmap, twg, scan, &o, &nvo, &nto); rc != RNB_OK) return rc;
 		HIP_TRY(hipMemcpyAsync(&hv, dv, sizeof(hv), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(used); ws.release(flag); ws.release(vmark); ws.release(parent); ws.release(vmap); ws.release(scan); ws.release(twg); ws.release(dv);
-	} else if (!alloc_mesh(ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_visibility_select: hipMalloc failed for the output mesh");
-	hand_over(ws, o, out);
+		call.ws.release(used, flag, vmark, parent, vmap, scan, twg, dv);
+	} else if (int rc = call.alloc_like(m, &o, 0, 0); rc != RNB_OK)
+		return rc;
+	hand_over(call.ws, o, out);
 	if (stats) {
 		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
 		stats->n_seeds = hv.n_seeds; stats->n_candidates = hv.n_candidates; stats->n_components = hv.n_components; stats->n_components_kept = hv.n_components_kept;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD
@@ -1155,13 +1180,23 @@ int rnb_mesh_texture_layout(uint32_t n_tris, uint32_t size, uint32_t block, uint
 
 int rnb_mesh_texture_free(rnb_ctx* c, rnb_mesh_texture* tex) try {
 	if (!c || !tex) return fail(RNB_ERR_INVALID, "null argument");
-	if (tex->uv) (void)hipFree(tex->uv);
-	if (tex->albedo) (void)hipFree(tex->albedo);
-	if (tex->normal) (void)hipFree(tex->normal);
-	if (tex->position) (void)hipFree(tex->position);
-	std::memset(tex, 0, sizeof(*tex));
+	free_device(tex, {tex->uv, tex->albedo, tex->normal, tex->position});
 	return RNB_OK;
 } RNB_GUARD
+
+extern "C++" {
+namespace {
+// The atlas of rnb_mesh_texture_layout for nt triangles, for the baker and the projection (the layout's own failures).
+int make_atlas(uint32_t nt, uint32_t size, uint32_t block, MtAtlas* A) {
+	std::memset(A, 0, sizeof(*A));
+	uint32_t n_blocks = 0;
+	if (int rc = rnb_mesh_texture_layout(nt, size, block, &A->block, &A->bpr, &n_blocks); rc != RNB_OK) return rc;
+	A->size = size; A->n_tris = nt;
+	A->n_texels = n_blocks * A->block * A->block; // at most size * size = 2^26
+	return RNB_OK;
+}
+} // namespace
+} // extern "C++"
 
 int rnb_mesh_bake_texture(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const rnb_mesh_texture_options* opt, rnb_mesh_texture* out, rnb_mesh_texture_stats* stats) try {
 	if (stats) std::memset(stats, 0, sizeof(*stats));
@@ -1171,77 +1206,62 @@ int rnb_mesh_bake_texture(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const 
 	if (opt->size < RNB_MESH_TEXTURE_MIN_SIZE || opt->size > RNB_MESH_TEXTURE_MAX_SIZE) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: size must be 4 .. 8192");
 	if (opt->maps == 0 || (opt->maps & ~(RNB_MESH_TEXTURE_ALBEDO | RNB_MESH_TEXTURE_NORMAL | RNB_MESH_TEXTURE_POSITION)))
 		return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: maps must be a non-empty set of RNB_MESH_TEXTURE_ALBEDO, _NORMAL and _POSITION");
-	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: a reserved word of the options is not 0");
-	{
-		rnb_mesh unused;
-		if (int rc = check_mesh_input("rnb_mesh_bake_texture", mesh, &unused); rc != RNB_OK) return rc;
-	}
+	if (int rc = check_reserved("rnb_mesh_bake_texture", opt->reserved); rc != RNB_OK) return rc;
+	if (int rc = check_mesh_input("rnb_mesh_bake_texture", mesh); rc != RNB_OK) return rc;
 	const rnb_mesh m = *mesh;
 	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, S = opt->size;
 	MtAtlas A;
-	std::memset(&A, 0, sizeof(A));
-	uint32_t n_blocks = 0;
-	if (int rc = rnb_mesh_texture_layout(nt, S, opt->block, &A.block, &A.bpr, &n_blocks); rc != RNB_OK) return rc;
-	A.size = S; A.n_tris = nt;
-	A.n_texels = n_blocks * A.block * A.block; // at most S * S = 2^26
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c); // the side stream's optimizer launch writes the weights the network evaluations read
+	if (int rc = make_atlas(nt, S, opt->block, &A); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_bake_texture", c, stream);
+	const hipStream_t s = call.s;
 
-	MeshWorkspace ws;
 	const size_t n_pix = (size_t)S * S;
 	const bool network = (opt->maps & (RNB_MESH_TEXTURE_ALBEDO | RNB_MESH_TEXTURE_NORMAL)) != 0;
 	float* uv = nullptr;
 	f4* map[3] = {nullptr, nullptr, nullptr}; // albedo, normal, position
-	if (!ws.alloc(&uv, (size_t)nt * 6)) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for the UVs of " + std::to_string(nt) + " triangles");
+	if (!call.ws.alloc(&uv, (size_t)nt * 6)) return call.nomem("hipMalloc failed for the UVs of " + std::to_string(nt) + " triangles");
 	for (int k = 0; k < 3; ++k)
 		if (opt->maps & (1u << k)) {
-			if (!ws.alloc(&map[k], n_pix)) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for a map of " + std::to_string(S) + "^2 texels");
+			if (!call.ws.alloc(&map[k], n_pix)) return call.nomem("hipMalloc failed for a map of " + std::to_string(S) + "^2 texels");
 			HIP_TRY(hipMemsetAsync(map[k], 0, n_pix * sizeof(f4), s));
 		}
 	uint32_t n_batches = 0;
 	if (nt) {
-		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
-		uint32_t *used = nullptr, *dflags = nullptr, hflags = 0;
-		if (!ws.alloc(&used, nv) || !ws.alloc(&dflags, 1)) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		// 1. every index is range-checked before any is used as an address
+		uint32_t *used = nullptr, *dflags = nullptr;
+		if (!call.ws.alloc(&used, nv) || !call.ws.alloc(&dflags, 1)) return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
 		HIP_TRY(hipMemsetAsync(dflags, 0, 4, s));
-		hipLaunchKernelGGL(k_mesh_validate, dim3((nt + MT_WG - 1) / MT_WG), dim3(MT_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, dflags, MT_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hflags, dflags, 4, hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hflags & MT_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_bake_texture: an index is out of range (>= n_verts)");
-		ws.release(used); ws.release(dflags);
+		if (int rc = call.check_indices(m, used, dflags); rc != RNB_OK) return rc;
+		call.ws.release(used, dflags);
 		// 2. the texels, in batches: positions, the corners' UVs and network inputs, the network, the maps
 		const uint32_t per_launch = std::min<uint32_t>(opt->max_texels_in_flight ? opt->max_texels_in_flight : (1u << 20), RNB_MESH_TEXTURE_MAX_IN_FLIGHT);
 		const uint32_t batch = std::min(per_launch, A.n_texels);
 		float* coords = nullptr;
 		half_t* net = nullptr;
-		if (network && (!ws.alloc(&coords, (size_t)batch * 7) || !ws.alloc(&net, (size_t)batch * 16))) return fail(RNB_ERR_NOMEM, "rnb_mesh_bake_texture: hipMalloc failed for a batch of " + std::to_string(batch) + " texels");
+		if (network && (!call.ws.alloc(&coords, (size_t)batch * 7) || !call.ws.alloc(&net, (size_t)batch * 16))) return call.nomem("hipMalloc failed for a batch of " + std::to_string(batch) + " texels");
 		const float diag = c->aabb.mx - c->aabb.mn;
 		const bool inference = opt->use_inference_params != 0;
 		for (uint32_t w0 = 0; w0 < A.n_texels; w0 += batch) {
 			const uint32_t nb = std::min(batch, A.n_texels - w0);
-			hipLaunchKernelGGL(k_mt_texels, dim3((nb + MT_WG - 1) / MT_WG), dim3(MT_WG), 0, s, A, (const float*)m.verts, (const uint32_t*)m.indices, w0, nb, c->aabb.mn, diag, uv, map[2], coords);
+			hipLaunchKernelGGL(k_mt_texels, dim3(groups(nb)), dim3(MESH_WG), 0, s, A, (const float*)m.verts, (const uint32_t*)m.indices, w0, nb, c->aabb.mn, diag, uv, map[2], coords);
 			HIP_TRY(hipGetLastError());
 			if (!network) continue;
 			if (int rc = launch_forward(c, s, coords, nullptr, nb, net, inference); rc != RNB_OK) return rc;
-			hipLaunchKernelGGL(k_mt_maps, dim3((nb + MT_WG - 1) / MT_WG), dim3(MT_WG), 0, s, A, (const half_t*)net, w0, nb, map[0], map[1]);
+			hipLaunchKernelGGL(k_mt_maps, dim3(groups(nb)), dim3(MESH_WG), 0, s, A, (const half_t*)net, w0, nb, map[0], map[1]);
 			HIP_TRY(hipGetLastError());
 			++n_batches;
 		}
 		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(coords); ws.release(net);
+		call.ws.release(coords, net);
 	}
 	HIP_TRY(hipStreamSynchronize(s));
-	out->uv = (float*)ws.keep(uv);
-	out->albedo = (float*)ws.keep(map[0]); out->normal = (float*)ws.keep(map[1]); out->position = (float*)ws.keep(map[2]);
+	out->uv = (float*)call.ws.keep(uv);
+	out->albedo = (float*)call.ws.keep(map[0]); out->normal = (float*)call.ws.keep(map[1]); out->position = (float*)call.ws.keep(map[2]);
 	out->size = S; out->block = A.block; out->blocks_per_row = A.bpr; out->n_tris = nt;
 	if (stats) {
 		stats->n_texels = network ? A.n_texels : 0u;
 		stats->n_batches = n_batches;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD
@@ -1266,10 +1286,7 @@ int rnb_mesh_project_default_options(rnb_mesh_project_options* opt) try {
 
 int rnb_mesh_projection_free(rnb_ctx* c, rnb_mesh_projection* out) try {
 	if (!c || !out) return fail(RNB_ERR_INVALID, "null argument");
-	if (out->uv) (void)hipFree(out->uv);
-	if (out->color) (void)hipFree(out->color);
-	if (out->info) (void)hipFree(out->info);
-	std::memset(out, 0, sizeof(*out));
+	free_device(out, {out->uv, out->color, out->info});
 	return RNB_OK;
 } RNB_GUARD
 
@@ -1278,7 +1295,7 @@ namespace {
 constexpr bool MP_FILL_TALLIES = false; // the projection reads the keys of the fill and none of the visibility stage's tallies
 template <int FMT>
 void launch_mp_accumulate(hipStream_t s, const MrCamera& cam, const MpState& st, const unsigned long long* keys, const MpImage& img, const MpParams& P, MpResult* dres) {
-	hipLaunchKernelGGL(k_mp_accumulate<FMT>, dim3((st.n + MP_WG - 1) / MP_WG), dim3(MP_WG), 0, s, cam, st, keys, img, P, dres);
+	hipLaunchKernelGGL(k_mp_accumulate<FMT>, dim3(groups(st.n)), dim3(MESH_WG), 0, s, cam, st, keys, img, P, dres);
 }
 } // namespace
 } // extern "C++"
@@ -1296,9 +1313,8 @@ int rnb_mesh_project_views(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const
 	if (opt->weight_power > RNB_MESH_PROJECT_MAX_WEIGHT_POWER) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: weight_power must be 0 .. 8");
 	if (!(opt->min_cos >= 0.0f && opt->min_cos < 1.0f)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: min_cos must be in [0, 1)");
 	if (!(opt->depth_tolerance >= 0.0f) || !std::isfinite(opt->depth_tolerance)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: depth_tolerance must be finite and >= 0");
-	if (!(opt->near > 0.0f) || !std::isfinite(opt->near)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: near must be finite and > 0");
-	if (opt->cull > RNB_MESH_RASTER_CULL_FRONT) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: cull must be 0 (none), 1 (back) or 2 (front)");
-	for (uint32_t r : opt->reserved) if (r) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: a reserved word of the options is not 0");
+	if (int rc = check_near_cull("rnb_mesh_project_views", opt->near, opt->cull); rc != RNB_OK) return rc;
+	if (int rc = check_reserved("rnb_mesh_project_views", opt->reserved); rc != RNB_OK) return rc;
 	if (opt->fallback_dev && ((uintptr_t)opt->fallback_dev & 15u)) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: fallback_dev is not aligned to 16 bytes");
 	uint32_t max_pix = 0;
 	for (uint32_t v = 0; v < n_views; ++v) {
@@ -1312,32 +1328,23 @@ int rnb_mesh_project_views(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const
 		if (V.reserved) return fail(RNB_ERR_INVALID, who + " has a reserved word that is not 0");
 		max_pix = std::max(max_pix, V.view.width * V.view.height); // at most 2^28
 	}
-	{
-		rnb_mesh unused;
-		if (int rc = check_mesh_input("rnb_mesh_project_views", mesh, &unused); rc != RNB_OK) return rc;
-	}
+	if (int rc = check_mesh_input("rnb_mesh_project_views", mesh); rc != RNB_OK) return rc;
 	if (opt->normals == RNB_MESH_PROJECT_NORMALS_VERTEX && !mesh->normals) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: normals = VERTEX needs a mesh with normals");
 	const rnb_mesh m = *mesh;
 	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, S = opt->size;
 	MtAtlas A;
-	std::memset(&A, 0, sizeof(A));
-	uint32_t n_blocks = 0;
-	if (int rc = rnb_mesh_texture_layout(nt, S, opt->block, &A.block, &A.bpr, &n_blocks); rc != RNB_OK) return rc;
-	A.size = S; A.n_tris = nt;
-	A.n_texels = n_blocks * A.block * A.block; // at most S * S = 2^26
-	const auto t_begin = std::chrono::steady_clock::now();
-	hipStream_t s = as_stream(stream);
-	join_tail_host(c);
+	if (int rc = make_atlas(nt, S, opt->block, &A); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_project_views", c, stream);
+	const hipStream_t s = call.s;
 
-	MeshWorkspace ws;
 	const size_t n_pix = (size_t)S * S, n = A.n_texels;
 	float* uv = nullptr;
 	f4* color = nullptr;
 	mp_u2* info = nullptr;
 	MpResult hres;
 	std::memset(&hres, 0, sizeof(hres));
-	if (!ws.alloc(&uv, (size_t)nt * 6) || !ws.alloc(&color, n_pix) || !ws.alloc(&info, n_pix))
-		return fail(RNB_ERR_NOMEM, "rnb_mesh_project_views: hipMalloc failed for the maps of " + std::to_string(S) + "^2 texels and the UVs of " + std::to_string(nt) + " triangles");
+	if (!call.ws.alloc(&uv, (size_t)nt * 6) || !call.ws.alloc(&color, n_pix) || !call.ws.alloc(&info, n_pix))
+		return call.nomem("hipMalloc failed for the maps of " + std::to_string(S) + "^2 texels and the UVs of " + std::to_string(nt) + " triangles");
 	HIP_TRY(hipMemsetAsync(color, 0, n_pix * sizeof(f4), s));
 	HIP_TRY(hipMemsetAsync(info, 0, n_pix * sizeof(mp_u2), s));
 	if (nt) {
@@ -1349,21 +1356,16 @@ int rnb_mesh_project_views(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const
 		MpState st;
 		std::memset(&st, 0, sizeof(st));
 		st.n = A.n_texels;
-		if (!ws.alloc(&keys, max_pix) || !ws.alloc(&counts, max_pix) || !ws.alloc(&used, nv) || !ws.alloc(&dfill, 1) || !ws.alloc(&dres, 1) || !ws.alloc(&st.p, 3 * n) || !ws.alloc(&st.nrm, 3 * n) ||
-		    !ws.alloc(&st.acc, 4 * n) || !ws.alloc(&st.w_best, n) || !ws.alloc(&st.count, n) || !ws.alloc(&st.best, n))
-			return fail(RNB_ERR_NOMEM, "rnb_mesh_project_views: hipMalloc failed for the workspace of " + std::to_string(max_pix) + " pixels, " + std::to_string(n) + " texels and " + std::to_string(nv) + " vertices");
-		// 1. every index is range-checked before any is used as an address (nv >= 1: check_mesh_input)
-		HIP_TRY(hipMemsetAsync(used, 0, (size_t)nv * 4, s));
+		if (!call.ws.alloc(&keys, max_pix) || !call.ws.alloc(&counts, max_pix) || !call.ws.alloc(&used, nv) || !call.ws.alloc(&dfill, 1) || !call.ws.alloc(&dres, 1) || !call.ws.alloc(&st.p, 3 * n) || !call.ws.alloc(&st.nrm, 3 * n) ||
+		    !call.ws.alloc(&st.acc, 4 * n) || !call.ws.alloc(&st.w_best, n) || !call.ws.alloc(&st.count, n) || !call.ws.alloc(&st.best, n))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(max_pix) + " pixels, " + std::to_string(n) + " texels and " + std::to_string(nv) + " vertices");
+		// 1. every index is range-checked before any is used as an address
 		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
-		hipLaunchKernelGGL(k_mesh_validate, dim3((nt + MP_WG - 1) / MP_WG), dim3(MP_WG), 0, s, (const uint32_t*)m.indices, nt, nv, used, &dres->flags, MP_BAD_INDEX);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipStreamSynchronize(s));
-		if (hres.flags & MP_BAD_INDEX) return fail(RNB_ERR_INVALID, "rnb_mesh_project_views: an index is out of range (>= n_verts)");
-		ws.release(used);
+		if (int rc = call.check_indices(m, used, &dres->flags); rc != RNB_OK) return rc;
+		call.ws.release(used);
 		// 2. p and N of every texel, the accumulators cleared
-		const uint32_t g_w = (A.n_texels + MP_WG - 1) / MP_WG;
-		hipLaunchKernelGGL(k_mp_setup, dim3(g_w), dim3(MP_WG), 0, s, A, (const float*)m.verts, (const uint32_t*)m.indices, (const float*)m.normals, opt->normals, st);
+		const uint32_t g_w = groups(A.n_texels);
+		hipLaunchKernelGGL(k_mp_setup, dim3(g_w), dim3(MESH_WG), 0, s, A, (const float*)m.verts, (const uint32_t*)m.indices, (const float*)m.normals, opt->normals, st);
 		HIP_TRY(hipGetLastError());
 		// 3. view by view: the rasteriser's fill, then every texel against its keys and its image
 		MpParams P;
@@ -1372,14 +1374,10 @@ int rnb_mesh_project_views(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const
 		P.power = opt->weight_power; P.mode = opt->mode;
 		for (uint32_t v = 0; v < n_views; ++v) {
 			const rnb_mesh_project_view& V = views[v];
-			const uint32_t n_view_pix = V.view.width * V.view.height;
 			const MrCamera cam = raster_camera(&V.view, opt->near, opt->cull, RNB_MESH_RASTER_NORMALS_FACE);
 			MrResult hfill;
-			std::memset(&hfill, 0, sizeof(hfill));
-			HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)n_view_pix * 8, s));
-			HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_view_pix * 4, s));
-			HIP_TRY(hipMemcpyAsync(dfill, &hfill, sizeof(hfill), hipMemcpyHostToDevice, s));
-			if (int rc = raster_fill<MP_FILL_TALLIES>("rnb_mesh_project_views", ws, s, cam, M, keys, counts, dfill, &hfill, &list, &list_cap, MrTally{}); rc != RNB_OK) return rc;
+			if (int rc = raster_clear(s, cam, keys, counts, dfill, &hfill); rc != RNB_OK) return rc;
+			if (int rc = raster_fill<MP_FILL_TALLIES>("rnb_mesh_project_views", call, cam, M, keys, counts, dfill, &hfill, &list, &list_cap, MrTally{}); rc != RNB_OK) return rc;
 			const MpImage img{V.image_dev, V.image_width, V.image_height};
 			P.view = v;
 			if (V.format == RNB_MESH_PROJECT_FORMAT_F32) launch_mp_accumulate<RNB_MESH_PROJECT_FORMAT_F32>(s, cam, st, keys, img, P, dres);
@@ -1388,20 +1386,18 @@ int rnb_mesh_project_views(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const
 			HIP_TRY(hipGetLastError());
 		}
 		// 4. the result
-		hipLaunchKernelGGL(k_mp_finish, dim3(g_w), dim3(MP_WG), 0, s, A, st, (const f4*)opt->fallback_dev, uv, color, info, dres);
+		hipLaunchKernelGGL(k_mp_finish, dim3(g_w), dim3(MESH_WG), 0, s, A, st, (const f4*)opt->fallback_dev, uv, color, info, dres);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
-		ws.release(keys); ws.release(counts); ws.release(list); ws.release(dfill); ws.release(dres);
-		ws.release(st.p); ws.release(st.nrm); ws.release(st.acc); ws.release(st.w_best); ws.release(st.count); ws.release(st.best);
+		call.ws.release(keys, counts, list, dfill, dres, st.p, st.nrm, st.acc, st.w_best, st.count, st.best);
 	}
 	HIP_TRY(hipStreamSynchronize(s));
-	out->uv = (float*)ws.keep(uv); out->color = (float*)ws.keep(color); out->info = (uint32_t*)ws.keep(info);
+	out->uv = (float*)call.ws.keep(uv); out->color = (float*)call.ws.keep(color); out->info = (uint32_t*)call.ws.keep(info);
 	out->size = S; out->block = A.block; out->blocks_per_row = A.bpr; out->n_tris = nt;
 	if (stats) {
 		stats->n_texels = hres.n_texels; stats->n_textured = hres.n_textured; stats->n_pairs_tested = hres.n_tested; stats->n_occluded = hres.n_occluded;
-		stats->peak_workspace = ws.peak;
-		stats->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+		call.finish(stats);
 	}
 	return RNB_OK;
 } RNB_GUARD

@@ -23,9 +23,9 @@ struct McArgs {
 // of the two values. WRITE = false: per-workgroup counts; WRITE = true: positions + the edge -> vertex index grid [3][res^3]
 // (MESH_NONE: no vertex), numbered from wg_offset.
 template <bool WRITE>
-__global__ __launch_bounds__(MC_WG) void k_mc_verts(const McArgs a, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, float* __restrict__ verts, uint32_t* __restrict__ vidx) {
+__global__ __launch_bounds__(MESH_WG) void k_mc_verts(const McArgs a, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, float* __restrict__ verts, uint32_t* __restrict__ vidx) {
 	const uint64_t res2 = (uint64_t)a.rx * a.ry, res3 = res2 * a.rz;
-	const uint64_t idx = (uint64_t)blockIdx.x * MC_WG + threadIdx.x;
+	const uint64_t idx = (uint64_t)blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t cross = 0; // bit a: the edge from this point along axis a carries a vertex
 	float f0 = 0.f, f1[3] = {0.f, 0.f, 0.f};
 	uint32_t p[3] = {0, 0, 0};
@@ -57,10 +57,10 @@ __global__ __launch_bounds__(MC_WG) void k_mc_verts(const McArgs a, uint32_t* __
 
 // gen_faces: the cell whose lowest corner is this lattice point.
 template <bool WRITE>
-__global__ __launch_bounds__(MC_WG) void k_mc_faces(const McArgs a, const McTable* __restrict__ T, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset,
+__global__ __launch_bounds__(MESH_WG) void k_mc_faces(const McArgs a, const McTable* __restrict__ T, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset,
                                                     const uint32_t* __restrict__ vidx, uint32_t* __restrict__ indices) {
 	const uint64_t res2 = (uint64_t)a.rx * a.ry, res3 = res2 * a.rz;
-	const uint64_t idx = (uint64_t)blockIdx.x * MC_WG + threadIdx.x;
+	const uint64_t idx = (uint64_t)blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t mask = 0;
 	if (idx < res3) {
 		const uint32_t x = (uint32_t)(idx % a.rx), y = (uint32_t)((idx / a.rx) % a.ry), z = (uint32_t)(idx / res2);

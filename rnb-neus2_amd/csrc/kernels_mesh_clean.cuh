@@ -6,8 +6,8 @@
 //   k_cl_roots / k_cl_relabel   roots of used vertices -> component ids by an exclusive sum (ascending label = table order); parent[] becomes the component id per vertex
 //   k_cl_sums<TRI>              per-component fixed-point area / volume / triangle count (TRI) or vertex count, summed in the wavefront and the workgroup first
 //   k_cl_select                 one workgroup: the component of the greatest area, the kept / flip flag of every component, the totals of the statistics
-//   k_cl_vflag, k_cl_verts      kept vertices: flags -> exclusive sum = the new numbering -> positions and attributes copied
-//   k_cl_tris<WRITE>            kept triangles: per-workgroup counts -> exclusive sum -> renumbered indices, second and third swapped where the component is flipped
+//   k_cl_vflag, ClKeep          kept vertices: flags -> exclusive sum = the new numbering; the predicate of the shared compaction (k_compact_verts, k_compact_tris<WRITE> of
+//                               mesh_common.cuh): renumbered indices, second and third swapped where the component is flipped
 // Why the labels do not depend on the schedule: parent[x] <= x always, a compare-and-swap only ever replaces a root r by a smaller root, and a non-root never becomes
 // a root again; so when k_cl_hook has finished, the root of a component is its smallest vertex. Path halving only writes an ancestor into a non-root's parent.
 // Everything that numbers a vertex or a triangle is a prefix sum, as in kernels_mesh.cuh (mesh_common.cuh). Vector loads, stores and atomics only.
@@ -17,8 +17,7 @@
 
 namespace rnb {
 
-constexpr uint32_t CL_WG = 256;
-constexpr uint32_t CL_BAD_INDEX = 1u, CL_BAD_TERM = 2u; // bits of ClResult::flags
+constexpr uint32_t CL_BAD_TERM = 2u; // bit of ClResult::flags, beside MESH_BAD_INDEX
 
 struct ClResult { // written by the kernels, read by the driver
 	uint32_t flags;     // first: k_mesh_validate is handed its address
@@ -52,19 +51,19 @@ __device__ __forceinline__ void cl_unite(uint32_t* parent, uint32_t u, uint32_t 
 	}
 }
 
-__global__ __launch_bounds__(CL_WG) void k_cl_init(uint32_t* __restrict__ parent, const uint32_t nv) {
-	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_cl_init(uint32_t* __restrict__ parent, const uint32_t nv) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	if (v < nv) parent[v] = v;
 }
-__global__ __launch_bounds__(CL_WG) void k_cl_hook(const uint32_t* __restrict__ idx, const uint32_t nt, uint32_t* parent) {
-	const uint32_t t = blockIdx.x * CL_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_cl_hook(const uint32_t* __restrict__ idx, const uint32_t nt, uint32_t* parent) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t >= nt) return;
 	const uint32_t a = idx[3 * (size_t)t], b = idx[3 * (size_t)t + 1], c = idx[3 * (size_t)t + 2];
 	cl_unite(parent, a, b);
 	cl_unite(parent, b, c);
 }
-__global__ __launch_bounds__(CL_WG) void k_cl_flatten(uint32_t* parent, const uint32_t nv) {
-	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_cl_flatten(uint32_t* parent, const uint32_t nv) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	if (v >= nv) return;
 	// read-only walk: a thread writes its own entry and nothing else, so the last value an entry receives is its root (a halving store of another thread could put a
 	// mere ancestor back after it). Entries other threads have already flattened shorten the walk. The roots do not change any more: k_cl_hook has finished.
@@ -76,13 +75,13 @@ __global__ __launch_bounds__(CL_WG) void k_cl_flatten(uint32_t* parent, const ui
 	}
 	if (x != v) cl_store(parent + v, x);
 }
-__global__ __launch_bounds__(CL_WG) void k_cl_roots(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ used, uint32_t* __restrict__ cid, const uint32_t nv) {
-	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_cl_roots(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ used, uint32_t* __restrict__ cid, const uint32_t nv) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	if (v < nv) cid[v] = (used[v] && parent[v] == v) ? 1u : 0u;
 }
 // parent[v] <- component id of v (MESH_NONE for a vertex no triangle uses); the root writes its label into the table. cid holds the exclusive sums of k_cl_roots' flags.
-__global__ __launch_bounds__(CL_WG) void k_cl_relabel(uint32_t* __restrict__ parent, const uint32_t* __restrict__ used, const uint32_t* __restrict__ cid, rnb_mesh_component* __restrict__ table, const uint32_t nv) {
-	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_cl_relabel(uint32_t* __restrict__ parent, const uint32_t* __restrict__ used, const uint32_t* __restrict__ cid, rnb_mesh_component* __restrict__ table, const uint32_t nv) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	if (v >= nv) return;
 	if (!used[v]) { parent[v] = MESH_NONE; return; }
 	const uint32_t r = parent[v], c = cid[r]; // (a thread writes its own entry only and reads its own entry and cid: no other thread's write is observed)
@@ -150,9 +149,9 @@ __device__ __forceinline__ void cl_accumulate(rnb_mesh_component* __restrict__ t
 
 // comp: component id per vertex (k_cl_relabel). TRI: n = triangles; else n = vertices.
 template <bool TRI>
-__global__ __launch_bounds__(CL_WG) void k_cl_sums(const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t n, const uint32_t* __restrict__ comp,
+__global__ __launch_bounds__(MESH_WG) void k_cl_sums(const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t n, const uint32_t* __restrict__ comp,
                                                   rnb_mesh_component* __restrict__ table, ClResult* __restrict__ res) {
-	const uint32_t i = blockIdx.x * CL_WG + threadIdx.x;
+	const uint32_t i = blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t c = MESH_NONE;
 	long long area = 0, vol = 0;
 	bool valid = false;
@@ -213,45 +212,19 @@ __global__ __launch_bounds__(1024) void k_cl_select(rnb_mesh_component* __restri
 	if (t == 0) { res->best = best; res->n_kept = s_id[0]; res->area_in = area_in; res->area_out = s_sum[0]; }
 }
 
-__global__ __launch_bounds__(CL_WG) void k_cl_vflag(const uint32_t* __restrict__ comp, const uint32_t* __restrict__ cflags, uint32_t* __restrict__ vmap, const uint32_t nv) {
-	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_cl_vflag(const uint32_t* __restrict__ comp, const uint32_t* __restrict__ cflags, uint32_t* __restrict__ vmap, const uint32_t nv) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	if (v >= nv) return;
 	const uint32_t c = comp[v];
 	vmap[v] = (c != MESH_NONE && (cflags[c] & 1u)) ? 1u : 0u;
 }
-// vmap: exclusive sums of k_cl_vflag's flags = the new index of a kept vertex
-__global__ __launch_bounds__(CL_WG) void k_cl_verts(const uint32_t* __restrict__ comp, const uint32_t* __restrict__ cflags, const uint32_t* __restrict__ vmap, const uint32_t nv,
-                                                   const float* __restrict__ verts, const float* __restrict__ colors, const float* __restrict__ normals,
-                                                   float* __restrict__ overts, float* __restrict__ ocolors, float* __restrict__ onormals) {
-	const uint32_t v = blockIdx.x * CL_WG + threadIdx.x;
-	if (v >= nv) return;
-	const uint32_t c = comp[v];
-	if (c == MESH_NONE || !(cflags[c] & 1u)) return;
-	const size_t s = 3 * (size_t)v, d = 3 * (size_t)vmap[v];
-	overts[d] = verts[s]; overts[d + 1] = verts[s + 1]; overts[d + 2] = verts[s + 2];
-	if (colors) { ocolors[d] = colors[s]; ocolors[d + 1] = colors[s + 1]; ocolors[d + 2] = colors[s + 2]; }
-	if (normals) { onormals[d] = normals[s]; onormals[d + 1] = normals[s + 1]; onormals[d + 2] = normals[s + 2]; }
-}
-// WRITE = false: kept triangles per workgroup; WRITE = true: their renumbered indices from wg_offset (in triangles) on, in input order.
-template <bool WRITE>
-__global__ __launch_bounds__(CL_WG) void k_cl_tris(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ comp, const uint32_t* __restrict__ cflags,
-                                                  const uint32_t* __restrict__ vmap, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, uint32_t* __restrict__ oidx) {
-	const uint32_t t = blockIdx.x * CL_WG + threadIdx.x;
-	uint32_t a = 0, b = 0, c = 0, f = 0;
-	if (t < nt) {
-		a = idx[3 * (size_t)t]; b = idx[3 * (size_t)t + 1]; c = idx[3 * (size_t)t + 2];
-		f = cflags[comp[a]];
-	}
-	uint32_t total;
-	const uint32_t local = wg_exclusive_256(f & 1u, &total);
-	if (!WRITE) {
-		if (threadIdx.x == 0) wg_count[blockIdx.x] = total;
-		return;
-	}
-	if (!(f & 1u)) return;
-	const size_t d = 3 * ((size_t)wg_offset[blockIdx.x] + local);
-	const bool flip = (f & 2u) != 0;
-	oidx[d] = vmap[a]; oidx[d + 1] = vmap[flip ? c : b]; oidx[d + 2] = vmap[flip ? b : c];
-}
+// What MeshCall::compact keeps of the cleaner's input (k_compact_verts, k_compact_tris of mesh_common.cuh): the vertices and triangles of the kept components, the
+// triangles of a flipped component with their second and third corner swapped.
+struct ClKeep {
+	const uint32_t* comp;   // component id per vertex (k_cl_relabel)
+	const uint32_t* cflags; // kept | flip << 1 per component (k_cl_select)
+	__device__ __forceinline__ bool vertex(const uint32_t v) const { const uint32_t c = comp[v]; return c != MESH_NONE && (cflags[c] & 1u); }
+	__device__ __forceinline__ uint32_t triangle(const uint32_t* __restrict__ idx, const uint32_t t) const { return cflags[comp[idx[3 * (size_t)t]]]; }
+};
 
 } // namespace rnb

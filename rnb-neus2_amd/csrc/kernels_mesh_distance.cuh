@@ -16,8 +16,7 @@
 
 namespace rnb {
 
-constexpr uint32_t MD_WG = 256;
-constexpr uint32_t MD_BAD_INDEX_FROM = 1u, MD_BAD_INDEX_TO = 2u, MD_BAD_VALUE = 4u, MD_BAD_TERM = 8u; // bits of MdResult::flags
+constexpr uint32_t MD_BAD_INDEX_TO = 2u, MD_BAD_VALUE = 4u, MD_BAD_TERM = 8u; // bits of MdResult::flags, beside MESH_BAD_INDEX (an index of from)
 constexpr int MD_NSUM = 3 + RNB_MESH_DISTANCE_MAX_TAUS;                                                 // S(w), S(w d'), S(w d'^2), within[4]
 
 struct MdResult { // written by the kernels, read by the driver
@@ -108,8 +107,8 @@ __device__ __forceinline__ double md_point_triangle(const double p[3], const dou
 
 // One thread per vertex. Counts the used ones and checks them; BOX: min / max of their images into res->bmin / bmax (reduced over the wavefront first).
 template <bool BOX>
-__global__ __launch_bounds__(MD_WG) void k_md_verts(const float* __restrict__ verts, const uint32_t nv, const uint32_t* __restrict__ used, MdResult* __restrict__ res) {
-	const uint32_t v = blockIdx.x * MD_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_md_verts(const float* __restrict__ verts, const uint32_t nv, const uint32_t* __restrict__ used, MdResult* __restrict__ res) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	const bool live = v < nv && used[v] != 0u;
 	uint32_t mn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, mx[3] = {0u, 0u, 0u};
 	bool bad = false;
@@ -144,8 +143,8 @@ __global__ __launch_bounds__(MD_WG) void k_md_verts(const float* __restrict__ ve
 	}
 }
 
-__global__ __launch_bounds__(MD_WG) void k_md_degenerate(const MdMesh B, MdResult* __restrict__ res) {
-	const uint32_t t = blockIdx.x * MD_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_md_degenerate(const MdMesh B, MdResult* __restrict__ res) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	bool deg = false;
 	if (t < B.nt) {
 		double a[3], b[3], c[3];
@@ -160,8 +159,8 @@ __global__ __launch_bounds__(MD_WG) void k_md_degenerate(const MdMesh B, MdResul
 // counter; the list is complete only if res->n_large <= RNB_MESH_DISTANCE_MAX_LARGE). FILL = true: cursor[cell] (in: the exclusive sums of the counts) hands out the slots
 // of entries[]; afterwards cursor[cell] is the end of the cell's list.
 template <bool FILL>
-__global__ __launch_bounds__(MD_WG) void k_md_register(const MdGrid g, const MdMesh B, uint32_t* __restrict__ cells, uint32_t* __restrict__ entries, uint32_t* __restrict__ large, MdResult* __restrict__ res) {
-	const uint32_t t = blockIdx.x * MD_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_md_register(const MdGrid g, const MdMesh B, uint32_t* __restrict__ cells, uint32_t* __restrict__ entries, uint32_t* __restrict__ large, MdResult* __restrict__ res) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	long long mine = 0;
 	if (t < B.nt) {
 		double a[3], b[3], c[3];
@@ -268,10 +267,10 @@ __device__ __forceinline__ bool md_q(const double term, unsigned long long* lo, 
 // VERTS = true: thread i is vertex i of A (samples (a)): vert_dist / vert_nearest, the maximum, n_verts_beyond. VERTS = false: thread i is sub-centroid i % n^2 of triangle
 // i / n^2 of A (samples (b)): the sums, the maximum, the counts.
 template <bool VERTS>
-__global__ __launch_bounds__(MD_WG) void k_md_query(const MdGrid g, const MdQuery Q, const MdMesh A, const uint32_t* __restrict__ used, const MdSearch S, float* __restrict__ vert_dist,
+__global__ __launch_bounds__(MESH_WG) void k_md_query(const MdGrid g, const MdQuery Q, const MdMesh A, const uint32_t* __restrict__ used, const MdSearch S, float* __restrict__ vert_dist,
                                                    uint32_t* __restrict__ vert_nearest, MdResult* __restrict__ res) {
 #pragma clang fp contract(off)
-	const unsigned long long i = (unsigned long long)blockIdx.x * MD_WG + threadIdx.x;
+	const unsigned long long i = (unsigned long long)blockIdx.x * MESH_WG + threadIdx.x;
 	const uint32_t n = 1u << Q.level, nn = n * n;
 	bool sample = false, degenerate = false;
 	double p[3] = {0.0, 0.0, 0.0}, w = 0.0;

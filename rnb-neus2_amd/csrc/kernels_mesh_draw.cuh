@@ -77,11 +77,11 @@ __device__ __forceinline__ bool draw_sample(const float* __restrict__ map, const
 }
 
 template <int FILTER, bool COLOR, bool NORMAL, bool VEC>
-__global__ __launch_bounds__(MR_WG) void k_md_resolve(const MrCamera cam, const MrMesh m, const DrawTexture tex, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ counts,
+__global__ __launch_bounds__(MESH_WG) void k_md_resolve(const MrCamera cam, const MrMesh m, const DrawTexture tex, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ counts,
                                                       float* __restrict__ out, uint32_t* __restrict__ faces, MrResult* __restrict__ res, DrawResult* __restrict__ dres) {
 #pragma clang fp contract(off)
-	__shared__ __attribute__((aligned(16))) float tile[MR_WG * RNB_MESH_RASTER_CHANNELS];
-	const uint32_t n_pix = cam.w * cam.h, first = blockIdx.x * MR_WG, p = first + threadIdx.x;
+	__shared__ __attribute__((aligned(16))) float tile[MESH_WG * RNB_MESH_RASTER_CHANNELS];
+	const uint32_t n_pix = cam.w * cam.h, first = blockIdx.x * MESH_WG, p = first + threadIdx.x;
 	float ch[RNB_MESH_RASTER_CHANNELS];
 #pragma unroll
 	for (uint32_t k = 0; k < RNB_MESH_RASTER_CHANNELS; ++k) ch[k] = 0.0f;
@@ -169,14 +169,14 @@ __global__ __launch_bounds__(MR_WG) void k_md_resolve(const MrCamera cam, const 
 #pragma unroll
 	for (uint32_t k = 0; k < RNB_MESH_RASTER_CHANNELS; ++k) tile[threadIdx.x * RNB_MESH_RASTER_CHANNELS + k] = ch[k];
 	__syncthreads();
-	const uint32_t n_here = min(MR_WG, n_pix - first) * RNB_MESH_RASTER_CHANNELS; // floats of this workgroup (first < n_pix: the grid is ceil(n_pix / MR_WG))
+	const uint32_t n_here = min(MESH_WG, n_pix - first) * RNB_MESH_RASTER_CHANNELS; // floats of this workgroup (first < n_pix: the grid is ceil(n_pix / MESH_WG))
 	float* dst = out + (size_t)first * RNB_MESH_RASTER_CHANNELS;
 	if (VEC) {
 		const uint32_t n4 = n_here / 4u;
-		for (uint32_t q = threadIdx.x; q < n4; q += MR_WG) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(tile)[q];
-		for (uint32_t q = n4 * 4u + threadIdx.x; q < n_here; q += MR_WG) dst[q] = tile[q];
+		for (uint32_t q = threadIdx.x; q < n4; q += MESH_WG) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(tile)[q];
+		for (uint32_t q = n4 * 4u + threadIdx.x; q < n_here; q += MESH_WG) dst[q] = tile[q];
 	} else {
-		for (uint32_t q = threadIdx.x; q < n_here; q += MR_WG) dst[q] = tile[q];
+		for (uint32_t q = threadIdx.x; q < n_here; q += MESH_WG) dst[q] = tile[q];
 	}
 }
 

@@ -16,8 +16,6 @@
 
 namespace rnb {
 
-constexpr uint32_t MP_WG = 256;
-constexpr uint32_t MP_BAD_INDEX = 1u; // bit of MpResult::flags
 
 struct MpResult { // written by the kernels, read by the driver
 	uint32_t flags, pad; // first: k_mesh_validate is handed its address
@@ -42,10 +40,10 @@ typedef uint32_t mp_u2 __attribute__((ext_vector_type(2)));
 typedef unsigned short mp_us4 __attribute__((ext_vector_type(4)));
 typedef unsigned char mp_uc4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(MP_WG) void k_mp_setup(const MtAtlas A, const float* __restrict__ verts, const uint32_t* __restrict__ idx, const float* __restrict__ vnormals, const uint32_t normals,
+__global__ __launch_bounds__(MESH_WG) void k_mp_setup(const MtAtlas A, const float* __restrict__ verts, const uint32_t* __restrict__ idx, const float* __restrict__ vnormals, const uint32_t normals,
                                                     const MpState st) {
 #pragma clang fp contract(off)
-	const uint32_t w = blockIdx.x * MP_WG + threadIdx.x;
+	const uint32_t w = blockIdx.x * MESH_WG + threadIdx.x;
 	if (w >= st.n) return;
 	const size_t n = st.n;
 	float p[3] = {0.f, 0.f, 0.f};
@@ -150,9 +148,9 @@ __device__ __forceinline__ uint32_t mp_view(const MrCamera& cam, const MpState& 
 }
 
 template <int FMT>
-__global__ __launch_bounds__(MP_WG) void k_mp_accumulate(const MrCamera cam, const MpState st, const unsigned long long* __restrict__ keys, const MpImage img, const MpParams P,
+__global__ __launch_bounds__(MESH_WG) void k_mp_accumulate(const MrCamera cam, const MpState st, const unsigned long long* __restrict__ keys, const MpImage img, const MpParams P,
                                                          MpResult* __restrict__ res) {
-	const uint32_t w = blockIdx.x * MP_WG + threadIdx.x;
+	const uint32_t w = blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t code = 0u;
 	if (w < st.n) {
 		const size_t n = st.n;
@@ -170,10 +168,10 @@ __global__ __launch_bounds__(MP_WG) void k_mp_accumulate(const MrCamera cam, con
 }
 
 // P6. color and info are zero on entry (the texels no triangle owns stay so); fallback: float[S][S][4] or null.
-__global__ __launch_bounds__(MP_WG) void k_mp_finish(const MtAtlas A, const MpState st, const f4* __restrict__ fallback, float* __restrict__ uv, f4* __restrict__ color, mp_u2* __restrict__ info,
+__global__ __launch_bounds__(MESH_WG) void k_mp_finish(const MtAtlas A, const MpState st, const f4* __restrict__ fallback, float* __restrict__ uv, f4* __restrict__ color, mp_u2* __restrict__ info,
                                                      MpResult* __restrict__ res) {
 #pragma clang fp contract(off)
-	const uint32_t w = blockIdx.x * MP_WG + threadIdx.x;
+	const uint32_t w = blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t owned = 0u, textured = 0u;
 	MtTexel t;
 	if (w < st.n && mt_texel(A, w, t)) {

@@ -18,8 +18,6 @@
 
 namespace rnb {
 
-constexpr uint32_t MR_WG = 256;
-constexpr uint32_t MR_BAD_INDEX = 1u; // bit of MrResult::flags
 enum : uint32_t { MR_BEHIND = 0, MR_OUT_OF_RANGE, MR_DEGENERATE, MR_CULLED, MR_OFFSCREEN, MR_SMALL, MR_LARGE, MR_NCLASS };
 
 struct MrResult { // written by the kernels, read by the driver
@@ -166,9 +164,9 @@ __device__ __forceinline__ uint32_t mr_fragment(const MrTri& T, const uint32_t t
 }
 
 template <bool LIST, bool VIS>
-__global__ __launch_bounds__(MR_WG) void k_mr_bin(const MrCamera cam, const MrMesh m, unsigned long long* __restrict__ keys, uint32_t* __restrict__ counts, uint32_t* __restrict__ list,
+__global__ __launch_bounds__(MESH_WG) void k_mr_bin(const MrCamera cam, const MrMesh m, unsigned long long* __restrict__ keys, uint32_t* __restrict__ counts, uint32_t* __restrict__ list,
                                                   const uint32_t list_len, MrResult* __restrict__ res, const MrTally y) {
-	const uint32_t t = blockIdx.x * MR_WG + threadIdx.x;
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	MrTri T;
 	const uint32_t cls = t < m.nt ? mr_setup(cam, m, t, &T) : (uint32_t)MR_NCLASS;
 	if (LIST) {
@@ -195,9 +193,9 @@ __global__ __launch_bounds__(MR_WG) void k_mr_bin(const MrCamera cam, const MrMe
 }
 
 template <bool VIS>
-__global__ __launch_bounds__(MR_WG) void k_mr_fill_large(const MrCamera cam, const MrMesh m, const uint32_t* __restrict__ list, const uint32_t list_len, unsigned long long* __restrict__ keys,
+__global__ __launch_bounds__(MESH_WG) void k_mr_fill_large(const MrCamera cam, const MrMesh m, const uint32_t* __restrict__ list, const uint32_t list_len, unsigned long long* __restrict__ keys,
                                                          uint32_t* __restrict__ counts, const MrTally y) {
-	const uint32_t entry = blockIdx.x * (MR_WG / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+	const uint32_t entry = blockIdx.x * (MESH_WG / 64u) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
 	if (entry >= list_len) return;
 	const uint32_t t = list[entry];
 	if (t >= m.nt) return; // (never: the list holds what k_mr_bin<true> wrote)
@@ -216,11 +214,11 @@ __global__ __launch_bounds__(MR_WG) void k_mr_fill_large(const MrCamera cam, con
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(MR_WG) void k_mr_resolve(const MrCamera cam, const MrMesh m, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ counts, float* __restrict__ out,
+__global__ __launch_bounds__(MESH_WG) void k_mr_resolve(const MrCamera cam, const MrMesh m, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ counts, float* __restrict__ out,
                                                       uint32_t* __restrict__ faces, MrResult* __restrict__ res) {
 #pragma clang fp contract(off)
-	__shared__ __attribute__((aligned(16))) float tile[MR_WG * RNB_MESH_RASTER_CHANNELS];
-	const uint32_t n_pix = cam.w * cam.h, first = blockIdx.x * MR_WG, p = first + threadIdx.x;
+	__shared__ __attribute__((aligned(16))) float tile[MESH_WG * RNB_MESH_RASTER_CHANNELS];
+	const uint32_t n_pix = cam.w * cam.h, first = blockIdx.x * MESH_WG, p = first + threadIdx.x;
 	float ch[RNB_MESH_RASTER_CHANNELS];
 #pragma unroll
 	for (uint32_t k = 0; k < RNB_MESH_RASTER_CHANNELS; ++k) ch[k] = 0.0f;
@@ -282,14 +280,14 @@ __global__ __launch_bounds__(MR_WG) void k_mr_resolve(const MrCamera cam, const 
 #pragma unroll
 	for (uint32_t k = 0; k < RNB_MESH_RASTER_CHANNELS; ++k) tile[threadIdx.x * RNB_MESH_RASTER_CHANNELS + k] = ch[k];
 	__syncthreads();
-	const uint32_t n_here = min(MR_WG, n_pix - first) * RNB_MESH_RASTER_CHANNELS; // floats of this workgroup (first < n_pix: the grid is ceil(n_pix / MR_WG))
+	const uint32_t n_here = min(MESH_WG, n_pix - first) * RNB_MESH_RASTER_CHANNELS; // floats of this workgroup (first < n_pix: the grid is ceil(n_pix / MESH_WG))
 	float* dst = out + (size_t)first * RNB_MESH_RASTER_CHANNELS;
 	if (VEC) {
 		const uint32_t n4 = n_here / 4u;
-		for (uint32_t q = threadIdx.x; q < n4; q += MR_WG) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(tile)[q];
-		for (uint32_t q = n4 * 4u + threadIdx.x; q < n_here; q += MR_WG) dst[q] = tile[q];
+		for (uint32_t q = threadIdx.x; q < n4; q += MESH_WG) reinterpret_cast<float4*>(dst)[q] = reinterpret_cast<const float4*>(tile)[q];
+		for (uint32_t q = n4 * 4u + threadIdx.x; q < n_here; q += MESH_WG) dst[q] = tile[q];
 	} else {
-		for (uint32_t q = threadIdx.x; q < n_here; q += MR_WG) dst[q] = tile[q];
+		for (uint32_t q = threadIdx.x; q < n_here; q += MESH_WG) dst[q] = tile[q];
 	}
 }
 

@@ -17,8 +17,7 @@
 
 namespace rnb {
 
-constexpr uint32_t SP_WG = 256;
-constexpr uint32_t SP_BAD_INDEX = 1u, SP_BAD_VALUE = 2u, SP_BAD_TERM = 4u; // bits of SpResult::flags
+constexpr uint32_t SP_BAD_VALUE = 2u, SP_BAD_TERM = 4u; // bits of SpResult::flags, beside MESH_BAD_INDEX
 // the record of a cluster: SP_NSUM 64-bit sums
 constexpr uint32_t SP_A = 0, SP_B = 6, SP_COUNT = 9, SP_X = 10, SP_COL = 13, SP_NRM = 16, SP_NSUM = 19;
 
@@ -83,9 +82,9 @@ __device__ __forceinline__ void sp_accumulate(long long* __restrict__ sums, cons
 }
 
 // vkey[v] = the key of a used vertex (< 2^30: RNB_MESH_SIMPLIFY_MAX_CELLS), MESH_NONE otherwise; bits: one per cell
-__global__ __launch_bounds__(SP_WG) void k_sp_cells(const SpGrid g, const float* __restrict__ verts, const float* __restrict__ colors, const float* __restrict__ normals, const uint32_t nv,
+__global__ __launch_bounds__(MESH_WG) void k_sp_cells(const SpGrid g, const float* __restrict__ verts, const float* __restrict__ colors, const float* __restrict__ normals, const uint32_t nv,
                                                    const uint32_t* __restrict__ used, uint32_t* __restrict__ vkey, uint32_t* __restrict__ bits, SpResult* __restrict__ res) {
-	const uint32_t v = blockIdx.x * SP_WG + threadIdx.x;
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	if (v >= nv) return;
 	uint32_t key = MESH_NONE;
 	if (used[v]) {
@@ -100,16 +99,16 @@ __global__ __launch_bounds__(SP_WG) void k_sp_cells(const SpGrid g, const float*
 	}
 	vkey[v] = key;
 }
-__global__ __launch_bounds__(SP_WG) void k_sp_popc(const uint32_t* __restrict__ bits, uint32_t* __restrict__ rank, const uint32_t n_words) {
-	const uint32_t w = blockIdx.x * SP_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_sp_popc(const uint32_t* __restrict__ bits, uint32_t* __restrict__ rank, const uint32_t n_words) {
+	const uint32_t w = blockIdx.x * MESH_WG + threadIdx.x;
 	if (w < n_words) rank[w] = __popc(bits[w]);
 }
 // vcl (in) the key of the vertex, (out) its cluster id; rank: the exclusive sums of k_sp_popc's counts
-__global__ __launch_bounds__(SP_WG) void k_sp_members(const SpGrid g, const float* __restrict__ verts, const float* __restrict__ colors, const float* __restrict__ normals, const uint32_t nv,
+__global__ __launch_bounds__(MESH_WG) void k_sp_members(const SpGrid g, const float* __restrict__ verts, const float* __restrict__ colors, const float* __restrict__ normals, const uint32_t nv,
                                                      const uint32_t* __restrict__ bits, const uint32_t* __restrict__ rank, uint32_t* __restrict__ vcl, uint32_t* __restrict__ ckey,
                                                      long long* __restrict__ sums, SpResult* __restrict__ res) {
 #pragma clang fp contract(off)
-	const uint32_t v = blockIdx.x * SP_WG + threadIdx.x;
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t c = MESH_NONE;
 	long long q[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // count, x, colour, normal
 	const uint32_t key = v < nv ? vcl[v] : MESH_NONE;
@@ -157,10 +156,10 @@ __device__ __forceinline__ bool sp_quadric_terms(const double a[3], const double
 	if (!ok) *bad = true;
 	return true;
 }
-__global__ __launch_bounds__(SP_WG) void k_sp_quadric(const SpGrid g, const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ vcl,
+__global__ __launch_bounds__(MESH_WG) void k_sp_quadric(const SpGrid g, const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ vcl,
                                                      long long* __restrict__ sums, SpResult* __restrict__ res) {
 #pragma clang fp contract(off)
-	const uint32_t t = blockIdx.x * SP_WG + threadIdx.x;
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	const bool live = t < nt;
 	uint32_t cl[3] = {MESH_NONE, MESH_NONE, MESH_NONE};
 	double p[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, ctr[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
@@ -193,9 +192,9 @@ __global__ __launch_bounds__(SP_WG) void k_sp_quadric(const SpGrid g, const floa
 // vcl: cluster id per vertex. WRITE = false: surviving triangles per workgroup, cused[c] = 1 for the clusters they use; WRITE = true: their indices (cmap: the
 // exclusive sums of cused = the output vertex of a cluster) from wg_offset (in triangles) on, in input order.
 template <bool WRITE>
-__global__ __launch_bounds__(SP_WG) void k_sp_tris(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ vcl, uint32_t* __restrict__ cused, const uint32_t* __restrict__ cmap,
+__global__ __launch_bounds__(MESH_WG) void k_sp_tris(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ vcl, uint32_t* __restrict__ cused, const uint32_t* __restrict__ cmap,
                                                   uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, uint32_t* __restrict__ oidx) {
-	const uint32_t t = blockIdx.x * SP_WG + threadIdx.x;
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t a = 0, b = 0, c = 0, f = 0;
 	if (t < nt) {
 		a = vcl[idx[3 * (size_t)t]]; b = vcl[idx[3 * (size_t)t + 1]]; c = vcl[idx[3 * (size_t)t + 2]];
@@ -214,11 +213,11 @@ __global__ __launch_bounds__(SP_WG) void k_sp_tris(const uint32_t* __restrict__ 
 }
 
 // rule 4, one thread per cluster; only the clusters a surviving triangle uses are output vertices
-__global__ __launch_bounds__(SP_WG) void k_sp_solve(const SpGrid g, const uint32_t placement, const uint32_t n_clusters, const long long* __restrict__ sums, const uint32_t* __restrict__ ckey,
+__global__ __launch_bounds__(MESH_WG) void k_sp_solve(const SpGrid g, const uint32_t placement, const uint32_t n_clusters, const long long* __restrict__ sums, const uint32_t* __restrict__ ckey,
                                                    const uint32_t* __restrict__ cused, const uint32_t* __restrict__ cmap, float* __restrict__ overts, float* __restrict__ ocolors,
                                                    float* __restrict__ onormals, SpResult* __restrict__ res) {
 #pragma clang fp contract(off)
-	const uint32_t c = blockIdx.x * SP_WG + threadIdx.x;
+	const uint32_t c = blockIdx.x * MESH_WG + threadIdx.x;
 	bool clamped = false, fallback = false;
 	if (c < n_clusters && cused[c]) {
 		const long long* __restrict__ r = sums + (size_t)c * SP_NSUM;

@@ -91,8 +91,8 @@ __global__ __launch_bounds__(256) void k_ms_classify(const MsArgs a, const doubl
 // A brick is evaluated if it or one of the bricks at -1 along any subset of the axes is kept. WRITE = false: per-workgroup counts; WRITE = true: the brick words and
 // the slot -> brick list, slots numbered in brick order from wg_offset. (Bit 0 of a word is final before this kernel runs and is written back unchanged.)
 template <bool WRITE>
-__global__ __launch_bounds__(MC_WG) void k_ms_mark(const MsArgs a, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, uint32_t* __restrict__ list) {
-	const uint32_t brick = blockIdx.x * MC_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_ms_mark(const MsArgs a, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, uint32_t* __restrict__ list) {
+	const uint32_t brick = blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t eval = 0, self = 0;
 	if (brick < a.n_bricks) {
 		const uint32_t bc[3] = {brick % a.nb[0], (brick / a.nb[0]) % a.nb[1], brick / (a.nb[0] * a.nb[1])};
@@ -180,7 +180,7 @@ __device__ __forceinline__ MsPoint ms_point(const MsArgs& a, uint32_t* as_out) {
 // (up to four) cells around it belongs to a kept brick; then both ends are corners of that cell, so the far end's brick was evaluated. The position is k_mc_verts' own
 // arithmetic (mc_emit_verts) on global lattice coordinates. vidx: [n_active][3][brick^3], MESH_NONE = no vertex.
 template <bool WRITE>
-__global__ __launch_bounds__(MC_WG) void k_ms_verts(const MsArgs a, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, float* __restrict__ verts, uint32_t* __restrict__ vidx) {
+__global__ __launch_bounds__(MESH_WG) void k_ms_verts(const MsArgs a, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset, float* __restrict__ verts, uint32_t* __restrict__ vidx) {
 	uint32_t as;
 	const MsPoint p = ms_point(a, &as);
 	uint32_t cross = 0;
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(MC_WG) void k_ms_verts(const MsArgs a, uint32_t* __
 
 // k_mc_faces for the cells of the kept bricks among those: the cell whose lowest corner is this lattice point.
 template <bool WRITE>
-__global__ __launch_bounds__(MC_WG) void k_ms_faces(const MsArgs a, const McTable* __restrict__ T, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset,
+__global__ __launch_bounds__(MESH_WG) void k_ms_faces(const MsArgs a, const McTable* __restrict__ T, uint32_t* __restrict__ wg_count, const uint32_t* __restrict__ wg_offset,
                                                     const uint32_t* __restrict__ vidx, uint32_t* __restrict__ indices) {
 	uint32_t as;
 	const MsPoint p = ms_point(a, &as);

@@ -15,8 +15,6 @@
 
 namespace rnb {
 
-constexpr uint32_t MT_WG = 256;
-constexpr uint32_t MT_BAD_INDEX = 1u; // bit of the flag word k_mesh_validate is handed
 
 struct MtAtlas {
 	uint32_t size, block, bpr; // S, b, blocks per row
@@ -61,10 +59,10 @@ __device__ __forceinline__ void mt_corner_uv(const MtAtlas& A, const MtTexel& t,
 
 // Texels w0 .. w0 + nb - 1. uv: float[n_tris][3][2], written by the three corner texels of every triangle. position (or null): the position map. coords (or null): the network input of the batch, 7 floats per texel; a texel without a triangle gets
 // the input of the point (0, 0, 0), so that the batch stays dense (its output is not used).
-__global__ __launch_bounds__(MT_WG) void k_mt_texels(const MtAtlas A, const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t w0, const uint32_t nb,
+__global__ __launch_bounds__(MESH_WG) void k_mt_texels(const MtAtlas A, const float* __restrict__ verts, const uint32_t* __restrict__ idx, const uint32_t w0, const uint32_t nb,
                                                      const float aabb_min, const float aabb_diag, float* __restrict__ uv, f4* __restrict__ position, float* __restrict__ coords) {
 #pragma clang fp contract(off)
-	const uint32_t q = blockIdx.x * MT_WG + threadIdx.x;
+	const uint32_t q = blockIdx.x * MESH_WG + threadIdx.x;
 	if (q >= nb) return;
 	MtTexel t;
 	float v[3] = {0.f, 0.f, 0.f};
@@ -89,8 +87,8 @@ __global__ __launch_bounds__(MT_WG) void k_mt_texels(const MtAtlas A, const floa
 }
 
 // albedo: rgb_activation = Logistic of outputs 0..2; normal: outputs 4..6 normalised, zeros where the gradient is zero (k_ms_vertex_attr). Either may be null.
-__global__ __launch_bounds__(MT_WG) void k_mt_maps(const MtAtlas A, const half_t* __restrict__ net, const uint32_t w0, const uint32_t nb, f4* __restrict__ albedo, f4* __restrict__ normal) {
-	const uint32_t q = blockIdx.x * MT_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mt_maps(const MtAtlas A, const half_t* __restrict__ net, const uint32_t w0, const uint32_t nb, f4* __restrict__ albedo, f4* __restrict__ normal) {
+	const uint32_t q = blockIdx.x * MESH_WG + threadIdx.x;
 	if (q >= nb) return;
 	MtTexel t;
 	if (!mt_texel(A, w0 + q, t)) return;

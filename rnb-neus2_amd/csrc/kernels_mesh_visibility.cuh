@@ -9,7 +9,8 @@
 //   k_mv_flags          candidate / seed bits per triangle from the records
 //   k_mv_ring_mark, k_mv_ring_grow    UNIT_FACE, one ring: the corners of the marked triangles are marked; a candidate with a marked corner joins. Every writer writes 1
 //   k_mv_comp_seed, k_mv_comp_keep, k_mv_comp_count    UNIT_COMPONENT: the root of a seed's component is marked; the candidates of marked roots are kept; roots counted
-//   k_mv_vflag, k_mv_verts, k_mv_tris<WRITE>           the stable compaction of the cleaner, keyed by the kept flag of a triangle instead of that of a component
+//   k_mv_vflag, MvKeep                                 the corners of the kept triangles flagged; the predicate of the shared compaction (k_compact_verts, k_compact_tris<WRITE>
+//                                                      of mesh_common.cuh), keyed by the kept flag of a triangle where the cleaner's is keyed by that of a component
 // Integers only: sums, maxima with a fixed order of the views, prefix sums. Nothing depends on the schedule. Vector loads, stores and atomics only.
 #pragma once
 #include "kernels_mesh_raster.cuh"
@@ -18,8 +19,6 @@
 
 namespace rnb {
 
-constexpr uint32_t MV_WG = 256;
-constexpr uint32_t MV_BAD_INDEX = 1u;           // bit of MvResult::flags
 constexpr uint32_t MV_CANDIDATE = 1u, MV_SEED = 2u, MV_KEPT = 4u; // bits of a triangle's flag word
 
 struct MvResult { // written by the kernels, read by the driver
@@ -35,8 +34,8 @@ __device__ __forceinline__ void mv_count(uint32_t* dst, const bool mine) {
 	if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)m) - 1)) (void)atomicAdd(dst, (uint32_t)__popcll(m));
 }
 
-__global__ __launch_bounds__(MV_WG) void k_mv_tally(const uint32_t w, const uint32_t h, const uint32_t nt, const MrTally y, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ won) {
-	const uint32_t n_pix = w * h, p = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_tally(const uint32_t w, const uint32_t h, const uint32_t nt, const MrTally y, const unsigned long long* __restrict__ keys, uint32_t* __restrict__ won) {
+	const uint32_t n_pix = w * h, p = blockIdx.x * MESH_WG + threadIdx.x;
 	uint32_t face = MESH_NONE;
 	bool valid = false;
 	if (p < n_pix) {
@@ -52,10 +51,10 @@ __global__ __launch_bounds__(MV_WG) void k_mv_tally(const uint32_t w, const uint
 	if (valid) (void)atomicAdd(&won[face], 1u);
 }
 
-__global__ __launch_bounds__(MV_WG) void k_mv_fold(const uint32_t nt, const uint32_t v, const uint32_t first, const uint32_t last, const uint32_t has_mask, const uint32_t min_pixels,
+__global__ __launch_bounds__(MESH_WG) void k_mv_fold(const uint32_t nt, const uint32_t v, const uint32_t first, const uint32_t last, const uint32_t has_mask, const uint32_t min_pixels,
                                                   uint32_t* __restrict__ cov, uint32_t* __restrict__ on, uint32_t* __restrict__ won, rnb_mesh_face_visibility* __restrict__ faces,
                                                   MvResult* __restrict__ res) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	bool seen_ever = false, off_ever = false;
 	if (t < nt) {
 		const uint32_t cw = cov[t], c = cw & ~MR_DRAWN, o = on[t], wn = won[t];
@@ -83,9 +82,9 @@ __global__ __launch_bounds__(MV_WG) void k_mv_fold(const uint32_t nt, const uint
 }
 
 // ---- rnb_mesh_visibility_select ----
-__global__ __launch_bounds__(MV_WG) void k_mv_flags(const rnb_mesh_face_visibility* __restrict__ faces, const uint32_t nt, const uint32_t min_views_seen, const uint32_t max_views_off_mask,
+__global__ __launch_bounds__(MESH_WG) void k_mv_flags(const rnb_mesh_face_visibility* __restrict__ faces, const uint32_t nt, const uint32_t min_views_seen, const uint32_t max_views_off_mask,
                                                    uint32_t* __restrict__ flag, MvResult* __restrict__ res) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	bool cand = false, seed = false;
 	if (t < nt) {
 		cand = faces[t].n_off_mask <= max_views_off_mask;
@@ -96,73 +95,54 @@ __global__ __launch_bounds__(MV_WG) void k_mv_flags(const rnb_mesh_face_visibili
 	mv_count(&res->n_seeds, seed);
 }
 // kept <- the seeds (UNIT_FACE, ring 0)
-__global__ __launch_bounds__(MV_WG) void k_mv_seeds_kept(uint32_t* __restrict__ flag, const uint32_t nt) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_seeds_kept(uint32_t* __restrict__ flag, const uint32_t nt) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t < nt && (flag[t] & MV_SEED)) flag[t] |= MV_KEPT;
 }
-__global__ __launch_bounds__(MV_WG) void k_mv_ring_mark(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ flag, uint32_t* __restrict__ vmark) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_ring_mark(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ flag, uint32_t* __restrict__ vmark) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t >= nt || !(flag[t] & MV_KEPT)) return;
 	vmark[idx[3 * (size_t)t]] = 1u; vmark[idx[3 * (size_t)t + 1]] = 1u; vmark[idx[3 * (size_t)t + 2]] = 1u;
 }
-__global__ __launch_bounds__(MV_WG) void k_mv_ring_grow(const uint32_t* __restrict__ idx, const uint32_t nt, uint32_t* __restrict__ flag, const uint32_t* __restrict__ vmark) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_ring_grow(const uint32_t* __restrict__ idx, const uint32_t nt, uint32_t* __restrict__ flag, const uint32_t* __restrict__ vmark) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t >= nt) return;
 	const uint32_t f = flag[t];
 	if (!(f & MV_CANDIDATE) || (f & MV_KEPT)) return;
 	if (vmark[idx[3 * (size_t)t]] | vmark[idx[3 * (size_t)t + 1]] | vmark[idx[3 * (size_t)t + 2]]) flag[t] = f | MV_KEPT; // (a thread writes its own word only)
 }
 // parent: the root of every vertex (k_cl_flatten). rmark[root] <- 1 for the component of a seed.
-__global__ __launch_bounds__(MV_WG) void k_mv_comp_seed(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ parent, uint32_t* __restrict__ rmark) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_comp_seed(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ parent, uint32_t* __restrict__ rmark) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t < nt && (flag[t] & MV_SEED)) rmark[parent[idx[3 * (size_t)t]]] = 1u;
 }
-__global__ __launch_bounds__(MV_WG) void k_mv_comp_keep(const uint32_t* __restrict__ idx, const uint32_t nt, uint32_t* __restrict__ flag, const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rmark) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_comp_keep(const uint32_t* __restrict__ idx, const uint32_t nt, uint32_t* __restrict__ flag, const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rmark) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t >= nt) return;
 	const uint32_t f = flag[t];
 	if ((f & MV_CANDIDATE) && rmark[parent[idx[3 * (size_t)t]]]) flag[t] = f | MV_KEPT;
 }
-__global__ __launch_bounds__(MV_WG) void k_mv_comp_count(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ used, const uint32_t* __restrict__ rmark, const uint32_t nv, MvResult* __restrict__ res) {
-	const uint32_t v = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_comp_count(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ used, const uint32_t* __restrict__ rmark, const uint32_t nv, MvResult* __restrict__ res) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
 	const bool root = v < nv && used[v] && parent[v] == v;
 	mv_count(&res->n_components, root);
 	mv_count(&res->n_components_kept, root && rmark[v]);
 }
 // vkeep[v] <- 1 for the corners of the kept triangles (zero on entry); kept_out (or null) <- 1 / 0 per triangle
-__global__ __launch_bounds__(MV_WG) void k_mv_vflag(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ flag, uint32_t* __restrict__ vkeep, uint32_t* __restrict__ kept_out) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mv_vflag(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ flag, uint32_t* __restrict__ vkeep, uint32_t* __restrict__ kept_out) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t >= nt) return;
 	const bool kept = (flag[t] & MV_KEPT) != 0;
 	if (kept_out) kept_out[t] = kept ? 1u : 0u;
 	if (!kept) return;
 	vkeep[idx[3 * (size_t)t]] = 1u; vkeep[idx[3 * (size_t)t + 1]] = 1u; vkeep[idx[3 * (size_t)t + 2]] = 1u;
 }
-// vmap: exclusive sums of vkeep = the new index of a kept vertex
-__global__ __launch_bounds__(MV_WG) void k_mv_verts(const uint32_t* __restrict__ vkeep, const uint32_t* __restrict__ vmap, const uint32_t nv, const float* __restrict__ verts, const float* __restrict__ colors,
-                                                   const float* __restrict__ normals, float* __restrict__ overts, float* __restrict__ ocolors, float* __restrict__ onormals) {
-	const uint32_t v = blockIdx.x * MV_WG + threadIdx.x;
-	if (v >= nv || !vkeep[v]) return;
-	const size_t s = 3 * (size_t)v, d = 3 * (size_t)vmap[v];
-	overts[d] = verts[s]; overts[d + 1] = verts[s + 1]; overts[d + 2] = verts[s + 2];
-	if (colors) { ocolors[d] = colors[s]; ocolors[d + 1] = colors[s + 1]; ocolors[d + 2] = colors[s + 2]; }
-	if (normals) { onormals[d] = normals[s]; onormals[d + 1] = normals[s + 1]; onormals[d + 2] = normals[s + 2]; }
-}
-// WRITE = false: kept triangles per workgroup; WRITE = true: their renumbered indices from wg_offset (in triangles) on, in input order.
-template <bool WRITE>
-__global__ __launch_bounds__(MV_WG) void k_mv_tris(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ vmap, uint32_t* __restrict__ wg_count,
-                                                  const uint32_t* __restrict__ wg_offset, uint32_t* __restrict__ oidx) {
-	const uint32_t t = blockIdx.x * MV_WG + threadIdx.x;
-	const uint32_t kept = (t < nt && (flag[t] & MV_KEPT)) ? 1u : 0u;
-	uint32_t total;
-	const uint32_t local = wg_exclusive_256(kept, &total);
-	if (!WRITE) {
-		if (threadIdx.x == 0) wg_count[blockIdx.x] = total;
-		return;
-	}
-	if (!kept) return;
-	const size_t d = 3 * ((size_t)wg_offset[blockIdx.x] + local);
-	oidx[d] = vmap[idx[3 * (size_t)t]]; oidx[d + 1] = vmap[idx[3 * (size_t)t + 1]]; oidx[d + 2] = vmap[idx[3 * (size_t)t + 2]];
-}
+// What MeshCall::compact keeps of the input of rnb_mesh_visibility_select (k_compact_verts, k_compact_tris of mesh_common.cuh): the kept triangles and their corners.
+struct MvKeep {
+	const uint32_t* flag;  // MV_KEPT per triangle
+	const uint32_t* vkeep; // 1 per corner of a kept triangle (k_mv_vflag)
+	__device__ __forceinline__ bool vertex(const uint32_t v) const { return vkeep[v] != 0u; }
+	__device__ __forceinline__ uint32_t triangle(const uint32_t*, const uint32_t t) const { return (flag[t] & MV_KEPT) ? 1u : 0u; }
+};
 
 } // namespace rnb

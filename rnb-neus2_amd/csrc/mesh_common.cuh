@@ -1,7 +1,11 @@
-// mesh_common.cuh — what the mesh stages share (kernels_mesh.cuh, kernels_mesh_sparse.cuh, kernels_mesh_clean.cuh, kernels_mesh_simplify.cuh, ...); the only header they
-// include from each other (but for kernels_mesh_visibility.cuh, which runs the rasteriser's fill and the cleaner's components and includes both):
+// mesh_common.cuh — what the mesh stages share (every kernels_mesh*.cuh file); the only header they include from each other (but for kernels_mesh_visibility.cuh, which
+// runs the rasteriser's fill and the cleaner's components and includes both, and kernels_mesh_project.cuh and kernels_mesh_draw.cuh, which call the baker's and the
+// rasteriser's device functions):
+//   MESH_WG, MESH_NONE, MESH_BAD_INDEX             the workgroup width of every mesh kernel, the "none" index, the bit k_mesh_validate sets in a stage's flag word
 //   k_scan_blocks / k_scan_add, wg_exclusive_256   the prefix sums that number every vertex, triangle, brick and cluster (the driver's scan_exclusive; the count / write kernel pairs)
 //   k_mesh_validate                                every index of a triangle list range-checked before any is used as an address, used[v] marked
+//   k_compact_verts, k_compact_tris<WRITE>         the stable compaction of a mesh to the part a predicate keeps (the cleaner's ClKeep, the visibility stage's MvKeep;
+//                                                  the driver's MeshCall::compact)
 //   wave_sum, wave_group_next                      the sums of the lanes of a wavefront that hold the same key, group by group
 //   mc_emit_verts, mc_corner, mc_edge, McTable     the marching-cubes arithmetic and numbering: stated once, so the dense and the sparse extractor agree bit for bit by construction
 // Vector loads, stores and atomics only.
@@ -10,7 +14,8 @@
 
 namespace rnb {
 
-constexpr uint32_t MC_WG = 256;
+constexpr uint32_t MESH_WG = 256;           // threads per workgroup of every mesh kernel but the scans and k_cl_select (1024)
+constexpr uint32_t MESH_BAD_INDEX = 1u;     // bit of a stage's flag word: k_mesh_validate met an index >= n_verts
 constexpr uint32_t MESH_NONE = 0xFFFFFFFFu; // no vertex on this edge, no component, no cluster
 constexpr int MESH_GROUP_ROUNDS = 4;         // groups a wavefront sums with shuffles before the lanes left over issue their own atomics
 
@@ -37,6 +42,7 @@ __global__ __launch_bounds__(1024) void k_scan_add(uint32_t* __restrict__ data, 
 }
 
 // Workgroup-local exclusive sum of one small count per thread (256 threads); returns the thread's offset, *total = workgroup sum.
+static_assert(MESH_WG == 256, "wg_exclusive_256 sums the four wavefronts of a 256-thread workgroup");
 __device__ __forceinline__ uint32_t wg_exclusive_256(const uint32_t c, uint32_t* total) {
 	__shared__ uint32_t wsum[4];
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -54,12 +60,43 @@ __device__ __forceinline__ uint32_t wg_exclusive_256(const uint32_t c, uint32_t*
 }
 
 // One thread per triangle: bad_bit is set in *flags if one of its indices is >= nv, else used[] of its corners is marked (every writer writes the same value).
-__global__ __launch_bounds__(MC_WG) void k_mesh_validate(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t nv, uint32_t* __restrict__ used, uint32_t* __restrict__ flags, const uint32_t bad_bit) {
-	const uint32_t t = blockIdx.x * MC_WG + threadIdx.x;
+__global__ __launch_bounds__(MESH_WG) void k_mesh_validate(const uint32_t* __restrict__ idx, const uint32_t nt, const uint32_t nv, uint32_t* __restrict__ used, uint32_t* __restrict__ flags, const uint32_t bad_bit) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
 	if (t >= nt) return;
 	const uint32_t a = idx[3 * (size_t)t], b = idx[3 * (size_t)t + 1], c = idx[3 * (size_t)t + 2];
 	if (a >= nv || b >= nv || c >= nv) { (void)atomicOr(flags, bad_bit); return; }
 	used[a] = 1u; used[b] = 1u; used[c] = 1u;
+}
+
+// The stable compaction of a mesh to what a predicate object keeps. KEEP has two device members: vertex(v), whether vertex v is kept, and triangle(idx, t), bit 0 whether
+// triangle t is kept and bit 1 whether its winding is flipped (its second and third corner swapped). vmap: the exclusive sums of the kept vertices' flags = their new index.
+template <typename KEEP>
+__global__ __launch_bounds__(MESH_WG) void k_compact_verts(const KEEP keep, const uint32_t* __restrict__ vmap, const uint32_t nv, const float* __restrict__ verts, const float* __restrict__ colors,
+                                                          const float* __restrict__ normals, float* __restrict__ overts, float* __restrict__ ocolors, float* __restrict__ onormals) {
+	const uint32_t v = blockIdx.x * MESH_WG + threadIdx.x;
+	if (v >= nv || !keep.vertex(v)) return;
+	const size_t s = 3 * (size_t)v, d = 3 * (size_t)vmap[v];
+	overts[d] = verts[s]; overts[d + 1] = verts[s + 1]; overts[d + 2] = verts[s + 2];
+	if (colors) { ocolors[d] = colors[s]; ocolors[d + 1] = colors[s + 1]; ocolors[d + 2] = colors[s + 2]; }
+	if (normals) { onormals[d] = normals[s]; onormals[d + 1] = normals[s + 1]; onormals[d + 2] = normals[s + 2]; }
+}
+// WRITE = false: kept triangles per workgroup; WRITE = true: their renumbered indices from wg_offset (in triangles) on, in input order.
+template <bool WRITE, typename KEEP>
+__global__ __launch_bounds__(MESH_WG) void k_compact_tris(const uint32_t* __restrict__ idx, const uint32_t nt, const KEEP keep, const uint32_t* __restrict__ vmap, uint32_t* __restrict__ wg_count,
+                                                         const uint32_t* __restrict__ wg_offset, uint32_t* __restrict__ oidx) {
+	const uint32_t t = blockIdx.x * MESH_WG + threadIdx.x;
+	const uint32_t f = t < nt ? keep.triangle(idx, t) : 0u;
+	uint32_t total;
+	const uint32_t local = wg_exclusive_256(f & 1u, &total);
+	if (!WRITE) {
+		if (threadIdx.x == 0) wg_count[blockIdx.x] = total;
+		return;
+	}
+	if (!(f & 1u)) return;
+	const uint32_t a = idx[3 * (size_t)t], b = idx[3 * (size_t)t + 1], c = idx[3 * (size_t)t + 2];
+	const size_t d = 3 * ((size_t)wg_offset[blockIdx.x] + local);
+	const bool flip = (f & 2u) != 0;
+	oidx[d] = vmap[a]; oidx[d + 1] = vmap[flip ? c : b]; oidx[d + 2] = vmap[flip ? b : c];
 }
 
 template <typename T> // long long or uint32_t

@@ -36,9 +36,9 @@ def kernel_bytes(nv, nt, nvo, nto, n_comp, attrs):
         "k_cl_sums<vert>": 4 * nv,
         "k_cl_select": 2 * 32 * n_comp + 4 * n_comp,
         "k_cl_vflag": 8 * nv,
-        "k_cl_verts": 8 * nv + (12 * nv + 12 * nvo) * (1 + attrs),
-        "k_cl_tris<count>": 12 * nt + 4 * nv,
-        "k_cl_tris<write>": 12 * nt + 8 * nv + 12 * nto,
+        "k_compact_verts<ClKeep>": 8 * nv + (12 * nv + 12 * nvo) * (1 + attrs),
+        "k_compact_tris<count, ClKeep>": 12 * nt + 4 * nv,
+        "k_compact_tris<write, ClKeep>": 12 * nt + 8 * nv + 12 * nto,
         "k_scan_blocks/k_scan_add (3 scans)": 2 * (2 * 8 * nv) + 8 * (nt // 256 + 1),
     }
 
