@@ -466,6 +466,19 @@ __device__ __forceinline__ void camera_ray(const ViewDev& m, const float xy[2], 
 __device__ __forceinline__ uint32_t image_idx(uint32_t base_idx, uint32_t n_rays, uint32_t n_rays_total, uint32_t n_images) { // testbed_nerf.cu:1194-1214
 	return (((base_idx + n_rays_total) * n_images) / n_rays) % n_images;
 }
+// Where a ray of the batch looks: its view, its image position, and its random stream behind the position's two draws. The march generates the ray from it (march_ray), the
+// loss its targets (ray_constants_core). Args: MarchArgs or RayConstIn.
+struct RayPixel { ViewDev m; Pcg32 rng; float xy[2]; };
+template <typename Args>
+__device__ __forceinline__ RayPixel ray_pixel(const Args& a, const uint32_t ray_idx, const bool snap) {
+	const uint32_t gi = a.ray_offset + ray_idx;
+	RayPixel p;
+	p.m = a.views[image_idx(gi, a.n_rays_global, a.n_rays_total, a.n_images)];
+	p.rng = a.rng;
+	p.rng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY);
+	random_image_pos(p.rng, p.m.width, p.m.height, snap, p.xy);
+	return p;
+}
 
 // ---------------------------------------------------------------------------------------------
 // K6: ray generation + DDA march (testbed_nerf.cu:1216-1387)
@@ -476,6 +489,8 @@ struct LossFlags {
 };
 
 constexpr int RAY_CONST_FLOATS = 12; // rgbtarget[4], light[3], mask_certainty, mask_gt, pad[3]
+// MarchArgs::lattice_ok, beside bit 0. RNB_MARCH_SKIP=2 (tests): the forms that skip never accept a re-entry cell, so every ray that skips takes the path of a failed search
+constexpr uint32_t LATTICE_REFUSE_REENTRY = 2u;
 
 struct MarchArgs {
 	uint32_t n_rays;        // this rank's rays
@@ -491,7 +506,7 @@ struct MarchArgs {
 	const uint8_t* bitfield;
 	const uint32_t* coarse; // k_coarse_bitfield of cascade 0
 	uint32_t n_blocks_lds;  // how many of its blocks the launch's LDS holds
-	uint32_t lattice_ok;    // the march lattice t_{k+1} = fl(t_k + MIN_CONE_STEPSIZE) is linear inside every binade of [0.25, 8) (no rounding ties): closed form allowed
+	uint32_t lattice_ok;    // the march lattice t_{k+1} = fl(t_k + MIN_CONE_STEPSIZE) is linear inside every binade of [0.25, 8) (no rounding ties): closed form allowed; | LATTICE_REFUSE_REENTRY
 	// per-ray scratch
 	float* setup;       // [n_rays][8]: o(3) dir(3) startt alive
 	float* ray_t;       // [n_rays][RNB_MAX_STEPS]: t of every sample found by the counting pass
@@ -513,6 +528,61 @@ struct MarchArgs {
 	unsigned long long* stats; // RNB_MARCH_STATS=1 (measurement aid, k_march_count_skip): [0] wavefronts, [1] loop iterations, [2] rays, [3] rays that skipped, [4] start-overs, [5] rounds spent looking for a re-entry cell, [6] rays ended early
 };
 
+// Ray i of the batch as the reference generates it (testbed_nerf.cu:1216-1335): the pixel; on an empty pixel (red channel of the normal map) a draw that drops the ray nine
+// times in ten; the discarded motion-blur draw; the camera ray; its span [startt, tmax] in the scene box, startt moved a random fraction of a step into it. A ray dropped at
+// its pixel -- and a lane that has no ray -- is the default: alive = 0, no step. Every counting march starts from this and ends with store_march_ray.
+struct MarchRay { Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1}; float startt = 0.f, tmax = 0.f, alive = 0.f; };
+__device__ __forceinline__ MarchRay march_ray(const MarchArgs& a, const uint32_t i) {
+	MarchRay r;
+	RayPixel p = ray_pixel(a, i, a.snap != 0);
+	if (red_is_nonpositive(p.xy, p.m, p.m.normal) && p.rng.next_float() >= 0.9) return r; // testbed_nerf.cu:1264, short-circuit draw
+	(void)p.rng.next_float(); // motionblur_time, testbed_nerf.cu:1270
+	camera_ray(p.m, p.xy, r.o, r.du, r.dir);
+	float tmin;
+	ray_intersect(a.A, r.o, r.dir, &tmin, &r.tmax);
+	tmin = fmaxf(tmin, 0.0f);
+	r.startt = tmin;
+	r.startt += calc_dt(r.startt, a.A.cone_angle) * p.rng.next_float();
+	r.alive = 1.f;
+	return r;
+}
+// what the scans and k_march_write read of ray i: the setup record, the unnormalised direction, the number of samples found
+__device__ __forceinline__ void store_march_ray(const MarchArgs& a, const uint32_t i, const MarchRay& r, const uint32_t steps) {
+	float* st = a.setup + (size_t)i * 8;
+	st[0] = r.o.x; st[1] = r.o.y; st[2] = r.o.z; st[3] = r.dir.x; st[4] = r.dir.y; st[5] = r.dir.z; st[6] = r.startt; st[7] = r.alive;
+	a.d_unnorm[(size_t)i * 3 + 0] = r.du.x; a.d_unnorm[(size_t)i * 3 + 1] = r.du.y; a.d_unnorm[(size_t)i * 3 + 2] = r.du.z;
+	a.steps[i] = steps;
+}
+// The ray against the bounding box of the non-empty blocks, dilated by a block (bb: COARSE_BBOX_OFF): its span [t_in, t_out] in it. false: the ray misses the box or the grid
+// is empty -- it has no sample. (Round 6: where the ray leaves this box it is over.)
+__device__ __forceinline__ bool occupied_box_span(const uint32_t* __restrict__ bb, const Vec3& o, const Vec3& dir, float& t_in, float& t_out) {
+	const float lo[3] = {((float)bb[0] - 1.0f) * (1.0f / 32.0f), ((float)bb[1] - 1.0f) * (1.0f / 32.0f), ((float)bb[2] - 1.0f) * (1.0f / 32.0f)};
+	const float hi[3] = {((float)bb[3] + 2.0f) * (1.0f / 32.0f), ((float)bb[4] + 2.0f) * (1.0f / 32.0f), ((float)bb[5] + 2.0f) * (1.0f / 32.0f)};
+	const float oo[3] = {o.x, o.y, o.z}, dd[3] = {dir.x, dir.y, dir.z};
+	t_in = -3.0e38f; t_out = 3.0e38f;
+	bool can_hit = bb[0] <= bb[3];
+#pragma unroll
+	for (int d = 0; d < 3; ++d) {
+		if (fabsf(dd[d]) < 1e-12f) { if (oo[d] < lo[d] || oo[d] > hi[d]) can_hit = false; continue; }
+		const float ta = (lo[d] - oo[d]) / dd[d], tb = (hi[d] - oo[d]) / dd[d];
+		t_in = fmaxf(t_in, fminf(ta, tb)); t_out = fminf(t_out, fmaxf(ta, tb));
+	}
+	return can_hit && !(t_in > t_out);
+}
+// One step of the reference's walk in a single-cascade scene, from a probed position (probe_single_cascade): occupied -- a sample, one step on; empty -- steps until the
+// voxel's exit is reached (testbed_nerf.cu:311-323).
+template <typename F>
+__device__ __forceinline__ void walk_step(const bool occ, const float dist, const Vec3& pos, uint32_t& j, float& t, F&& emit) {
+	if (occ) {
+		emit(j, pos, MIN_CONE_STEPSIZE, t);
+		++j;
+		t += MIN_CONE_STEPSIZE;
+	} else {
+		const float t_target = t + dist;
+		do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
+	}
+}
+
 // SC: one cascade and no cone (aabb_scale 1, every RNb scene): dt is the constant step and every position strictly inside the box is in
 // mip 0 (mip_from_dt returns mip_from_pos because dt * 2 * GRIDSIZE < 1), so the per-position frexp / scalbn / variable-resolution
 // arithmetic folds into constants; a position ON a face of the box is in mip 1 (probe_single_cascade). Same values, fewer dependent
@@ -529,15 +599,13 @@ __device__ __forceinline__ uint32_t march(const SceneAabb& A, const uint8_t* __r
 		bool occ = false;
 		float dist = 0.f;
 		while ((SC ? probe_single_cascade(A, pos = o + t * dir, dir, idir, bitfield, coarse_lds, n_blocks_lds, check_face, occ, dist) : aabb_contains(A, pos = o + t * dir)) && j < max_steps && t <= t_last) {
-			const float dt = SC ? MIN_CONE_STEPSIZE : calc_dt(t, A.cone_angle);
-			const uint32_t mip = SC ? 0u : (uint32_t)mip_from_dt(dt, pos);
-			if (SC ? occ : density_grid_occupied_at(pos, bitfield, mip)) {
+			if (SC) { walk_step(occ, dist, pos, j, t, emit); continue; }
+			const float dt = calc_dt(t, A.cone_angle);
+			const uint32_t mip = (uint32_t)mip_from_dt(dt, pos);
+			if (density_grid_occupied_at(pos, bitfield, mip)) {
 				emit(j, pos, dt, t);
 				++j;
 				t += dt;
-			} else if (SC) {
-				const float t_target = t + dist;
-				do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
 			} else {
 				const uint32_t res = GRIDSIZE >> mip;
 				t = advance_to_next_voxel(t, A.cone_angle, pos, dir, idir, res);
@@ -563,48 +631,19 @@ __global__ __launch_bounds__(512) void k_march_count(const MarchArgs a) { // (la
 	if (SC) { load_coarse(coarse_lds, a.coarse, a.n_blocks_lds, threadIdx.x, blockDim.x); __syncthreads(); }
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
 	if (i >= a.n_rays) return;
-	const uint32_t gi = a.ray_offset + i;
-	const uint32_t img = image_idx(gi, a.n_rays_global, a.n_rays_total, a.n_images);
-	const ViewDev m = a.views[img];
-	Pcg32 rng = a.rng;
-	rng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY);
-	float xy[2];
-	random_image_pos(rng, m.width, m.height, a.snap != 0, xy);
+	const MarchRay r = march_ray(a, i);
+	const Vec3 o = r.o, dir = r.dir;
+	const float startt = r.startt, tmax = r.tmax;
 	uint32_t steps = 0;
-	float alive = 0.f;
-	Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1};
-	float startt = 0.f;
-	bool dead = false;
-	if (red_is_nonpositive(xy, m, m.normal)) {
-		if (rng.next_float() >= 0.9) dead = true; // testbed_nerf.cu:1264, short-circuit draw
-	}
-	if (!dead) {
-		(void)rng.next_float(); // motionblur_time, testbed_nerf.cu:1270
-		camera_ray(m, xy, o, du, dir);
-		float tmin, tmax;
-		ray_intersect(a.A, o, dir, &tmin, &tmax);
-		tmin = fmaxf(tmin, 0.0f);
-		startt = tmin;
-		startt += calc_dt(startt, a.A.cone_angle) * rng.next_float();
-		alive = 1.f;
+	if (r.alive != 0.f) {
 		float* tt = a.ray_t + (size_t)i * RNB_MAX_STEPS;
 		float t_stop = 3.0e38f;
 		bool can_hit = true;
 		bool bbox_clear = false; // the occupied region's (dilated) bounding box keeps a block's width from every face of the scene box
 		if (SC && a.use_bbox) { // round 6: where the ray leaves the (dilated) bounding box of the non-empty blocks it is over; a ray that misses the box has no sample
 			const uint32_t* bb = a.coarse + COARSE_BBOX_OFF;
-			const float lo[3] = {((float)bb[0] - 1.0f) * (1.0f / 32.0f), ((float)bb[1] - 1.0f) * (1.0f / 32.0f), ((float)bb[2] - 1.0f) * (1.0f / 32.0f)};
-			const float hi[3] = {((float)bb[3] + 2.0f) * (1.0f / 32.0f), ((float)bb[4] + 2.0f) * (1.0f / 32.0f), ((float)bb[5] + 2.0f) * (1.0f / 32.0f)};
-			const float oo[3] = {o.x, o.y, o.z}, dd[3] = {dir.x, dir.y, dir.z};
-			float t0 = -3.0e38f, t1 = 3.0e38f;
-			can_hit = bb[0] <= bb[3];
-#pragma unroll
-			for (int d = 0; d < 3; ++d) {
-				if (fabsf(dd[d]) < 1e-12f) { if (oo[d] < lo[d] || oo[d] > hi[d]) can_hit = false; continue; }
-				const float ta = (lo[d] - oo[d]) / dd[d], tb = (hi[d] - oo[d]) / dd[d];
-				t0 = fmaxf(t0, fminf(ta, tb)); t1 = fminf(t1, fmaxf(ta, tb));
-			}
-			if (t0 > t1) can_hit = false;
+			float t0, t1;
+			can_hit = occupied_box_span(bb, o, dir, t0, t1);
 			t_stop = t1 + 4.0f * MIN_CONE_STEPSIZE; // (the box is already a block = 18 steps wider than the non-empty blocks on every side)
 			bbox_clear = bb[0] >= 2u && bb[1] >= 2u && bb[2] >= 2u && bb[3] <= 29u && bb[4] <= 29u && bb[5] <= 29u;
 		}
@@ -619,10 +658,47 @@ __global__ __launch_bounds__(512) void k_march_count(const MarchArgs a) { // (la
 		}
 		if (can_hit) steps = march<SC>(a.A, a.bitfield, coarse_lds, a.n_blocks_lds, o, dir, startt, RNB_MAX_STEPS, [&](uint32_t j, const Vec3&, float, float t) { tt[j] = t; }, t_stop, t_face);
 	}
-	float* st = a.setup + (size_t)i * 8;
-	st[0] = o.x; st[1] = o.y; st[2] = o.z; st[3] = dir.x; st[4] = dir.y; st[5] = dir.z; st[6] = startt; st[7] = alive;
-	a.d_unnorm[(size_t)i * 3 + 0] = du.x; a.d_unnorm[(size_t)i * 3 + 1] = du.y; a.d_unnorm[(size_t)i * 3 + 2] = du.z;
-	a.steps[i] = steps;
+	store_march_ray(a, i, r, steps);
+}
+
+// The lanes-per-ray forms below (k_march_count_wide, k_march_count_skip) test MG consecutive positions of a ray per round; this is the replay of the reference's sequential
+// visit order over one round's outcomes, from position `cur` on, by every lane of the ray's group alike. occ16 / in16: the group's ballots "occupied" / "inside the box";
+// nxt: for this lane's position, were it visited and empty, the next visited position (MG: behind the round); gb: the group's first lane; j: samples so far.
+struct RoundReplay {
+	uint64_t vis; // the positions that are samples
+	uint32_t j;   // samples behind the round
+	int pend_src; // >= 0: the empty position whose jump leaves the round (pending_handover)
+	bool term;    // the ray is over: a visited position outside the box (testbed_nerf.cu:1337), or RNB_MAX_STEPS samples
+};
+template <int MG>
+__device__ __forceinline__ RoundReplay replay_round(int cur, const uint32_t j, const uint64_t occ16, const uint64_t in16, const uint32_t nxt, const int gb) {
+	RoundReplay r = {0ull, j, -1, false};
+	while (cur < MG) {
+		if (!((in16 >> cur) & 1ull)) { r.term = true; break; } // left the box
+		if ((occ16 >> cur) & 1ull) {
+			const uint64_t run_mask = (occ16 & in16) >> cur;
+			int run = (MG == 64 && run_mask == ~0ull) ? 64 : __builtin_ctzll(~run_mask); // bits above the group are zero in run_mask: the complement has a set bit unless the group is the whole ballot
+			run = min(run, MG - cur);
+			const int allowed = min(run, (int)(RNB_MAX_STEPS - r.j));
+			r.vis |= (MG == 64 && allowed >= 64 ? ~0ull : ((1ull << allowed) - 1ull)) << cur;
+			r.j += (uint32_t)allowed;
+			cur += allowed;
+			if (r.j >= RNB_MAX_STEPS) { r.term = true; break; }
+		} else {
+			// the visited empty lane's own answer, through one cross-lane read (carried in four ballot masks = eight more SGPRs, the
+			// kernel spilled masks into VGPR lanes and was not reproducible beside k_fwd_bwd: rnb_neus2_hip.hip, launch_premarch)
+			const int nx = (int)__shfl(nxt, gb + cur, 64);
+			if (nx >= MG) r.pend_src = cur;
+			cur = nx;
+		}
+	}
+	return r;
+}
+// ... and behind it: the empty position that jumped beyond the round hands its voxel-exit target to the whole group, which continues the reference's
+// do { t += dt } while (t < t_target) in the next round. (Every lane of the wavefront takes part in the cross-lane read.)
+__device__ __forceinline__ void pending_handover(const int pend_src, const float t_target, const int gb, bool& have_pending, float& pending_target) {
+	const float tgt = __shfl(t_target, gb + (pend_src < 0 ? 0 : pend_src), 64);
+	if (pend_src >= 0) { have_pending = true; pending_target = tgt; }
 }
 
 // Same result as k_march_count, 16 lanes per ray. The sequence of march positions t_0 = startt, t_{k+1} = t_k + dt(t_k)
@@ -648,36 +724,11 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 	const int g = lane & (MG - 1);
 	const int gb = lane & ~(MG - 1); // first lane of the group inside the wavefront
 	const bool ray_exists = i < a.n_rays;
-	Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1}, idir = {0, 0, 1};
-	float t_cur = 0.f, startt = 0.f, alive = 0.f, t_face = 3.0e38f;
-	bool term = true;
-	if (ray_exists) {
-		const uint32_t gi = a.ray_offset + i;
-		const uint32_t img = image_idx(gi, a.n_rays_global, a.n_rays_total, a.n_images);
-		const ViewDev m = a.views[img];
-		Pcg32 rng = a.rng;
-		rng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY);
-		float xy[2];
-		random_image_pos(rng, m.width, m.height, a.snap != 0, xy);
-		bool dead = false;
-		if (red_is_nonpositive(xy, m, m.normal)) {
-			if (rng.next_float() >= 0.9) dead = true; // testbed_nerf.cu:1264
-		}
-		if (!dead) {
-			(void)rng.next_float(); // motionblur_time
-			camera_ray(m, xy, o, du, dir);
-			idir = v3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
-			float tmin, tmax;
-			ray_intersect(a.A, o, dir, &tmin, &tmax);
-			tmin = fmaxf(tmin, 0.0f);
-			startt = tmin;
-			startt += calc_dt(startt, a.A.cone_angle) * rng.next_float();
-			t_cur = startt;
-			alive = 1.f;
-			term = false;
-			if (SC) t_face = face_check_from(o, dir, startt, tmax);
-		}
-	}
+	const MarchRay r = ray_exists ? march_ray(a, i) : MarchRay();
+	const Vec3 o = r.o, dir = r.dir, idir = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z}; // (a lane without a ray, or with a dropped one, probes nothing)
+	bool term = r.alive == 0.f;
+	float t_cur = r.startt;
+	const float t_face = SC && !term ? face_check_from(o, dir, r.startt, r.tmax) : 3.0e38f;
 	uint32_t j = 0;
 	bool have_pending = false;
 	float pending_target = 0.f;
@@ -755,9 +806,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 		const unsigned long long occ_w = __ballot(occ), in_w = __ballot(inside);
 		const uint64_t occ16 = ((uint64_t)occ_w >> gb) & GM, in16 = ((uint64_t)in_w >> gb) & GM;
 		// replay of the sequential visit order over this round's outcomes
-		uint64_t vis = 0;
-		const uint32_t j0 = j;
-		int pend_src = -1;
+		RoundReplay rr = {0ull, j, -1, term}; // (no replay: nothing visited)
 		if (!term) {
 			int cur = 0;
 			if (have_pending) { // continue the reference's do { t += dt } while (t < t_target) across the round boundary
@@ -776,38 +825,14 @@ __global__ __launch_bounds__(WGS) void k_march_count_wide(const MarchArgs a) {
 				}
 				if (cur < MG) have_pending = false;
 			}
-			while (cur < MG) {
-				if (!((in16 >> cur) & 1ull)) { term = true; break; } // left the box (testbed_nerf.cu:1337)
-				if ((occ16 >> cur) & 1ull) {
-					const uint64_t run_mask = (occ16 & in16) >> cur;
-					int run = (MG == 64 && run_mask == ~0ull) ? 64 : __builtin_ctzll(~run_mask); // bits above the group are zero in run_mask: the complement has a set bit unless the group is the whole ballot
-					run = min(run, MG - cur);
-					const int allowed = min(run, (int)(RNB_MAX_STEPS - j));
-					vis |= (allowed >= 64 ? ~0ull : ((1ull << allowed) - 1ull)) << cur;
-					j += (uint32_t)allowed;
-					cur += allowed;
-					if (j >= RNB_MAX_STEPS) { term = true; break; }
-				} else {
-					// the visited empty lane's own answer, through one cross-lane read (carried in four ballot masks = eight more SGPRs, the
-					// kernel spilled masks into VGPR lanes and was not reproducible beside k_fwd_bwd: rnb_neus2_hip.hip, launch_premarch)
-					const int nx = (int)__shfl(nxt, gb + cur, 64);
-					if (nx >= MG) { have_pending = true; pend_src = cur; }
-					cur = nx;
-				}
-			}
+			rr = replay_round<MG>(cur, j, occ16, in16, nxt, gb);
 		}
-		// the empty lane that jumped beyond the round hands its voxel-exit target to the whole group
-		const float tgt = __shfl(t_target, gb + (pend_src < 0 ? 0 : pend_src), 64);
-		if (pend_src >= 0) pending_target = tgt;
-		if ((vis >> g) & 1ull) tt[j0 + __popcll(vis & ((1ull << g) - 1ull))] = my_t;
+		pending_handover(rr.pend_src, t_target, gb, have_pending, pending_target);
+		if ((rr.vis >> g) & 1ull) tt[j + __popcll(rr.vis & ((1ull << g) - 1ull))] = my_t;
+		j = rr.j; term = rr.term;
 		t_cur = t_end;
 	}
-	if (ray_exists && g == 0) {
-		float* st = a.setup + (size_t)i * 8;
-		st[0] = o.x; st[1] = o.y; st[2] = o.z; st[3] = dir.x; st[4] = dir.y; st[5] = dir.z; st[6] = startt; st[7] = alive;
-		a.d_unnorm[(size_t)i * 3 + 0] = du.x; a.d_unnorm[(size_t)i * 3 + 1] = du.y; a.d_unnorm[(size_t)i * 3 + 2] = du.z;
-		a.steps[i] = j;
-	}
+	if (ray_exists && g == 0) store_march_ray(a, i, r, j);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -851,6 +876,58 @@ __device__ __forceinline__ float lattice_advance(float t, int n) { // t_{k+n} of
 	}
 	return t;
 }
+// The skip plan, shared by every skipping form (k_march_count_skip; thread per ray: march_skip_narrow, k_march_count_bbox, find_reentry). In march steps:
+constexpr float SKIP_LANDING_STEPS = 52.0f;  // a skip lands this far in front of the next stretch of interest (skip_length takes 2 more off), which leaves the window in which
+                                             // the re-entry cell has to be found: up to 48 positions (find_reentry), rounds of 16 (k_march_count_skip)
+constexpr float SKIP_DEADLINE_STEPS = 17.0f; // ... a window that ends here: a round that starts closer to the stretch than this (16 positions and the one behind them) is replayed, not searched
+constexpr int SKIP_MIN_STEPS = 32;           // a stretch is skipped only if that saves this many steps
+// Skipped positions are never tested against the box, and the reference ENDS a ray at the first visited position outside it (testbed_nerf.cu:1337) -- which happens
+// at a ray's very first position when startt = tmin + a tiny fraction of a step rounds to just outside the entry face (one ray in 5 million: found by the pinned
+// states' hashes, tests/golden/pinned_states.json). So a stretch is skipped only if both its ends lie inside the box with a margin far above any rounding: the
+// box is convex, every position between them then does too. The first position of a ray lies on the entry face and is therefore always visited the reference's way.
+constexpr float SKIP_BOX_MARGIN = 1e-4f;
+__device__ __forceinline__ bool safely_inside(const SceneAabb& A, const Vec3& p) {
+	const float mlo = A.mn + SKIP_BOX_MARGIN, mhi = A.mx - SKIP_BOX_MARGIN;
+	return p.x > mlo && p.x < mhi && p.y > mlo && p.y < mhi && p.z > mlo && p.z < mhi;
+}
+// the dilated coarse occupancy (COARSE_DIL_OFF) behind the march's LDS image of the grid (load_coarse); the caller's barrier covers both
+__device__ __forceinline__ const uint32_t* load_dilated(uint32_t* __restrict__ coarse_lds, const MarchArgs& a) {
+	uint32_t* dil = coarse_lds + 2 * COARSE_WORDS + 2 * a.n_blocks_lds;
+	for (uint32_t q = threadIdx.x; q < COARSE_WORDS; q += blockDim.x) dil[q] = a.coarse[COARSE_DIL_OFF + q];
+	return dil;
+}
+// (1) the interest bit of a sample point of the ray: the dilated occupancy of its block (the point clamped into the box: a sample point just outside the box still answers
+// for the positions just inside it)
+__device__ __forceinline__ bool interest_at(const uint32_t* __restrict__ dil, const Vec3& p) {
+	const int bx = min(max((int)(p.x * 32.0f), 0), 31), by = min(max((int)(p.y * 32.0f), 0), 31), bz = min(max((int)(p.z * 32.0f), 0), 31);
+	return (dil[(uint32_t)by | ((uint32_t)bz << 5)] >> bx) & 1u;
+}
+// how many steps to skip from t to land SKIP_LANDING_STEPS in front of t_int (a skip is taken if these are SKIP_MIN_STEPS or more), and where the re-entry search gives up
+__device__ __forceinline__ int skip_length(const float t, const float t_int) {
+	return (int)floorf((t_int - SKIP_LANDING_STEPS * MIN_CONE_STEPSIZE - t) * (1.0f / MIN_CONE_STEPSIZE)) - 2;
+}
+__device__ __forceinline__ float skip_deadline(const float t_int) { return t_int - SKIP_DEADLINE_STEPS * MIN_CONE_STEPSIZE; }
+// What a ray at lattice position t (in [0.25, LATTICE_SKIP_FROM_BELOW)) does, from its interest bits (bit i: the sample point startt + i / 32, which answers for the stretch
+// half a spacing to either side). n < 0: nothing of interest ever again -- the ray is over (the reference marches on to the box exit, or ends at a position outside it, and
+// emits nothing either way). n == 0: no skip (one of the four sample points from the one in front of t on is of interest -- this round's stretch and the two behind it --, or the next one that
+// is lies less than SKIP_MIN_STEPS in front of where a skip would land). Otherwise: skip n steps
+// towards the stretch of interest that starts at t_int.
+struct SkipPlan { int n; float t_int; };
+__device__ __forceinline__ SkipPlan skip_plan(const float t, const float startt, const uint64_t interest) {
+	const int i_first = max((int)floorf((t - startt) * 32.0f) - 1, 0);
+	const uint64_t ahead = i_first < 64 ? (interest >> i_first) : 0ull;
+	if ((ahead & 0xFull) != 0ull) return {0, 0.f};
+	if (ahead == 0ull) return {-1, 0.f};
+	const int nb = i_first + __builtin_ctzll(ahead);
+	const float t_int = startt + ((float)nb - 0.5f) * (1.0f / 32.0f);
+	const int n = skip_length(t, t_int);
+	return {n >= SKIP_MIN_STEPS ? n : 0, t_int};
+}
+// the cell of a position (cascaded_grid_idx_at's integer coordinates, as occupied_mip0 forms them), 7 bits a coordinate
+__device__ __forceinline__ uint32_t cell_index(const Vec3& p) {
+	const int cx = min(max((int)(p.x * GRIDSIZE), 0), (int)GRIDSIZE - 1), cy = min(max((int)(p.y * GRIDSIZE), 0), (int)GRIDSIZE - 1), cz = min(max((int)(p.z * GRIDSIZE), 0), (int)GRIDSIZE - 1);
+	return (uint32_t)cx | ((uint32_t)cy << 7) | ((uint32_t)cz << 14);
+}
 
 template <int WGS = 256>
 __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
@@ -858,8 +935,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 	constexpr bool SC = true;
 	extern __shared__ __attribute__((aligned(16))) uint32_t coarse_lds[];
 	load_coarse(coarse_lds, a.coarse, a.n_blocks_lds, threadIdx.x, blockDim.x);
-	uint32_t* dil = coarse_lds + 2 * COARSE_WORDS + 2 * a.n_blocks_lds;
-	for (uint32_t q = threadIdx.x; q < COARSE_WORDS; q += blockDim.x) dil[q] = a.coarse[COARSE_DIL_OFF + q];
+	const uint32_t* dil = load_dilated(coarse_lds, a);
 	__syncthreads();
 	constexpr uint64_t GM = (1ull << MG) - 1ull;
 	const uint32_t i = blockIdx.x * (WGS / MG) + (threadIdx.x / MG);
@@ -867,39 +943,13 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 	const int g = lane & (MG - 1);
 	const int gb = lane & ~(MG - 1);
 	const bool ray_exists = i < a.n_rays;
-	Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1}, idir = {0, 0, 1};
-	float t_cur = 0.f, startt = 0.f, alive = 0.f, t_exit = 0.f, t_face = 3.0e38f;
-	bool term = true;
-	if (ray_exists) {
-		const uint32_t gi = a.ray_offset + i;
-		const uint32_t img = image_idx(gi, a.n_rays_global, a.n_rays_total, a.n_images);
-		const ViewDev m = a.views[img];
-		Pcg32 rng = a.rng;
-		rng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY);
-		float xy[2];
-		random_image_pos(rng, m.width, m.height, a.snap != 0, xy);
-		bool dead = false;
-		if (red_is_nonpositive(xy, m, m.normal)) {
-			if (rng.next_float() >= 0.9) dead = true; // testbed_nerf.cu:1264
-		}
-		if (!dead) {
-			(void)rng.next_float(); // motionblur_time
-			camera_ray(m, xy, o, du, dir);
-			idir = v3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
-			float tmin, tmax;
-			ray_intersect(a.A, o, dir, &tmin, &tmax);
-			tmin = fmaxf(tmin, 0.0f);
-			startt = tmin;
-			startt += calc_dt(startt, a.A.cone_angle) * rng.next_float();
-			t_cur = startt;
-			t_exit = tmax;
-			alive = 1.f;
-			term = false;
-			t_face = face_check_from(o, dir, startt, tmax);
-		}
-	}
-	// (1) the ray's stretches of interest: bit i = the dilated coarse occupancy at startt + i / 32 (the point clamped into the box: a sample point just outside the box still
-	// answers for the positions just inside it)
+	const MarchRay r = ray_exists ? march_ray(a, i) : MarchRay();
+	const Vec3 o = r.o, dir = r.dir, idir = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z}; // (a lane without a ray, or with a dropped one, probes nothing)
+	const float startt = r.startt, t_exit = r.tmax;
+	bool term = r.alive == 0.f;
+	float t_cur = startt;
+	const float t_face = term ? 3.0e38f : face_check_from(o, dir, startt, t_exit);
+	// (1) the ray's stretches of interest: bit i = interest_at the point startt + i / 32
 	uint64_t interest = 0;
 	bool skipping = a.lattice_ok != 0;
 	{
@@ -907,12 +957,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 		for (int it = 0; it < 4; ++it) {
 			const int k = g + 16 * it;
 			const float ts = startt + (float)k * (1.0f / 32.0f);
-			bool hit = false;
-			if (!term && ts <= t_exit + (1.5f / 32.0f)) {
-				const Vec3 p = o + ts * dir;
-				const int bx = min(max((int)(p.x * 32.0f), 0), 31), by = min(max((int)(p.y * 32.0f), 0), 31), bz = min(max((int)(p.z * 32.0f), 0), 31);
-				hit = (dil[(uint32_t)by | ((uint32_t)bz << 5)] >> bx) & 1u;
-			}
+			const bool hit = !term && ts <= t_exit + (1.5f / 32.0f) && interest_at(dil, o + ts * dir);
 			const unsigned long long w = __ballot(hit);
 			interest |= (((uint64_t)w >> gb) & GM) << (16 * it);
 		}
@@ -924,7 +969,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 	float pending_target = 0.f;
 	bool anchoring = false;      // behind a skip: rounds are evaluated but not replayed until a cell with unanimous votes is found
 	float anchor_deadline = 0.f; // ... which has to happen before the round that starts here
-	const bool force_restart = (a.lattice_ok & 2u) != 0u; // RNB_MARCH_SKIP=2 (tests): no cell is ever accepted, every skipping ray takes the start-over path
+	const bool force_restart = (a.lattice_ok & LATTICE_REFUSE_REENTRY) != 0u; // no cell is ever accepted, every skipping ray takes the start-over path
 	float* tt = a.ray_t + (size_t)(ray_exists ? i : 0) * RNB_MAX_STEPS;
 	float bin_lo = 1.f, bin_hi = 0.f, dlt = 0.f, d2 = 0.f, inv_dlt = 0.f, inv_d2 = 0.f; // the binade of t_cur and its lattice steps (formed again when t_cur leaves it)
 	// does a ray of this wavefront start below t = 0.25 or reach t = 8 (its last round begins at or before the box exit and ends 17 steps behind it)? Then none of the wavefront's
@@ -936,29 +981,16 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 		++st_iters;
 		// ---- skip / end decision (group-uniform: every lane of a ray holds the same state) ----
 		if (!term && skipping && !anchoring && t_cur >= 0.25f && t_cur < LATTICE_SKIP_FROM_BELOW) {
-			const int i_first = max((int)floorf((t_cur - startt) * 32.0f) - 1, 0);
-			const uint64_t ahead = i_first < 64 ? (interest >> i_first) : 0ull;
-			if ((ahead & 0xFull) == 0ull) { // this round's stretch and the two behind it: nothing
-				if (ahead == 0ull) { term = true; st_early = 1; } // nothing ever again: the reference marches on to the box exit (or ends at a position outside it) and emits nothing either way
-				else {
-					const int nb = i_first + __builtin_ctzll(ahead);
-					const float t_int = startt + ((float)nb - 0.5f) * (1.0f / 32.0f);
-					const int n = (int)floorf((t_int - 52.0f * MIN_CONE_STEPSIZE - t_cur) * (1.0f / MIN_CONE_STEPSIZE)) - 2;
-					// Skipped positions are never tested against the box, and the reference ENDS a ray at the first visited position outside it (testbed_nerf.cu:1337) -- which happens
-					// at a ray's very first position when startt = tmin + a tiny fraction of a step rounds to just outside the entry face (one ray in 5 million: found by the pinned
-					// states' hashes, tests/golden/pinned_states.json). So a stretch is skipped only if both its ends lie inside the box with a margin far above any rounding: the
-					// box is convex, every position between them then does too. The first round of a ray starts on the entry face and is therefore always replayed.
-					const float t_new = n >= 32 ? lattice_advance(t_cur, n) : t_cur;
-					const Vec3 p0 = o + t_cur * dir, p1 = o + t_new * dir;
-					const float mlo = a.A.mn + 1e-4f, mhi = a.A.mx - 1e-4f;
-					const bool safe = p0.x > mlo && p0.x < mhi && p0.y > mlo && p0.y < mhi && p0.z > mlo && p0.z < mhi && p1.x > mlo && p1.x < mhi && p1.y > mlo && p1.y < mhi && p1.z > mlo && p1.z < mhi;
-					if (n >= 32 && safe) {
-						t_cur = t_new;
-						anchoring = true;
-						++st_skips;
-						have_pending = false;
-						anchor_deadline = t_int - 17.0f * MIN_CONE_STEPSIZE;
-					}
+			const SkipPlan plan = skip_plan(t_cur, startt, interest);
+			if (plan.n < 0) { term = true; st_early = 1; }
+			else if (plan.n > 0) {
+				const float t_new = lattice_advance(t_cur, plan.n);
+				if (safely_inside(a.A, o + t_cur * dir) && safely_inside(a.A, o + t_new * dir)) { // (SKIP_BOX_MARGIN. The first round of a ray starts on the entry face and is therefore always replayed)
+					t_cur = t_new;
+					anchoring = true;
+					++st_skips;
+					have_pending = false;
+					anchor_deadline = skip_deadline(plan.t_int);
 				}
 			}
 		}
@@ -1038,9 +1070,7 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 		int start_cur = 0;
 		bool replay = !term && !anchoring;
 		if (__any(!term && anchoring)) { // (wave-uniform: most rounds have no ray looking for its way back in)
-			// the cell of the position (cascaded_grid_idx_at's integer coordinates, as occupied_mip0 forms them)
-			const int cx = min(max((int)(pos.x * GRIDSIZE), 0), (int)GRIDSIZE - 1), cy = min(max((int)(pos.y * GRIDSIZE), 0), (int)GRIDSIZE - 1), cz = min(max((int)(pos.z * GRIDSIZE), 0), (int)GRIDSIZE - 1);
-			const uint32_t cell = (uint32_t)cx | ((uint32_t)cy << 7) | ((uint32_t)cz << 14);
+			const uint32_t cell = cell_index(pos);
 			const uint32_t prev = (uint32_t)__shfl((int)cell, gb + max(g - 1, 0), 64);
 			const bool bnd = g > 0 && cell != prev; // a cell begins at this position (position 0: unknown, the cell may have begun in the round before)
 			const unsigned long long bnd_w = __ballot(bnd);
@@ -1066,48 +1096,25 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 			}
 		}
 		// ---- replay of the sequential visit order over this round's outcomes (as k_march_count_wide; start_cur: the position the chain is known to arrive on) ----
-		uint64_t vis = 0;
-		const uint32_t j0 = j;
-		int pend_src = -1;
+		RoundReplay rr = {0ull, j, -1, term}; // (no replay: nothing visited)
 		if (replay) {
 			int cur = start_cur;
 			if (have_pending) {
 				cur = first_at_or_after(pending_target, 0);
 				if (cur < MG) have_pending = false;
 			}
-			while (cur < MG) {
-				if (!((in16 >> cur) & 1ull)) { term = true; break; }
-				if ((occ16 >> cur) & 1ull) {
-					const uint64_t run_mask = (occ16 & in16) >> cur;
-					int run = __builtin_ctzll(~run_mask);
-					run = min(run, MG - cur);
-					const int allowed = min(run, (int)(RNB_MAX_STEPS - j));
-					vis |= ((1ull << allowed) - 1ull) << cur;
-					j += (uint32_t)allowed;
-					cur += allowed;
-					if (j >= RNB_MAX_STEPS) { term = true; break; }
-				} else {
-					const int nx = (int)__shfl(nxt, gb + cur, 64);
-					if (nx >= MG) { have_pending = true; pend_src = cur; }
-					cur = nx;
-				}
-			}
+			rr = replay_round<MG>(cur, j, occ16, in16, nxt, gb);
 		}
-		const float tgt = __shfl(t_target, gb + (pend_src < 0 ? 0 : pend_src), 64);
-		if (pend_src >= 0) pending_target = tgt;
-		if ((vis >> g) & 1ull) tt[j0 + __popcll(vis & ((1ull << g) - 1ull))] = my_t;
+		pending_handover(rr.pend_src, t_target, gb, have_pending, pending_target);
+		if ((rr.vis >> g) & 1ull) tt[j + __popcll(rr.vis & ((1ull << g) - 1ull))] = my_t;
+		j = rr.j; term = rr.term;
 		t_cur = t_end;
 	}
 	if (a.stats) {
 		if (lane == 0) { atomicAdd(a.stats + 0, 1ull); atomicAdd(a.stats + 1, (unsigned long long)st_iters); }
 		if (ray_exists && g == 0) { atomicAdd(a.stats + 2, 1ull); atomicAdd(a.stats + 3, (unsigned long long)(st_skips != 0)); atomicAdd(a.stats + 4, (unsigned long long)st_restarts); atomicAdd(a.stats + 5, (unsigned long long)st_anchor_rounds); atomicAdd(a.stats + 6, (unsigned long long)st_early); }
 	}
-	if (ray_exists && g == 0) {
-		float* st = a.setup + (size_t)i * 8;
-		st[0] = o.x; st[1] = o.y; st[2] = o.z; st[3] = dir.x; st[4] = dir.y; st[5] = dir.z; st[6] = startt; st[7] = alive;
-		a.d_unnorm[(size_t)i * 3 + 0] = du.x; a.d_unnorm[(size_t)i * 3 + 1] = du.y; a.d_unnorm[(size_t)i * 3 + 2] = du.z;
-		a.steps[i] = j;
-	}
+	if (ray_exists && g == 0) store_march_ray(a, i, r, j);
 }
 
 // The same two facts for the ONE-THREAD-PER-RAY march (k_march_count<true>, batches from 18 432 rays on: the window's second half and the late regime, where a ray holds ~20 marched
@@ -1119,13 +1126,9 @@ __global__ __launch_bounds__(WGS) void k_march_count_skip(const MarchArgs a) {
 // FIRST position to its last, all of them inside the box, empty, and jumping to the position behind the cell's last one; that position (a position the reference's chain visits,
 // see k_march_count_skip) is returned in t_found. false: none before t_limit (nothing has been changed; the caller walks on from where it stood).
 __device__ __forceinline__ bool find_reentry(const MarchArgs& a, const uint32_t* __restrict__ coarse_lds, const Vec3& o, const Vec3& dir, const Vec3& idir, float tq, const float t_limit, const float t_face, float& t_found) {
-	auto cell_of = [&](const Vec3& p) {
-		const int cx = min(max((int)(p.x * GRIDSIZE), 0), (int)GRIDSIZE - 1), cy = min(max((int)(p.y * GRIDSIZE), 0), (int)GRIDSIZE - 1), cz = min(max((int)(p.z * GRIDSIZE), 0), (int)GRIDSIZE - 1);
-		return (uint32_t)cx | ((uint32_t)cy << 7) | ((uint32_t)cz << 14);
-	};
-	const bool force_fail = (a.lattice_ok & 2u) != 0u; // RNB_MARCH_SKIP=2 (tests): no re-entry cell is ever accepted
+	const bool force_fail = (a.lattice_ok & LATTICE_REFUSE_REENTRY) != 0u;
 	Vec3 pq = o + tq * dir;
-	uint32_t prev_cell = cell_of(pq);
+	uint32_t prev_cell = cell_index(pq);
 	float cell_first = -1.f, t_prev = tq; // cell_first < 0: the first position of the cell being examined was not seen
 	bool cell_ok = false;                 // every position of the examined cell so far is inside and empty ...
 	float max_target = 0.f, min_target = 3.0e38f; // ... and their jump targets: all must land on the position behind the cell (t_last < target <= t_next for every one of them)
@@ -1141,7 +1144,7 @@ __device__ __forceinline__ bool find_reentry(const MarchArgs& a, const uint32_t*
 		}
 		const float t_next = t_prev + MIN_CONE_STEPSIZE;
 		const Vec3 p_next = o + t_next * dir;
-		const uint32_t c_next = cell_of(p_next);
+		const uint32_t c_next = cell_index(p_next);
 		if (c_next != prev_cell) {
 			if (cell_first >= 0.f && cell_ok && min_target > t_prev && max_target <= t_next && aabb_contains(a.A, p_next) && !force_fail) { t_found = t_next; return true; }
 			cell_first = t_next; cell_ok = true; max_target = 0.f; min_target = 3.0e38f; // the next cell starts here: its first position is seen
@@ -1164,13 +1167,9 @@ __device__ __forceinline__ uint32_t march_skip_narrow(const MarchArgs& a, const 
 		const int n_pts = min(64, (int)((t_exit - startt) * 32.0f) + 3);
 #pragma unroll 1
 		for (int k = 0; k < n_pts; ++k) {
-			const Vec3 p = o + (startt + (float)k * (1.0f / 32.0f)) * dir;
-			const int bx = min(max((int)(p.x * 32.0f), 0), 31), by = min(max((int)(p.y * 32.0f), 0), 31), bz = min(max((int)(p.z * 32.0f), 0), 31);
-			interest |= (uint64_t)((dil[(uint32_t)by | ((uint32_t)bz << 5)] >> bx) & 1u) << k;
+			interest |= (uint64_t)interest_at(dil, o + (startt + (float)k * (1.0f / 32.0f)) * dir) << k;
 		}
 	}
-	const float mlo = a.A.mn + 1e-4f, mhi = a.A.mx - 1e-4f;
-	auto safely_inside = [&](const Vec3& p) { return p.x > mlo && p.x < mhi && p.y > mlo && p.y < mhi && p.z > mlo && p.z < mhi; };
 	uint32_t j = 0, n_skips = 0, n_fail = 0, n_early = 0;
 	float t = startt;
 	Vec3 pos;
@@ -1179,34 +1178,18 @@ __device__ __forceinline__ uint32_t march_skip_narrow(const MarchArgs& a, const 
 	const float t_face = face_check_from(o, dir, startt, t_exit);
 	while (probe_single_cascade(a.A, pos = o + t * dir, dir, idir, a.bitfield, coarse_lds, a.n_blocks_lds, t >= t_face, occ, dist) && j < RNB_MAX_STEPS) {
 		if (skipping && t >= 0.25f && t < LATTICE_SKIP_FROM_BELOW) {
-			const int i_first = max((int)floorf((t - startt) * 32.0f) - 1, 0);
-			const uint64_t ahead = i_first < 64 ? (interest >> i_first) : 0ull;
-			if ((ahead & 0xFull) == 0ull) {
-				if (ahead == 0ull) { n_early = 1; break; } // nothing ever again: the reference marches on (or ends at a position outside the box) and emits nothing
-				const int nb = i_first + __builtin_ctzll(ahead);
-				const float t_int = startt + ((float)nb - 0.5f) * (1.0f / 32.0f);
-				const int n = (int)floorf((t_int - 52.0f * MIN_CONE_STEPSIZE - t) * (1.0f / MIN_CONE_STEPSIZE)) - 2;
-				if (n >= 32 && safely_inside(pos)) {
-					float tq = lattice_advance(t, n);
-					Vec3 pq = o + tq * dir;
-					if (safely_inside(pq)) {
-						float t_re = 0.f;
-						const bool found = find_reentry(a, coarse_lds, o, dir, idir, tq, t_int - 17.0f * MIN_CONE_STEPSIZE, t_face, t_re);
-						if (found) tq = t_re;
-						if (found) { t = tq; ++n_skips; continue; } // t is a position the reference's chain visits: go on from it
-						skipping = false; ++n_fail;                 // nothing was changed: every voxel from here on
-					}
+			const SkipPlan plan = skip_plan(t, startt, interest);
+			if (plan.n < 0) { n_early = 1; break; }
+			if (plan.n > 0 && safely_inside(a.A, pos)) {
+				const float tq = lattice_advance(t, plan.n);
+				if (safely_inside(a.A, o + tq * dir)) {
+					float t_re = 0.f;
+					if (find_reentry(a, coarse_lds, o, dir, idir, tq, skip_deadline(plan.t_int), t_face, t_re)) { t = t_re; ++n_skips; continue; } // t is a position the reference's chain visits: go on from it
+					skipping = false; ++n_fail;                                                                                                   // nothing was changed: every voxel from here on
 				}
 			}
 		}
-		if (occ) {
-			emit(j, pos, MIN_CONE_STEPSIZE, t);
-			++j;
-			t += MIN_CONE_STEPSIZE;
-		} else {
-			const float t_target = t + dist;
-			do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
-		}
+		walk_step(occ, dist, pos, j, t, emit);
 	}
 	if (stats) { atomicAdd(stats + 2, 1ull); atomicAdd(stats + 3, (unsigned long long)(n_skips != 0)); atomicAdd(stats + 4, (unsigned long long)n_fail); atomicAdd(stats + 6, (unsigned long long)n_early); }
 	return j;
@@ -1223,125 +1206,55 @@ __global__ __launch_bounds__(128) void k_march_count_bbox(const MarchArgs a) {
 	__syncthreads();
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
 	if (i >= a.n_rays) return;
-	const uint32_t gi = a.ray_offset + i;
-	const uint32_t img = image_idx(gi, a.n_rays_global, a.n_rays_total, a.n_images);
-	const ViewDev m = a.views[img];
-	Pcg32 rng = a.rng;
-	rng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY);
-	float xy[2];
-	random_image_pos(rng, m.width, m.height, a.snap != 0, xy);
+	const MarchRay r = march_ray(a, i);
+	const Vec3 o = r.o, dir = r.dir;
 	uint32_t j = 0;
-	float alive = 0.f;
-	Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1};
-	float startt = 0.f;
-	bool dead = false;
-	if (red_is_nonpositive(xy, m, m.normal)) {
-		if (rng.next_float() >= 0.9) dead = true; // testbed_nerf.cu:1264, short-circuit draw
-	}
-	if (!dead) {
-		(void)rng.next_float(); // motionblur_time, testbed_nerf.cu:1270
-		camera_ray(m, xy, o, du, dir);
-		float tmin, tmax;
-		ray_intersect(a.A, o, dir, &tmin, &tmax);
-		tmin = fmaxf(tmin, 0.0f);
-		startt = tmin;
-		startt += calc_dt(startt, a.A.cone_angle) * rng.next_float();
-		alive = 1.f;
+	if (r.alive != 0.f) {
 		float* tt = a.ray_t + (size_t)i * RNB_MAX_STEPS;
-		// the ray against the dilated bounding box of the non-empty blocks: [t_in, t_out]
-		const uint32_t* bb = a.coarse + COARSE_BBOX_OFF;
-		const float lo[3] = {((float)bb[0] - 1.0f) * (1.0f / 32.0f), ((float)bb[1] - 1.0f) * (1.0f / 32.0f), ((float)bb[2] - 1.0f) * (1.0f / 32.0f)};
-		const float hi[3] = {((float)bb[3] + 2.0f) * (1.0f / 32.0f), ((float)bb[4] + 2.0f) * (1.0f / 32.0f), ((float)bb[5] + 2.0f) * (1.0f / 32.0f)};
-		const float oo[3] = {o.x, o.y, o.z}, dd[3] = {dir.x, dir.y, dir.z};
-		float t_in = -3.0e38f, t_out = 3.0e38f;
-		bool can_hit = bb[0] <= bb[3];
-#pragma unroll
-		for (int d = 0; d < 3; ++d) {
-			if (fabsf(dd[d]) < 1e-12f) { if (oo[d] < lo[d] || oo[d] > hi[d]) can_hit = false; continue; }
-			const float ta = (lo[d] - oo[d]) / dd[d], tb = (hi[d] - oo[d]) / dd[d];
-			t_in = fmaxf(t_in, fminf(ta, tb)); t_out = fminf(t_out, fmaxf(ta, tb));
-		}
-		if (t_in > t_out) can_hit = false;
-		if (can_hit) {
+		float t_in, t_out;
+		if (occupied_box_span(a.coarse + COARSE_BBOX_OFF, o, dir, t_in, t_out)) {
 			const float t_stop = t_out + 4.0f * MIN_CONE_STEPSIZE;
 			const Vec3 idir = {1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z};
-			const float mlo = a.A.mn + 1e-4f, mhi = a.A.mx - 1e-4f;
-			auto safely_inside = [&](const Vec3& p) { return p.x > mlo && p.x < mhi && p.y > mlo && p.y < mhi && p.z > mlo && p.z < mhi; };
 			bool may_jump = (a.lattice_ok & 1u) != 0u && a.use_bbox >= 2u;
 			uint32_t jumped = 0, failed = 0;
-			float t = startt;
+			float t = r.startt;
 			Vec3 pos;
 			bool occ = false;
 			float dist = 0.f;
-			const float t_face = face_check_from(o, dir, startt, tmax);
+			const float t_face = face_check_from(o, dir, r.startt, r.tmax);
 			while (probe_single_cascade(a.A, pos = o + t * dir, dir, idir, a.bitfield, coarse_lds, a.n_blocks_lds, t >= t_face, occ, dist) && j < RNB_MAX_STEPS && t <= t_stop) {
-				if (may_jump && t >= 0.25f && t < LATTICE_SKIP_FROM_BELOW && safely_inside(pos)) { // (the ray's first position lies ON the entry face: it is always visited the reference's way)
+				if (may_jump && t >= 0.25f && t < LATTICE_SKIP_FROM_BELOW && safely_inside(a.A, pos)) { // (the ray's first position lies ON the entry face: it is always visited the reference's way)
 					may_jump = false; // one attempt per ray
-					const int n = (int)floorf((t_in - 52.0f * MIN_CONE_STEPSIZE - t) * (1.0f / MIN_CONE_STEPSIZE)) - 2;
-					if (n >= 32) {
+					const int n = skip_length(t, t_in);
+					if (n >= SKIP_MIN_STEPS) {
 						const float tq = lattice_advance(t, n);
 						float t_re = 0.f;
-						if (safely_inside(o + tq * dir) && find_reentry(a, coarse_lds, o, dir, idir, tq, t_in - 17.0f * MIN_CONE_STEPSIZE, t_face, t_re)) { t = t_re; jumped = 1; continue; }
+						if (safely_inside(a.A, o + tq * dir) && find_reentry(a, coarse_lds, o, dir, idir, tq, skip_deadline(t_in), t_face, t_re)) { t = t_re; jumped = 1; continue; }
 						failed = 1;
 					}
 				}
-				if (occ) {
-					tt[j] = t;
-					++j;
-					t += MIN_CONE_STEPSIZE;
-				} else {
-					const float t_target = t + dist;
-					do { t += MIN_CONE_STEPSIZE; } while (t < t_target);
-				}
+				walk_step(occ, dist, pos, j, t, [&](uint32_t k, const Vec3&, float, float ts) { tt[k] = ts; });
 			}
 			if (a.stats) { atomicAdd(a.stats + 2, 1ull); atomicAdd(a.stats + 3, (unsigned long long)jumped); atomicAdd(a.stats + 4, (unsigned long long)failed); }
 		}
 	}
-	float* st = a.setup + (size_t)i * 8;
-	st[0] = o.x; st[1] = o.y; st[2] = o.z; st[3] = dir.x; st[4] = dir.y; st[5] = dir.z; st[6] = startt; st[7] = alive;
-	a.d_unnorm[(size_t)i * 3 + 0] = du.x; a.d_unnorm[(size_t)i * 3 + 1] = du.y; a.d_unnorm[(size_t)i * 3 + 2] = du.z;
-	a.steps[i] = j;
+	store_march_ray(a, i, r, j);
 }
 
 __global__ __launch_bounds__(128) void k_march_count_skip_narrow(const MarchArgs a) {
 	extern __shared__ __attribute__((aligned(16))) uint32_t coarse_lds[];
 	load_coarse(coarse_lds, a.coarse, a.n_blocks_lds, threadIdx.x, blockDim.x);
-	uint32_t* dil = coarse_lds + 2 * COARSE_WORDS + 2 * a.n_blocks_lds;
-	for (uint32_t q = threadIdx.x; q < COARSE_WORDS; q += blockDim.x) dil[q] = a.coarse[COARSE_DIL_OFF + q];
+	const uint32_t* dil = load_dilated(coarse_lds, a);
 	__syncthreads();
 	const uint32_t i = threadIdx.x + blockIdx.x * blockDim.x;
 	if (i >= a.n_rays) return;
-	const uint32_t gi = a.ray_offset + i;
-	const uint32_t img = image_idx(gi, a.n_rays_global, a.n_rays_total, a.n_images);
-	const ViewDev m = a.views[img];
-	Pcg32 rng = a.rng;
-	rng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY);
-	float xy[2];
-	random_image_pos(rng, m.width, m.height, a.snap != 0, xy);
+	const MarchRay r = march_ray(a, i);
 	uint32_t steps = 0;
-	float alive = 0.f;
-	Vec3 o = {0, 0, 0}, dir = {0, 0, 1}, du = {0, 0, 1};
-	float startt = 0.f;
-	bool dead = false;
-	if (red_is_nonpositive(xy, m, m.normal)) {
-		if (rng.next_float() >= 0.9) dead = true; // testbed_nerf.cu:1264, short-circuit draw
-	}
-	if (!dead) {
-		(void)rng.next_float(); // motionblur_time, testbed_nerf.cu:1270
-		camera_ray(m, xy, o, du, dir);
-		float tmin, tmax;
-		ray_intersect(a.A, o, dir, &tmin, &tmax);
-		tmin = fmaxf(tmin, 0.0f);
-		startt = tmin;
-		startt += calc_dt(startt, a.A.cone_angle) * rng.next_float();
-		alive = 1.f;
+	if (r.alive != 0.f) {
 		float* tt = a.ray_t + (size_t)i * RNB_MAX_STEPS;
-		steps = march_skip_narrow(a, coarse_lds, dil, o, dir, startt, tmax, a.stats, [&](uint32_t j, const Vec3&, float, float t) { tt[j] = t; });
+		steps = march_skip_narrow(a, coarse_lds, dil, r.o, r.dir, r.startt, r.tmax, a.stats, [&](uint32_t j, const Vec3&, float, float t) { tt[j] = t; });
 	}
-	float* st = a.setup + (size_t)i * 8;
-	st[0] = o.x; st[1] = o.y; st[2] = o.z; st[3] = dir.x; st[4] = dir.y; st[5] = dir.z; st[6] = startt; st[7] = alive;
-	a.d_unnorm[(size_t)i * 3 + 0] = du.x; a.d_unnorm[(size_t)i * 3 + 1] = du.y; a.d_unnorm[(size_t)i * 3 + 2] = du.z;
-	a.steps[i] = steps;
+	store_march_ray(a, i, r, steps);
 }
 
 // inclusive prefix sum over the 64 lanes of a wavefront
@@ -1728,21 +1641,23 @@ __device__ __forceinline__ void ray_targets(const LossFlags& F, const float (&xf
 
 // Per-ray constants of the loss kernel (testbed_nerf.cu:1485-1593): pixel, target normal, light triplet, shading target.
 struct RayConstIn { Pcg32 rng; uint32_t ray_offset, n_rays_global, n_rays_total, n_images; const ViewDev* views; LossFlags F; const float* light_dirs; };
+template <typename Args> // MarchArgs (k_ray_constants) or LossArgs (the loss passes without precomputed constants)
+__device__ __forceinline__ RayConstIn ray_const_in(const Args& a) {
+	RayConstIn in;
+	in.rng = a.rng; in.ray_offset = a.ray_offset; in.n_rays_global = a.n_rays_global; in.n_rays_total = a.n_rays_total; in.n_images = a.n_images;
+	in.views = a.views; in.F = a.F; in.light_dirs = a.light_dirs;
+	return in;
+}
 
 template <typename RayOut>
 __device__ __forceinline__ void ray_constants_core(const RayConstIn& a, const uint32_t ray_idx, RayOut& R) {
-	const uint32_t gi = a.ray_offset + ray_idx;
-	Pcg32 rng = a.rng;
-	rng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY);
-	const uint32_t img = image_idx(gi, a.n_rays_global, a.n_rays_total, a.n_images);
-	const ViewDev m = a.views[img];
-	float xy[2];
-	random_image_pos(rng, m.width, m.height, a.F.snap != 0, xy);
+	const RayPixel p = ray_pixel(a, ray_idx, a.F.snap != 0);
+	const ViewDev& m = p.m;
 	float tex_albedo[4], tex_normal[4];
-	read_rgba(xy, m, m.albedo, tex_albedo);
-	read_rgba(xy, m, m.normal, tex_normal);
+	read_rgba(p.xy, m, m.albedo, tex_albedo);
+	read_rgba(p.xy, m, m.normal, tex_normal);
 	Pcg32 lrng = a.rng; // deterministic light pick: draw #7 of the ray's stream (the reference seeds curand with clock64())
-	lrng.advance((int64_t)gi * N_MAX_RANDOM_SAMPLES_PER_RAY + 7);
+	lrng.advance((int64_t)(a.ray_offset + ray_idx) * N_MAX_RANDOM_SAMPLES_PER_RAY + 7);
 	const int random_light = (int)(lrng.next_uint() % 3u);
 	ray_targets(a.F, m.xform, tex_normal, tex_albedo, a.light_dirs, random_light, R.rgbtarget, R.light);
 	R.mask_certainty = (float)(tex_albedo[3] > 0.99);
@@ -1759,10 +1674,7 @@ __device__ __forceinline__ void ray_constants(const LossArgs& a, const uint32_t 
 		R.mask_certainty = q[7]; R.mask_gt = q[8];
 		return;
 	}
-	RayConstIn in;
-	in.rng = a.rng; in.ray_offset = a.ray_offset; in.n_rays_global = a.n_rays_global; in.n_rays_total = a.n_rays_total; in.n_images = a.n_images;
-	in.views = a.views; in.F = a.F; in.light_dirs = a.light_dirs;
-	ray_constants_core(in, a.ray_indices[i], R);
+	ray_constants_core(ray_const_in(a), a.ray_indices[i], R);
 }
 
 // Second pass of the reference's kernel (testbed_nerf.cu:1366-1380) without re-marching: LR lanes per ray expand the t values
@@ -1820,11 +1732,8 @@ __global__ __launch_bounds__(WGS) void k_march_write(const MarchArgs a) {
 __global__ __launch_bounds__(64) void k_ray_constants(const MarchArgs a, float* __restrict__ ray_const) {
 	const uint32_t s = blockIdx.x * 64 + threadIdx.x;
 	if (s >= min(a.counters[2], a.n_rays)) return;
-	RayConstIn in;
-	in.rng = a.rng; in.ray_offset = a.ray_offset; in.n_rays_global = a.n_rays_global; in.n_rays_total = a.n_rays_total; in.n_images = a.n_images;
-	in.views = a.views; in.F = a.F; in.light_dirs = a.light_dirs;
 	struct { float rgbtarget[4], light[3], mask_certainty, mask_gt; } rc;
-	ray_constants_core(in, a.ray_indices[s], rc);
+	ray_constants_core(ray_const_in(a), a.ray_indices[s], rc);
 	float* q = ray_const + (size_t)s * RAY_CONST_FLOATS;
 #pragma unroll
 	for (int k = 0; k < 4; ++k) q[k] = rc.rgbtarget[k];

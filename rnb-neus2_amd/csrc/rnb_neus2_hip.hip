@@ -726,15 +726,16 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 	// kernel, which in turn wins below ~30 k rays (0.20 vs 0.30 ms at 14 k), where a ray per thread leaves the GPU to latency.
 	const bool sc = c->aabb.cone_angle == 0.f && c->aabb.max_cascade == 0; // one cascade, constant step: the specialised instances
 	const size_t march_lds = sc ? (size_t)(2 * COARSE_WORDS + 2 * a.n_blocks_lds) * sizeof(uint32_t) : 0;
+	// The three forms that leave the reference's visit chain and look for their way back into it (k_march_count_skip, k_march_count_skip_narrow, k_march_count_bbox) take
+	// `ar`: under RNB_MARCH_SKIP=2 (tests) no re-entry cell is accepted -- the skipping march starts every skipping ray over from its box entry, the thread-per-ray forms
+	// walk every voxel (k_march_count_bbox: up to the occupied box's exit). They need the closed form of the lattice (lattice_ok) and are not launched without it.
+	MarchArgs ar = a;
+	if (c->knobs.march_skip == 2) ar.lattice_ok |= LATTICE_REFUSE_REENTRY;
 	if (c->knobs.march_narrow || large_batch(c, n_rays)) {
 		if (sc && c->knobs.march_skip && c->knobs.march_skip_narrow && a.lattice_ok) { // RNB_MARCH_SKIP_NARROW=1 (dropped, kept as an A/B knob): the thread-per-ray march minus the stretches that cannot hold a sample (kernels_ray.cuh: march_skip_narrow)
-			if (c->knobs.march_skip == 2) a.lattice_ok |= 2u;
-			hipLaunchKernelGGL(k_march_count_skip_narrow, dim3(blocks), dim3(128), march_lds + COARSE_WORDS * sizeof(uint32_t), s, a);
-			a.lattice_ok &= 1u;
+			hipLaunchKernelGGL(k_march_count_skip_narrow, dim3(blocks), dim3(128), march_lds + COARSE_WORDS * sizeof(uint32_t), s, ar);
 		} else if (sc && c->knobs.march_bbox >= 2 && a.lattice_ok) {
-			if (c->knobs.march_skip == 2) a.lattice_ok |= 2u; // (tests: no re-entry cell is accepted -- every ray walks every voxel up to the occupied box's exit)
-			hipLaunchKernelGGL(k_march_count_bbox, dim3(blocks), dim3(128), march_lds, s, a);
-			a.lattice_ok &= 1u;
+			hipLaunchKernelGGL(k_march_count_bbox, dim3(blocks), dim3(128), march_lds, s, ar);
 		} else if (sc) hipLaunchKernelGGL(k_march_count<true>, dim3(blocks), dim3(128), march_lds, s, a); // 128 rays per workgroup: it keeps its slots until its slowest ray is through (profiles/r06_ab_march_wgs.txt)
 		else hipLaunchKernelGGL(k_march_count<false>, dim3(blocks), dim3(128), 0, s, a);
 	} else if (sc && n_rays <= MARCH_WAVE_PER_RAY_BELOW) {
@@ -745,9 +746,7 @@ int generate_training_samples(rnb_ctx* c, hipStream_t s, uint32_t n_rays, uint32
 		const dim3 grid((n_rays + 15) / 16); // 16 lanes per ray (8: 0.19 ms alone but a slower step; 32: 0.32 ms, measured in round 1)
 		if (sc && c->knobs.march_skip && a.lattice_ok) {
 			// round 6: the same rounds, minus the stretches of the ray that cannot hold a sample (kernels_ray.cuh: k_march_count_skip); bit-identical sample set and t
-			if (c->knobs.march_skip == 2) a.lattice_ok |= 2u;
-			hipLaunchKernelGGL((k_march_count_skip<1024>), dim3((n_rays + 63) / 64), dim3(1024), march_lds + COARSE_WORDS * sizeof(uint32_t), s, a); // 64 rays per load of the occupancy's LDS form (profiles/r06_ab_march_wgs.txt)
-			a.lattice_ok &= 1u;
+			hipLaunchKernelGGL((k_march_count_skip<1024>), dim3((n_rays + 63) / 64), dim3(1024), march_lds + COARSE_WORDS * sizeof(uint32_t), s, ar); // 64 rays per load of the occupancy's LDS form (profiles/r06_ab_march_wgs.txt)
 		} else if (sc) hipLaunchKernelGGL((k_march_count_wide<16, true>), grid, dim3(256), march_lds, s, a);
 		else hipLaunchKernelGGL((k_march_count_wide<16, false>), grid, dim3(256), 0, s, a);
 	}

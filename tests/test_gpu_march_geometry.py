@@ -4,7 +4,7 @@ direction components, grazing rays, the 1024-step diagonal, rays that miss the b
 form against the oracle's walk, bit for bit: COUNTERS[0, 2, 3], RAY_INDICES, NUMSTEPS, RAYS and every word of COORDS. There is no tolerance anywhere in the march part.
 
   form                                                                   selected by
-  one wavefront per ray, k_march_count_wide<64, true>                    1000 rays
+  one wavefront per ray, k_march_count_wide<64, true>                    1000 rays (and 999: a workgroup with a wavefront that has no ray)
   the skipping march, k_march_count_skip                                 4200 rays (not a multiple of 64)
   its start-over path                                                    RNB_MARCH_SKIP=2
   k_march_count_wide<16, true>                                           RNB_MARCH_SKIP=0
@@ -162,6 +162,22 @@ def test_march_empty_bitfield(contexts, fam):
     bf = np.zeros(cpu.get("DENSITY_BITFIELD").size, dtype=np.uint8)
     counters = _march_and_compare(cpu, gpus, bf, max_samples, "%s / empty" % fam)
     assert all(cc[0] == 0 and cc[2] == 0 and cc[3] == 0 for cc in counters.values())
+
+
+def test_march_wavefront_per_ray_with_rayless_lanes(contexts):
+    """999 rays in the one-wavefront-per-ray form: 250 workgroups of 4 rays, the last of which has a wavefront without a ray (the 1000 rays of the other tests fill every
+    workgroup). Eyes inside the box and far outside it over the thin shell; every ray that has one is marched as the oracle marches it."""
+    for fam in ("inside", "far"):
+        cpu, gpus, max_samples = contexts.get(False, fam)
+        gpu = gpus["default"]
+        bf = mg.bitfield("thin_shell", cpu.get("DENSITY_BITFIELD").size)
+        for c in (cpu, gpu):
+            c.put("DENSITY_BITFIELD", bf)
+        for n_rays_total in (0, 12345):
+            for c in (cpu, gpu):
+                c.generate_training_samples(999, n_rays_total, max_samples)
+            cc = _compare(gpu, cpu, "%s / thin_shell, form default, 999 rays, n_rays_total %d" % (fam, n_rays_total))
+            assert cc[2] > 0 and cc[0] == cc[3]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
