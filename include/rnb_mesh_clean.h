@@ -84,7 +84,8 @@ int rnb_mesh_clean_default_options(rnb_mesh_clean_options* opt);
  * A term that is not finite or not below 2^RNB_MESH_Q_TERM_LOG2 in magnitude fails the call with RNB_ERR_INVALID.
  *
  * keep: RNB_MESH_KEEP_ALL or RNB_MESH_KEEP_LARGEST. orient: RNB_MESH_ORIENT_OUTWARD swaps the second and third index of every triangle of a kept component whose
- * volume_q is negative. The input is taken to be consistently wound inside each component, as marching-cubes output is: the winding is not repaired across edges.
+ * volume_q is negative. The input is taken to be consistently wound inside each component, as marching-cubes output is: the winding is not repaired across edges
+ * (rnb_mesh_repair of rnb_mesh_topology.h does that, and welds: run it first on a mesh that needs either).
  * Vertex attributes are carried unchanged (out->colors / out->normals are set exactly when the input has them).
  *
  * Order: kept vertices in input order, kept triangles in input order, indices renumbered (prefix sums, no atomics). The same input gives the same bits, and a

@@ -84,7 +84,7 @@ int rnb_mesh_simplify_default_options(rnb_mesh_simplify_options* opt);
  *    Colour: (float) (S(colour_k) / (double) count). Normal: s_k = S(normal_k), l = sqrt((s.x * s.x + s.y * s.y) + s.z * s.z), (float) (s_k / l), zero if l == 0.
  * 5. Triangles. Each corner becomes its cluster. A triangle two of whose corners are equal is dropped; the others stay in input order with their winding. Vertices:
  *    the clusters a surviving triangle uses, in ascending key, renumbered by prefix sums. Duplicate triangles and the non-manifold edges clustering can create
- *    are KEPT; removing them is not this call's job.
+ *    are KEPT; removing them is not this call's job (rnb_mesh_repair of rnb_mesh_topology.h removes the duplicates, rnb_mesh_topology counts the edges).
  *
  * Consequences: the same input gives the same bits; a permutation of the input's triangles permutes the output's triangles and changes nothing else; a renumbering
  * of the input's vertices changes nothing at all.

@@ -762,6 +762,112 @@ MESH_DRAW_PROTOTYPES = {
     "mesh_draw_textured": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshDrawTexture), C.POINTER(View), C.POINTER(MeshDrawOptions), C.c_void_p, C.c_void_p, C.POINTER(MeshDrawStats)]),
 }
 
+# ---- include/rnb_mesh_topology.h: the edge census and the repair of a device mesh, a header of its own with its own version (the HIP library only) ----
+MESH_TOPOLOGY_ABI_VERSION = 1
+MESH_TOPOLOGY_NONE, MESH_TOPOLOGY_MAX_BUCKET = 0xFFFFFFFF, 65536
+MESH_DUPLICATES_KEEP, MESH_DUPLICATES_FIRST, MESH_DUPLICATES_CANCEL = 0, 1, 2
+MESH_REPAIR_ORIENT_NONE, MESH_REPAIR_ORIENT_CONSISTENT = 0, 1
+
+
+class MeshTopologyOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("buckets_log2", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshTopologyComponent(C.Structure):
+    _fields_ = [
+        ("label", C.c_uint32),
+        ("n_vertices", C.c_uint32),
+        ("n_edges", C.c_uint32),
+        ("n_triangles", C.c_uint32),
+        ("n_boundary_edges", C.c_uint32),
+        ("n_nonmanifold_edges", C.c_uint32),
+        ("n_inconsistent_edges", C.c_uint32),
+        ("n_patches", C.c_uint32),
+        ("euler", C.c_int32),
+        ("genus", C.c_int32),
+    ]
+
+
+# the same record as a numpy dtype (DeviceMesh.topology returns the table as a structured array)
+MESH_TOPOLOGY_COMPONENT_DTYPE = [(name, "<i4" if name in ("euler", "genus") else "<u4") for name, _ in MeshTopologyComponent._fields_]
+
+
+class MeshTopologyStats(C.Structure):
+    _fields_ = [
+        ("n_verts_used", C.c_uint32),
+        ("n_tris", C.c_uint32),
+        ("n_degenerate", C.c_uint32),
+        ("n_edges", C.c_uint32),
+        ("n_boundary_edges", C.c_uint32),
+        ("n_manifold_edges", C.c_uint32),
+        ("n_nonmanifold_edges", C.c_uint32),
+        ("n_inconsistent_edges", C.c_uint32),
+        ("max_faces_on_edge", C.c_uint32),
+        ("n_duplicate_tris", C.c_uint32),
+        ("n_folded_pairs", C.c_uint32),
+        ("n_components", C.c_uint32),
+        ("n_patches", C.c_uint32),
+        ("n_unorientable_patches", C.c_uint32),
+        ("n_boundary_components", C.c_uint32),
+        ("closed", C.c_uint32),
+        ("oriented", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("euler", C.c_int64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved2", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+class MeshRepairOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("weld", C.c_uint32),
+        ("drop_degenerate", C.c_uint32),
+        ("duplicates", C.c_uint32),
+        ("orient", C.c_uint32),
+        ("buckets_log2", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshRepairStats(C.Structure):
+    _fields_ = [
+        ("n_welded", C.c_uint32),
+        ("n_degenerate_dropped", C.c_uint32),
+        ("n_duplicates_dropped", C.c_uint32),
+        ("n_flipped", C.c_uint32),
+        ("n_patches", C.c_uint32),
+        ("n_unorientable_patches", C.c_uint32),
+        ("n_verts_in", C.c_uint32),
+        ("n_verts_out", C.c_uint32),
+        ("n_tris_in", C.c_uint32),
+        ("n_tris_out", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_TOPOLOGY_PROTOTYPES = {
+    "mesh_topology_abi_version": (_u32, []),
+    "mesh_topology_default_options": (_i, [C.POINTER(MeshTopologyOptions)]),
+    "mesh_topology": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshTopologyOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MeshTopologyStats)]),
+    "mesh_topology_table_free": (_i, [_ctx, C.c_void_p]),
+    "mesh_repair_default_options": (_i, [C.POINTER(MeshRepairOptions)]),
+    "mesh_repair": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshRepairOptions), C.POINTER(Mesh), C.c_void_p, C.POINTER(MeshRepairStats)]),
+}
+
 
 class Functions:
     """Bound, typed entry points of one library."""
@@ -784,13 +890,13 @@ class Functions:
 
 
 def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
-            mesh_visibility=False, mesh_project=False, mesh_draw=False):
+            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
     mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
     mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h),
-    mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h); only the HIP library exports those."""
+    mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h), mesh_topology=True MESH_TOPOLOGY_PROTOTYPES (include/rnb_mesh_topology.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
                      + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ())
-                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()))
+                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()) + ((MESH_TOPOLOGY_PROTOTYPES,) if mesh_topology else ()))

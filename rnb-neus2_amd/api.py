@@ -47,7 +47,7 @@ def load_library():
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
-                              mesh_visibility=True, mesh_project=True, mesh_draw=True)
+                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -70,6 +70,8 @@ def load_library():
             raise RuntimeError("mesh-project ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_draw_abi_version() != _abi.MESH_DRAW_ABI_VERSION:
             raise RuntimeError("mesh-draw ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_topology_abi_version() != _abi.MESH_TOPOLOGY_ABI_VERSION:
+            raise RuntimeError("mesh-topology ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -589,7 +591,7 @@ class Context:
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
-                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None):
+                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None, repair=None, topology=False):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -611,7 +613,15 @@ class Context:
         texture_from = (views, images) (with texture = S only): the texture is not baked from the model but projected from these images (rnb_mesh_project_views, see
         project_views, its defaults; the mesh's vertex normals weight the views when normals=True), with the model's albedo as the fallback of the texels no view
         reaches, and `texture` is the dict of DeviceMesh.project_views (`color` where a bake has `albedo`; texture_maps does not apply). With None (the default) nothing
-        of that runs."""
+        of that runs.
+        repair = dict(...): after simplify and before error / texture, still on the device, the mesh goes through rnb_mesh_repair with these arguments of
+        DeviceMesh.repair (weld, drop_degenerate, duplicates, orient, buckets_log2), and the dict gains `repair_stats`; with error=True the distance is then measured to
+        the repaired mesh. topology=True: the dict gains `topology`, the statistics of DeviceMesh.topology() of the final mesh. With None / False (the defaults)
+        nothing of that runs and the calls made are exactly those made without them."""
+        if repair is not None and not isinstance(repair, dict):
+            raise ValueError("repair must be None or a dict of DeviceMesh.repair's arguments")
+        if repair is not None and set(repair) - {"weld", "drop_degenerate", "duplicates", "orient", "buckets_log2"}:
+            raise ValueError("repair takes weld, drop_degenerate, duplicates, orient and buckets_log2")
         if texture_from is not None and texture is None:
             raise ValueError("texture_from needs texture")
         if texture_from is not None and len(texture_from) != 2:
@@ -631,8 +641,15 @@ class Context:
                 chain.append(culled)
             if grid is not None:
                 chain.append(chain[-1].simplify(*grid, placement=placement, stream=stream))
-                if error:
-                    simplify_error = chain[-2].distance_to(chain[-1], symmetric=True, stream=stream)
+                simplified = chain[-1]
+                before = chain[-2]
+            if repair is not None:
+                chain.append(chain[-1].repair(stream=stream, **repair))
+                repaired = chain[-1]
+            if grid is not None and error:
+                simplify_error = before.distance_to(chain[-1], symmetric=True, stream=stream)
+            if topology:
+                census = chain[-1].topology(stream=stream)
             if texture is not None and texture_from is not None:
                 baked = chain[-1].project_views(texture_from[0], texture_from[1], texture, fallback="model", inference=inference, stream=stream)
             elif texture is not None:
@@ -648,7 +665,11 @@ class Context:
             if keep is not None or orient is not None:
                 out["clean_stats"] = chain[1].stats
             if grid is not None:
-                out["simplify_stats"] = chain[-1].stats
+                out["simplify_stats"] = simplified.stats
+            if repair is not None:
+                out["repair_stats"] = repaired.stats
+            if topology:
+                out["topology"] = census
         finally:
             for m in chain:  # whatever exists by now, oldest first
                 m.free()
@@ -700,6 +721,44 @@ class Context:
             out["stats"] = cleaned.stats
             if table:
                 out["table"] = cleaned.table
+        return out
+
+    def _topology_options(self, buckets_log2=0):
+        opt = _abi.MeshTopologyOptions()
+        self._check(self.f.mesh_topology_default_options(C.byref(opt)))
+        opt.buckets_log2 = int(buckets_log2)
+        return opt
+
+    def _repair_options(self, weld=False, drop_degenerate=True, duplicates="first", orient="none", buckets_log2=0):
+        dups = {"keep": _abi.MESH_DUPLICATES_KEEP, "first": _abi.MESH_DUPLICATES_FIRST, "cancel": _abi.MESH_DUPLICATES_CANCEL}
+        orients = {"none": _abi.MESH_REPAIR_ORIENT_NONE, "consistent": _abi.MESH_REPAIR_ORIENT_CONSISTENT}
+        if duplicates not in dups:
+            raise ValueError("duplicates must be 'keep', 'first' or 'cancel'")
+        if orient not in orients:
+            raise ValueError("orient must be 'none' or 'consistent'")
+        opt = _abi.MeshRepairOptions()
+        self._check(self.f.mesh_repair_default_options(C.byref(opt)))
+        opt.weld, opt.drop_degenerate, opt.duplicates, opt.orient, opt.buckets_log2 = int(bool(weld)), int(bool(drop_degenerate)), dups[duplicates], orients[orient], int(buckets_log2)
+        return opt
+
+    def mesh_topology(self, verts, indices, edges=False, table=False, buckets_log2=0, stream=None):
+        """rnb_mesh_topology (include/rnb_mesh_topology.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3]): the dict of DeviceMesh.topology, which
+        describes the keys. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices) as m:
+            return m.topology(edges, table, buckets_log2, stream)
+
+    def repair_mesh(self, verts, indices, colors=None, normals=None, weld=False, drop_degenerate=True, duplicates="first", orient="none", vertex_map=False, buckets_log2=0,
+                    stream=None):
+        """rnb_mesh_repair (include/rnb_mesh_topology.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals; the
+        steps and their arguments are those of DeviceMesh.repair. Returns a dict of numpy arrays like clean_mesh, with `stats` = `repair_stats` and, with
+        vertex_map=True, `vertex_map`. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            repaired = m.repair(weld, drop_degenerate, duplicates, orient, vertex_map, buckets_log2, stream)
+        with repaired:
+            out = repaired.download()
+            out["stats"] = out["repair_stats"] = repaired.stats
+            if vertex_map:
+                out["vertex_map"] = repaired.vertex_map
         return out
 
     @staticmethod
@@ -1124,6 +1183,7 @@ class DeviceMesh(_abi.Mesh):
         super().__init__()
         self.ctx, self._buffers, self._stats, self._freed = ctx, buffers, None, False
         self._table, self._table_host = C.c_void_p(), None
+        self.vertex_map = None  # set by repair(vertex_map=True) on the mesh it returns
 
     n_verts = property(lambda self: _abi.Mesh.n_verts.__get__(self))
     n_triangles = property(lambda self: self.n_indices // 3)
@@ -1200,6 +1260,58 @@ class DeviceMesh(_abi.Mesh):
         c = self._live()
         opt, st = c._simplify_options(origin, cell, dims, placement), _abi.MeshSimplifyStats()
         return _returned_mesh(c, st, lambda m: c.f.mesh_simplify(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), m, C.byref(st)))
+
+    def topology(self, edges=False, table=False, buckets_log2=0, stream=None):
+        """rnb_mesh_topology (include/rnb_mesh_topology.h): the edge census of the mesh -> the dict of rnb_mesh_topology_stats (n_edges, n_boundary_edges,
+        n_nonmanifold_edges, n_inconsistent_edges, n_duplicate_tris, n_folded_pairs, n_components, n_patches, n_unorientable_patches, n_boundary_components, euler,
+        closed, oriented, ...). edges=True adds `n_faces`, `n_same` and `mate`, uint32[n_indices] per half-edge h = 3t + k (mate 0xFFFFFFFF where the edge is not
+        shared by exactly two faces); table=True adds `table`, one record per component (label, n_vertices, n_edges, n_triangles, n_boundary_edges,
+        n_nonmanifold_edges, n_inconsistent_edges, n_patches, euler, genus), ascending label. Nothing of the mesh changes; vertex-manifoldness is not examined."""
+        c = self._live()
+        opt, st, tab = c._topology_options(buckets_log2), _abi.MeshTopologyStats(), C.c_void_p()
+        n = max(self.n_indices, 1) * 4
+        arrays = []
+        try:
+            for _ in range(3 if edges else 0):
+                arrays.append(c.device_malloc(n))
+            ptrs = arrays if edges else [None] * 3
+            try:
+                c._check(c.f.mesh_topology(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), ptrs[0], ptrs[1], ptrs[2], C.byref(tab) if table else None, C.byref(st)))
+                out = st.as_dict()
+                if edges:
+                    for key, p in zip(("n_faces", "n_same", "mate"), arrays):
+                        out[key] = c.download(p, self.n_indices, np.uint32) if self.n_indices else np.empty(0, np.uint32)
+                if table:
+                    dt = np.dtype(_abi.MESH_TOPOLOGY_COMPONENT_DTYPE)
+                    out["table"] = c.download(tab.value, st.n_components, dt) if st.n_components else np.empty(0, dt)
+            finally:
+                if tab:
+                    c.f.mesh_topology_table_free(c._h, tab)
+        finally:
+            for p in arrays:
+                c.device_free(p)
+        return out
+
+    def repair(self, weld=False, drop_degenerate=True, duplicates="first", orient="none", vertex_map=False, buckets_log2=0, stream=None):
+        """rnb_mesh_repair (include/rnb_mesh_topology.h) -> the repaired DeviceMesh; its `stats` are the repair stats. In this order: weld (used vertices at one
+        position become the lowest-indexed of them), drop_degenerate, duplicates ("keep" / "first": the lowest-numbered triangle of a vertex set stays / "cancel":
+        opposite windings cancel, a folded pair goes entirely), orient ("none" / "consistent": every orientable patch is wound consistently across its manifold edges
+        by the smaller set of flips). vertex_map=True: `vertex_map` of the returned mesh is uint32[n_verts of this mesh], each input vertex's output index or 0xFFFFFFFF."""
+        c = self._live()
+        opt, st = c._repair_options(weld, drop_degenerate, duplicates, orient, buckets_log2), _abi.MeshRepairStats()
+        vmap = c.device_malloc(max(self.n_verts, 1) * 4) if vertex_map else None
+        try:
+            out = _returned_mesh(c, st, lambda m: c.f.mesh_repair(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), m, vmap, C.byref(st)))
+            if vertex_map:
+                try:
+                    out.vertex_map = c.download(vmap, self.n_verts, np.uint32) if self.n_verts else np.empty(0, np.uint32)
+                except BaseException:
+                    out.free()
+                    raise
+        finally:
+            if vmap:
+                c.device_free(vmap)
+        return out
 
     def _distance(self, other, opt, per_vertex, stream):
         """One rnb_mesh_distance call, self -> other; the dict distance_to returns for one direction."""

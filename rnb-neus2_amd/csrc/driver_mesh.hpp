@@ -1,5 +1,6 @@
 // driver_mesh.hpp -- rnb_sdf_lattice, rnb_marching_cubes and the mesh stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster,
-// rnb_mesh_draw_textured, rnb_mesh_visibility, rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views. What they share:
+// rnb_mesh_draw_textured, rnb_mesh_visibility, rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views, rnb_mesh_topology, rnb_mesh_repair
+// (include/rnb_mesh_topology.h; their hash join is tp_join, beside them). What they share:
 //   scan_exclusive, count_and_scan                  the prefix sums behind every numbering, and the count half of a count / write kernel pair
 //   MeshWorkspace, alloc_mesh, hand_over            the device memory of one call and the mesh it returns
 //   check_mesh_input, check_reserved, free_device   the argument checks every stage makes; the *_free functions
@@ -193,6 +194,10 @@ struct MeshCall {
 		if (int rc = read_flags(dflags, &hflags); rc != RNB_OK) return rc;
 		return (hflags & MESH_BAD_INDEX) ? bad_index() : RNB_OK;
 	}
+
+	// kernel(args...) in n_wg workgroups of MESH_WG threads on the call's stream (the topology stage's launches, the cleaner's kernels it reuses among them).
+	template <typename K, typename... A>
+	void launch(uint32_t n_wg, K kernel, A... args) const { hipLaunchKernelGGL(kernel, dim3(n_wg), dim3(MESH_WG), 0, s, args...); }
 
 	// An output mesh shaped like m (its attributes), held by the workspace.
 	int alloc_like(const rnb_mesh& m, rnb_mesh* o, uint32_t nvo, uint32_t nto) {
@@ -1397,6 +1402,273 @@ int rnb_mesh_project_views(rnb_ctx* c, void* stream, const rnb_mesh* mesh, const
 	out->size = S; out->block = A.block; out->blocks_per_row = A.bpr; out->n_tris = nt;
 	if (stats) {
 		stats->n_texels = hres.n_texels; stats->n_textured = hres.n_textured; stats->n_pairs_tested = hres.n_tested; stats->n_occluded = hres.n_occluded;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+
+// ---- mesh topology: census and repair (include/rnb_mesh_topology.h) ----
+uint32_t rnb_mesh_topology_abi_version(void) { return RNB_MESH_TOPOLOGY_ABI_VERSION; }
+
+int rnb_mesh_topology_default_options(rnb_mesh_topology_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_TOPOLOGY_ABI_VERSION;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_repair_default_options(rnb_mesh_repair_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_TOPOLOGY_ABI_VERSION;
+	opt->drop_degenerate = 1;
+	opt->duplicates = RNB_MESH_DUPLICATES_FIRST;
+	opt->orient = RNB_MESH_REPAIR_ORIENT_NONE;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_topology_table_free(rnb_ctx* c, rnb_mesh_topology_component* table) try {
+	if (!c) return fail(RNB_ERR_INVALID, "null argument");
+	if (table) (void)hipFree(table);
+	return RNB_OK;
+} RNB_GUARD
+
+extern "C++" {
+namespace {
+// The hash join of kernels_mesh_topology.cuh over n items: buckets counted, the guard, offsets, lists filled. j->join is ready for a walk; the caller releases j->offs and
+// j->items after it.
+struct TpTable { uint32_t* offs = nullptr; uint32_t* items = nullptr; TpJoin join{nullptr, nullptr, 0}; };
+template <typename KEYS>
+int tp_join(MeshCall& call, const KEYS& keys, uint32_t n, uint32_t forced_log2, TpResult* dres, TpTable* j) {
+	uint32_t log2 = forced_log2;
+	if (!log2) for (log2 = 4; log2 < 30 && (1ull << log2) < 2ull * n; ++log2) {}
+	const uint32_t n_buckets = 1u << log2;
+	uint32_t* scan = nullptr;
+	if (!call.ws.alloc(&j->offs, n_buckets) || !call.ws.alloc(&j->items, n) || !call.ws.alloc(&scan, scan_scratch_elems(n_buckets)))
+		return call.nomem("hipMalloc failed for " + std::to_string(n_buckets) + " buckets of " + std::to_string(n) + " items");
+	HIP_TRY(hipMemsetAsync(j->offs, 0, (size_t)n_buckets * 4, call.s));
+	call.launch(groups(n), k_tp_count<KEYS>, keys, n, log2, j->offs);
+	call.launch(groups(n_buckets), k_tp_max_load, (const uint32_t*)j->offs, n_buckets, dres);
+	HIP_TRY(hipGetLastError());
+	uint32_t fullest = 0, total = 0;
+	HIP_TRY(hipMemcpyAsync(&fullest, &dres->max_bucket, 4, hipMemcpyDeviceToHost, call.s));
+	HIP_TRY(hipStreamSynchronize(call.s));
+	if (fullest > RNB_MESH_TOPOLOGY_MAX_BUCKET)
+		return call.invalid("a bucket of the grouping holds " + std::to_string(fullest) + " items (more than RNB_MESH_TOPOLOGY_MAX_BUCKET = 65536): an edge, triangle or position is repeated that often" +
+		                    (forced_log2 ? ", or buckets_log2 forces too few buckets" : ""));
+	if (int rc = scan_exclusive(j->offs, n_buckets, call.s, &total, scan); rc != RNB_OK) return rc;
+	call.ws.release(scan);
+	call.launch(groups(n), k_tp_fill<KEYS>, keys, n, log2, j->offs, j->items);
+	HIP_TRY(hipGetLastError());
+	j->join = TpJoin{j->offs, j->items, log2};
+	return RNB_OK;
+}
+int tp_check_buckets(const char* name, uint32_t b) {
+	return (b == 0 || (b >= 4 && b <= 30)) ? RNB_OK : fail(RNB_ERR_INVALID, std::string(name) + ": buckets_log2 must be 0 or 4 .. 30");
+}
+} // namespace
+} // extern "C++"
+
+int rnb_mesh_topology(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_topology_options* opt, uint32_t* n_faces, uint32_t* n_same, uint32_t* mate,
+                      rnb_mesh_topology_component** table_dev, rnb_mesh_topology_stats* stats) try {
+	if (table_dev) *table_dev = nullptr;
+	if (!c || !in || !opt) return fail(RNB_ERR_INVALID, "rnb_mesh_topology: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_topology", in); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_TOPOLOGY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_topology: options abi_version mismatch (expected RNB_MESH_TOPOLOGY_ABI_VERSION)");
+	if (int rc = tp_check_buckets("rnb_mesh_topology", opt->buckets_log2); rc != RNB_OK) return rc;
+	if (int rc = check_reserved("rnb_mesh_topology", opt->reserved); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_topology", c, stream);
+	const hipStream_t s = call.s;
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	TpResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	uint32_t n_comp = 0;
+	rnb_mesh_topology_component* table = nullptr;
+	if (nt) {
+		const uint32_t g_v = groups(nv), g_t = groups(nt), g_h = groups(m.n_indices);
+		uint32_t *parent = nullptr, *used = nullptr, *cid = nullptr, *scan = nullptr;
+		TpResult* dres = nullptr;
+		if (!call.ws.alloc(&parent, nv) || !call.ws.alloc(&used, nv) || !call.ws.alloc(&cid, nv) || !call.ws.alloc(&scan, scan_scratch_elems(nv)) || !call.ws.alloc(&dres, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
+		HIP_TRY(hipMemsetAsync(dres, 0, sizeof(hres), s));
+		// 1. every index is range-checked before any is used as an address
+		call.launch(g_v, k_cl_init, parent, nv);
+		if (int rc = call.check_indices(m, used, &dres->flags); rc != RNB_OK) return rc;
+		// 2. the cleaner's components; the table's labels and vertex counts
+		call.launch(g_t, k_cl_hook, (const uint32_t*)m.indices, nt, parent);
+		call.launch(g_v, k_cl_flatten, parent, nv);
+		call.launch(g_v, k_cl_roots, (const uint32_t*)parent, (const uint32_t*)used, cid, nv);
+		HIP_TRY(hipGetLastError());
+		if (int rc = scan_exclusive(cid, nv, s, &n_comp, scan); rc != RNB_OK) return rc;
+		if (!call.ws.alloc(&table, n_comp)) return call.nomem("hipMalloc failed for the table of " + std::to_string(n_comp) + " components");
+		HIP_TRY(hipMemsetAsync(table, 0, std::max<size_t>(n_comp, 1) * sizeof(rnb_mesh_topology_component), s));
+		call.launch(g_v, k_tp_relabel, parent, (const uint32_t*)used, (const uint32_t*)cid, table, nv);
+		const uint32_t* comp = parent;
+		call.launch(g_v, k_tp_comp_sums, comp, nv, table, dres);
+		HIP_TRY(hipGetLastError());
+		call.ws.release(used, cid, scan);
+		const TpTris tris{(const uint32_t*)m.indices, nullptr};
+		// 3. triangles by vertex set: degenerate ones, duplicates, folded pairs
+		{
+			TpTable j;
+			const TpTriKeys keys{tris};
+			if (int rc = tp_join(call, keys, nt, opt->buckets_log2, dres, &j); rc != RNB_OK) return rc;
+			call.launch(g_t, k_tp_tris<false>, keys, nt, j.join, 0u, (uint32_t*)nullptr, comp, table, dres);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			call.ws.release(j.offs, j.items);
+		}
+		// 4. half-edges by edge: the per-half-edge arrays, the edge counts, the double cover and the boundary components united
+		uint32_t *cover = nullptr, *bparent = nullptr, *bmark = nullptr;
+		if (!call.ws.alloc(&cover, 2 * (size_t)nt) || !call.ws.alloc(&bparent, nv) || !call.ws.alloc(&bmark, nv)) return call.nomem("hipMalloc failed for the double cover of " + std::to_string(nt) + " triangles");
+		call.launch(groups(2 * (uint64_t)nt), k_cl_init, cover, 2u * nt);
+		call.launch(g_v, k_cl_init, bparent, nv);
+		HIP_TRY(hipMemsetAsync(bmark, 0, (size_t)nv * 4, s));
+		{
+			TpTable j;
+			const TpEdgeKeys keys{tris};
+			if (int rc = tp_join(call, keys, m.n_indices, opt->buckets_log2, dres, &j); rc != RNB_OK) return rc;
+			call.launch(g_h, k_tp_edges, keys, m.n_indices, j.join, n_faces, n_same, mate, cover, bparent, bmark, comp, table, dres);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			call.ws.release(j.offs, j.items);
+		}
+		// 5. patches, boundary components, the table's derived columns
+		call.launch(groups(2 * (uint64_t)nt), k_cl_flatten, cover, 2u * nt);
+		call.launch(g_t, k_tp_patches, tris, nt, (const uint32_t*)cover, (uint32_t*)nullptr, comp, table, dres);
+		call.launch(g_v, k_tp_boundary_roots, (const uint32_t*)bparent, (const uint32_t*)bmark, nv, dres);
+		call.launch(groups(std::max(n_comp, 1u)), k_tp_table_finish, table, n_comp);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		call.ws.release(parent, cover, bparent, bmark, dres);
+	} else if (table_dev && !call.ws.alloc(&table, 1))
+		return call.nomem("hipMalloc failed for the table");
+	if (table_dev) *table_dev = (rnb_mesh_topology_component*)call.ws.keep(table);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_verts_used = hres.n_verts_used; stats->n_tris = nt; stats->n_degenerate = hres.n_degenerate;
+		stats->n_edges = hres.n_edges; stats->n_boundary_edges = hres.n_boundary_edges; stats->n_manifold_edges = hres.n_manifold_edges;
+		stats->n_nonmanifold_edges = hres.n_nonmanifold_edges; stats->n_inconsistent_edges = hres.n_inconsistent_edges; stats->max_faces_on_edge = hres.max_faces_on_edge;
+		stats->n_duplicate_tris = hres.n_duplicate_tris; stats->n_folded_pairs = hres.n_folded_pairs;
+		stats->n_components = n_comp; stats->n_patches = hres.n_patches; stats->n_unorientable_patches = hres.n_unorientable_patches;
+		stats->n_boundary_components = hres.n_boundary_components;
+		stats->closed = (!hres.n_boundary_edges && !hres.n_nonmanifold_edges) ? 1u : 0u;
+		stats->oriented = (stats->closed && !hres.n_inconsistent_edges) ? 1u : 0u;
+		stats->euler = (int64_t)hres.n_verts_used - (int64_t)hres.n_edges + ((int64_t)nt - (int64_t)hres.n_degenerate);
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_repair(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_repair_options* opt, rnb_mesh* out, uint32_t* vertex_map, rnb_mesh_repair_stats* stats) try {
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_repair: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_repair", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_TOPOLOGY_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_repair: options abi_version mismatch (expected RNB_MESH_TOPOLOGY_ABI_VERSION)");
+	if (opt->weld > 1u || opt->drop_degenerate > 1u) return fail(RNB_ERR_INVALID, "rnb_mesh_repair: weld and drop_degenerate must be 0 or 1");
+	if (opt->duplicates > RNB_MESH_DUPLICATES_CANCEL) return fail(RNB_ERR_INVALID, "rnb_mesh_repair: unknown duplicates mode");
+	if (opt->orient > RNB_MESH_REPAIR_ORIENT_CONSISTENT) return fail(RNB_ERR_INVALID, "rnb_mesh_repair: unknown orient mode");
+	if (int rc = tp_check_buckets("rnb_mesh_repair", opt->buckets_log2); rc != RNB_OK) return rc;
+	if (int rc = check_reserved("rnb_mesh_repair", opt->reserved); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_repair", c, stream);
+	const hipStream_t s = call.s;
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	TpResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	uint32_t nvo = 0, nto = 0;
+	rnb_mesh o;
+	if (nt) {
+		const uint32_t g_v = groups(nv), g_t = groups(nt), g_h = groups(m.n_indices);
+		uint32_t *used = nullptr, *widx = nullptr, *flags = nullptr, *rep = nullptr;
+		TpResult* dres = nullptr;
+		if (!call.ws.alloc(&used, nv) || !call.ws.alloc(&widx, m.n_indices) || !call.ws.alloc(&flags, nt) || !call.ws.alloc(&dres, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nt) + " triangles");
+		HIP_TRY(hipMemsetAsync(dres, 0, sizeof(hres), s));
+		if (int rc = call.check_indices(m, used, &dres->flags); rc != RNB_OK) return rc;
+		// 1. weld: the working indices point at the lowest vertex of every position
+		if (opt->weld) {
+			uint32_t hflags = 0;
+			call.launch(g_v, k_tp_finite, (const uint32_t*)m.verts, (const uint32_t*)used, nv, dres);
+			HIP_TRY(hipGetLastError());
+			if (int rc = call.read_flags(&dres->flags, &hflags); rc != RNB_OK) return rc;
+			if (hflags & TP_NOT_FINITE) return call.invalid("a coordinate of a used vertex is not finite (weld compares coordinates)");
+			if (!call.ws.alloc(&rep, nv)) return call.nomem("hipMalloc failed for the weld map");
+			TpTable j;
+			const TpPosKeys keys{(const uint32_t*)m.verts, used};
+			if (int rc = tp_join(call, keys, nv, opt->buckets_log2, dres, &j); rc != RNB_OK) return rc;
+			call.launch(g_v, k_tp_weld, keys, nv, j.join, rep, dres);
+			call.launch(g_h, k_tp_rewrite, (const uint32_t*)m.indices, (const uint32_t*)rep, m.n_indices, widx);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			call.ws.release(j.offs, j.items);
+		} else HIP_TRY(hipMemcpyAsync(widx, m.indices, (size_t)m.n_indices * 4, hipMemcpyDeviceToDevice, s));
+		call.ws.release(used);
+		// 2. degenerate triangles
+		call.launch(g_t, k_tp_degenerate, (const uint32_t*)widx, nt, opt->drop_degenerate, flags, dres);
+		HIP_TRY(hipGetLastError());
+		const TpTris tris{widx, flags};
+		// 3. duplicates
+		if (opt->duplicates != RNB_MESH_DUPLICATES_KEEP) {
+			uint32_t* stay = nullptr;
+			if (!call.ws.alloc(&stay, nt)) return call.nomem("hipMalloc failed for the duplicate flags");
+			TpTable j;
+			const TpTriKeys keys{tris};
+			if (int rc = tp_join(call, keys, nt, opt->buckets_log2, dres, &j); rc != RNB_OK) return rc;
+			call.launch(g_t, k_tp_tris<true>, keys, nt, j.join, opt->duplicates, stay, (const uint32_t*)nullptr, (rnb_mesh_topology_component*)nullptr, dres);
+			call.launch(g_t, k_tp_apply, (const uint32_t*)stay, nt, flags, dres);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			call.ws.release(j.offs, j.items, stay);
+		}
+		// 4. orient: the double cover over the manifold edges of what is left, the sheet that flips fewer
+		if (opt->orient == RNB_MESH_REPAIR_ORIENT_CONSISTENT) {
+			uint32_t *cover = nullptr, *sheet = nullptr;
+			if (!call.ws.alloc(&cover, 2 * (size_t)nt) || !call.ws.alloc(&sheet, 2 * (size_t)nt)) return call.nomem("hipMalloc failed for the double cover of " + std::to_string(nt) + " triangles");
+			call.launch(groups(2 * (uint64_t)nt), k_cl_init, cover, 2u * nt);
+			HIP_TRY(hipMemsetAsync(sheet, 0, 2 * (size_t)nt * 4, s));
+			TpTable j;
+			const TpEdgeKeys keys{tris};
+			if (int rc = tp_join(call, keys, m.n_indices, opt->buckets_log2, dres, &j); rc != RNB_OK) return rc;
+			call.launch(g_h, k_tp_edges, keys, m.n_indices, j.join, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, cover, (uint32_t*)nullptr, (uint32_t*)nullptr,
+			                   (const uint32_t*)nullptr, (rnb_mesh_topology_component*)nullptr, (TpResult*)nullptr);
+			call.launch(groups(2 * (uint64_t)nt), k_cl_flatten, cover, 2u * nt);
+			call.launch(g_t, k_tp_patches, tris, nt, (const uint32_t*)cover, sheet, (const uint32_t*)nullptr, (rnb_mesh_topology_component*)nullptr, dres);
+			call.launch(g_t, k_tp_flip, tris, nt, (const uint32_t*)cover, (const uint32_t*)sheet, flags, dres);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			call.ws.release(j.offs, j.items, cover, sheet);
+		}
+		// 5. compaction: the vertices the remaining triangles use, the new numbering
+		uint32_t *vkeep = nullptr, *vmap = nullptr, *twg = nullptr, *scan = nullptr;
+		if (!call.ws.alloc(&vkeep, nv) || !call.ws.alloc(&vmap, nv) || !call.ws.alloc(&twg, g_t) || !call.ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))))
+			return call.nomem("hipMalloc failed for the compaction of " + std::to_string(nv) + " vertices");
+		HIP_TRY(hipMemsetAsync(vkeep, 0, (size_t)nv * 4, s));
+		call.launch(g_t, k_tp_mark, (const uint32_t*)widx, (const uint32_t*)flags, nt, vkeep);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(vmap, vkeep, (size_t)nv * 4, hipMemcpyDeviceToDevice, s));
+		rnb_mesh w = m;
+		w.indices = widx;
+		if (int rc = call.compact(w, TpKeep{vkeep, flags}, vmap, twg, scan, &o, &nvo, &nto); rc != RNB_OK) return rc;
+		if (vertex_map) call.launch(g_v, k_tp_vertex_map, (const uint32_t*)rep, (const uint32_t*)vkeep, (const uint32_t*)vmap, nv, vertex_map);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		call.ws.release(widx, flags, rep, vkeep, vmap, twg, scan, dres);
+	} else {
+		if (!alloc_mesh(call.ws, &o, 0, 0, m.colors != nullptr, m.normals != nullptr)) return call.nomem("hipMalloc failed for the output mesh");
+		if (vertex_map && nv) { HIP_TRY(hipMemsetAsync(vertex_map, 0xFF, (size_t)nv * 4, s)); HIP_TRY(hipStreamSynchronize(s)); }
+	}
+	hand_over(call.ws, o, out);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_welded = hres.n_welded; stats->n_degenerate_dropped = hres.n_degenerate; stats->n_duplicates_dropped = hres.n_dropped; stats->n_flipped = hres.n_flipped;
+		stats->n_patches = hres.n_patches; stats->n_unorientable_patches = hres.n_unorientable_patches;
+		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
 		call.finish(stats);
 	}
 	return RNB_OK;

@@ -1,11 +1,11 @@
 // mesh_common.cuh — what the mesh stages share (every kernels_mesh*.cuh file); the only header they include from each other (but for kernels_mesh_visibility.cuh, which
-// runs the rasteriser's fill and the cleaner's components and includes both, and kernels_mesh_project.cuh and kernels_mesh_draw.cuh, which call the baker's and the
+// runs the rasteriser's fill and the cleaner's components and includes both, kernels_mesh_topology.cuh, which unites with the cleaner's cl_find / cl_unite, and kernels_mesh_project.cuh and kernels_mesh_draw.cuh, which call the baker's and the
 // rasteriser's device functions):
 //   MESH_WG, MESH_NONE, MESH_BAD_INDEX             the workgroup width of every mesh kernel, the "none" index, the bit k_mesh_validate sets in a stage's flag word
 //   k_scan_blocks / k_scan_add, wg_exclusive_256   the prefix sums that number every vertex, triangle, brick and cluster (the driver's scan_exclusive; the count / write kernel pairs)
 //   k_mesh_validate                                every index of a triangle list range-checked before any is used as an address, used[v] marked
-//   k_compact_verts, k_compact_tris<WRITE>         the stable compaction of a mesh to the part a predicate keeps (the cleaner's ClKeep, the visibility stage's MvKeep;
-//                                                  the driver's MeshCall::compact)
+//   k_compact_verts, k_compact_tris<WRITE>         the stable compaction of a mesh to the part a predicate keeps (the cleaner's ClKeep, the visibility stage's MvKeep,
+//                                                  the repair's TpKeep of kernels_mesh_topology.cuh, include/rnb_mesh_topology.h; the driver's MeshCall::compact)
 //   wave_sum, wave_group_next                      the sums of the lanes of a wavefront that hold the same key, group by group
 //   mc_emit_verts, mc_corner, mc_edge, McTable     the marching-cubes arithmetic and numbering: stated once, so the dense and the sparse extractor agree bit for bit by construction
 // Vector loads, stores and atomics only.

@@ -6,6 +6,7 @@
 //        [--keep all|largest] [--orient none|outward] [--simplify N [--placement quadric|mean] [--report-error]] [--report-views [--views-out FILE]]
 //        [--texture S [--texture-maps albedo[,normal]] [--texture-from views [--texture-mode blend|best] [--texture-depth-tolerance T] [--texture-min-cos C]]]
 //        [--keep-seen component|faces [--seen-min-views N] [--seen-rings R] [--seen-masks [--seen-max-off N]] [--seen-supersample K]]
+//        [--repair [--weld] [--duplicates keep|first|cancel] [--orient-consistent]] [--report-topology]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -33,6 +34,11 @@
 // include/rnb_mesh_draw.h): per view and in the means textured_mean_angle_deg and textured_median_angle_deg (when a normal map was baked: the normal-mapped surface
 // against the input normal maps) and albedo_mae, albedo_rmse, albedo_psnr_db (when there is a colour map and the scene has albedo maps), with every digit of a double.
 // A PSNR that is not finite (the drawn colours equal the input's: mse 0), per view or in the means, is written as null (view_metrics::num_full).
+// With --repair the device mesh goes through rnb_mesh_repair (include/rnb_mesh_topology.h) after --simplify, whose clustering creates what it removes: degenerate
+// triangles, duplicate triangles (--duplicates first, the default: one per vertex set stays; cancel: opposite windings cancel, a folded pair goes entirely; keep),
+// with --weld vertices at one position first, with --orient-consistent every orientable patch wound consistently across its manifold edges. When --keep / --orient
+// are given too, the cleaning then runs after the repair instead of first (extract, keep-seen, simplify, repair, clean), so that --orient outward acts on
+// consistently wound components. With --report-topology the census of the mesh as written (rnb_mesh_topology) is printed as one JSON line, {"topology": {...}}.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -44,6 +50,7 @@
 #include "../../include/rnb_mesh_draw.h"
 #include "../../include/rnb_mesh_visibility.h"
 #include "../../include/rnb_mesh_project.h"
+#include "../../include/rnb_mesh_topology.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -95,6 +102,11 @@ const Flag FLAGS[] = {
 	{"texture-mode", "MODE", "--texture-from only. blend (default): the views weighted by cos^2 * alpha; best: the view of the greatest weight alone."},
 	{"texture-depth-tolerance", "T", "--texture-from only. Relative depth slack of the occlusion test (>= 0, default 0.00390625)."},
 	{"texture-min-cos", "C", "--texture-from only. A view that looks at the surface at a cosine of at most C is skipped ([0, 1), default 0.1)."},
+	{"repair", nullptr, "(takes no value). Repair the mesh on the device after --simplify: degenerate and duplicate triangles go; --keep / --orient then act on the repaired mesh."},
+	{"weld", nullptr, "--repair only (takes no value). Vertices at one position become one vertex first."},
+	{"duplicates", "MODE", "--repair only. first (default): one triangle per vertex set stays; cancel: opposite windings cancel, folded pairs go entirely; keep: none is removed."},
+	{"orient-consistent", nullptr, "--repair only (takes no value). Wind every orientable patch consistently across its shared edges, by the smaller set of flips."},
+	{"report-topology", nullptr, "(takes no value). Print the edge census of the written mesh as one JSON line: edges by kind, duplicates, patches, boundary loops, Euler characteristic."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -364,6 +376,9 @@ int main(int argc, char** argv) {
 	bool want_seen = false, texture_from = false;
 	SeenOptions seen;
 	ProjectOptions project;
+	bool repair = false, report_topology = false;
+	rnb_mesh_repair_options repair_opt;
+	std::memset(&repair_opt, 0, sizeof(repair_opt));
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -464,6 +479,11 @@ int main(int argc, char** argv) {
 			project.min_cos_given = true;
 			if (!(project.min_cos >= 0.0f && project.min_cos < 1.0f)) throw ParseError("Argument 'texture-min-cos' must be in [0, 1)");
 		}
+		if (a.count("repair")) repair = true;
+		for (const char* sub : {"weld", "duplicates", "orient-consistent"})
+			if (a.count(sub) && !repair) throw ParseError(std::string("Argument '") + sub + "' is only used with --repair");
+		if (a.count("duplicates") && a["duplicates"] != "keep" && a["duplicates"] != "first" && a["duplicates"] != "cancel") throw ParseError("Argument 'duplicates' must be keep, first or cancel");
+		if (a.count("report-topology")) report_topology = true;
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
 		print_help(std::cerr, argv[0]);
@@ -513,7 +533,7 @@ int main(int argc, char** argv) {
 		rnb_mesh_stats st;
 		RNB_CHECK(rnb_extract_mesh(ctx, nullptr, &mo, &dm, &st));
 		rnb_mesh_clean_stats cs;
-		if (clean) { // device to device; the ring normals below are then those of the cleaned mesh
+		const auto run_clean = [&]() { // device to device; the ring normals below are then those of the cleaned mesh
 			rnb_mesh_clean_options co;
 			RNB_CHECK(rnb_mesh_clean_default_options(&co));
 			co.keep = keep; co.orient = orient;
@@ -521,7 +541,8 @@ int main(int argc, char** argv) {
 			RNB_CHECK(rnb_mesh_free(ctx, &dm));
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
-		}
+		};
+		if (clean && !repair) run_clean(); // (with --repair: after it, below)
 		std::string seen_report;
 		if (want_seen) { // device to device, after the cleaning and before the simplification
 			keep_seen(ctx, ds, dm, seen, &cm, seen_report);
@@ -549,6 +570,24 @@ int main(int argc, char** argv) {
 			RNB_CHECK(rnb_mesh_free(ctx, &dm));
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
+		}
+		rnb_mesh_repair_stats rs;
+		if (repair) { // device to device, after the simplification; the cleaning, if asked for, on what it leaves
+			RNB_CHECK(rnb_mesh_repair_default_options(&repair_opt));
+			repair_opt.weld = a.count("weld") ? 1u : 0u;
+			if (a.count("duplicates")) repair_opt.duplicates = a["duplicates"] == "keep" ? RNB_MESH_DUPLICATES_KEEP : (a["duplicates"] == "cancel" ? RNB_MESH_DUPLICATES_CANCEL : RNB_MESH_DUPLICATES_FIRST);
+			if (a.count("orient-consistent")) repair_opt.orient = RNB_MESH_REPAIR_ORIENT_CONSISTENT;
+			RNB_CHECK(rnb_mesh_repair(ctx, nullptr, &dm, &repair_opt, &cm, nullptr, &rs));
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+			if (clean) run_clean();
+		}
+		rnb_mesh_topology_stats tp;
+		if (report_topology) { // of the mesh as it will be written
+			rnb_mesh_topology_options to;
+			RNB_CHECK(rnb_mesh_topology_default_options(&to));
+			RNB_CHECK(rnb_mesh_topology(ctx, nullptr, &dm, &to, nullptr, nullptr, nullptr, nullptr, &tp));
 		}
 		// --report-views: made here, while the mesh is on the device and in the frame of the loaded views; printed and written after the mesh's own lines, below
 		std::string views_report, views_json;
@@ -598,11 +637,22 @@ int main(int argc, char** argv) {
 		std::printf("%u^3: %llu of %llu bricks kept, %llu evaluated (%.1f %% of the lattice), %llu with a sign change, peak workspace %.1f MB, %.1f ms\n", res,
 		            (unsigned long long)st.n_kept, (unsigned long long)st.n_bricks, (unsigned long long)st.n_evaluated,
 		            100.0 * (double)st.n_points_evaluated / ((double)res * res * res), (unsigned long long)st.n_sign_change, (double)st.peak_workspace / 1e6, st.ms);
-		if (clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
+		if (clean && !repair) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
 		                       cs.n_verts_in, cs.n_verts_out, cs.ms);
 		if (want_seen) std::fputs(seen_report.c_str(), stdout);
 		if (simplify) std::printf("simplify: %u clusters, %u -> %u triangles (%u collapsed), %u -> %u vertices, %u clamped, %u at the mean, %.1f ms\n", ss.n_clusters, ss.n_tris_in,
 		                          ss.n_tris_out, ss.n_tris_collapsed, ss.n_verts_in, ss.n_verts_out, ss.n_clamped, ss.n_fallback, ss.ms);
+		if (repair) std::printf("repair: %u welded, %u degenerate and %u duplicate triangles dropped, %u flipped, %u patches of which %u unorientable, %u -> %u triangles, %u -> %u vertices, %.1f ms\n",
+		                        rs.n_welded, rs.n_degenerate_dropped, rs.n_duplicates_dropped, rs.n_flipped, rs.n_patches, rs.n_unorientable_patches, rs.n_tris_in, rs.n_tris_out, rs.n_verts_in,
+		                        rs.n_verts_out, rs.ms);
+		if (clean && repair) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
+		                                 cs.n_verts_in, cs.n_verts_out, cs.ms);
+		if (report_topology)
+			std::printf("{\"topology\": {\"n_verts_used\": %u, \"n_tris\": %u, \"n_degenerate\": %u, \"n_edges\": %u, \"n_boundary_edges\": %u, \"n_manifold_edges\": %u, \"n_nonmanifold_edges\": %u, "
+			            "\"n_inconsistent_edges\": %u, \"max_faces_on_edge\": %u, \"n_duplicate_tris\": %u, \"n_folded_pairs\": %u, \"n_components\": %u, \"n_patches\": %u, "
+			            "\"n_unorientable_patches\": %u, \"n_boundary_components\": %u, \"closed\": %u, \"oriented\": %u, \"euler\": %lld}}\n",
+			            tp.n_verts_used, tp.n_tris, tp.n_degenerate, tp.n_edges, tp.n_boundary_edges, tp.n_manifold_edges, tp.n_nonmanifold_edges, tp.n_inconsistent_edges, tp.max_faces_on_edge,
+			            tp.n_duplicate_tris, tp.n_folded_pairs, tp.n_components, tp.n_patches, tp.n_unorientable_patches, tp.n_boundary_components, tp.closed, tp.oriented, (long long)tp.euler);
 		if (report_error) {
 			double mean[2], rms[2];
 			for (int k = 0; k < 2; ++k) {

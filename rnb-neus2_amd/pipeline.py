@@ -168,7 +168,8 @@ def postprocess_mesh(data_dir, output_mesh_path, logger=None):
     shutil.rmtree(os.path.join(data_dir, "output"), ignore_errors=True)
 
 
-def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None, texture_from=None):
+def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None, texture_from=None,
+                            repair=None, report_topology=False):
     """The last stage on the device: one `build/mesh` process that extracts the mesh of the stage-2 snapshot (plan_two_stage passes --save-snapshot) at `resolution`,
     keeps the largest connected component and turns it outward (include/rnb_mesh_clean.h), and writes `output_mesh_path`. Pure; the snapshot named here is the first
     of snapshot_candidates, run_device_postprocess replaces it by the one that exists. simplify = N: the cleaned mesh is then simplified on N^3 cells over the
@@ -179,7 +180,10 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
     keep_seen = "component" or "faces", or a dict(unit=..., min_views=N, rings=R, masks=True, max_off=N, supersample=K) of which only `unit` is needed: what no camera of
     the scene sees is dropped on the device after the cleaning and before the simplification (include/rnb_mesh_visibility.h, build/mesh --keep-seen ... and its
     --seen-* flags); None (the default) plans the command without it. texture_from = "views" (with texture only): the texture is projected from the scene's albedo maps
-    through their cameras (include/rnb_mesh_project.h, build/mesh --texture-from views), the model's albedo where no view reaches; None (the default) plans the command without it."""
+    through their cameras (include/rnb_mesh_project.h, build/mesh --texture-from views), the model's albedo where no view reaches; None (the default) plans the command without it.
+    repair = True or a dict(weld=bool, duplicates="keep" / "first" / "cancel", orient_consistent=bool): the mesh is repaired on the device after the simplification, and
+    the cleaning then acts on the repaired mesh (include/rnb_mesh_topology.h, build/mesh --repair and its flags); report_topology: build/mesh --report-topology prints
+    the census of the final mesh as one JSON line. None / False (the defaults) plan the command without them."""
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if texture_from not in (None, "views"):
@@ -196,6 +200,25 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
         argv += ["--texture-from", texture_from]
     if keep_seen is not None:
         argv += keep_seen_flags(keep_seen)
+    if repair:
+        argv += repair_flags(repair)
+    if report_topology:
+        argv += ["--report-topology"]
+    return argv
+
+
+def repair_flags(repair):
+    """The --repair flags of build/mesh for plan_device_postprocess' repair."""
+    rp = {} if repair is True else dict(repair)
+    if set(rp) - {"weld", "duplicates", "orient_consistent"} or rp.get("duplicates") not in (None, "keep", "first", "cancel"):
+        raise ValueError("repair must be True or a dict of weld, duplicates ('keep', 'first' or 'cancel') and orient_consistent")
+    argv = ["--repair"]
+    if rp.get("weld"):
+        argv += ["--weld"]
+    if rp.get("duplicates") is not None:
+        argv += ["--duplicates", rp["duplicates"]]
+    if rp.get("orient_consistent"):
+        argv += ["--orient-consistent"]
     return argv
 
 
@@ -228,11 +251,11 @@ def default_mesh_exe(testbed_path):
 
 
 def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None, simplify=None, report_views=False, texture=None, keep_seen=None,
-                           texture_from=None):
+                           texture_from=None, repair=None, report_topology=False):
     """postprocess_mesh's job without the OBJ round trip: runs plan_device_postprocess' command, then drops the training output directory as postprocess_mesh does."""
     logger = logger or SimpleLogger()
     cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=simplify, report_views=report_views, texture=texture, keep_seen=keep_seen,
-                                  texture_from=texture_from)
+                                  texture_from=texture_from, repair=repair, report_topology=report_topology)
     found = [p for p in snapshot_candidates(data_dir, max_steps) if os.path.exists(p)]
     if not found:
         raise RuntimeError("Snapshot not found after {} iterations".format(max_steps))
@@ -254,7 +277,7 @@ def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, me
 def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mesh_resolution=1024, scaling_mode="auto", sphere_scale=1.0, margin_px=20,
                       warmup_ratio=0.1, mask_weight=1.0, super_normal=False, use_l1=False, use_rgb_plus=True, has_albedo=False,
                       albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None, device_postprocess=False, mesh_exe=None, simplify=None, report_views=False, texture=None,
-                      keep_seen=None, texture_from=None):
+                      keep_seen=None, texture_from=None, repair=None, report_topology=False):
     """load -> prepare (<output_dir>/prepared_data) -> train (two-stage, or warm-up + albedo scaling + two-stage when
     `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
     device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh;
@@ -263,7 +286,11 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     the textured mesh's, textured_* and albedo_* of include/rnb_mesh_draw.h, whose lines build/mesh prints and this function logs with the others);
     texture = S (with device_postprocess only): that step also bakes an albedo texture of S x S texels: mesh.obj gets vt records, mesh.mtl and mesh_albedo.png beside it;
     keep_seen (with device_postprocess only): that step also drops what no camera sees (plan_device_postprocess describes the value; build/mesh --keep-seen);
-    texture_from = "views" (with texture only): the texture is projected from the input albedo maps instead of baked from the model (build/mesh --texture-from views)."""
+    texture_from = "views" (with texture only): the texture is projected from the input albedo maps instead of baked from the model (build/mesh --texture-from views);
+    repair / report_topology (with device_postprocess only): that step also repairs the mesh after the simplification / prints its census (plan_device_postprocess
+    describes the values; build/mesh --repair, --report-topology)."""
+    if (repair or report_topology) and not device_postprocess:
+        raise ValueError("repair and report_topology need device_postprocess")
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if keep_seen is not None and not device_postprocess:
@@ -291,7 +318,7 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     output_mesh = os.path.join(output_dir, "mesh.obj")
     if device_postprocess:
         run_device_postprocess(data_dir, max_steps, mesh_resolution, output_mesh, mesh_exe or default_mesh_exe(testbed_path), logger, simplify=simplify, report_views=report_views, texture=texture,
-                               keep_seen=keep_seen, texture_from=texture_from)
+                               keep_seen=keep_seen, texture_from=texture_from, repair=repair, report_topology=report_topology)
     else:
         postprocess_mesh(data_dir, output_mesh, logger)
     logger.info("=== Pipeline complete ===")

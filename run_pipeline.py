@@ -46,6 +46,11 @@ _SPEC = """
 --seen-masks        | flag  |        | --keep-seen only: the alpha of the input normal maps are the masks
 --seen-max-off      | int   |        | --seen-masks only: also drop what lies off the mask in more than N views
 --seen-supersample  | int   |        | --keep-seen only: measure at K times the views' resolution
+--repair            | flag  |        | --device-postprocess only: repair the final mesh on the GPU after --simplify: degenerate and duplicate triangles go (build/mesh --repair)
+--weld              | flag  |        | --repair only: vertices at one position become one vertex first
+--duplicates        | str   |        | --repair only: keep, first (build/mesh's default) or cancel
+--orient-consistent | flag  |        | --repair only: wind every orientable patch consistently across its shared edges
+--report-topology   | flag  |        | --device-postprocess only: print the edge census of the final mesh as one JSON line (build/mesh --report-topology)
 """
 
 
@@ -75,7 +80,8 @@ def pipeline_kwargs(ns):
     renamed = {"input": "input_path", "testbed": "testbed_path", "output": "output_dir", "supernormal": "super_normal", "l1": "use_l1",
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
     kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "texture_from", "keep_seen", "seen_min_views",
-                                                                                "seen_rings", "seen_masks", "seen_max_off", "seen_supersample")}
+                                                                                "seen_rings", "seen_masks", "seen_max_off", "seen_supersample", "repair", "weld", "duplicates", "orient_consistent",
+                                                                                "report_topology")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
@@ -91,6 +97,10 @@ def pipeline_kwargs(ns):
         if ns.keep_seen:
             ks = dict(unit=ns.keep_seen, min_views=ns.seen_min_views, rings=ns.seen_rings, masks=ns.seen_masks or None, max_off=ns.seen_max_off, supersample=ns.seen_supersample)
             kw["keep_seen"] = {k: v for k, v in ks.items() if v is not None}
+        if ns.repair:
+            kw["repair"] = dict(weld=ns.weld, orient_consistent=ns.orient_consistent, **({"duplicates": ns.duplicates} if ns.duplicates else {}))
+        if ns.report_topology:
+            kw["report_topology"] = True
     return kw
 
 
@@ -122,6 +132,15 @@ def main(argv=None):
         parser.error("--seen-rings is only used with --keep-seen faces")
     if ns.seen_max_off is not None and not ns.seen_masks:
         parser.error("--seen-max-off is only used with --seen-masks")
+    if ns.repair and not ns.device_postprocess:
+        parser.error("--repair is only used with --device-postprocess")
+    if ns.report_topology and not ns.device_postprocess:
+        parser.error("--report-topology is only used with --device-postprocess")
+    for name in ("weld", "duplicates", "orient_consistent"):
+        if getattr(ns, name) and not ns.repair:
+            parser.error("--%s is only used with --repair" % name.replace("_", "-"))
+    if ns.duplicates and ns.duplicates not in ("keep", "first", "cancel"):
+        parser.error("--duplicates must be keep, first or cancel")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
         parser.error("--simplify must be 1 .. 1024")
     np.random.seed(ns.seed)
