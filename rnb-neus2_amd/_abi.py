@@ -868,6 +868,96 @@ MESH_TOPOLOGY_PROTOTYPES = {
     "mesh_repair": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshRepairOptions), C.POINTER(Mesh), C.c_void_p, C.POINTER(MeshRepairStats)]),
 }
 
+# ---- include/rnb_mesh_holes.h: the boundary loops of a device mesh and their fill, a header of its own with its own version (the HIP library only) ----
+MESH_HOLES_ABI_VERSION = 1
+MESH_HOLES_MAX_EDGES, MESH_HOLES_Q_SHIFT, MESH_HOLES_Q_TERM_LOG2 = 1 << 20, 32, 10
+
+
+class MeshBoundaryLoopsOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("buckets_log2", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshBoundaryLoop(C.Structure):
+    _fields_ = [
+        ("label", C.c_uint32),
+        ("n_edges", C.c_uint32),
+        ("simple", C.c_uint32),
+        ("n_irregular", C.c_uint32),
+        ("component", C.c_uint32),
+        ("centroid", C.c_float * 3),
+        ("normal", C.c_float * 3),
+        ("reserved", C.c_uint32),
+        ("perimeter", C.c_double),
+        ("area", C.c_double),
+    ]
+
+
+# the same record as a numpy dtype (DeviceMesh.boundary_loops returns the table as a structured array)
+MESH_BOUNDARY_LOOP_DTYPE = [("label", "<u4"), ("n_edges", "<u4"), ("simple", "<u4"), ("n_irregular", "<u4"), ("component", "<u4"), ("centroid", "<f4", (3,)), ("normal", "<f4", (3,)),
+                            ("reserved", "<u4"), ("perimeter", "<f8"), ("area", "<f8")]
+
+
+class MeshBoundaryLoopsStats(C.Structure):
+    _fields_ = [
+        ("n_boundary_edges", C.c_uint32),
+        ("n_loops", C.c_uint32),
+        ("n_simple", C.c_uint32),
+        ("n_irregular_vertices", C.c_uint32),
+        ("max_loop_edges", C.c_uint32),
+        ("n_too_long", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+class MeshFillHolesOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("max_edges", C.c_uint32),
+        ("skip_largest", C.c_uint32),
+        ("buckets_log2", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshFillHolesStats(C.Structure):
+    _fields_ = [
+        ("n_loops", C.c_uint32),
+        ("n_filled", C.c_uint32),
+        ("n_skipped_not_simple", C.c_uint32),
+        ("n_skipped_over_max", C.c_uint32),
+        ("n_skipped_largest", C.c_uint32),
+        ("n_verts_added", C.c_uint32),
+        ("n_tris_added", C.c_uint32),
+        ("n_verts_out", C.c_uint32),
+        ("n_tris_out", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved2", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_HOLES_PROTOTYPES = {
+    "mesh_holes_abi_version": (_u32, []),
+    "mesh_boundary_loops_default_options": (_i, [C.POINTER(MeshBoundaryLoopsOptions)]),
+    "mesh_boundary_loops": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshBoundaryLoopsOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MeshBoundaryLoopsStats)]),
+    "mesh_boundary_loops_free": (_i, [_ctx, C.c_void_p]),
+    "mesh_fill_holes_default_options": (_i, [C.POINTER(MeshFillHolesOptions)]),
+    "mesh_fill_holes": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshFillHolesOptions), C.POINTER(Mesh), C.c_void_p, C.POINTER(MeshFillHolesStats)]),
+}
+
 
 class Functions:
     """Bound, typed entry points of one library."""
@@ -890,13 +980,14 @@ class Functions:
 
 
 def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
-            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False):
+            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False, mesh_holes=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
     mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
     mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h),
-    mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h), mesh_topology=True MESH_TOPOLOGY_PROTOTYPES (include/rnb_mesh_topology.h); only the HIP library exports those."""
+    mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h), mesh_topology=True MESH_TOPOLOGY_PROTOTYPES (include/rnb_mesh_topology.h),
+    mesh_holes=True MESH_HOLES_PROTOTYPES (include/rnb_mesh_holes.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
                      + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ())
-                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()) + ((MESH_TOPOLOGY_PROTOTYPES,) if mesh_topology else ()))
+                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()) + ((MESH_TOPOLOGY_PROTOTYPES,) if mesh_topology else ()) + ((MESH_HOLES_PROTOTYPES,) if mesh_holes else ()))

@@ -47,7 +47,7 @@ def load_library():
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
-                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True)
+                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True, mesh_holes=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -72,6 +72,8 @@ def load_library():
             raise RuntimeError("mesh-draw ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_topology_abi_version() != _abi.MESH_TOPOLOGY_ABI_VERSION:
             raise RuntimeError("mesh-topology ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_holes_abi_version() != _abi.MESH_HOLES_ABI_VERSION:
+            raise RuntimeError("mesh-holes ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -591,7 +593,7 @@ class Context:
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
-                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None, repair=None, topology=False):
+                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None, repair=None, topology=False, fill_holes=None):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -617,7 +619,17 @@ class Context:
         repair = dict(...): after simplify and before error / texture, still on the device, the mesh goes through rnb_mesh_repair with these arguments of
         DeviceMesh.repair (weld, drop_degenerate, duplicates, orient, buckets_log2), and the dict gains `repair_stats`; with error=True the distance is then measured to
         the repaired mesh. topology=True: the dict gains `topology`, the statistics of DeviceMesh.topology() of the final mesh. With None / False (the defaults)
-        nothing of that runs and the calls made are exactly those made without them."""
+        nothing of that runs and the calls made are exactly those made without them.
+        fill_holes = True or dict(...): after seen_by and repair and before error / topology / texture, still on the device, the boundary loops of the mesh are closed by
+        rnb_mesh_fill_holes (include/rnb_mesh_holes.h) with these arguments of DeviceMesh.fill_holes (max_edges, skip_largest, buckets_log2; True: its defaults), and
+        the dict gains `fill_stats`; with error=True the distance is then measured to the filled mesh. With None (the default) nothing of that runs and the calls made
+        are exactly those made without it."""
+        if fill_holes is True:
+            fill_holes = {}
+        if fill_holes is not None and not isinstance(fill_holes, dict):
+            raise ValueError("fill_holes must be None, True or a dict of DeviceMesh.fill_holes' arguments")
+        if fill_holes is not None and set(fill_holes) - {"max_edges", "skip_largest", "buckets_log2"}:
+            raise ValueError("fill_holes takes max_edges, skip_largest and buckets_log2")
         if repair is not None and not isinstance(repair, dict):
             raise ValueError("repair must be None or a dict of DeviceMesh.repair's arguments")
         if repair is not None and set(repair) - {"weld", "drop_degenerate", "duplicates", "orient", "buckets_log2"}:
@@ -646,6 +658,9 @@ class Context:
             if repair is not None:
                 chain.append(chain[-1].repair(stream=stream, **repair))
                 repaired = chain[-1]
+            if fill_holes is not None:
+                chain.append(chain[-1].fill_holes(stream=stream, **fill_holes))
+                filled = chain[-1]
             if grid is not None and error:
                 simplify_error = before.distance_to(chain[-1], symmetric=True, stream=stream)
             if topology:
@@ -668,6 +683,8 @@ class Context:
                 out["simplify_stats"] = simplified.stats
             if repair is not None:
                 out["repair_stats"] = repaired.stats
+            if fill_holes is not None:
+                out["fill_stats"] = filled.stats
             if topology:
                 out["topology"] = census
         finally:
@@ -759,6 +776,39 @@ class Context:
             out["stats"] = out["repair_stats"] = repaired.stats
             if vertex_map:
                 out["vertex_map"] = repaired.vertex_map
+        return out
+
+    def _boundary_loops_options(self, buckets_log2=0):
+        opt = _abi.MeshBoundaryLoopsOptions()
+        self._check(self.f.mesh_boundary_loops_default_options(C.byref(opt)))
+        opt.buckets_log2 = int(buckets_log2)
+        return opt
+
+    def _fill_holes_options(self, max_edges=0, skip_largest=False, buckets_log2=0):
+        if int(max_edges) < 0 or int(max_edges) > 0xFFFFFFFF:
+            raise ValueError("max_edges must be 0 (every loop) or a positive count")
+        opt = _abi.MeshFillHolesOptions()
+        self._check(self.f.mesh_fill_holes_default_options(C.byref(opt)))
+        opt.max_edges, opt.skip_largest, opt.buckets_log2 = int(max_edges), int(bool(skip_largest)), int(buckets_log2)
+        return opt
+
+    def mesh_boundary_loops(self, verts, indices, colors=None, edges=False, table=True, buckets_log2=0, stream=None):
+        """rnb_mesh_boundary_loops (include/rnb_mesh_holes.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3]; colors only take part in the checks): the
+        dict of DeviceMesh.boundary_loops, which describes the keys. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, colors) as m:
+            return m.boundary_loops(edges, table, buckets_log2, stream)
+
+    def fill_mesh_holes(self, verts, indices, colors=None, normals=None, max_edges=0, skip_largest=False, loop_of_tri=False, buckets_log2=0, stream=None):
+        """rnb_mesh_fill_holes (include/rnb_mesh_holes.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals; the
+        arguments are those of DeviceMesh.fill_holes. Returns a dict of numpy arrays like clean_mesh, with `stats` = `fill_stats` and, with loop_of_tri=True,
+        `loop_of_tri`. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            filled = m.fill_holes(max_edges, skip_largest, loop_of_tri, buckets_log2, stream)
+        with filled:
+            out = filled.download()
+            out["stats"] = out["fill_stats"] = filled.stats
+            if loop_of_tri:
+                out["loop_of_tri"] = filled.loop_of_tri
         return out
 
     @staticmethod
@@ -1184,6 +1234,7 @@ class DeviceMesh(_abi.Mesh):
         self.ctx, self._buffers, self._stats, self._freed = ctx, buffers, None, False
         self._table, self._table_host = C.c_void_p(), None
         self.vertex_map = None  # set by repair(vertex_map=True) on the mesh it returns
+        self.loop_of_tri = None  # set by fill_holes(loop_of_tri=True) on the mesh it returns
 
     n_verts = property(lambda self: _abi.Mesh.n_verts.__get__(self))
     n_triangles = property(lambda self: self.n_indices // 3)
@@ -1311,6 +1362,59 @@ class DeviceMesh(_abi.Mesh):
         finally:
             if vmap:
                 c.device_free(vmap)
+        return out
+
+    def boundary_loops(self, edges=False, table=True, buckets_log2=0, stream=None):
+        """rnb_mesh_boundary_loops (include/rnb_mesh_holes.h): the boundary of the mesh as loops -> the dict of rnb_mesh_boundary_loops_stats (n_boundary_edges, n_loops,
+        n_simple, n_irregular_vertices, max_loop_edges, n_too_long, ...). table=True (the default) adds `table`, one record per boundary component in ascending label
+        (label = its lowest boundary half-edge, n_edges, simple, n_irregular, component, centroid, normal, perimeter, area); edges=True adds `loop`, `next` and `pos`,
+        uint32[n_indices] per half-edge h = 3t + k (0xFFFFFFFF off the boundary; next and pos also on a component that is not one simple cycle). Nothing of the mesh changes."""
+        c = self._live()
+        opt, st, tab = c._boundary_loops_options(buckets_log2), _abi.MeshBoundaryLoopsStats(), C.c_void_p()
+        n = max(self.n_indices, 1) * 4
+        arrays = []
+        try:
+            for _ in range(3 if edges else 0):
+                arrays.append(c.device_malloc(n))
+            ptrs = arrays if edges else [None] * 3
+            try:
+                c._check(c.f.mesh_boundary_loops(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), ptrs[0], ptrs[1], ptrs[2], C.byref(tab) if table else None, C.byref(st)))
+                out = st.as_dict()
+                if edges:
+                    for key, p in zip(("loop", "next", "pos"), arrays):
+                        out[key] = c.download(p, self.n_indices, np.uint32) if self.n_indices else np.empty(0, np.uint32)
+                if table:
+                    dt = np.dtype(_abi.MESH_BOUNDARY_LOOP_DTYPE)
+                    out["table"] = c.download(tab.value, st.n_loops, dt) if st.n_loops else np.empty(0, dt)
+            finally:
+                if tab:
+                    c.f.mesh_boundary_loops_free(c._h, tab)
+        finally:
+            for p in arrays:
+                c.device_free(p)
+        return out
+
+    def fill_holes(self, max_edges=0, skip_largest=False, loop_of_tri=False, buckets_log2=0, stream=None):
+        """rnb_mesh_fill_holes (include/rnb_mesh_holes.h) -> a new DeviceMesh with every selected simple boundary loop closed; its `stats` are the fill stats. The input's
+        vertices and triangles come first, unchanged; a loop of 3 edges gets one triangle, a longer one a fan around a new vertex at its centroid (colour and normal
+        the loop's mean colour and normal), loop by loop in ascending label. max_edges=N: only loops of up to N edges (0: all, up to 2^20); skip_largest=True: the
+        longest simple loop of every connected component stays open (the rim of a relief). Components that are not one simple cycle are never filled (see
+        boundary_loops; repair(orient="consistent") first). loop_of_tri=True: `loop_of_tri` of the returned mesh is uint32[its triangles], the label of the loop a
+        triangle closes or 0xFFFFFFFF for an input triangle."""
+        c = self._live()
+        opt, st = c._fill_holes_options(max_edges, skip_largest, buckets_log2), _abi.MeshFillHolesStats()
+        lot = c.device_malloc(max(self.n_triangles + self.n_indices, 1) * 4) if loop_of_tri else None  # (at most one new triangle per boundary half-edge)
+        try:
+            out = _returned_mesh(c, st, lambda m: c.f.mesh_fill_holes(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), m, lot, C.byref(st)))
+            if loop_of_tri:
+                try:
+                    out.loop_of_tri = c.download(lot, out.n_triangles, np.uint32) if out.n_triangles else np.empty(0, np.uint32)
+                except BaseException:
+                    out.free()
+                    raise
+        finally:
+            if lot:
+                c.device_free(lot)
         return out
 
     def _distance(self, other, opt, per_vertex, stream):

@@ -1,6 +1,7 @@
 // driver_mesh.hpp -- rnb_sdf_lattice, rnb_marching_cubes and the mesh stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster,
 // rnb_mesh_draw_textured, rnb_mesh_visibility, rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views, rnb_mesh_topology, rnb_mesh_repair
-// (include/rnb_mesh_topology.h; their hash join is tp_join, beside them). What they share:
+// (include/rnb_mesh_topology.h; their hash join is tp_join, beside them), rnb_mesh_boundary_loops, rnb_mesh_fill_holes (include/rnb_mesh_holes.h; hl_census is the
+// part they share). What they share:
 //   scan_exclusive, count_and_scan                  the prefix sums behind every numbering, and the count half of a count / write kernel pair
 //   MeshWorkspace, alloc_mesh, hand_over            the device memory of one call and the mesh it returns
 //   check_mesh_input, check_reserved, free_device   the argument checks every stage makes; the *_free functions
@@ -1669,6 +1670,242 @@ int rnb_mesh_repair(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh
 		stats->n_welded = hres.n_welded; stats->n_degenerate_dropped = hres.n_degenerate; stats->n_duplicates_dropped = hres.n_dropped; stats->n_flipped = hres.n_flipped;
 		stats->n_patches = hres.n_patches; stats->n_unorientable_patches = hres.n_unorientable_patches;
 		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- holes: the boundary loops and their fill (include/rnb_mesh_holes.h) ----
+uint32_t rnb_mesh_holes_abi_version(void) { return RNB_MESH_HOLES_ABI_VERSION; }
+
+int rnb_mesh_boundary_loops_default_options(rnb_mesh_boundary_loops_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_HOLES_ABI_VERSION;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_fill_holes_default_options(rnb_mesh_fill_holes_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_HOLES_ABI_VERSION;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_boundary_loops_free(rnb_ctx* c, rnb_mesh_boundary_loop* table) try {
+	if (!c) return fail(RNB_ERR_INVALID, "null argument");
+	if (table) (void)hipFree(table);
+	return RNB_OK;
+} RNB_GUARD
+
+extern "C++" {
+namespace {
+// What the census leaves on the device for its caller (all held by the call's workspace): the boundary half-edges as a list of nb items, and per item its loop and
+// its position; per half-edge the faces on its edge and its item; per vertex the outgoing boundary half-edge; per loop its record and its sums.
+struct HlCensus {
+	uint32_t nb = 0, n_loops = 0;
+	uint32_t *n_faces = nullptr, *bidx = nullptr, *list = nullptr, *iloop = nullptr, *ipos = nullptr, *outh = nullptr, *comp = nullptr;
+	rnb_mesh_boundary_loop* table = nullptr;
+	long long* sums = nullptr;
+	HlResult* dres = nullptr;
+	HlResult hres;
+};
+// The census of a mesh with at least one triangle: steps 1 .. 6 of the header's definitions. Synchronised on return.
+int hl_census(MeshCall& call, const rnb_mesh& m, uint32_t buckets_log2, HlCensus* C) {
+	const hipStream_t s = call.s;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, nh = m.n_indices;
+	const uint32_t g_v = groups(nv), g_t = groups(nt), g_h = groups(nh);
+	const uint32_t* idx = (const uint32_t*)m.indices;
+	std::memset(&C->hres, 0, sizeof(C->hres));
+	uint32_t *used = nullptr, *cover = nullptr, *broot = nullptr, *bmark = nullptr, *scan = nullptr;
+	TpResult* tres = nullptr;
+	if (!call.ws.alloc(&C->comp, nv) || !call.ws.alloc(&used, nv) || !call.ws.alloc(&broot, nv) || !call.ws.alloc(&bmark, nv) || !call.ws.alloc(&cover, 2 * (size_t)nt) ||
+	    !call.ws.alloc(&C->n_faces, nh) || !call.ws.alloc(&C->bidx, nh) || !call.ws.alloc(&scan, scan_scratch_elems(nh)) || !call.ws.alloc(&tres, 1) || !call.ws.alloc(&C->dres, 1))
+		return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nt) + " triangles");
+	HIP_TRY(hipMemsetAsync(tres, 0, sizeof(TpResult), s));
+	HIP_TRY(hipMemsetAsync(C->dres, 0, sizeof(HlResult), s));
+	// 1. every index is range-checked before any is used as an address; the cleaner's components
+	if (int rc = call.check_indices(m, used, &tres->flags); rc != RNB_OK) return rc;
+	call.ws.release(used);
+	call.launch(g_v, k_cl_init, C->comp, nv);
+	call.launch(g_t, k_cl_hook, idx, nt, C->comp);
+	call.launch(g_v, k_cl_flatten, C->comp, nv);
+	// 2. the topology stage's edge join: faces per half-edge; the boundary edges unite their ends (the double cover is its by-product)
+	call.launch(groups(2 * (uint64_t)nt), k_cl_init, cover, 2u * nt);
+	call.launch(g_v, k_cl_init, broot, nv);
+	HIP_TRY(hipMemsetAsync(bmark, 0, (size_t)nv * 4, s));
+	{
+		TpTable j;
+		const TpEdgeKeys keys{TpTris{idx, nullptr}};
+		if (int rc = tp_join(call, keys, nh, buckets_log2, tres, &j); rc != RNB_OK) return rc;
+		call.launch(g_h, k_tp_edges, keys, nh, j.join, C->n_faces, (uint32_t*)nullptr, (uint32_t*)nullptr, cover, broot, bmark, (const uint32_t*)nullptr, (rnb_mesh_topology_component*)nullptr,
+		            (TpResult*)nullptr);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipStreamSynchronize(s));
+		call.ws.release(j.offs, j.items, cover);
+	}
+	call.launch(g_v, k_cl_flatten, broot, nv);
+	// 3. the boundary half-edges as a list
+	call.launch(g_h, k_hl_flag, (const uint32_t*)C->n_faces, nh, C->bidx);
+	HIP_TRY(hipGetLastError());
+	if (int rc = scan_exclusive(C->bidx, nh, s, &C->nb, scan); rc != RNB_OK) return rc;
+	const uint32_t nb = C->nb;
+	if (!nb) { call.ws.release(broot, bmark, scan, tres); return RNB_OK; }
+	const uint32_t g_b = groups(nb);
+	uint32_t *outc = nullptr, *inc = nullptr, *lab = nullptr, *lrank = nullptr;
+	if (!call.ws.alloc(&C->list, nb) || !call.ws.alloc(&C->iloop, nb) || !call.ws.alloc(&C->ipos, nb) || !call.ws.alloc(&lrank, nb) || !call.ws.alloc(&outc, nv) || !call.ws.alloc(&inc, nv) ||
+	    !call.ws.alloc(&C->outh, nv) || !call.ws.alloc(&lab, nv))
+		return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nb) + " boundary edges");
+	HIP_TRY(hipMemsetAsync(outc, 0, (size_t)nv * 4, s));
+	HIP_TRY(hipMemsetAsync(inc, 0, (size_t)nv * 4, s));
+	HIP_TRY(hipMemsetAsync(C->outh, 0xFF, (size_t)nv * 4, s));
+	HIP_TRY(hipMemsetAsync(lab, 0xFF, (size_t)nv * 4, s));
+	HIP_TRY(hipMemsetAsync(lrank, 0, (size_t)nb * 4, s));
+	call.launch(g_h, k_hl_list, (const uint32_t*)C->n_faces, (const uint32_t*)C->bidx, nh, C->list);
+	// 4. per vertex: counts, the outgoing half-edge; per component: the label; the loops numbered in ascending label
+	call.launch(g_b, k_hl_vertex, idx, (const uint32_t*)C->list, nb, (const uint32_t*)broot, outc, inc, C->outh, lab);
+	call.launch(g_v, k_hl_label_flags, (const uint32_t*)broot, (const uint32_t*)bmark, (const uint32_t*)lab, (const uint32_t*)C->bidx, nv, lrank);
+	HIP_TRY(hipGetLastError());
+	if (int rc = scan_exclusive(lrank, nb, s, &C->n_loops, scan); rc != RNB_OK) return rc;
+	const uint32_t nl = C->n_loops, g_l = groups(nl);
+	if (!call.ws.alloc(&C->table, nl) || !call.ws.alloc(&C->sums, (size_t)nl * HL_NSUM)) return call.nomem("hipMalloc failed for the table of " + std::to_string(nl) + " loops");
+	HIP_TRY(hipMemsetAsync(C->table, 0, (size_t)nl * sizeof(rnb_mesh_boundary_loop), s));
+	HIP_TRY(hipMemsetAsync(C->sums, 0, (size_t)nl * HL_NSUM * 8, s));
+	call.launch(g_b, k_hl_loops, idx, (const uint32_t*)C->list, nb, (const uint32_t*)broot, (const uint32_t*)lab, (const uint32_t*)C->bidx, (const uint32_t*)lrank, C->iloop, C->table);
+	call.launch(g_v, k_hl_vertices, (const uint32_t*)broot, (const uint32_t*)bmark, (const uint32_t*)outc, (const uint32_t*)inc, (const uint32_t*)lab, (const uint32_t*)C->bidx,
+	            (const uint32_t*)lrank, (const uint32_t*)C->comp, nv, C->table);
+	call.launch(g_l, k_hl_classify, C->table, nl, C->dres);
+	// 5. the sums (they need the labels only), then the longest simple loop read back: it fixes the number of ranking rounds
+	call.launch(g_b, k_hl_sums, idx, (const float*)m.verts, (const float*)m.colors, (const uint32_t*)C->list, nb, (const uint32_t*)C->iloop, (const rnb_mesh_boundary_loop*)C->table, C->sums, C->dres);
+	call.launch(g_l, k_hl_finish, idx, (const float*)m.verts, C->table, (const long long*)C->sums, nl);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(&C->hres, C->dres, sizeof(HlResult), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	call.ws.release(broot, bmark, outc, inc, lab, lrank, scan, tres);
+	if (C->hres.flags & HL_NOT_FINITE) return call.invalid("a coordinate of a boundary vertex is not finite");
+	if (C->hres.flags & HL_BAD_TERM) return call.invalid("a term of a boundary component's sums is not below 2^10 in magnitude (a boundary vertex too far from its component's first, or a colour)");
+	// 6. list ranking: ceil(log2(longest simple loop)) rounds of pointer jumping, each from one buffer into the other
+	uint2 *cur = nullptr, *nxt = nullptr;
+	if (!call.ws.alloc(&cur, nb) || !call.ws.alloc(&nxt, nb)) return call.nomem("hipMalloc failed for the ranking of " + std::to_string(nb) + " boundary edges");
+	call.launch(g_b, k_hl_rank_init, idx, (const uint32_t*)C->list, nb, (const uint32_t*)C->iloop, (const rnb_mesh_boundary_loop*)C->table, (const uint32_t*)C->outh, (const uint32_t*)C->bidx, cur);
+	uint32_t rounds = 0;
+	while ((1ull << rounds) < C->hres.max_simple_edges) ++rounds;
+	for (uint32_t r = 0; r < rounds; ++r) {
+		call.launch(g_b, k_hl_rank_round, (const uint2*)cur, nxt, nb);
+		std::swap(cur, nxt);
+	}
+	call.launch(g_b, k_hl_pos, (const uint2*)cur, (const uint32_t*)C->iloop, (const rnb_mesh_boundary_loop*)C->table, nb, C->ipos);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));
+	call.ws.release(cur, nxt);
+	return RNB_OK;
+}
+} // namespace
+} // extern "C++"
+
+int rnb_mesh_boundary_loops(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_boundary_loops_options* opt, uint32_t* loop_dev, uint32_t* next_dev, uint32_t* pos_dev,
+                            rnb_mesh_boundary_loop** table_dev, rnb_mesh_boundary_loops_stats* stats) try {
+	if (table_dev) *table_dev = nullptr;
+	if (!c || !in || !opt) return fail(RNB_ERR_INVALID, "rnb_mesh_boundary_loops: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_boundary_loops", in); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_HOLES_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_boundary_loops: options abi_version mismatch (expected RNB_MESH_HOLES_ABI_VERSION)");
+	if (int rc = tp_check_buckets("rnb_mesh_boundary_loops", opt->buckets_log2); rc != RNB_OK) return rc;
+	if (int rc = check_reserved("rnb_mesh_boundary_loops", opt->reserved); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_boundary_loops", c, stream);
+	const hipStream_t s = call.s;
+
+	HlCensus C;
+	std::memset(&C.hres, 0, sizeof(C.hres));
+	const uint32_t nh = m.n_indices;
+	if (nh) {
+		if (int rc = hl_census(call, m, opt->buckets_log2, &C); rc != RNB_OK) return rc;
+		if (loop_dev || next_dev || pos_dev) {
+			if (C.nb)
+				call.launch(groups(nh), k_hl_write, (const uint32_t*)m.indices, (const uint32_t*)C.n_faces, (const uint32_t*)C.bidx, (const uint32_t*)C.iloop, (const uint32_t*)C.ipos,
+				            (const rnb_mesh_boundary_loop*)C.table, (const uint32_t*)C.outh, nh, loop_dev, next_dev, pos_dev);
+			else
+				for (uint32_t* p : {loop_dev, next_dev, pos_dev})
+					if (p) HIP_TRY(hipMemsetAsync(p, 0xFF, (size_t)nh * 4, s));
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+		}
+	}
+	if (table_dev) {
+		if (!C.table && !call.ws.alloc(&C.table, 1)) return call.nomem("hipMalloc failed for the table");
+		*table_dev = (rnb_mesh_boundary_loop*)call.ws.keep(C.table);
+	}
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_boundary_edges = C.nb; stats->n_loops = C.n_loops; stats->n_simple = C.hres.n_simple; stats->n_irregular_vertices = C.hres.n_irregular_vertices;
+		stats->max_loop_edges = C.hres.max_loop_edges; stats->n_too_long = C.hres.n_too_long;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_fill_holes(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_fill_holes_options* opt, rnb_mesh* out, uint32_t* loop_of_tri, rnb_mesh_fill_holes_stats* stats) try {
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_fill_holes: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_fill_holes", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_HOLES_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_fill_holes: options abi_version mismatch (expected RNB_MESH_HOLES_ABI_VERSION)");
+	if (opt->skip_largest > 1u) return fail(RNB_ERR_INVALID, "rnb_mesh_fill_holes: skip_largest must be 0 or 1");
+	if (int rc = tp_check_buckets("rnb_mesh_fill_holes", opt->buckets_log2); rc != RNB_OK) return rc;
+	if (int rc = check_reserved("rnb_mesh_fill_holes", opt->reserved); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_fill_holes", c, stream);
+	const hipStream_t s = call.s;
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	HlCensus C;
+	std::memset(&C.hres, 0, sizeof(C.hres));
+	if (nt)
+		if (int rc = hl_census(call, m, opt->buckets_log2, &C); rc != RNB_OK) return rc;
+	const uint32_t nb = C.nb, nl = C.n_loops;
+	uint32_t nva = 0, nta = 0;
+	uint32_t *fill = nullptr, *voff = nullptr, *toff = nullptr;
+	if (nl) {
+		// who is filled; what each loop appends, and from where
+		unsigned long long* big = nullptr;
+		uint32_t* scan = nullptr;
+		if (!call.ws.alloc(&fill, nl) || !call.ws.alloc(&voff, nl) || !call.ws.alloc(&toff, nl) || !call.ws.alloc(&scan, scan_scratch_elems(nl)) || (opt->skip_largest && !call.ws.alloc(&big, nv)))
+			return call.nomem("hipMalloc failed for the selection among " + std::to_string(nl) + " loops");
+		if (big) {
+			HIP_TRY(hipMemsetAsync(big, 0, (size_t)nv * 8, s));
+			call.launch(groups(nl), k_hl_largest, (const rnb_mesh_boundary_loop*)C.table, nl, big);
+		}
+		const uint32_t limit = opt->max_edges ? std::min<uint32_t>(opt->max_edges, RNB_MESH_HOLES_MAX_EDGES) : RNB_MESH_HOLES_MAX_EDGES;
+		call.launch(groups(nl), k_hl_select, (const rnb_mesh_boundary_loop*)C.table, nl, (const unsigned long long*)big, limit, fill, voff, toff, C.dres);
+		HIP_TRY(hipGetLastError());
+		if (int rc = scan_exclusive(voff, nl, s, &nva, scan); rc != RNB_OK) return rc;
+		if (int rc = scan_exclusive(toff, nl, s, &nta, scan); rc != RNB_OK) return rc;
+		HIP_TRY(hipMemcpyAsync(&C.hres, C.dres, sizeof(HlResult), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		call.ws.release(big, scan);
+	}
+	const uint64_t nvo = (uint64_t)nv + nva, nto = (uint64_t)nt + nta;
+	if (nvo > 0xFFFFFFFEull || 3 * nto > 0xFFFFFFFFull) return call.invalid("the filled mesh would hold " + std::to_string(nto) + " triangles: more than an index count of 32 bits takes");
+	rnb_mesh o;
+	if (int rc = call.alloc_like(m, &o, (uint32_t)nvo, (uint32_t)nto); rc != RNB_OK) return rc;
+	if (nv) {
+		HIP_TRY(hipMemcpyAsync(o.verts, m.verts, (size_t)nv * 12, hipMemcpyDeviceToDevice, s));
+		if (m.colors) HIP_TRY(hipMemcpyAsync(o.colors, m.colors, (size_t)nv * 12, hipMemcpyDeviceToDevice, s));
+		if (m.normals) HIP_TRY(hipMemcpyAsync(o.normals, m.normals, (size_t)nv * 12, hipMemcpyDeviceToDevice, s));
+	}
+	if (nt) HIP_TRY(hipMemcpyAsync(o.indices, m.indices, (size_t)nt * 12, hipMemcpyDeviceToDevice, s));
+	if (loop_of_tri && nto) HIP_TRY(hipMemsetAsync(loop_of_tri, 0xFF, (size_t)nto * 4, s));
+	if (nta) {
+		call.launch(groups(nb), k_hl_emit_tris, (const uint32_t*)m.indices, (const uint32_t*)C.list, nb, (const uint32_t*)C.iloop, (const uint32_t*)C.ipos, (const rnb_mesh_boundary_loop*)C.table,
+		            (const uint32_t*)fill, (const uint32_t*)voff, (const uint32_t*)toff, (const uint32_t*)C.outh, nv, nt, o.indices, loop_of_tri);
+		if (nva)
+			call.launch(groups(nl), k_hl_emit_verts, (const rnb_mesh_boundary_loop*)C.table, (const long long*)C.sums, nl, (const uint32_t*)fill, (const uint32_t*)voff, nv, o.verts, o.colors, o.normals);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	hand_over(call.ws, o, out);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_loops = nl; stats->n_filled = C.hres.n_filled; stats->n_skipped_not_simple = C.hres.n_not_simple; stats->n_skipped_over_max = C.hres.n_over_max;
+		stats->n_skipped_largest = C.hres.n_largest; stats->n_verts_added = nva; stats->n_tris_added = nta; stats->n_verts_out = (uint32_t)nvo; stats->n_tris_out = (uint32_t)nto;
 		call.finish(stats);
 	}
 	return RNB_OK;

@@ -17,6 +17,7 @@
 #include "kernels_mesh_project.cuh"
 #include "kernels_mesh_draw.cuh"
 #include "kernels_mesh_topology.cuh"
+#include "kernels_mesh_holes.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>

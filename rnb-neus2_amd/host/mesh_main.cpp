@@ -7,6 +7,7 @@
 //        [--texture S [--texture-maps albedo[,normal]] [--texture-from views [--texture-mode blend|best] [--texture-depth-tolerance T] [--texture-min-cos C]]]
 //        [--keep-seen component|faces [--seen-min-views N] [--seen-rings R] [--seen-masks [--seen-max-off N]] [--seen-supersample K]]
 //        [--repair [--weld] [--duplicates keep|first|cancel] [--orient-consistent]] [--report-topology]
+//        [--fill-holes [--fill-max-edges N] [--fill-skip-largest]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -39,6 +40,10 @@
 // with --weld vertices at one position first, with --orient-consistent every orientable patch wound consistently across its manifold edges. When --keep / --orient
 // are given too, the cleaning then runs after the repair instead of first (extract, keep-seen, simplify, repair, clean), so that --orient outward acts on
 // consistently wound components. With --report-topology the census of the mesh as written (rnb_mesh_topology) is printed as one JSON line, {"topology": {...}}.
+// With --fill-holes the boundary loops of the device mesh are closed by rnb_mesh_fill_holes (include/rnb_mesh_holes.h) after --keep-seen, --simplify and --repair: a
+// triangle for a loop of 3 edges, a fan around a new vertex at the centroid for a longer one; --fill-max-edges N leaves longer loops open, --fill-skip-largest the
+// longest loop of every connected component (the rim of a relief). Boundary components that are not one simple cycle stay open and are counted in the `fill:` line.
+// --keep / --orient, if given, then act on the filled mesh, as they do on the repaired one; --report-topology and --texture describe the filled mesh.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -51,6 +56,7 @@
 #include "../../include/rnb_mesh_visibility.h"
 #include "../../include/rnb_mesh_project.h"
 #include "../../include/rnb_mesh_topology.h"
+#include "../../include/rnb_mesh_holes.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -106,6 +112,9 @@ const Flag FLAGS[] = {
 	{"weld", nullptr, "--repair only (takes no value). Vertices at one position become one vertex first."},
 	{"duplicates", "MODE", "--repair only. first (default): one triangle per vertex set stays; cancel: opposite windings cancel, folded pairs go entirely; keep: none is removed."},
 	{"orient-consistent", nullptr, "--repair only (takes no value). Wind every orientable patch consistently across its shared edges, by the smaller set of flips."},
+	{"fill-holes", nullptr, "(takes no value). Close the boundary loops of the mesh on the device, after --keep-seen, --simplify and --repair; --keep / --orient then act on the filled mesh."},
+	{"fill-max-edges", "N", "--fill-holes only. Leave loops of more than N edges open (default: fill every simple loop)."},
+	{"fill-skip-largest", nullptr, "--fill-holes only (takes no value). Leave the longest loop of every connected component open: the rim of a relief."},
 	{"report-topology", nullptr, "(takes no value). Print the edge census of the written mesh as one JSON line: edges by kind, duplicates, patches, boundary loops, Euler characteristic."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -376,7 +385,8 @@ int main(int argc, char** argv) {
 	bool want_seen = false, texture_from = false;
 	SeenOptions seen;
 	ProjectOptions project;
-	bool repair = false, report_topology = false;
+	bool repair = false, report_topology = false, fill_holes = false;
+	uint32_t fill_max_edges = 0;
 	rnb_mesh_repair_options repair_opt;
 	std::memset(&repair_opt, 0, sizeof(repair_opt));
 	try {
@@ -484,6 +494,13 @@ int main(int argc, char** argv) {
 			if (a.count(sub) && !repair) throw ParseError(std::string("Argument '") + sub + "' is only used with --repair");
 		if (a.count("duplicates") && a["duplicates"] != "keep" && a["duplicates"] != "first" && a["duplicates"] != "cancel") throw ParseError("Argument 'duplicates' must be keep, first or cancel");
 		if (a.count("report-topology")) report_topology = true;
+		if (a.count("fill-holes")) fill_holes = true;
+		for (const char* sub : {"fill-max-edges", "fill-skip-largest"})
+			if (a.count(sub) && !fill_holes) throw ParseError(std::string("Argument '") + sub + "' is only used with --fill-holes");
+		if (a.count("fill-max-edges")) {
+			fill_max_edges = parse_u32("fill-max-edges", a["fill-max-edges"]);
+			if (fill_max_edges < 3) throw ParseError("Argument 'fill-max-edges' must be at least 3");
+		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
 		print_help(std::cerr, argv[0]);
@@ -542,7 +559,8 @@ int main(int argc, char** argv) {
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		};
-		if (clean && !repair) run_clean(); // (with --repair: after it, below)
+		const bool late_clean = repair || fill_holes;
+		if (clean && !late_clean) run_clean(); // (with --repair or --fill-holes: after them, below)
 		std::string seen_report;
 		if (want_seen) { // device to device, after the cleaning and before the simplification
 			keep_seen(ctx, ds, dm, seen, &cm, seen_report);
@@ -581,8 +599,19 @@ int main(int argc, char** argv) {
 			RNB_CHECK(rnb_mesh_free(ctx, &dm));
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
-			if (clean) run_clean();
 		}
+		rnb_mesh_fill_holes_stats fs;
+		if (fill_holes) { // device to device, after the repair
+			rnb_mesh_fill_holes_options fo;
+			RNB_CHECK(rnb_mesh_fill_holes_default_options(&fo));
+			fo.max_edges = fill_max_edges;
+			fo.skip_largest = a.count("fill-skip-largest") ? 1u : 0u;
+			RNB_CHECK(rnb_mesh_fill_holes(ctx, nullptr, &dm, &fo, &cm, nullptr, &fs));
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+		}
+		if (clean && late_clean) run_clean(); // on what the repair and the fill leave
 		rnb_mesh_topology_stats tp;
 		if (report_topology) { // of the mesh as it will be written
 			rnb_mesh_topology_options to;
@@ -637,7 +666,7 @@ int main(int argc, char** argv) {
 		std::printf("%u^3: %llu of %llu bricks kept, %llu evaluated (%.1f %% of the lattice), %llu with a sign change, peak workspace %.1f MB, %.1f ms\n", res,
 		            (unsigned long long)st.n_kept, (unsigned long long)st.n_bricks, (unsigned long long)st.n_evaluated,
 		            100.0 * (double)st.n_points_evaluated / ((double)res * res * res), (unsigned long long)st.n_sign_change, (double)st.peak_workspace / 1e6, st.ms);
-		if (clean && !repair) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
+		if (clean && !late_clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
 		                       cs.n_verts_in, cs.n_verts_out, cs.ms);
 		if (want_seen) std::fputs(seen_report.c_str(), stdout);
 		if (simplify) std::printf("simplify: %u clusters, %u -> %u triangles (%u collapsed), %u -> %u vertices, %u clamped, %u at the mean, %.1f ms\n", ss.n_clusters, ss.n_tris_in,
@@ -645,7 +674,10 @@ int main(int argc, char** argv) {
 		if (repair) std::printf("repair: %u welded, %u degenerate and %u duplicate triangles dropped, %u flipped, %u patches of which %u unorientable, %u -> %u triangles, %u -> %u vertices, %.1f ms\n",
 		                        rs.n_welded, rs.n_degenerate_dropped, rs.n_duplicates_dropped, rs.n_flipped, rs.n_patches, rs.n_unorientable_patches, rs.n_tris_in, rs.n_tris_out, rs.n_verts_in,
 		                        rs.n_verts_out, rs.ms);
-		if (clean && repair) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
+		if (fill_holes) std::printf("fill: %u loops, %u filled, %u not simple, %u over the limit, %u largest left open, %u vertices and %u triangles added, %u -> %u triangles, %.1f ms\n", fs.n_loops,
+		                            fs.n_filled, fs.n_skipped_not_simple, fs.n_skipped_over_max, fs.n_skipped_largest, fs.n_verts_added, fs.n_tris_added, fs.n_tris_out - fs.n_tris_added,
+		                            fs.n_tris_out, fs.ms);
+		if (clean && late_clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
 		                                 cs.n_verts_in, cs.n_verts_out, cs.ms);
 		if (report_topology)
 			std::printf("{\"topology\": {\"n_verts_used\": %u, \"n_tris\": %u, \"n_degenerate\": %u, \"n_edges\": %u, \"n_boundary_edges\": %u, \"n_manifold_edges\": %u, \"n_nonmanifold_edges\": %u, "

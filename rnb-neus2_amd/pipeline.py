@@ -169,7 +169,7 @@ def postprocess_mesh(data_dir, output_mesh_path, logger=None):
 
 
 def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None, texture_from=None,
-                            repair=None, report_topology=False):
+                            repair=None, report_topology=False, fill_holes=None):
     """The last stage on the device: one `build/mesh` process that extracts the mesh of the stage-2 snapshot (plan_two_stage passes --save-snapshot) at `resolution`,
     keeps the largest connected component and turns it outward (include/rnb_mesh_clean.h), and writes `output_mesh_path`. Pure; the snapshot named here is the first
     of snapshot_candidates, run_device_postprocess replaces it by the one that exists. simplify = N: the cleaned mesh is then simplified on N^3 cells over the
@@ -183,7 +183,9 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
     through their cameras (include/rnb_mesh_project.h, build/mesh --texture-from views), the model's albedo where no view reaches; None (the default) plans the command without it.
     repair = True or a dict(weld=bool, duplicates="keep" / "first" / "cancel", orient_consistent=bool): the mesh is repaired on the device after the simplification, and
     the cleaning then acts on the repaired mesh (include/rnb_mesh_topology.h, build/mesh --repair and its flags); report_topology: build/mesh --report-topology prints
-    the census of the final mesh as one JSON line. None / False (the defaults) plan the command without them."""
+    the census of the final mesh as one JSON line. None / False (the defaults) plan the command without them.
+    fill_holes = True or a dict(max_edges=N, skip_largest=bool): the boundary loops of the mesh are closed on the device after keep_seen, the simplification and the repair,
+    and the cleaning then acts on the filled mesh (include/rnb_mesh_holes.h, build/mesh --fill-holes and its flags); None (the default) plans the command without it."""
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if texture_from not in (None, "views"):
@@ -204,6 +206,21 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
         argv += repair_flags(repair)
     if report_topology:
         argv += ["--report-topology"]
+    if fill_holes:
+        argv += fill_holes_flags(fill_holes)
+    return argv
+
+
+def fill_holes_flags(fill_holes):
+    """The --fill-holes flags of build/mesh for plan_device_postprocess' fill_holes."""
+    fh = {} if fill_holes is True else dict(fill_holes)
+    if set(fh) - {"max_edges", "skip_largest"} or (fh.get("max_edges") is not None and int(fh["max_edges"]) < 3):
+        raise ValueError("fill_holes must be True or a dict of max_edges (at least 3) and skip_largest")
+    argv = ["--fill-holes"]
+    if fh.get("max_edges") is not None:
+        argv += ["--fill-max-edges", str(int(fh["max_edges"]))]
+    if fh.get("skip_largest"):
+        argv += ["--fill-skip-largest"]
     return argv
 
 
@@ -251,11 +268,11 @@ def default_mesh_exe(testbed_path):
 
 
 def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None, simplify=None, report_views=False, texture=None, keep_seen=None,
-                           texture_from=None, repair=None, report_topology=False):
+                           texture_from=None, repair=None, report_topology=False, fill_holes=None):
     """postprocess_mesh's job without the OBJ round trip: runs plan_device_postprocess' command, then drops the training output directory as postprocess_mesh does."""
     logger = logger or SimpleLogger()
     cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=simplify, report_views=report_views, texture=texture, keep_seen=keep_seen,
-                                  texture_from=texture_from, repair=repair, report_topology=report_topology)
+                                  texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes)
     found = [p for p in snapshot_candidates(data_dir, max_steps) if os.path.exists(p)]
     if not found:
         raise RuntimeError("Snapshot not found after {} iterations".format(max_steps))
@@ -277,7 +294,7 @@ def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, me
 def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mesh_resolution=1024, scaling_mode="auto", sphere_scale=1.0, margin_px=20,
                       warmup_ratio=0.1, mask_weight=1.0, super_normal=False, use_l1=False, use_rgb_plus=True, has_albedo=False,
                       albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None, device_postprocess=False, mesh_exe=None, simplify=None, report_views=False, texture=None,
-                      keep_seen=None, texture_from=None, repair=None, report_topology=False):
+                      keep_seen=None, texture_from=None, repair=None, report_topology=False, fill_holes=None):
     """load -> prepare (<output_dir>/prepared_data) -> train (two-stage, or warm-up + albedo scaling + two-stage when
     `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
     device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh;
@@ -288,9 +305,12 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     keep_seen (with device_postprocess only): that step also drops what no camera sees (plan_device_postprocess describes the value; build/mesh --keep-seen);
     texture_from = "views" (with texture only): the texture is projected from the input albedo maps instead of baked from the model (build/mesh --texture-from views);
     repair / report_topology (with device_postprocess only): that step also repairs the mesh after the simplification / prints its census (plan_device_postprocess
-    describes the values; build/mesh --repair, --report-topology)."""
+    describes the values; build/mesh --repair, --report-topology);
+    fill_holes (with device_postprocess only): that step also closes the boundary loops of the mesh (plan_device_postprocess describes the value; build/mesh --fill-holes)."""
     if (repair or report_topology) and not device_postprocess:
         raise ValueError("repair and report_topology need device_postprocess")
+    if fill_holes and not device_postprocess:
+        raise ValueError("fill_holes needs device_postprocess")
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if keep_seen is not None and not device_postprocess:
@@ -318,7 +338,7 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     output_mesh = os.path.join(output_dir, "mesh.obj")
     if device_postprocess:
         run_device_postprocess(data_dir, max_steps, mesh_resolution, output_mesh, mesh_exe or default_mesh_exe(testbed_path), logger, simplify=simplify, report_views=report_views, texture=texture,
-                               keep_seen=keep_seen, texture_from=texture_from, repair=repair, report_topology=report_topology)
+                               keep_seen=keep_seen, texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes)
     else:
         postprocess_mesh(data_dir, output_mesh, logger)
     logger.info("=== Pipeline complete ===")

@@ -51,6 +51,9 @@ _SPEC = """
 --duplicates        | str   |        | --repair only: keep, first (build/mesh's default) or cancel
 --orient-consistent | flag  |        | --repair only: wind every orientable patch consistently across its shared edges
 --report-topology   | flag  |        | --device-postprocess only: print the edge census of the final mesh as one JSON line (build/mesh --report-topology)
+--fill-holes        | flag  |        | --device-postprocess only: close the boundary loops of the final mesh on the GPU after --keep-seen and --repair (build/mesh --fill-holes)
+--fill-max-edges    | int   |        | --fill-holes only: leave loops of more than N edges open
+--fill-skip-largest | flag  |        | --fill-holes only: leave the longest loop of every connected component open
 """
 
 
@@ -81,7 +84,7 @@ def pipeline_kwargs(ns):
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
     kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "texture_from", "keep_seen", "seen_min_views",
                                                                                 "seen_rings", "seen_masks", "seen_max_off", "seen_supersample", "repair", "weld", "duplicates", "orient_consistent",
-                                                                                "report_topology")}
+                                                                                "report_topology", "fill_holes", "fill_max_edges", "fill_skip_largest")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
@@ -101,6 +104,8 @@ def pipeline_kwargs(ns):
             kw["repair"] = dict(weld=ns.weld, orient_consistent=ns.orient_consistent, **({"duplicates": ns.duplicates} if ns.duplicates else {}))
         if ns.report_topology:
             kw["report_topology"] = True
+        if ns.fill_holes:
+            kw["fill_holes"] = dict(skip_largest=ns.fill_skip_largest, **({"max_edges": ns.fill_max_edges} if ns.fill_max_edges is not None else {}))
     return kw
 
 
@@ -139,6 +144,13 @@ def main(argv=None):
     for name in ("weld", "duplicates", "orient_consistent"):
         if getattr(ns, name) and not ns.repair:
             parser.error("--%s is only used with --repair" % name.replace("_", "-"))
+    if ns.fill_holes and not ns.device_postprocess:
+        parser.error("--fill-holes is only used with --device-postprocess")
+    for name in ("fill_max_edges", "fill_skip_largest"):
+        if getattr(ns, name) not in (None, False) and not ns.fill_holes:
+            parser.error("--%s is only used with --fill-holes" % name.replace("_", "-"))
+    if ns.fill_max_edges is not None and ns.fill_max_edges < 3:
+        parser.error("--fill-max-edges must be at least 3")
     if ns.duplicates and ns.duplicates not in ("keep", "first", "cancel"):
         parser.error("--duplicates must be keep, first or cancel")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
