@@ -388,9 +388,13 @@ int rnb_set_controller(rnb_ctx* ctx, uint32_t training_step, uint32_t rays_per_b
  *                    out the 4 x 4 weight gradient dW[o][i] = sum_s Y[o][s] X[i][s] as accumulate = RNB_ACCUM_HALF forms it (float bit patterns of half values): slices of 4096 samples
  *                    (here 4096 + 4096 + 64), a half accumulator per slice rounded after every 16-sample k-step, the slices' results added in half
  *                    (tcnn cutlass_matmul.h:83, 315-322 as the oracle's emulated_dw models it; the library's own k_dw_sliced / k_dw_finish code)
+ *   RNB_PRIM_ENCODE_FORM in mask    out the mask that was in force. Not a function of its input but this context's choice, from the next launch on, of how the hash-grid encode
+ *                    gathers: a set bit = eight lanes per sample, an instruction fetching the 8 corners of 8 samples (csrc/common.cuh: level_issue_corners), a clear bit = one lane per
+ *                    sample, an instruction fetching one corner of 64. Bit 0: the network evaluation, bit 1: the point query, bit 2: the training kernels k_fwd_bwd_sdf*. Same bits
+ *                    either way (tests/test_gpu_encode_corners.py); the default, 5, is what measures faster (profiles/ab_encode_corners.txt). Only the HIP library knows it.
  * Host pointers; syncs. */
 typedef enum rnb_primitive { RNB_PRIM_PCG32 = 0, RNB_PRIM_MORTON = 1, RNB_PRIM_SRGB = 2, RNB_PRIM_RAY_BOX = 3, RNB_PRIM_MARCH = 4,
-                             RNB_PRIM_ACTIVATION = 5, RNB_PRIM_WARP = 6, RNB_PRIM_LOSS = 7, RNB_PRIM_PIXEL = 8, RNB_PRIM_GRID = 9, RNB_PRIM_READ_RGBA = 10, RNB_PRIM_CAMERA_RAY = 11, RNB_PRIM_RAY_TARGETS = 12, RNB_PRIM_LOSS_SAMPLE = 13, RNB_PRIM_RAY_LOSS = 14, RNB_PRIM_ENCODE = 15, RNB_PRIM_MARCH_RAY = 16, RNB_PRIM_SDF_DENSITY = 17, RNB_PRIM_PREP_DUE = 18, RNB_PRIM_DW_SLICED = 19 } rnb_primitive;
+                             RNB_PRIM_ACTIVATION = 5, RNB_PRIM_WARP = 6, RNB_PRIM_LOSS = 7, RNB_PRIM_PIXEL = 8, RNB_PRIM_GRID = 9, RNB_PRIM_READ_RGBA = 10, RNB_PRIM_CAMERA_RAY = 11, RNB_PRIM_RAY_TARGETS = 12, RNB_PRIM_LOSS_SAMPLE = 13, RNB_PRIM_RAY_LOSS = 14, RNB_PRIM_ENCODE = 15, RNB_PRIM_MARCH_RAY = 16, RNB_PRIM_SDF_DENSITY = 17, RNB_PRIM_PREP_DUE = 18, RNB_PRIM_DW_SLICED = 19, RNB_PRIM_ENCODE_FORM = 20 } rnb_primitive;
 int rnb_eval_primitives(rnb_ctx* ctx, int kind, const uint32_t* in_host, uint32_t n_items, uint32_t* out_host);
 
 /* Data parallel only: gradient blocks in the order they become final during the backward pass queued by

@@ -372,6 +372,11 @@ class Context:
         self._check(self.f.eval_primitives(self._h, k, a.ctypes.data_as(C.c_void_p), a.shape[0], out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def set_encode_corners(self, mask):
+        """RNB_PRIM_ENCODE_FORM: which kernel groups gather the hash grid with eight lanes per sample (bit 0 network evaluation, 1 point query, 2 training kernels) from the
+        next launch on; returns the mask that was in force. Same results either way."""
+        return int(self.eval_primitives("ENCODE_FORM", [int(mask)])[0, 0])
+
     # -- a training state as data (what a snapshot holds, src/testbed.cu:3333-3390, plus the optimizer's moments) ---------------------------
     def training_state(self, last_stats=None):
         """Everything a fresh context needs to continue this run: master weights, Adam moments and per-parameter step counts, EMA weights, the number of optimizer

@@ -356,6 +356,56 @@ __device__ __forceinline__ void level_consume(const LevelMeta* __restrict__ lm, 
 	}
 }
 
+// ---- the gathers of a level with the tile turned round: eight lanes per sample (RNB_PRIM_ENCODE_FORM) ----
+// level_issue fetches corner c of the wavefront's 64 samples per instruction: up to 64 cache lines, and the x-neighbour of every entry (the next table entry on dense
+// levels, and on hashed levels when x is even) follows one instruction later as a second look-up of the same line. Here instruction i (0..7) serves samples 8 i .. 8 i + 7:
+// lane l fetches corner l & 7 (bit 0 = x, bit 1 = y, bit 2 = z: v's index) of sample 8 i + (l >> 3), so the x-pair is lanes 2 k / 2 k + 1 of one instruction and the y- and
+// z-neighbours of a dense level the rest of the same group of eight. The same eight load instructions per level and the same entries: only which lane asks for which.
+//   issue    every lane forms its own sample's cell as level_issue does (pos_fract, the two multiplies) and leaves {x, y my, z mz} in the slab; the eight lanes of a sample read
+//            them back (one 16-byte read per instruction, 8 addresses per wavefront) and add their corner's offsets: grid_entry's index in the same uint32 arithmetic.
+//   collect  the lanes' eight dwords go back through the slab, [sample][corner]: instruction i writes the 64 consecutive words of its 8 samples; a sample's own lane reads its row
+//            as two 16-byte halves. The halves of the samples with bit 3 set are swapped (lane ^ 4 on the odd instructions), which spreads a ds_read_b128 lane group's 16 rows
+//            over the 16 slots of the 256-byte bank row: conflict-free writes and reads.
+// level_consume then runs unchanged on the eight words. One slab per wavefront, whatever the number of levels in flight: the values in flight stay in registers, the slab is in
+// use only between a write and the reads behind it, and the LDS executes a wavefront's operations in issue order.
+struct __attribute__((aligned(16))) CornerSlab { uint4 cell[64]; uint32_t val[64 * 8]; }; // 3 KB per wavefront
+__device__ __forceinline__ void level_issue_corners(const LevelMeta* __restrict__ lm, const uint32_t* __restrict__ grid, const uint32_t level, const float x, const float y, const float z,
+                                                    CornerSlab* __restrict__ cs, const int lane, uint32_t (&r)[8]) {
+	const uint4 raw = reinterpret_cast<const uint4*>(lm + level)[0], raw2 = reinterpret_cast<const uint4*>(lm + level)[1];
+	const uint32_t off = __builtin_amdgcn_readfirstlane(raw.x), hashmap_size = __builtin_amdgcn_readfirstlane(raw.y);
+	const float scale = __uint_as_float(__builtin_amdgcn_readfirstlane(raw.w));
+	const uint32_t my = __builtin_amdgcn_readfirstlane(raw2.x), mz = __builtin_amdgcn_readfirstlane(raw2.y);
+	const bool dense = __builtin_amdgcn_readfirstlane(raw2.z) != 0u, pow2 = __builtin_amdgcn_readfirstlane(raw2.w) != 0u;
+	const uint32_t* __restrict__ g = grid + off;
+	float pos[3];
+	uint32_t pg[3];
+	pos_fract(x, scale, &pos[0], &pg[0]);
+	pos_fract(y, scale, &pos[1], &pg[1]);
+	pos_fract(z, scale, &pos[2], &pg[2]);
+	cs->cell[lane] = uint4{pg[0], pg[1] * my, pg[2] * mz, 0u};
+	wave_lds_sync();
+	const uint32_t cx = (uint32_t)lane & 1u, cy = ((uint32_t)lane & 2u) ? my : 0u, cz = ((uint32_t)lane & 4u) ? mz : 0u;
+#pragma unroll
+	for (uint32_t i = 0; i < 8; ++i) {
+		const uint4 b = cs->cell[8u * i + ((uint32_t)lane >> 3)];
+		const uint32_t px = b.x + cx, ty = b.y + cy, tz = b.z + cz;
+		uint32_t e = dense ? px + ty + tz : (px ^ (ty ^ tz));
+		const uint32_t w = e >= hashmap_size ? e - hashmap_size : e;
+		e = pow2 ? (e & (hashmap_size - 1u)) : w;
+		r[i] = g[e];
+	}
+}
+__device__ __forceinline__ void level_collect_corners(CornerSlab* __restrict__ cs, const int lane, const uint32_t (&r)[8], uint32_t (&v)[8]) {
+#pragma unroll
+	for (uint32_t i = 0; i < 8; ++i) cs->val[64u * i + ((uint32_t)lane ^ ((i & 1u) ? 4u : 0u))] = r[i];
+	wave_lds_sync();
+	const uint32_t swap = ((uint32_t)lane >> 3) & 1u;
+	const uint4 lo = *reinterpret_cast<const uint4*>(cs->val + 8u * (uint32_t)lane + 4u * swap), hi = *reinterpret_cast<const uint4*>(cs->val + 8u * (uint32_t)lane + 4u * (swap ^ 1u));
+	v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
+	v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+	wave_lds_sync(); // (the next collect rewrites the rows)
+}
+
 // ---- occupancy helpers (src/testbed_nerf.cu:439-475, 569-583, 153-155, 301-323, 429-437) ----
 struct Vec3 { float x, y, z; };
 __device__ __forceinline__ Vec3 v3(float x, float y, float z) { return {x, y, z}; }

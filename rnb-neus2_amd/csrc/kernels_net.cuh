@@ -54,25 +54,45 @@ __device__ __forceinline__ void encode_all_lm(const LevelMeta* __restrict__ lm, 
 	}
 }
 
+// The lane number as a value the compiler cannot follow out of the tile loop. The corner-parallel encode adds per-level offsets that depend on the lane and the level alone
+// (common.cuh: level_issue_corners, cy / cz): hoisted out of the tile loop they are 28 registers that live across the MFMA phases, where the evaluation kernel has none to
+// spare (scratch); formed again for every tile they are two instructions per level.
+__device__ __forceinline__ int tile_local(int lane) { asm volatile("" : "+v"(lane)); return lane; }
+
 // The same encode with the gathers of DEPTH levels in flight (common.cuh: level_issue / level_consume). Levels [0, n_live) are encoded, the others give zeros
 // (grid.h:192-210); n_live is wave-uniform. Fully unrolled: the in-flight values live in registers v[l % DEPTH].
-template <bool GRAD, int DEPTH>
+// CORNERS: the gathers of a level with eight lanes per sample (common.cuh: level_issue_corners / level_collect_corners, through the wavefront's slab `cs`); same bits.
+template <bool GRAD, int DEPTH, bool CORNERS = false>
 __device__ __forceinline__ void encode_all_pipelined(const LevelMeta* __restrict__ lm, const uint32_t n_levels, const uint32_t valid_level, const uint32_t* __restrict__ grid,
-                                                     const float x, const float y, const float z, half_t (&feat)[28], float (&dydx)[GRAD ? 28 : 1][3]) {
+                                                     const float x, const float y, const float z, half_t (&feat)[28], float (&dydx)[GRAD ? 28 : 1][3],
+                                                     CornerSlab* __restrict__ cs = nullptr, const int lane = 0) {
 	const uint32_t n_live = min(n_levels, valid_level + 1u);
 	uint32_t v[DEPTH][8];
 	// No branch anywhere (a branch ends the scheduling region and with it the overlap of the levels' gathers): a level that is not live gathers from the last live
 	// level's table instead (its values are dropped below) -- only before training step 660, when fewer than 14 levels are live.
-	const uint32_t last = n_live ? n_live - 1u : 0u;
+	uint32_t last = n_live ? n_live - 1u : 0u;
+	const int cl = CORNERS ? tile_local(lane) : 0;
+	if constexpr (CORNERS) last = __builtin_amdgcn_readfirstlane((uint32_t)tile_local((int)last)); // (likewise the 14 LDS addresses lm + min(level, last): formed per tile, not kept -- or spilled -- across the MFMA phases)
 #pragma unroll
-	for (uint32_t l = 0; l < (uint32_t)DEPTH; ++l) level_issue(lm, grid, min(l, last), x, y, z, v[l]);
+	for (uint32_t l = 0; l < (uint32_t)DEPTH; ++l) {
+		if constexpr (CORNERS) level_issue_corners(lm, grid, min(l, last), x, y, z, cs, cl, v[l]);
+		else level_issue(lm, grid, min(l, last), x, y, z, v[l]);
+	}
 #pragma unroll
 	for (uint32_t level = 0; level < 14; ++level) {
 		half_t f0, f1;
 		float d0[3], d1[3];
 		const bool live = level < n_live;
-		level_consume<GRAD>(lm, min(level, last), x, y, z, v[level % DEPTH], f0, f1, d0, d1);
-		if (level + DEPTH < 14) level_issue(lm, grid, min(level + (uint32_t)DEPTH, last), x, y, z, v[level % DEPTH]);
+		if constexpr (CORNERS) {
+			uint32_t w[8];
+			level_collect_corners(cs, cl, v[level % DEPTH], w);
+			level_consume<GRAD>(lm, min(level, last), x, y, z, w, f0, f1, d0, d1);
+			if (level + DEPTH < 14) level_issue_corners(lm, grid, min(level + (uint32_t)DEPTH, last), x, y, z, cs, cl, v[level % DEPTH]);
+			__builtin_amdgcn_sched_barrier(0); // one level's arithmetic at a time: interleaved across levels it runs the kernel out of registers (scratch)
+		} else {
+			level_consume<GRAD>(lm, min(level, last), x, y, z, v[level % DEPTH], f0, f1, d0, d1);
+			if (level + DEPTH < 14) level_issue(lm, grid, min(level + (uint32_t)DEPTH, last), x, y, z, v[level % DEPTH]);
+		}
 		feat[level * 2 + 0] = live ? f0 : (half_t)0.f;
 		feat[level * 2 + 1] = live ? f1 : (half_t)0.f;
 		if (GRAD) {
@@ -145,8 +165,8 @@ __device__ __forceinline__ void poison_lds(char* smem_raw, const size_t bytes, c
 #endif
 }
 
-template <bool EMU, int DEPTH>
-__device__ __forceinline__ void point_query_chained_body(const GridMeta& G, const NetW& net, const PointArgs& a, const half_t* __restrict__ wimg, char* smem_raw, LevelMeta* lm) {
+template <bool EMU, int DEPTH, bool CORNERS = false>
+__device__ __forceinline__ void point_query_chained_body(const GridMeta& G, const NetW& net, const PointArgs& a, const half_t* __restrict__ wimg, char* smem_raw, LevelMeta* lm, CornerSlab* cs = nullptr) {
 	poison_lds(smem_raw, LDS_POINT2, threadIdx.x, WG);
 	half_t* wts = reinterpret_cast<half_t*>(smem_raw);
 	fill_level_meta(lm, G, threadIdx.x);
@@ -179,7 +199,7 @@ __device__ __forceinline__ void point_query_chained_body(const GridMeta& G, cons
 		if (valid && a.splat_idx) cell = a.splat_idx[s];
 		half_t feat[28];
 		float dummy[1][3];
-		encode_all_pipelined<false, DEPTH>(lm, n_levels, valid_level, net.grid, x, y, z, feat, dummy);
+		encode_all_pipelined<false, DEPTH, CORNERS>(lm, n_levels, valid_level, net.grid, x, y, z, feat, dummy, CORNERS ? cs + wave : nullptr, lane);
 		write_sdf_in_row(X, lane, x, y, z, feat);
 		wave_lds_sync();
 		h8 bz[4][2];
@@ -219,12 +239,27 @@ __global__ __launch_bounds__(WG, 2) void k_point_query_chained_emul_pipe(const G
 	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
 	point_query_chained_body<true, DEPTH>(G, net, a, wimg, smem_raw, lm);
 }
+// RNB_PRIM_ENCODE_FORM (bit 1): the same two kernels with the corner-parallel gathers; one 3 KB slab per wavefront beside the tiles
+template <int DEPTH>
+__global__ __launch_bounds__(WG, 3) void k_point_query_chained_corners(const GridMeta G, const NetW net, const PointArgs a, const half_t* __restrict__ wimg) {
+	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
+	__shared__ CornerSlab cs[WAVES_PER_WG];
+	point_query_chained_body<false, DEPTH, true>(G, net, a, wimg, smem_raw, lm, cs);
+}
+template <int DEPTH>
+__global__ __launch_bounds__(WG, 2) void k_point_query_chained_emul_corners(const GridMeta G, const NetW net, const PointArgs a, const half_t* __restrict__ wimg) {
+	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
+	__shared__ CornerSlab cs[WAVES_PER_WG];
+	point_query_chained_body<true, DEPTH, true>(G, net, a, wimg, smem_raw, lm, cs);
+}
 
 constexpr int FWD2_WAVE_HALFS = TILE * S32 + TILE * 8 + TILE;
 constexpr size_t LDS_FWD2 = (size_t)(W_FWD_END + WAVES_PER_WG * FWD2_WAVE_HALFS) * sizeof(half_t);
 
-template <bool EMU, int DEPTH>
-__device__ __forceinline__ void forward_chained_body(const GridMeta& G, const NetW& net, const FwdArgs& a, char* smem_raw, LevelMeta* lm) {
+template <bool EMU, int DEPTH, bool CORNERS = false>
+__device__ __forceinline__ void forward_chained_body(const GridMeta& G, const NetW& net, const FwdArgs& a, char* smem_raw, LevelMeta* lm, CornerSlab* cs = nullptr) {
 	poison_lds(smem_raw, LDS_FWD2, threadIdx.x, WG);
 	half_t* wts = reinterpret_cast<half_t*>(smem_raw);
 	fill_level_meta(lm, G, threadIdx.x);
@@ -254,7 +289,7 @@ __device__ __forceinline__ void forward_chained_body(const GridMeta& G, const Ne
 		}
 		half_t feat[28];
 		float dydx[28][3];
-		encode_all_pipelined<true, DEPTH>(lm, n_levels, valid_level, net.grid, c[0], c[1], c[2], feat, dydx);
+		encode_all_pipelined<true, DEPTH, CORNERS>(lm, n_levels, valid_level, net.grid, c[0], c[1], c[2], feat, dydx, CORNERS ? cs + wave : nullptr, lane);
 		write_sdf_in_row(X, lane, c[0], c[1], c[2], feat);
 		wave_lds_sync();
 		// z1 = relu(W0 sdf_in) (registers) ; dz1 = W1[0,:] (.) relu'(z1) (registers)   (nerf_network.h:159-176)
@@ -388,6 +423,21 @@ __global__ __launch_bounds__(WG, 2) void k_forward_chained_emul_pipe(const GridM
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
 	forward_chained_body<true, DEPTH>(G, net, a, smem_raw, lm);
+}
+// RNB_PRIM_ENCODE_FORM (bit 0): the same two kernels with the corner-parallel gathers
+template <int DEPTH>
+__global__ __launch_bounds__(WG, 2) void k_forward_chained_corners(const GridMeta G, const NetW net, const FwdArgs a) {
+	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
+	__shared__ CornerSlab cs[WAVES_PER_WG];
+	forward_chained_body<false, DEPTH, true>(G, net, a, smem_raw, lm, cs);
+}
+template <int DEPTH>
+__global__ __launch_bounds__(WG, 2) void k_forward_chained_emul_corners(const GridMeta G, const NetW net, const FwdArgs a) {
+	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
+	__shared__ CornerSlab cs[WAVES_PER_WG];
+	forward_chained_body<true, DEPTH, true>(G, net, a, smem_raw, lm, cs);
 }
 
 
@@ -794,8 +844,9 @@ __device__ __forceinline__ void export_frags(const h8 (&b)[4][2], half_t* __rest
 // which sums them in the reference's split-K order; without it (the albedo mode's FULL kernel, RNB_DW_SLICED=0) they keep fp32 accumulators in this kernel's tiling (deviation D1').
 // SLICED (half mode, round 6): the weight gradients are NOT accumulated here: the tile's GEMM operands leave feature-major (TrainScratch: dz, dz1, z1, front as the fragments they are formed in,
 // the two input tiles from LDS, dL/dsdf) for k_dw_sliced, which sums them in the reference's split-K order -- 642 B per sample of stores instead of 80 MFMAs per tile.
-template <bool FULL, bool EMU = false, bool SLICED = false>
-__device__ __forceinline__ void fwd_bwd_sdf_body(const GridMeta& G, const NetW& net, const TrainArgs& a, char* smem_raw, LevelMeta* lm) {
+// CORNERS (RNB_PRIM_ENCODE_FORM bit 2): a level's gathers with eight lanes per sample (common.cuh: level_issue_corners), consumed by level_consume: the bits of encode_level_lm.
+template <bool FULL, bool EMU = false, bool SLICED = false, bool CORNERS = false>
+__device__ __forceinline__ void fwd_bwd_sdf_body(const GridMeta& G, const NetW& net, const TrainArgs& a, char* smem_raw, LevelMeta* lm, CornerSlab* cs = nullptr) {
 	poison_lds(smem_raw, FULL ? LDS_FBS_FULL : LDS_FBS, threadIdx.x, WG);
 	half_t* wts = reinterpret_cast<half_t*>(smem_raw);
 	constexpr int W_END = FULL ? SWF_END : SW_END;
@@ -864,11 +915,19 @@ __device__ __forceinline__ void fwd_bwd_sdf_body(const GridMeta& G, const NetW& 
 		reinterpret_cast<f4*>(T.srec)[(size_t)s * 2 + 1] = f4{dn[1], dn[2], 0.f, 0.f};
 		uint32_t* Xrow = reinterpret_cast<uint32_t*>(X + lane * S32);
 		uint32_t* Drow = reinterpret_cast<uint32_t*>(D + lane * S32);
+		const int cl = CORNERS ? tile_local(lane) : 0;
 #pragma unroll 1
 		for (uint32_t level = 0; level < 14; ++level) {
 			half_t f0 = (half_t)0.f, f1 = (half_t)0.f;
 			float d0[3] = {0.f, 0.f, 0.f}, d1[3] = {0.f, 0.f, 0.f};
-			if (level < n_live) encode_level_lm<true>(lm, net.grid, level, c[0], c[1], c[2], f0, f1, d0, d1);
+			if constexpr (CORNERS) {
+				if (level < n_live) {
+					uint32_t gr[8], gv[8];
+					level_issue_corners(lm, net.grid, level, c[0], c[1], c[2], cs + wave, cl, gr);
+					level_collect_corners(cs + wave, cl, gr, gv);
+					level_consume<true>(lm, level, c[0], c[1], c[2], gv, f0, f1, d0, d1);
+				}
+			} else if (level < n_live) encode_level_lm<true>(lm, net.grid, level, c[0], c[1], c[2], f0, f1, d0, d1);
 			float r0 = 0.f, r1 = 0.f;
 #pragma unroll
 			for (int d = 0; d < 3; ++d) { r0 += d0[d] * dn[d]; r1 += d1[d] * dn[d]; }
@@ -1194,6 +1253,14 @@ __global__ __launch_bounds__(WG, 2) void k_fwd_bwd_sdf_full_h(const GridMeta G, 
 	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
 	fwd_bwd_sdf_body<true, true>(G, net, a, smem_raw, lm);
+}
+// RNB_PRIM_ENCODE_FORM (bit 2): the six kernels above with the corner-parallel gathers in their level loop
+template <bool FULL, bool EMU, bool SLICED>
+__global__ __launch_bounds__(WG, 2) void k_fwd_bwd_sdf_corners(const GridMeta G, const NetW net, const TrainArgs a) {
+	extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+	__shared__ LevelMeta lm[RNB_MAX_LEVELS];
+	__shared__ CornerSlab cs[WAVES_PER_WG];
+	fwd_bwd_sdf_body<FULL, EMU, SLICED, true>(G, net, a, smem_raw, lm, cs);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -246,6 +246,9 @@ struct rnb_ctx {
 		bool dw_sliced = true; // RNB_DW_SLICED=0: the half mode's weight gradients in the training kernel's own tiling (deviation D1') instead of the reference's split-K order
 		bool grid_presort = true; // RNB_GRID_PRESORT=0: occupancy updates evaluate their samples in the reference's order (no pregenerate_grid_samples)
 	} knobs;
+	uint32_t encode_corners = 5; // RNB_PRIM_ENCODE_FORM: the hash-grid gathers with eight lanes per sample (common.cuh: level_issue_corners; bit-identical) in bit 0: the network
+	                             // evaluation (k_forward_chained), bit 1: the point query, bit 2: the training kernels (k_fwd_bwd_sdf and its variants). Default 5: the step gains
+	                             // 0.8 % and 1.1 % from bits 0 and 2; the point query's 6 % once in 16 steps is inside the run-to-run spread of the step (profiles/ab_encode_corners.txt)
 	DevBuf<RayLoss> ray_loss;
 	DevBuf<McTable> mc_table; // marching-cubes case table, uploaded on first use
 	RenderWorkspace render; // rnb_render's (driver_render.hpp)
@@ -464,7 +467,10 @@ int launch_point_query(rnb_ctx* c, hipStream_t s, const float* xyz, uint32_t n, 
 	const uint32_t n_tiles = (n + TILE - 1) / TILE;
 	const uint32_t grid = std::min<uint32_t>((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG, (uint32_t)c->n_cus * 5); // 86 VGPRs, 28 KB of LDS: five workgroups per CU
 	const half_t* wimg = (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr;
-	if (c->half_acc()) hipLaunchKernelGGL(k_point_query_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, wimg);
+	if (c->encode_corners & 2u) {
+		if (c->half_acc()) hipLaunchKernelGGL(k_point_query_chained_emul_corners<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, wimg);
+		else hipLaunchKernelGGL(k_point_query_chained_corners<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, wimg);
+	} else if (c->half_acc()) hipLaunchKernelGGL(k_point_query_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, wimg);
 	else hipLaunchKernelGGL(k_point_query_chained_pipe<4>, dim3(grid), dim3(WG), LDS_POINT2, s, c->meta(), c->net(inference), a, wimg);
 	HIP_TRY(hipGetLastError());
 	return RNB_OK;
@@ -633,7 +639,10 @@ int launch_forward(rnb_ctx* c, hipStream_t s, const float* coords, const uint32_
 	a.wimg = (!inference && c->wimg_valid) ? c->wimg_fwd.p : nullptr;
 	const uint32_t n_tiles = (n_max + TILE - 1) / TILE;
 	const uint32_t grid = std::min<uint32_t>((n_tiles + WAVES_PER_WG - 1) / WAVES_PER_WG, (uint32_t)c->n_cus * 2);
-	if (c->half_acc()) hipLaunchKernelGGL(k_forward_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
+	if (c->encode_corners & 1u) {
+		if (c->half_acc()) hipLaunchKernelGGL(k_forward_chained_emul_corners<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
+		else hipLaunchKernelGGL(k_forward_chained_corners<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
+	} else if (c->half_acc()) hipLaunchKernelGGL(k_forward_chained_emul_pipe<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
 	else hipLaunchKernelGGL(k_forward_chained_pipe<4>, dim3(grid), dim3(WG), LDS_FWD2, s, c->meta(), c->net(inference), a);
 	HIP_TRY(hipGetLastError());
 	return RNB_OK;
@@ -880,6 +889,8 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 	// in their own tiling (deviation D1' of rounds 4-5; RNB_DW_SLICED=0: that form).
 	const bool sliced = half && sdf_only && c->knobs.dw_sliced; // (sdf_only: the SDF-only training kernel or the albedo mode's two -- not the generic kernel of RNB_FWD_BWD_GENERIC)
 	const uint32_t n_slices = (B + DW_SLICE - 1) / DW_SLICE;
+	const bool corners = (c->encode_corners & 4u) != 0u; // RNB_PRIM_ENCODE_FORM: the six k_fwd_bwd_sdf kernels with the corner-parallel gathers
+#define FBS_CORNERS(FULL, EMU, SLICED) (k_fwd_bwd_sdf_corners<FULL, EMU, SLICED>)
 	// partial weight gradients: one slab per producing workgroup -- k_dw's workgroups (generic kernel) or k_fwd_bwd_sdf's own; sliced: one per 4096-sample slice (never more than workgroups)
 	const size_t slab = sliced ? (size_t)n_slices : sdf_only ? (size_t)fb_grid : (size_t)c->dw_nwg;
 	float* p_rgb2; float* p_rgb1; float* p_rgb0; float* p_sdf1; float* p_sdf0; float* p_sdf0b; float* p_sdf1b;
@@ -916,13 +927,20 @@ int forward_backward(rnb_ctx* c, hipStream_t s, bool join_dw = true) {
 		else hipLaunchKernelGGL(k_rgb_fwd_bwd, dim3(fb_grid), dim3(WG), LDS_RGB, s, c->net(false), r);
 		a.dcin = c->dcin.p;
 		// (one workgroup per CU -- no register spills, the two-per-CU instance keeps ~80 values in scratch -- lost: 0.88 vs 0.80 ms/step, half the wavefronts to hide the gathers)
-		if (half && sliced) LAUNCH_EV(k_fwd_bwd_sdf_full_hs, dim3(fb_grid), dim3(WG), LDS_FBS_FULL, s, ev_fb, c->meta(), c->net(false), a);
+		if (corners && half && sliced) LAUNCH_EV(FBS_CORNERS(true, true, true), dim3(fb_grid), dim3(WG), LDS_FBS_FULL, s, ev_fb, c->meta(), c->net(false), a);
+		else if (corners && half) LAUNCH_EV(FBS_CORNERS(true, true, false), dim3(fb_grid), dim3(WG), LDS_FBS_FULL, s, ev_fb, c->meta(), c->net(false), a);
+		else if (corners) LAUNCH_EV(FBS_CORNERS(true, false, false), dim3(fb_grid), dim3(WG), LDS_FBS_FULL, s, ev_fb, c->meta(), c->net(false), a);
+		else if (half && sliced) LAUNCH_EV(k_fwd_bwd_sdf_full_hs, dim3(fb_grid), dim3(WG), LDS_FBS_FULL, s, ev_fb, c->meta(), c->net(false), a);
 		else if (half) LAUNCH_EV(k_fwd_bwd_sdf_full_h, dim3(fb_grid), dim3(WG), LDS_FBS_FULL, s, ev_fb, c->meta(), c->net(false), a);
 		else LAUNCH_EV(k_fwd_bwd_sdf_full, dim3(fb_grid), dim3(WG), LDS_FBS_FULL, s, ev_fb, c->meta(), c->net(false), a);
-	} else if (sdf_only && half && sliced) LAUNCH_EV(k_fwd_bwd_sdf_hs, dim3(fb_grid), dim3(WG), LDS_FBS, s, ev_fb, c->meta(), c->net(false), a);
+	} else if (sdf_only && corners && half && sliced) LAUNCH_EV(FBS_CORNERS(false, true, true), dim3(fb_grid), dim3(WG), LDS_FBS, s, ev_fb, c->meta(), c->net(false), a);
+	else if (sdf_only && corners && half) LAUNCH_EV(FBS_CORNERS(false, true, false), dim3(fb_grid), dim3(WG), LDS_FBS, s, ev_fb, c->meta(), c->net(false), a);
+	else if (sdf_only && corners) LAUNCH_EV(FBS_CORNERS(false, false, false), dim3(fb_grid), dim3(WG), LDS_FBS, s, ev_fb, c->meta(), c->net(false), a);
+	else if (sdf_only && half && sliced) LAUNCH_EV(k_fwd_bwd_sdf_hs, dim3(fb_grid), dim3(WG), LDS_FBS, s, ev_fb, c->meta(), c->net(false), a);
 	else if (sdf_only && half) LAUNCH_EV(k_fwd_bwd_sdf_h, dim3(fb_grid), dim3(WG), LDS_FBS, s, ev_fb, c->meta(), c->net(false), a);
 	else if (sdf_only) LAUNCH_EV(k_fwd_bwd_sdf, dim3(fb_grid), dim3(WG), LDS_FBS, s, ev_fb, c->meta(), c->net(false), a);
 	else LAUNCH_EV(k_fwd_bwd, dim3(fb_grid), dim3(WG), LDS_TRAIN, s, ev_fb, c->meta(), c->net(false), a);
+#undef FBS_CORNERS
 	c->prof.mark(s, P_FWD_BWD);
 	c->prof.units[P_FWD_BWD] += B;
 	const TrainScratch& T = c->ts;
@@ -1470,6 +1488,15 @@ int rnb_create(const rnb_config* cfg, rnb_ctx** out) try {
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rgb_fwd_bwd_hs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_RGB));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_full_h), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS_FULL));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_rgb_fwd_bwd_h), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_RGB));
+	// the corner-parallel forms (RNB_PRIM_ENCODE_FORM): the same dynamic LDS; their slabs are static
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_corners<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_forward_chained_emul_corners<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FWD2));
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_corners<false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS));
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_corners<false, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS));
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_corners<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS));
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_corners<true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS_FULL));
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_corners<true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS_FULL));
+	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fwd_bwd_sdf_corners<true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_FBS_FULL));
 	HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_scatter_lds_h), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
 	{
 		const int march_lds_max = (int)((2 * COARSE_WORDS + 2 * COARSE_MAX_BLOCKS) * sizeof(uint32_t));
@@ -2100,8 +2127,12 @@ uint32_t rnb_rays_per_batch(const rnb_ctx* c) { return c ? c->rays_per_batch : 0
 
 int rnb_eval_primitives(rnb_ctx* c, int kind, const uint32_t* in_host, uint32_t n_items, uint32_t* out_host) try {
 	if (!c || (!in_host && n_items) || (!out_host && n_items)) return fail(RNB_ERR_INVALID, "null argument");
-	if (kind < 0 || kind > RNB_PRIM_DW_SLICED) return fail(RNB_ERR_INVALID, "unknown primitive kind");
+	if (kind < 0 || kind > RNB_PRIM_ENCODE_FORM) return fail(RNB_ERR_INVALID, "unknown primitive kind");
 	if (n_items == 0) return RNB_OK;
+	if (kind == RNB_PRIM_ENCODE_FORM) { // host state: which kernel groups gather with eight lanes per sample, from the next launch on (the kernels of either form are always there)
+		for (uint32_t i = 0; i < n_items; ++i) { out_host[i] = c->encode_corners; c->encode_corners = in_host[i] & 7u; }
+		return RNB_OK;
+	}
 	if (kind == RNB_PRIM_PREP_DUE) { // host logic (Testbed::train, src/testbed.cu:2805-2806): does training step in[i] begin with an occupancy update, and the interval it is due at
 		for (uint32_t i = 0; i < n_items; ++i) { out_host[2 * i] = prep_due(in_host[i]) ? 1u : 0u; out_host[2 * i + 1] = std::min(std::max(in_host[i] / 16u, 1u), 16u); }
 		return RNB_OK;
