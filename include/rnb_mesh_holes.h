@@ -52,7 +52,8 @@ extern "C" {
  * area = 0.5 * l and normal[k] = (float)(A[k] / l), or 0 if l == 0.
  *
  * The groupings, their cost and the bucket-load guard are those of rnb_mesh_topology.h (the half-edges by edge); buckets_log2 must be 0 or 4 .. 30. Determinism:
- * the same input gives the same bits, whatever buckets_log2. Planarity and self-intersection of a fill are not examined. A lone triangle's fill is its own reversed
+ * the same input gives the same bits, whatever buckets_log2. Planarity and self-intersection of a fill are not examined here: a fan around the centroid of a strongly
+ * non-planar or non-convex loop can fold over itself, and rnb_mesh_intersections (rnb_mesh_intersect.h) on the filled mesh reports where. A lone triangle's fill is its own reversed
  * copy, a folded pair. A filled loop of 3 edges makes an edge non-manifold only if the input already held a triangle on those three vertices.
  */
 

@@ -958,6 +958,84 @@ MESH_HOLES_PROTOTYPES = {
     "mesh_fill_holes": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshFillHolesOptions), C.POINTER(Mesh), C.c_void_p, C.POINTER(MeshFillHolesStats)]),
 }
 
+# ---- include/rnb_mesh_intersect.h: the self-intersections of a device mesh and the mesh without them, a header of its own with its own version (the HIP library only) ----
+MESH_INTERSECT_ABI_VERSION = 1
+MESH_INTERSECT_PROPER, MESH_INTERSECT_CONTACT = 1, 2
+MESH_INTERSECT_MAX_RINGS, MESH_INTERSECT_MAX_CELLS = 8, 256
+MESH_INTERSECT_PAIR_DTYPE = [("s", "<u4"), ("t", "<u4"), ("cls", "<u4")]  # rnb_mesh_intersect_pair, 12 bytes
+
+
+class MeshIntersectOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("cells", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshIntersectStats(C.Structure):
+    _fields_ = [
+        ("n_tris", C.c_uint32),
+        ("n_degenerate", C.c_uint32),
+        ("n_tris_proper", C.c_uint32),
+        ("n_tris_contact", C.c_uint32),
+        ("n_same_set", C.c_uint64),
+        ("n_candidates", C.c_uint64),
+        ("n_pairs_proper", C.c_uint64),
+        ("n_pairs_contact", C.c_uint64),
+        ("n_coplanar_pairs", C.c_uint64),
+        ("n_pairs_written_would_be", C.c_uint64),
+        ("dims", C.c_uint32 * 3),
+        ("n_large", C.c_uint32),
+        ("cell", C.c_double),
+        ("n_cell_entries", C.c_uint64),
+        ("n_visited", C.c_uint64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("ms_grid", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: (list(getattr(self, name)) if name == "dims" else getattr(self, name)) for name, _ in self._fields_}
+
+
+class MeshIntersectSelectOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("classes", C.c_uint32),
+        ("rings", C.c_uint32),
+        ("drop_unused_vertices", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshIntersectSelectStats(C.Structure):
+    _fields_ = [
+        ("n_verts_in", C.c_uint32),
+        ("n_verts_out", C.c_uint32),
+        ("n_tris_in", C.c_uint32),
+        ("n_tris_out", C.c_uint32),
+        ("n_selected", C.c_uint32),
+        ("n_tris_removed", C.c_uint32),
+        ("n_verts_removed", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved2", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_INTERSECT_PROTOTYPES = {
+    "mesh_intersect_abi_version": (_u32, []),
+    "mesh_intersect_default_options": (_i, [C.POINTER(MeshIntersectOptions)]),
+    "mesh_intersections": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshIntersectOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MeshIntersectStats)]),
+    "mesh_intersections_select_default_options": (_i, [C.POINTER(MeshIntersectSelectOptions)]),
+    "mesh_intersections_select": (_i, [_ctx, _stream, C.POINTER(Mesh), C.c_void_p, C.c_void_p, C.POINTER(MeshIntersectSelectOptions), C.POINTER(Mesh), C.POINTER(MeshIntersectSelectStats)]),
+}
+
 
 class Functions:
     """Bound, typed entry points of one library."""
@@ -980,14 +1058,15 @@ class Functions:
 
 
 def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
-            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False, mesh_holes=False):
+            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False, mesh_holes=False, mesh_intersect=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
     mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
     mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h),
     mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h), mesh_topology=True MESH_TOPOLOGY_PROTOTYPES (include/rnb_mesh_topology.h),
-    mesh_holes=True MESH_HOLES_PROTOTYPES (include/rnb_mesh_holes.h); only the HIP library exports those."""
+    mesh_holes=True MESH_HOLES_PROTOTYPES (include/rnb_mesh_holes.h), mesh_intersect=True MESH_INTERSECT_PROTOTYPES (include/rnb_mesh_intersect.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
                      + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ())
-                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()) + ((MESH_TOPOLOGY_PROTOTYPES,) if mesh_topology else ()) + ((MESH_HOLES_PROTOTYPES,) if mesh_holes else ()))
+                     + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()) + ((MESH_TOPOLOGY_PROTOTYPES,) if mesh_topology else ()) + ((MESH_HOLES_PROTOTYPES,) if mesh_holes else ())
+                     + ((MESH_INTERSECT_PROTOTYPES,) if mesh_intersect else ()))

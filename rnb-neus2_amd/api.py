@@ -47,7 +47,7 @@ def load_library():
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
-                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True, mesh_holes=True)
+                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True, mesh_holes=True, mesh_intersect=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -74,6 +74,8 @@ def load_library():
             raise RuntimeError("mesh-topology ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_holes_abi_version() != _abi.MESH_HOLES_ABI_VERSION:
             raise RuntimeError("mesh-holes ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_intersect_abi_version() != _abi.MESH_INTERSECT_ABI_VERSION:
+            raise RuntimeError("mesh-intersect ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -598,7 +600,8 @@ class Context:
 
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
-                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None, repair=None, topology=False, fill_holes=None):
+                     simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None, repair=None, topology=False, fill_holes=None,
+                     self_intersections=None):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -628,7 +631,27 @@ class Context:
         fill_holes = True or dict(...): after seen_by and repair and before error / topology / texture, still on the device, the boundary loops of the mesh are closed by
         rnb_mesh_fill_holes (include/rnb_mesh_holes.h) with these arguments of DeviceMesh.fill_holes (max_edges, skip_largest, buckets_log2; True: its defaults), and
         the dict gains `fill_stats`; with error=True the distance is then measured to the filled mesh. With None (the default) nothing of that runs and the calls made
-        are exactly those made without it."""
+        are exactly those made without it.
+        self_intersections = True: the dict gains `self_intersections`, the dict of DeviceMesh.self_intersections() of the final mesh (after fill_holes: a fan can
+        fold through its neighbours, and this is the report that tells). "drop": after simplify / repair and before fill_holes, still on the device, the triangles
+        with a proper partner are removed (DeviceMesh.drop_intersecting, its defaults; fill_holes then closes the rims), and the dict gains `drop_stats`. A dict
+        chooses both: drop ("proper" / "all" / None), rings, cells, report (True / False). With None (the default) nothing of that runs and the calls made are
+        exactly those made without it."""
+        if self_intersections is True:
+            self_intersections = dict(report=True)
+        elif self_intersections == "drop":
+            self_intersections = dict(drop="proper")
+        if self_intersections is not None and not isinstance(self_intersections, dict):
+            raise ValueError("self_intersections must be None, True, 'drop' or a dict")
+        if self_intersections is not None and set(self_intersections) - {"drop", "rings", "cells", "report"}:
+            raise ValueError("self_intersections takes drop, rings, cells and report")
+        si = self_intersections or {}
+        si_drop, si_report, si_cells = si.get("drop"), bool(si.get("report")), si.get("cells", 0)
+        if si_drop not in (None, "proper", "all"):
+            raise ValueError("self_intersections['drop'] must be 'proper', 'all' or None")
+        if si:
+            self._intersect_options(si_cells)
+            self._intersect_select_options(si_drop or "proper", si.get("rings", 0))  # a bad argument fails before anything is extracted
         if fill_holes is True:
             fill_holes = {}
         if fill_holes is not None and not isinstance(fill_holes, dict):
@@ -663,9 +686,14 @@ class Context:
             if repair is not None:
                 chain.append(chain[-1].repair(stream=stream, **repair))
                 repaired = chain[-1]
+            if si_drop is not None:
+                chain.append(chain[-1].drop_intersecting(si_drop, si.get("rings", 0), cells=si_cells, stream=stream))
+                dropped = chain[-1]
             if fill_holes is not None:
                 chain.append(chain[-1].fill_holes(stream=stream, **fill_holes))
                 filled = chain[-1]
+            if si_report:
+                si_census = chain[-1].self_intersections(cells=si_cells, stream=stream)
             if grid is not None and error:
                 simplify_error = before.distance_to(chain[-1], symmetric=True, stream=stream)
             if topology:
@@ -692,6 +720,10 @@ class Context:
                 out["fill_stats"] = filled.stats
             if topology:
                 out["topology"] = census
+            if si_drop is not None:
+                out["drop_stats"] = dropped.stats
+            if si_report:
+                out["self_intersections"] = si_census
         finally:
             for m in chain:  # whatever exists by now, oldest first
                 m.free()
@@ -814,6 +846,42 @@ class Context:
             out["stats"] = out["fill_stats"] = filled.stats
             if loop_of_tri:
                 out["loop_of_tri"] = filled.loop_of_tri
+        return out
+
+    def _intersect_options(self, cells=0):
+        if not 0 <= int(cells) <= _abi.MESH_INTERSECT_MAX_CELLS:
+            raise ValueError("cells must be 0 .. 256")
+        opt = _abi.MeshIntersectOptions()
+        self._check(self.f.mesh_intersect_default_options(C.byref(opt)))
+        opt.cells = int(cells)
+        return opt
+
+    def _intersect_select_options(self, classes="proper", rings=0, drop_unused_vertices=True):
+        masks = {"proper": _abi.MESH_INTERSECT_PROPER, "contact": _abi.MESH_INTERSECT_CONTACT, "all": _abi.MESH_INTERSECT_PROPER | _abi.MESH_INTERSECT_CONTACT}
+        if classes not in masks:
+            raise ValueError("classes must be 'proper', 'contact' or 'all'")
+        if not 0 <= int(rings) <= _abi.MESH_INTERSECT_MAX_RINGS:
+            raise ValueError("rings must be 0 .. 8")
+        opt = _abi.MeshIntersectSelectOptions()
+        self._check(self.f.mesh_intersections_select_default_options(C.byref(opt)))
+        opt.classes, opt.rings, opt.drop_unused_vertices = masks[classes], int(rings), int(bool(drop_unused_vertices))
+        return opt
+
+    def mesh_self_intersections(self, verts, indices, pairs=False, cells=0, stream=None):
+        """rnb_mesh_intersections (include/rnb_mesh_intersect.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3]): the dict of
+        DeviceMesh.self_intersections, which describes the keys. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices) as m:
+            return m.self_intersections(pairs, cells, stream=stream)
+
+    def drop_intersecting_mesh(self, verts, indices, colors=None, normals=None, classes="proper", rings=0, drop_unused_vertices=True, cells=0, stream=None):
+        """rnb_mesh_intersections, then rnb_mesh_intersections_select (include/rnb_mesh_intersect.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]),
+        optional per-vertex colors / normals; the arguments are those of DeviceMesh.drop_intersecting. Returns a dict of numpy arrays like clean_mesh, with `stats` =
+        `drop_stats` (the select stats, the census under `census`). Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            dropped = m.drop_intersecting(classes, rings, drop_unused_vertices=drop_unused_vertices, cells=cells, stream=stream)
+        with dropped:
+            out = dropped.download()
+            out["stats"] = out["drop_stats"] = dropped.stats
         return out
 
     @staticmethod
@@ -1420,6 +1488,66 @@ class DeviceMesh(_abi.Mesh):
         finally:
             if lot:
                 c.device_free(lot)
+        return out
+
+    def self_intersections(self, pairs=False, cells=0, on_device=False, stream=None):
+        """rnb_mesh_intersections (include/rnb_mesh_intersect.h): which triangles of this mesh pass through or touch others -> the dict of rnb_mesh_intersect_stats
+        (n_tris, n_degenerate, n_same_set, n_candidates, n_pairs_proper, n_pairs_contact, n_tris_proper, n_tris_contact, n_coplanar_pairs, the grid block dims, cell,
+        n_cell_entries, n_large, n_visited, peak_workspace, ms, ms_grid) with `n_proper` and `n_contact`, uint32[n_triangles]: the partners of every triangle in
+        each class. PROPER: an edge passes through the other triangle's interior, certain in double precision; CONTACT: touching, folded, coplanar overlap or
+        undecided. pairs=True adds `pairs`, uint32[n, 3]: (s, t, class) with s < t, ascending, class 1 = proper, 2 = contact (a second call with the exact capacity is
+        made when the first guess was short). on_device=True: `n_proper` and `n_contact` are device pointers instead, for drop_intersecting(counts=...); the caller
+        releases both with Context.device_free. `cells` (0 = automatic) changes the time, never a bit of the result. Nothing of the mesh changes."""
+        c = self._live()
+        opt, st = c._intersect_options(cells), _abi.MeshIntersectStats()
+        nt, rec = self.n_triangles, np.dtype(_abi.MESH_INTERSECT_PAIR_DTYPE)
+        counts, buf = [], None
+        try:
+            for _ in range(2):
+                counts.append(c.device_malloc(max(nt, 1) * 4))
+            cap = max(256, nt // 8) if pairs else 0
+            for attempt in range(2 if pairs else 1):
+                if pairs:
+                    buf = c.device_malloc(cap * rec.itemsize)
+                c._check(c.f.mesh_intersections(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), counts[0], counts[1], buf, cap, C.byref(st)))
+                if not pairs or st.n_pairs_written_would_be <= cap:
+                    break
+                c.device_free(buf)  # the guess was short: once more with what the list needs
+                buf, cap = None, st.n_pairs_written_would_be
+            out = st.as_dict()
+            if pairs:
+                n = st.n_pairs_written_would_be
+                got = c.download(buf, n, rec) if n else np.empty(0, rec)
+                out["pairs"] = np.stack([got["s"], got["t"], got["cls"]], 1) if n else np.empty((0, 3), np.uint32)
+            if on_device:
+                out["n_proper"], out["n_contact"] = counts
+                counts = []
+            else:
+                for key, ptr in zip(("n_proper", "n_contact"), counts):
+                    out[key] = c.download(ptr, nt, np.uint32) if nt else np.empty(0, np.uint32)
+        finally:
+            for ptr in counts + ([buf] if buf else []):
+                c.device_free(ptr)
+        return out
+
+    def drop_intersecting(self, classes="proper", rings=0, counts=None, drop_unused_vertices=True, cells=0, stream=None):
+        """rnb_mesh_intersections_select (include/rnb_mesh_intersect.h) -> a new DeviceMesh without the triangles that have a partner in `classes` ("proper",
+        "contact" or "all"), the selection grown `rings` times (0 .. 8) by the triangles that share a vertex with it; input order, colours and normals carried
+        along; its `stats` are the select stats. counts: the dict self_intersections(on_device=True) returned for this mesh (it stays the caller's); None: the census
+        is run here (with `cells`), its counts released whether or not a stage fails, and its statistics go to `stats["census"]`. Close the rims with fill_holes."""
+        c = self._live()
+        opt, st = c._intersect_select_options(classes, rings, drop_unused_vertices), _abi.MeshIntersectSelectStats()
+        own = counts is None
+        if own:
+            counts = self.self_intersections(cells=cells, on_device=True, stream=stream)
+        try:
+            out = _returned_mesh(c, st, lambda m: c.f.mesh_intersections_select(c._h, _stream_handle(stream), C.byref(self), counts["n_proper"], counts["n_contact"], C.byref(opt), m, C.byref(st)))
+        finally:
+            if own:
+                c.device_free(counts["n_proper"])
+                c.device_free(counts["n_contact"])
+        if own:
+            out._stats["census"] = {k: v for k, v in counts.items() if k not in ("n_proper", "n_contact")}
         return out
 
     def _distance(self, other, opt, per_vertex, stream):

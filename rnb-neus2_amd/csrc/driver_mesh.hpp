@@ -1,7 +1,8 @@
 // driver_mesh.hpp -- rnb_sdf_lattice, rnb_marching_cubes and the mesh stages rnb_extract_mesh, rnb_mesh_clean, rnb_mesh_simplify, rnb_mesh_distance, rnb_mesh_raster,
 // rnb_mesh_draw_textured, rnb_mesh_visibility, rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views, rnb_mesh_topology, rnb_mesh_repair
 // (include/rnb_mesh_topology.h; their hash join is tp_join, beside them), rnb_mesh_boundary_loops, rnb_mesh_fill_holes (include/rnb_mesh_holes.h; hl_census is the
-// part they share). What they share:
+// part they share), rnb_mesh_intersections, rnb_mesh_intersections_select (include/rnb_mesh_intersect.h; md_build_lists, beside rnb_mesh_distance, is the grid they
+// share with it). What they share:
 //   scan_exclusive, count_and_scan                  the prefix sums behind every numbering, and the count half of a count / write kernel pair
 //   MeshWorkspace, alloc_mesh, hand_over            the device memory of one call and the mesh it returns
 //   check_mesh_input, check_reserved, free_device   the argument checks every stage makes; the *_free functions
@@ -626,6 +627,55 @@ int rnb_mesh_simplify(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_me
 } RNB_GUARD
 
 // ---- mesh-to-mesh distance (include/rnb_mesh_distance.h) ----
+extern "C++" {
+namespace {
+// The search grid of rnb_mesh_distance.h and its cell lists, for the distance stage and for the self-intersection stage (rnb_mesh_intersect.h), which searches a mesh's
+// own box: hres->bmin / bmax hold the box of B's used vertices (k_md_verts<true>), m = B's non-degenerate triangles (>= 1), cells = the option. *g, and start / cursor
+// (the beginning and the end of every cell's list), entries and the large list (hres->n_large, n_entries) as k_md_register leaves them; `of` names B in a failure.
+int md_build_lists(MeshCall& call, const MdMesh& B, uint32_t cells, uint32_t m, const char* of, uint32_t* large, MdResult* dres, MdResult* hres, MdGrid* grid, uint32_t** start_out, uint32_t** cursor_out,
+                   uint32_t** scan_out, uint32_t** entries_out) {
+	const hipStream_t s = call.s;
+	const uint32_t g_tb = groups(B.nt);
+	MdGrid g;
+	std::memset(&g, 0, sizeof(g));
+	uint32_t *start = nullptr, *cursor = nullptr, *scan = nullptr, *entries = nullptr, n_entries = 0;
+	double longest = 0.0;
+	for (int k = 0; k < 3; ++k) {
+		const auto value = [](uint32_t image) { const uint32_t u = (image & 0x80000000u) ? (image ^ 0x80000000u) : ~image; float f; std::memcpy(&f, &u, 4); return (double)f; };
+		g.lo[k] = value(hres->bmin[k]); g.hi[k] = value(hres->bmax[k]);
+		longest = std::max(longest, g.hi[k] - g.lo[k]);
+	}
+	uint32_t n_axis = cells;
+	if (!n_axis) n_axis = (uint32_t)std::min<double>(std::max<double>(std::floor(std::sqrt((double)(m / 2u))), 1.0), (double)RNB_MESH_DISTANCE_MAX_CELLS);
+	g.cell = longest / (double)n_axis; // > 0: a non-degenerate triangle has an extent
+	uint64_t n_cells = 1;
+	for (int k = 0; k < 3; ++k) {
+		g.dims[k] = (uint32_t)std::min<double>((double)n_axis, std::floor((g.hi[k] - g.lo[k]) / g.cell) + 1.0);
+		n_cells *= g.dims[k];
+	}
+	if (!call.ws.alloc(&start, n_cells) || !call.ws.alloc(&cursor, n_cells) || !call.ws.alloc(&scan, scan_scratch_elems(n_cells)))
+		return call.nomem("hipMalloc failed for the lists of " + std::to_string(n_cells) + " cells");
+	HIP_TRY(hipMemsetAsync(start, 0, (size_t)n_cells * 4, s));
+	hipLaunchKernelGGL(k_md_register<false>, dim3(g_tb), dim3(MESH_WG), 0, s, g, B, start, (uint32_t*)nullptr, large, dres);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(hres, dres, sizeof(*hres), hipMemcpyDeviceToHost, s));
+	int rc = scan_exclusive(start, n_cells, s, &n_entries, scan); // (synchronises: hres has arrived)
+	if (rc != RNB_OK) return rc;
+	if (hres->n_large > RNB_MESH_DISTANCE_MAX_LARGE)
+		return call.invalid(std::to_string(hres->n_large) + " triangles " + of + "overlap more than 2048 cells each, the large list holds 4096 (a coarser grid: fewer cells)");
+	if (hres->n_entries > RNB_MESH_DISTANCE_MAX_ENTRIES)
+		return call.invalid(std::to_string(hres->n_entries) + " cell entries, more than 2^31 (a coarser grid: fewer cells)");
+	if (!call.ws.alloc(&entries, n_entries)) return call.nomem("hipMalloc failed for " + std::to_string(n_entries) + " cell entries");
+	HIP_TRY(hipMemcpyAsync(cursor, start, (size_t)n_cells * 4, hipMemcpyDeviceToDevice, s));
+	hipLaunchKernelGGL(k_md_register<true>, dim3(g_tb), dim3(MESH_WG), 0, s, g, B, cursor, entries, (uint32_t*)nullptr, dres);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));
+	*grid = g; *start_out = start; *cursor_out = cursor; *scan_out = scan; *entries_out = entries;
+	return RNB_OK;
+}
+} // namespace
+} // extern "C++"
+
 uint32_t rnb_mesh_distance_abi_version(void) { return RNB_MESH_DISTANCE_ABI_VERSION; }
 
 int rnb_mesh_distance_default_options(rnb_mesh_distance_options* opt) try {
@@ -664,7 +714,6 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 	for (int k = 0; k < 3; ++k) hres.bmin[k] = 0xFFFFFFFFu;
 	MdGrid g;
 	std::memset(&g, 0, sizeof(g));
-	uint32_t n_entries = 0;
 	float ms_grid = 0.0f;
 	int64_t sums[MD_NSUM] = {};
 	if (!nta) { // no sample: every vertex is unused
@@ -700,37 +749,7 @@ int rnb_mesh_distance(rnb_ctx* c, void* stream, const rnb_mesh* from, const rnb_
 		const uint32_t m = ntb - hres.n_deg_to;
 		if (!m) return call.invalid("to has no non-degenerate triangle");
 		// 2. the grid over B's box, the cell lists
-		double longest = 0.0;
-		for (int k = 0; k < 3; ++k) {
-			const auto value = [](uint32_t image) { const uint32_t u = (image & 0x80000000u) ? (image ^ 0x80000000u) : ~image; float f; std::memcpy(&f, &u, 4); return (double)f; };
-			g.lo[k] = value(hres.bmin[k]); g.hi[k] = value(hres.bmax[k]);
-			longest = std::max(longest, g.hi[k] - g.lo[k]);
-		}
-		uint32_t n_axis = opt->cells;
-		if (!n_axis) n_axis = (uint32_t)std::min<double>(std::max<double>(std::floor(std::sqrt((double)(m / 2u))), 1.0), (double)RNB_MESH_DISTANCE_MAX_CELLS);
-		g.cell = longest / (double)n_axis; // > 0: a non-degenerate triangle has an extent
-		uint64_t n_cells = 1;
-		for (int k = 0; k < 3; ++k) {
-			g.dims[k] = (uint32_t)std::min<double>((double)n_axis, std::floor((g.hi[k] - g.lo[k]) / g.cell) + 1.0);
-			n_cells *= g.dims[k];
-		}
-		if (!call.ws.alloc(&start, n_cells) || !call.ws.alloc(&cursor, n_cells) || !call.ws.alloc(&scan, scan_scratch_elems(n_cells)))
-			return call.nomem("hipMalloc failed for the lists of " + std::to_string(n_cells) + " cells");
-		HIP_TRY(hipMemsetAsync(start, 0, (size_t)n_cells * 4, s));
-		hipLaunchKernelGGL(k_md_register<false>, dim3(g_tb), dim3(MESH_WG), 0, s, g, B, start, (uint32_t*)nullptr, large, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
-		int rc = scan_exclusive(start, n_cells, s, &n_entries, scan); // (synchronises: hres has arrived)
-		if (rc != RNB_OK) return rc;
-		if (hres.n_large > RNB_MESH_DISTANCE_MAX_LARGE)
-			return call.invalid(std::to_string(hres.n_large) + " triangles of to overlap more than 2048 cells each, the large list holds 4096 (a coarser grid: fewer cells)");
-		if (hres.n_entries > RNB_MESH_DISTANCE_MAX_ENTRIES)
-			return call.invalid(std::to_string(hres.n_entries) + " cell entries, more than 2^31 (a coarser grid: fewer cells)");
-		if (!call.ws.alloc(&entries, n_entries)) return call.nomem("hipMalloc failed for " + std::to_string(n_entries) + " cell entries");
-		HIP_TRY(hipMemcpyAsync(cursor, start, (size_t)n_cells * 4, hipMemcpyDeviceToDevice, s));
-		hipLaunchKernelGGL(k_md_register<true>, dim3(g_tb), dim3(MESH_WG), 0, s, g, B, cursor, entries, (uint32_t*)nullptr, dres);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(s));
+		if (int rc = md_build_lists(call, B, opt->cells, m, "of to ", large, dres, &hres, &g, &start, &cursor, &scan, &entries); rc != RNB_OK) return rc;
 		ms_grid = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_grid).count();
 		// 3. the queries: the vertices of A, then the sub-centroids of its triangles
 		MdQuery q;
@@ -1906,6 +1925,191 @@ int rnb_mesh_fill_holes(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_
 		std::memset(stats, 0, sizeof(*stats));
 		stats->n_loops = nl; stats->n_filled = C.hres.n_filled; stats->n_skipped_not_simple = C.hres.n_not_simple; stats->n_skipped_over_max = C.hres.n_over_max;
 		stats->n_skipped_largest = C.hres.n_largest; stats->n_verts_added = nva; stats->n_tris_added = nta; stats->n_verts_out = (uint32_t)nvo; stats->n_tris_out = (uint32_t)nto;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- self-intersections (include/rnb_mesh_intersect.h) ----
+uint32_t rnb_mesh_intersect_abi_version(void) { return RNB_MESH_INTERSECT_ABI_VERSION; }
+
+int rnb_mesh_intersect_default_options(rnb_mesh_intersect_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_INTERSECT_ABI_VERSION;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_intersections_select_default_options(rnb_mesh_intersect_select_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_INTERSECT_ABI_VERSION;
+	opt->classes = RNB_MESH_INTERSECT_PROPER;
+	opt->drop_unused_vertices = 1u;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_intersections(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_intersect_options* opt, uint32_t* n_proper_dev, uint32_t* n_contact_dev,
+                           rnb_mesh_intersect_pair* pairs_dev, uint64_t pairs_capacity, rnb_mesh_intersect_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !in || !opt) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections: null argument");
+	if (opt->abi_version != RNB_MESH_INTERSECT_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections: options abi_version mismatch (expected RNB_MESH_INTERSECT_ABI_VERSION)");
+	if (opt->cells > RNB_MESH_INTERSECT_MAX_CELLS) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections: cells must be 0 .. 256");
+	if (int rc = check_reserved("rnb_mesh_intersections", opt->reserved); rc != RNB_OK) return rc;
+	if (pairs_capacity && !pairs_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections: pairs_capacity without pairs_dev");
+	if (n_proper_dev && n_proper_dev == n_contact_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections: n_proper_dev and n_contact_dev must be different buffers");
+	if (int rc = check_mesh_input("rnb_mesh_intersections", in); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	MeshCall call("rnb_mesh_intersections", c, stream);
+	const hipStream_t s = call.s;
+
+	MdResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	for (int k = 0; k < 3; ++k) hres.bmin[k] = 0xFFFFFFFFu;
+	MiResult hmi;
+	std::memset(&hmi, 0, sizeof(hmi));
+	MdGrid g;
+	std::memset(&g, 0, sizeof(g));
+	float ms_grid = 0.0f;
+	if (nt) {
+		const uint32_t g_t = groups(nt);
+		const MdMesh M{m.verts, m.indices, nv, nt};
+		uint32_t *used = nullptr, *large = nullptr, *own_proper = nullptr, *own_contact = nullptr;
+		MdResult* dres = nullptr;
+		MiResult* dmi = nullptr;
+		if (!call.ws.alloc(&used, nv) || !call.ws.alloc(&large, RNB_MESH_DISTANCE_MAX_LARGE) || !call.ws.alloc(&dres, 1) || !call.ws.alloc(&dmi, 1) || (!n_proper_dev && !call.ws.alloc(&own_proper, nt)) ||
+		    (!n_contact_dev && !call.ws.alloc(&own_contact, nt)))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(nt) + " triangles");
+		uint32_t *np = n_proper_dev ? n_proper_dev : own_proper, *nc = n_contact_dev ? n_contact_dev : own_contact;
+		HIP_TRY(hipMemcpyAsync(dres, &hres, sizeof(hres), hipMemcpyHostToDevice, s));
+		HIP_TRY(hipMemsetAsync(dmi, 0, sizeof(MiResult), s));
+		HIP_TRY(hipMemsetAsync(np, 0, (size_t)nt * 4, s));
+		HIP_TRY(hipMemsetAsync(nc, 0, (size_t)nt * 4, s));
+		// 1. every index is range-checked before any is used as an address; the used vertices, their box, the triangles that take part
+		if (int rc = call.check_indices(m, used, &dres->flags); rc != RNB_OK) return rc;
+		hipLaunchKernelGGL(k_md_verts<true>, dim3(groups(nv)), dim3(MESH_WG), 0, s, (const float*)m.verts, nv, (const uint32_t*)used, dres);
+		hipLaunchKernelGGL(k_md_degenerate, dim3(g_t), dim3(MESH_WG), 0, s, M, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (hres.flags & MD_BAD_VALUE) return call.invalid("a coordinate of a used vertex is not finite");
+		call.ws.release(used);
+		const uint32_t live = nt - hres.n_deg_to;
+		if (live) {
+			// 2. the grid over the mesh's own box, the cell lists (the distance stage's)
+			const auto t_grid = std::chrono::steady_clock::now();
+			uint32_t *start = nullptr, *cursor = nullptr, *scan = nullptr, *entries = nullptr, *own = nullptr, *offs = nullptr, *pscan = nullptr;
+			rnb_mesh_intersect_pair* tmp = nullptr;
+			if (int rc = md_build_lists(call, M, opt->cells, live, "", large, dres, &hres, &g, &start, &cursor, &scan, &entries); rc != RNB_OK) return rc;
+			ms_grid = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_grid).count();
+			// 3. the pairs: cell by cell, then against the large list
+			const bool want_pairs = pairs_dev && pairs_capacity;
+			if (want_pairs) {
+				if (!call.ws.alloc(&own, (size_t)nt + 1) || !call.ws.alloc(&offs, (size_t)nt + 1) || !call.ws.alloc(&pscan, scan_scratch_elems((uint64_t)nt + 1)))
+					return call.nomem("hipMalloc failed for the pair counts of " + std::to_string(nt) + " triangles");
+				HIP_TRY(hipMemsetAsync(own, 0, ((size_t)nt + 1) * 4, s));
+			}
+			const unsigned long long n_cells = (unsigned long long)g.dims[0] * g.dims[1] * g.dims[2];
+			const uint32_t g_c = (uint32_t)std::min<unsigned long long>((n_cells + MESH_WG / 64 - 1) / (MESH_WG / 64), 1u << 16);
+			const dim3 g_l(g_t, std::max(hres.n_large, 1u));
+			MiOut out{np, nc, own, nullptr, nullptr};
+			hipLaunchKernelGGL(k_mi_cells<false>, dim3(g_c), dim3(MESH_WG), 0, s, g, M, (const uint32_t*)start, (const uint32_t*)cursor, (const uint32_t*)entries, n_cells, out, dmi);
+			if (hres.n_large) hipLaunchKernelGGL(k_mi_large<false>, g_l, dim3(MESH_WG), 0, s, g, M, (const uint32_t*)large, out, dmi);
+			hipLaunchKernelGGL(k_mi_tally, dim3(g_t), dim3(MESH_WG), 0, s, (const uint32_t*)np, (const uint32_t*)nc, nt, dmi);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(&hmi, dmi, sizeof(hmi), hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			// 4. the pair list: the same pass again, every reported pair into its lower triangle's segment, then ranked inside it
+			const unsigned long long n_reported = hmi.n_proper + hmi.n_contact;
+			if (want_pairs && n_reported) {
+				if (n_reported > 0xFFFFFFFFull) return call.invalid(std::to_string(n_reported) + " pairs: more than 2^32 - 1, too many for a list");
+				uint32_t total = 0;
+				HIP_TRY(hipMemcpyAsync(offs, own, ((size_t)nt + 1) * 4, hipMemcpyDeviceToDevice, s));
+				if (int rc = scan_exclusive(offs, (uint64_t)nt + 1, s, &total, pscan); rc != RNB_OK) return rc;
+				if (total != (uint32_t)n_reported) return call.device("the pair counts do not add up");
+				if (!call.ws.alloc(&tmp, total)) return call.nomem("hipMalloc failed for " + std::to_string(total) + " pairs");
+				HIP_TRY(hipMemsetAsync(own, 0, ((size_t)nt + 1) * 4, s));
+				out = MiOut{np, nc, own, offs, tmp};
+				hipLaunchKernelGGL(k_mi_cells<true>, dim3(g_c), dim3(MESH_WG), 0, s, g, M, (const uint32_t*)start, (const uint32_t*)cursor, (const uint32_t*)entries, n_cells, out, dmi);
+				if (hres.n_large) hipLaunchKernelGGL(k_mi_large<true>, g_l, dim3(MESH_WG), 0, s, g, M, (const uint32_t*)large, out, dmi);
+				hipLaunchKernelGGL(k_mi_rank, dim3(groups(total)), dim3(MESH_WG), 0, s, (const rnb_mesh_intersect_pair*)tmp, (const uint32_t*)offs, total, pairs_dev, (unsigned long long)pairs_capacity);
+				HIP_TRY(hipGetLastError());
+				HIP_TRY(hipStreamSynchronize(s));
+			}
+			call.ws.release(start, cursor, scan, entries, own, offs, pscan, tmp);
+		}
+		call.ws.release(large, dres, dmi, own_proper, own_contact);
+	}
+	if (stats) {
+		stats->n_tris = nt; stats->n_degenerate = hres.n_deg_to; stats->n_tris_proper = hmi.n_tris_proper; stats->n_tris_contact = hmi.n_tris_contact;
+		stats->n_same_set = hmi.n_same; stats->n_candidates = hmi.n_cand; stats->n_pairs_proper = hmi.n_proper; stats->n_pairs_contact = hmi.n_contact;
+		stats->n_coplanar_pairs = hmi.n_coplanar; stats->n_pairs_written_would_be = pairs_dev ? hmi.n_proper + hmi.n_contact : 0ull;
+		for (int k = 0; k < 3; ++k) stats->dims[k] = g.dims[k];
+		stats->n_large = hres.n_large; stats->cell = g.cell; stats->n_cell_entries = hres.n_entries; stats->n_visited = hmi.n_visited;
+		stats->ms_grid = ms_grid;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_intersections_select(rnb_ctx* c, void* stream, const rnb_mesh* in, const uint32_t* n_proper_dev, const uint32_t* n_contact_dev, const rnb_mesh_intersect_select_options* opt,
+                                  rnb_mesh* out, rnb_mesh_intersect_select_stats* stats) try {
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections_select: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_intersections_select", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_INTERSECT_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections_select: options abi_version mismatch (expected RNB_MESH_INTERSECT_ABI_VERSION)");
+	if (!opt->classes || (opt->classes & ~(RNB_MESH_INTERSECT_PROPER | RNB_MESH_INTERSECT_CONTACT))) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections_select: classes must be PROPER, CONTACT or both");
+	if (opt->rings > RNB_MESH_INTERSECT_MAX_RINGS) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections_select: rings must be 0 .. 8");
+	if (opt->drop_unused_vertices > 1u) return fail(RNB_ERR_INVALID, "rnb_mesh_intersections_select: drop_unused_vertices must be 0 or 1");
+	if (int rc = check_reserved("rnb_mesh_intersections_select", opt->reserved); rc != RNB_OK) return rc;
+	if (m.n_indices && (((opt->classes & RNB_MESH_INTERSECT_PROPER) && !n_proper_dev) || ((opt->classes & RNB_MESH_INTERSECT_CONTACT) && !n_contact_dev)))
+		return fail(RNB_ERR_INVALID, "rnb_mesh_intersections_select: the counts of a selected class are null");
+	MeshCall call("rnb_mesh_intersections_select", c, stream);
+	const hipStream_t s = call.s;
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	MiResult hmi;
+	std::memset(&hmi, 0, sizeof(hmi));
+	uint32_t nvo = 0, nto = 0;
+	rnb_mesh o;
+	if (nt) {
+		const uint32_t g_t = groups(nt);
+		const uint32_t* idx = m.indices;
+		uint32_t *used = nullptr, *flag = nullptr, *vmark = nullptr, *vmap = nullptr, *scan = nullptr, *twg = nullptr, *dflags = nullptr;
+		MiResult* dmi = nullptr;
+		if (!call.ws.alloc(&used, nv) || !call.ws.alloc(&flag, nt) || !call.ws.alloc(&vmark, nv) || !call.ws.alloc(&vmap, nv) || !call.ws.alloc(&twg, g_t) ||
+		    !call.ws.alloc(&scan, scan_scratch_elems(std::max<uint64_t>(nv, g_t))) || !call.ws.alloc(&dmi, 1) || !call.ws.alloc(&dflags, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(nt) + " triangles");
+		HIP_TRY(hipMemsetAsync(vmark, 0, (size_t)nv * 4, s));
+		HIP_TRY(hipMemsetAsync(dmi, 0, sizeof(MiResult), s));
+		HIP_TRY(hipMemsetAsync(dflags, 0, 4, s));
+		// 1. every index is range-checked before any is used as an address
+		if (int rc = call.check_indices(m, used, dflags); rc != RNB_OK) return rc;
+		// 2. the selection and its rings (the marks of the earlier rings stay: their triangles are still selected)
+		call.launch(g_t, k_mi_sel_flags, n_proper_dev, n_contact_dev, opt->classes, nt, flag, dmi);
+		for (uint32_t r = 0; r < opt->rings; ++r) {
+			call.launch(g_t, k_mi_sel_mark, idx, nt, (const uint32_t*)flag, vmark);
+			call.launch(g_t, k_mi_sel_grow, idx, nt, flag, (const uint32_t*)vmark);
+		}
+		HIP_TRY(hipGetLastError());
+		// 3. compaction: the kept vertices numbered (used's memory holds their flags), the kept triangles per workgroup
+		uint32_t* vkeep = used;
+		HIP_TRY(hipMemsetAsync(vkeep, 0, (size_t)nv * 4, s));
+		call.launch(groups(opt->drop_unused_vertices ? nt : nv), k_mi_sel_vkeep, idx, nt, nv, (const uint32_t*)flag, opt->drop_unused_vertices ? 0u : 1u, vkeep);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(vmap, vkeep, (size_t)nv * 4, hipMemcpyDeviceToDevice, s));
+		if (int rc = call.compact(m, MiKeep{flag, vkeep}, vmap, twg, scan, &o, &nvo, &nto); rc != RNB_OK) return rc;
+		HIP_TRY(hipMemcpyAsync(&hmi, dmi, sizeof(hmi), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		call.ws.release(used, flag, vmark, vmap, scan, twg, dmi, dflags);
+	} else if (int rc = call.alloc_like(m, &o, 0, 0); rc != RNB_OK)
+		return rc;
+	hand_over(call.ws, o, out);
+	if (stats) {
+		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
+		stats->n_selected = hmi.n_selected; stats->n_tris_removed = nt - nto; stats->n_verts_removed = nv - nvo;
 		call.finish(stats);
 	}
 	return RNB_OK;

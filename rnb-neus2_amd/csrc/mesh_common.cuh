@@ -1,5 +1,5 @@
 // mesh_common.cuh — what the mesh stages share (every kernels_mesh*.cuh file); the only header they include from each other (but for kernels_mesh_visibility.cuh, which
-// runs the rasteriser's fill and the cleaner's components and includes both, kernels_mesh_topology.cuh, which unites with the cleaner's cl_find / cl_unite, kernels_mesh_holes.cuh, which reads the topology stage's edge join, and kernels_mesh_project.cuh and kernels_mesh_draw.cuh, which call the baker's and the
+// runs the rasteriser's fill and the cleaner's components and includes both, kernels_mesh_topology.cuh, which unites with the cleaner's cl_find / cl_unite, kernels_mesh_holes.cuh, which reads the topology stage's edge join, kernels_mesh_intersect.cuh, which searches the distance stage's cell lists, and kernels_mesh_project.cuh and kernels_mesh_draw.cuh, which call the baker's and the
 // rasteriser's device functions):
 //   MESH_WG, MESH_NONE, MESH_BAD_INDEX             the workgroup width of every mesh kernel, the "none" index, the bit k_mesh_validate sets in a stage's flag word
 //   k_scan_blocks / k_scan_add, wg_exclusive_256   the prefix sums that number every vertex, triangle, brick and cluster (the driver's scan_exclusive; the count / write kernel pairs)

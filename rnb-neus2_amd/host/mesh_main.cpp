@@ -7,7 +7,7 @@
 //        [--texture S [--texture-maps albedo[,normal]] [--texture-from views [--texture-mode blend|best] [--texture-depth-tolerance T] [--texture-min-cos C]]]
 //        [--keep-seen component|faces [--seen-min-views N] [--seen-rings R] [--seen-masks [--seen-max-off N]] [--seen-supersample K]]
 //        [--repair [--weld] [--duplicates keep|first|cancel] [--orient-consistent]] [--report-topology]
-//        [--fill-holes [--fill-max-edges N] [--fill-skip-largest]]
+//        [--drop-intersecting proper|all [--drop-rings R]] [--fill-holes [--fill-max-edges N] [--fill-skip-largest]] [--report-intersections]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -44,6 +44,9 @@
 // triangle for a loop of 3 edges, a fan around a new vertex at the centroid for a longer one; --fill-max-edges N leaves longer loops open, --fill-skip-largest the
 // longest loop of every connected component (the rim of a relief). Boundary components that are not one simple cycle stay open and are counted in the `fill:` line.
 // --keep / --orient, if given, then act on the filled mesh, as they do on the repaired one; --report-topology and --texture describe the filled mesh.
+// With --drop-intersecting the triangles that pass through other triangles of the mesh (proper), or also those that touch or overlap them (all), are removed by
+// rnb_mesh_intersections and rnb_mesh_intersections_select (include/rnb_mesh_intersect.h) after --simplify / --repair and before --fill-holes, which closes the rims;
+// with --report-intersections the census of the mesh as written is printed as one JSON line, {"intersections": {...}}.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -57,6 +60,7 @@
 #include "../../include/rnb_mesh_project.h"
 #include "../../include/rnb_mesh_topology.h"
 #include "../../include/rnb_mesh_holes.h"
+#include "../../include/rnb_mesh_intersect.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -115,6 +119,9 @@ const Flag FLAGS[] = {
 	{"fill-holes", nullptr, "(takes no value). Close the boundary loops of the mesh on the device, after --keep-seen, --simplify and --repair; --keep / --orient then act on the filled mesh."},
 	{"fill-max-edges", "N", "--fill-holes only. Leave loops of more than N edges open (default: fill every simple loop)."},
 	{"fill-skip-largest", nullptr, "--fill-holes only (takes no value). Leave the longest loop of every connected component open: the rim of a relief."},
+	{"drop-intersecting", "MODE", "Remove self-intersecting triangles on the device. proper: those an edge of another triangle of the mesh passes through; all: also those that touch or overlap others; after --simplify / --repair and before --fill-holes."},
+	{"drop-rings", "R", "--drop-intersecting only. Also remove R rings of triangles around them (0 .. 8, default 0)."},
+	{"report-intersections", nullptr, "(takes no value). Print the self-intersection census of the written mesh as one JSON line: candidates, proper and contact pairs and triangles."},
 	{"report-topology", nullptr, "(takes no value). Print the edge census of the written mesh as one JSON line: edges by kind, duplicates, patches, boundary loops, Euler characteristic."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -387,6 +394,8 @@ int main(int argc, char** argv) {
 	ProjectOptions project;
 	bool repair = false, report_topology = false, fill_holes = false;
 	uint32_t fill_max_edges = 0;
+	bool report_intersections = false;
+	uint32_t drop_classes = 0, drop_rings = 0; // 0: nothing is dropped
 	rnb_mesh_repair_options repair_opt;
 	std::memset(&repair_opt, 0, sizeof(repair_opt));
 	try {
@@ -501,6 +510,17 @@ int main(int argc, char** argv) {
 			fill_max_edges = parse_u32("fill-max-edges", a["fill-max-edges"]);
 			if (fill_max_edges < 3) throw ParseError("Argument 'fill-max-edges' must be at least 3");
 		}
+		if (a.count("report-intersections")) report_intersections = true;
+		if (a.count("drop-intersecting")) {
+			if (a["drop-intersecting"] == "proper") drop_classes = RNB_MESH_INTERSECT_PROPER;
+			else if (a["drop-intersecting"] == "all") drop_classes = RNB_MESH_INTERSECT_PROPER | RNB_MESH_INTERSECT_CONTACT;
+			else throw ParseError("Argument 'drop-intersecting' must be proper or all");
+		}
+		if (a.count("drop-rings")) {
+			if (!drop_classes) throw ParseError("Argument 'drop-rings' is only used with --drop-intersecting");
+			drop_rings = parse_u32("drop-rings", a["drop-rings"]);
+			if (drop_rings > RNB_MESH_INTERSECT_MAX_RINGS) throw ParseError("Argument 'drop-rings' must be 0 .. 8");
+		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
 		print_help(std::cerr, argv[0]);
@@ -559,8 +579,8 @@ int main(int argc, char** argv) {
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		};
-		const bool late_clean = repair || fill_holes;
-		if (clean && !late_clean) run_clean(); // (with --repair or --fill-holes: after them, below)
+		const bool late_clean = repair || fill_holes || drop_classes;
+		if (clean && !late_clean) run_clean(); // (with --repair, --drop-intersecting or --fill-holes: after them, below)
 		std::string seen_report;
 		if (want_seen) { // device to device, after the cleaning and before the simplification
 			keep_seen(ctx, ds, dm, seen, &cm, seen_report);
@@ -600,6 +620,27 @@ int main(int argc, char** argv) {
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		}
+		rnb_mesh_intersect_stats is;
+		rnb_mesh_intersect_select_stats xs;
+		if (drop_classes) { // device to device, after the repair and before the fill, which closes the rims this leaves
+			rnb_mesh_intersect_options io;
+			rnb_mesh_intersect_select_options xo;
+			RNB_CHECK(rnb_mesh_intersect_default_options(&io));
+			RNB_CHECK(rnb_mesh_intersections_select_default_options(&xo));
+			xo.classes = drop_classes; xo.rings = drop_rings;
+			const uint64_t nt = std::max<uint64_t>(dm.n_indices / 3u, 1);
+			void *np = nullptr, *nc = nullptr;
+			RNB_CHECK(rnb_device_malloc(ctx, nt * 4, &np));
+			int rc = rnb_device_malloc(ctx, nt * 4, &nc);
+			if (rc == RNB_OK) rc = rnb_mesh_intersections(ctx, nullptr, &dm, &io, (uint32_t*)np, (uint32_t*)nc, nullptr, 0, &is);
+			if (rc == RNB_OK) rc = rnb_mesh_intersections_select(ctx, nullptr, &dm, (const uint32_t*)np, (const uint32_t*)nc, &xo, &cm, &xs);
+			(void)rnb_device_free(ctx, np);
+			if (nc) (void)rnb_device_free(ctx, nc);
+			RNB_CHECK(rc);
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+		}
 		rnb_mesh_fill_holes_stats fs;
 		if (fill_holes) { // device to device, after the repair
 			rnb_mesh_fill_holes_options fo;
@@ -617,6 +658,12 @@ int main(int argc, char** argv) {
 			rnb_mesh_topology_options to;
 			RNB_CHECK(rnb_mesh_topology_default_options(&to));
 			RNB_CHECK(rnb_mesh_topology(ctx, nullptr, &dm, &to, nullptr, nullptr, nullptr, nullptr, &tp));
+		}
+		rnb_mesh_intersect_stats ri;
+		if (report_intersections) { // of the mesh as it will be written
+			rnb_mesh_intersect_options io;
+			RNB_CHECK(rnb_mesh_intersect_default_options(&io));
+			RNB_CHECK(rnb_mesh_intersections(ctx, nullptr, &dm, &io, nullptr, nullptr, nullptr, 0, &ri));
 		}
 		// --report-views: made here, while the mesh is on the device and in the frame of the loaded views; printed and written after the mesh's own lines, below
 		std::string views_report, views_json;
@@ -674,6 +721,10 @@ int main(int argc, char** argv) {
 		if (repair) std::printf("repair: %u welded, %u degenerate and %u duplicate triangles dropped, %u flipped, %u patches of which %u unorientable, %u -> %u triangles, %u -> %u vertices, %.1f ms\n",
 		                        rs.n_welded, rs.n_degenerate_dropped, rs.n_duplicates_dropped, rs.n_flipped, rs.n_patches, rs.n_unorientable_patches, rs.n_tris_in, rs.n_tris_out, rs.n_verts_in,
 		                        rs.n_verts_out, rs.ms);
+		if (drop_classes)
+			std::printf("drop intersecting: %llu proper and %llu contact pairs among %llu candidates, %u triangles selected, %u -> %u triangles, %u -> %u vertices, %.1f + %.1f ms\n",
+			            (unsigned long long)is.n_pairs_proper, (unsigned long long)is.n_pairs_contact, (unsigned long long)is.n_candidates, xs.n_selected, xs.n_tris_in, xs.n_tris_out, xs.n_verts_in,
+			            xs.n_verts_out, is.ms, xs.ms);
 		if (fill_holes) std::printf("fill: %u loops, %u filled, %u not simple, %u over the limit, %u largest left open, %u vertices and %u triangles added, %u -> %u triangles, %.1f ms\n", fs.n_loops,
 		                            fs.n_filled, fs.n_skipped_not_simple, fs.n_skipped_over_max, fs.n_skipped_largest, fs.n_verts_added, fs.n_tris_added, fs.n_tris_out - fs.n_tris_added,
 		                            fs.n_tris_out, fs.ms);
@@ -685,6 +736,13 @@ int main(int argc, char** argv) {
 			            "\"n_unorientable_patches\": %u, \"n_boundary_components\": %u, \"closed\": %u, \"oriented\": %u, \"euler\": %lld}}\n",
 			            tp.n_verts_used, tp.n_tris, tp.n_degenerate, tp.n_edges, tp.n_boundary_edges, tp.n_manifold_edges, tp.n_nonmanifold_edges, tp.n_inconsistent_edges, tp.max_faces_on_edge,
 			            tp.n_duplicate_tris, tp.n_folded_pairs, tp.n_components, tp.n_patches, tp.n_unorientable_patches, tp.n_boundary_components, tp.closed, tp.oriented, (long long)tp.euler);
+		if (report_intersections)
+			std::printf("{\"intersections\": {\"n_tris\": %u, \"n_degenerate\": %u, \"n_same_set\": %llu, \"n_candidates\": %llu, \"n_pairs_proper\": %llu, \"n_pairs_contact\": %llu, "
+			            "\"n_tris_proper\": %u, \"n_tris_contact\": %u, \"n_coplanar_pairs\": %llu, \"dims\": [%u, %u, %u], \"n_large\": %u, \"n_cell_entries\": %llu, \"n_visited\": %llu, "
+			            "\"ms\": %.3f}}\n",
+			            ri.n_tris, ri.n_degenerate, (unsigned long long)ri.n_same_set, (unsigned long long)ri.n_candidates, (unsigned long long)ri.n_pairs_proper, (unsigned long long)ri.n_pairs_contact,
+			            ri.n_tris_proper, ri.n_tris_contact, (unsigned long long)ri.n_coplanar_pairs, ri.dims[0], ri.dims[1], ri.dims[2], ri.n_large, (unsigned long long)ri.n_cell_entries,
+			            (unsigned long long)ri.n_visited, ri.ms);
 		if (report_error) {
 			double mean[2], rms[2];
 			for (int k = 0; k < 2; ++k) {

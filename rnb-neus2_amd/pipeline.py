@@ -169,7 +169,7 @@ def postprocess_mesh(data_dir, output_mesh_path, logger=None):
 
 
 def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None, texture_from=None,
-                            repair=None, report_topology=False, fill_holes=None):
+                            repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False):
     """The last stage on the device: one `build/mesh` process that extracts the mesh of the stage-2 snapshot (plan_two_stage passes --save-snapshot) at `resolution`,
     keeps the largest connected component and turns it outward (include/rnb_mesh_clean.h), and writes `output_mesh_path`. Pure; the snapshot named here is the first
     of snapshot_candidates, run_device_postprocess replaces it by the one that exists. simplify = N: the cleaned mesh is then simplified on N^3 cells over the
@@ -185,7 +185,11 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
     the cleaning then acts on the repaired mesh (include/rnb_mesh_topology.h, build/mesh --repair and its flags); report_topology: build/mesh --report-topology prints
     the census of the final mesh as one JSON line. None / False (the defaults) plan the command without them.
     fill_holes = True or a dict(max_edges=N, skip_largest=bool): the boundary loops of the mesh are closed on the device after keep_seen, the simplification and the repair,
-    and the cleaning then acts on the filled mesh (include/rnb_mesh_holes.h, build/mesh --fill-holes and its flags); None (the default) plans the command without it."""
+    and the cleaning then acts on the filled mesh (include/rnb_mesh_holes.h, build/mesh --fill-holes and its flags); None (the default) plans the command without it.
+    drop_intersecting = "proper" or "all", or a dict(classes=..., rings=R): the triangles that pass through (all: or touch) other triangles of the mesh are removed on
+    the device after the simplification and the repair and before fill_holes, which closes the rims (include/rnb_mesh_intersect.h, build/mesh --drop-intersecting and
+    --drop-rings); report_intersections: build/mesh --report-intersections prints the self-intersection census of the final mesh as one JSON line. None / False (the
+    defaults) plan the command without them."""
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if texture_from not in (None, "views"):
@@ -208,6 +212,21 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
         argv += ["--report-topology"]
     if fill_holes:
         argv += fill_holes_flags(fill_holes)
+    if drop_intersecting:
+        argv += drop_intersecting_flags(drop_intersecting)
+    if report_intersections:
+        argv += ["--report-intersections"]
+    return argv
+
+
+def drop_intersecting_flags(drop_intersecting):
+    """The --drop-intersecting flags of build/mesh for plan_device_postprocess' drop_intersecting."""
+    di = dict(classes=drop_intersecting) if isinstance(drop_intersecting, str) else dict(drop_intersecting)
+    if set(di) - {"classes", "rings"} or di.get("classes") not in ("proper", "all") or not 0 <= int(di.get("rings") or 0) <= 8:
+        raise ValueError("drop_intersecting must be 'proper', 'all' or a dict of classes ('proper' / 'all') and rings (0 .. 8)")
+    argv = ["--drop-intersecting", di["classes"]]
+    if di.get("rings") is not None:
+        argv += ["--drop-rings", str(int(di["rings"]))]
     return argv
 
 
@@ -268,11 +287,12 @@ def default_mesh_exe(testbed_path):
 
 
 def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None, simplify=None, report_views=False, texture=None, keep_seen=None,
-                           texture_from=None, repair=None, report_topology=False, fill_holes=None):
+                           texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False):
     """postprocess_mesh's job without the OBJ round trip: runs plan_device_postprocess' command, then drops the training output directory as postprocess_mesh does."""
     logger = logger or SimpleLogger()
     cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=simplify, report_views=report_views, texture=texture, keep_seen=keep_seen,
-                                  texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes)
+                                  texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes,
+                                  drop_intersecting=drop_intersecting, report_intersections=report_intersections)
     found = [p for p in snapshot_candidates(data_dir, max_steps) if os.path.exists(p)]
     if not found:
         raise RuntimeError("Snapshot not found after {} iterations".format(max_steps))
@@ -294,7 +314,7 @@ def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, me
 def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mesh_resolution=1024, scaling_mode="auto", sphere_scale=1.0, margin_px=20,
                       warmup_ratio=0.1, mask_weight=1.0, super_normal=False, use_l1=False, use_rgb_plus=True, has_albedo=False,
                       albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None, device_postprocess=False, mesh_exe=None, simplify=None, report_views=False, texture=None,
-                      keep_seen=None, texture_from=None, repair=None, report_topology=False, fill_holes=None):
+                      keep_seen=None, texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False):
     """load -> prepare (<output_dir>/prepared_data) -> train (two-stage, or warm-up + albedo scaling + two-stage when
     `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
     device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh;
@@ -306,11 +326,15 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     texture_from = "views" (with texture only): the texture is projected from the input albedo maps instead of baked from the model (build/mesh --texture-from views);
     repair / report_topology (with device_postprocess only): that step also repairs the mesh after the simplification / prints its census (plan_device_postprocess
     describes the values; build/mesh --repair, --report-topology);
-    fill_holes (with device_postprocess only): that step also closes the boundary loops of the mesh (plan_device_postprocess describes the value; build/mesh --fill-holes)."""
+    fill_holes (with device_postprocess only): that step also closes the boundary loops of the mesh (plan_device_postprocess describes the value; build/mesh --fill-holes).
+    drop_intersecting, report_intersections (with device_postprocess only): that step also removes the self-intersecting triangles before it fills, and prints the
+    self-intersection census of the final mesh (plan_device_postprocess describes the values; build/mesh --drop-intersecting, --report-intersections)."""
     if (repair or report_topology) and not device_postprocess:
         raise ValueError("repair and report_topology need device_postprocess")
     if fill_holes and not device_postprocess:
         raise ValueError("fill_holes needs device_postprocess")
+    if (drop_intersecting or report_intersections) and not device_postprocess:
+        raise ValueError("drop_intersecting and report_intersections need device_postprocess")
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if keep_seen is not None and not device_postprocess:
@@ -338,7 +362,8 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     output_mesh = os.path.join(output_dir, "mesh.obj")
     if device_postprocess:
         run_device_postprocess(data_dir, max_steps, mesh_resolution, output_mesh, mesh_exe or default_mesh_exe(testbed_path), logger, simplify=simplify, report_views=report_views, texture=texture,
-                               keep_seen=keep_seen, texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes)
+                               keep_seen=keep_seen, texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes,
+                               drop_intersecting=drop_intersecting, report_intersections=report_intersections)
     else:
         postprocess_mesh(data_dir, output_mesh, logger)
     logger.info("=== Pipeline complete ===")

@@ -54,6 +54,9 @@ _SPEC = """
 --fill-holes        | flag  |        | --device-postprocess only: close the boundary loops of the final mesh on the GPU after --keep-seen and --repair (build/mesh --fill-holes)
 --fill-max-edges    | int   |        | --fill-holes only: leave loops of more than N edges open
 --fill-skip-largest | flag  |        | --fill-holes only: leave the longest loop of every connected component open
+--drop-intersecting | str   |        | --device-postprocess only: remove the self-intersecting triangles of the final mesh on the GPU before --fill-holes, proper or all (build/mesh --drop-intersecting)
+--drop-rings        | int   |        | --drop-intersecting only: also remove R rings of triangles around them (0 .. 8)
+--report-intersections | flag |      | --device-postprocess only: print the self-intersection census of the final mesh as one JSON line (build/mesh --report-intersections)
 """
 
 
@@ -84,7 +87,8 @@ def pipeline_kwargs(ns):
                "albedo_sfm": "albedo_sfm_path", "mask_sfm": "mask_sfm_path", "mask_folder": "mask_folder_path"}
     kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "texture_from", "keep_seen", "seen_min_views",
                                                                                 "seen_rings", "seen_masks", "seen_max_off", "seen_supersample", "repair", "weld", "duplicates", "orient_consistent",
-                                                                                "report_topology", "fill_holes", "fill_max_edges", "fill_skip_largest")}
+                                                                                "report_topology", "fill_holes", "fill_max_edges", "fill_skip_largest", "drop_intersecting", "drop_rings",
+                                                                                "report_intersections")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
@@ -106,6 +110,10 @@ def pipeline_kwargs(ns):
             kw["report_topology"] = True
         if ns.fill_holes:
             kw["fill_holes"] = dict(skip_largest=ns.fill_skip_largest, **({"max_edges": ns.fill_max_edges} if ns.fill_max_edges is not None else {}))
+        if ns.drop_intersecting:
+            kw["drop_intersecting"] = dict(classes=ns.drop_intersecting, **({"rings": ns.drop_rings} if ns.drop_rings is not None else {}))
+        if ns.report_intersections:
+            kw["report_intersections"] = True
     return kw
 
 
@@ -151,6 +159,14 @@ def main(argv=None):
             parser.error("--%s is only used with --fill-holes" % name.replace("_", "-"))
     if ns.fill_max_edges is not None and ns.fill_max_edges < 3:
         parser.error("--fill-max-edges must be at least 3")
+    if (ns.drop_intersecting or ns.report_intersections) and not ns.device_postprocess:
+        parser.error("--drop-intersecting and --report-intersections are only used with --device-postprocess")
+    if ns.drop_intersecting and ns.drop_intersecting not in ("proper", "all"):
+        parser.error("--drop-intersecting must be proper or all")
+    if ns.drop_rings is not None and not ns.drop_intersecting:
+        parser.error("--drop-rings is only used with --drop-intersecting")
+    if ns.drop_rings is not None and not 0 <= ns.drop_rings <= 8:
+        parser.error("--drop-rings must be 0 .. 8")
     if ns.duplicates and ns.duplicates not in ("keep", "first", "cancel"):
         parser.error("--duplicates must be keep, first or cancel")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
