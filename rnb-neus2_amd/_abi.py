@@ -1037,6 +1037,81 @@ MESH_INTERSECT_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_smooth.h: Taubin passes over the one-ring and ring normals of a device mesh, a header of its own with its own version (the HIP library only) ----
+MESH_SMOOTH_ABI_VERSION = 1
+MESH_SMOOTH_MAX_RING, MESH_SMOOTH_MAX_PASSES, MESH_SMOOTH_MAX_SELECT_RINGS = 1 << 20, 10000, 1024
+MESH_SMOOTH_Q_SHIFT, MESH_SMOOTH_Q_TERM_LOG2, MESH_SMOOTH_NORMAL_Q_SHIFT, MESH_SMOOTH_NORMAL_Q_TERM_LOG2 = 32, 10, 40, 3
+MESH_SMOOTH_KIND_UNUSED, MESH_SMOOTH_KIND_INTERIOR, MESH_SMOOTH_KIND_BOUNDARY, MESH_SMOOTH_KIND_NONMANIFOLD = 0, 1, 2, 3
+MESH_SMOOTH_BOUNDARY_PIN, MESH_SMOOTH_BOUNDARY_SLIDE, MESH_SMOOTH_BOUNDARY_FREE = 0, 1, 2
+MESH_SMOOTH_NORMALS_KEEP, MESH_SMOOTH_NORMALS_RECOMPUTE = 0, 1
+
+
+class MeshSmoothOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("passes", C.c_uint32),
+        ("lambda_", C.c_double),  # `lambda` in the header
+        ("mu", C.c_double),
+        ("boundary", C.c_uint32),
+        ("select_rings", C.c_uint32),
+        ("normals", C.c_uint32),
+        ("buckets_log2", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshSmoothStats(C.Structure):
+    _fields_ = [
+        ("n_edges", C.c_uint32),
+        ("n_interior", C.c_uint32),
+        ("n_boundary", C.c_uint32),
+        ("n_nonmanifold", C.c_uint32),
+        ("n_unused", C.c_uint32),
+        ("n_selected", C.c_uint32),
+        ("n_moving", C.c_uint32),
+        ("max_valence", C.c_uint32),
+        ("passes", C.c_uint32),
+        ("n_wide", C.c_uint32),
+        ("max_displacement", C.c_double),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("ms_passes", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class MeshVertexNormalsOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("flip", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshVertexNormalsStats(C.Structure):
+    _fields_ = [
+        ("n_zero", C.c_uint32),
+        ("max_corners", C.c_uint32),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if not name.startswith("reserved")}
+
+
+MESH_SMOOTH_PROTOTYPES = {
+    "mesh_smooth_abi_version": (_u32, []),
+    "mesh_smooth_default_options": (_i, [C.POINTER(MeshSmoothOptions)]),
+    "mesh_vertex_normals_default_options": (_i, [C.POINTER(MeshVertexNormalsOptions)]),
+    "mesh_smooth": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshSmoothOptions), C.c_void_p, C.POINTER(Mesh), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MeshSmoothStats)]),
+    "mesh_vertex_normals": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshVertexNormalsOptions), C.c_void_p, C.POINTER(MeshVertexNormalsStats)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -1058,15 +1133,16 @@ class Functions:
 
 
 def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
-            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False, mesh_holes=False, mesh_intersect=False):
+            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False, mesh_holes=False, mesh_intersect=False, mesh_smooth=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
     mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
     mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h),
     mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h), mesh_topology=True MESH_TOPOLOGY_PROTOTYPES (include/rnb_mesh_topology.h),
-    mesh_holes=True MESH_HOLES_PROTOTYPES (include/rnb_mesh_holes.h), mesh_intersect=True MESH_INTERSECT_PROTOTYPES (include/rnb_mesh_intersect.h); only the HIP library exports those."""
+    mesh_holes=True MESH_HOLES_PROTOTYPES (include/rnb_mesh_holes.h), mesh_intersect=True MESH_INTERSECT_PROTOTYPES (include/rnb_mesh_intersect.h),
+    mesh_smooth=True MESH_SMOOTH_PROTOTYPES (include/rnb_mesh_smooth.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
                      + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ())
                      + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()) + ((MESH_TOPOLOGY_PROTOTYPES,) if mesh_topology else ()) + ((MESH_HOLES_PROTOTYPES,) if mesh_holes else ())
-                     + ((MESH_INTERSECT_PROTOTYPES,) if mesh_intersect else ()))
+                     + ((MESH_INTERSECT_PROTOTYPES,) if mesh_intersect else ()) + ((MESH_SMOOTH_PROTOTYPES,) if mesh_smooth else ()))

@@ -47,7 +47,7 @@ def load_library():
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
-                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True, mesh_holes=True, mesh_intersect=True)
+                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True, mesh_holes=True, mesh_intersect=True, mesh_smooth=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -76,6 +76,8 @@ def load_library():
             raise RuntimeError("mesh-holes ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_intersect_abi_version() != _abi.MESH_INTERSECT_ABI_VERSION:
             raise RuntimeError("mesh-intersect ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_smooth_abi_version() != _abi.MESH_SMOOTH_ABI_VERSION:
+            raise RuntimeError("mesh-smooth ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -601,7 +603,7 @@ class Context:
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
                      simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None, repair=None, topology=False, fill_holes=None,
-                     self_intersections=None):
+                     self_intersections=None, smooth=None):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -636,7 +638,30 @@ class Context:
         fold through its neighbours, and this is the report that tells). "drop": after simplify / repair and before fill_holes, still on the device, the triangles
         with a proper partner are removed (DeviceMesh.drop_intersecting, its defaults; fill_holes then closes the rims), and the dict gains `drop_stats`. A dict
         chooses both: drop ("proper" / "all" / None), rings, cells, report (True / False). With None (the default) nothing of that runs and the calls made are
-        exactly those made without it."""
+        exactly those made without it.
+        smooth = True, N or dict(...): after fill_holes and before the self-intersection report, error, topology and texture, still on the device, the mesh goes through
+        rnb_mesh_smooth (include/rnb_mesh_smooth.h): True = the defaults of DeviceMesh.smooth, N = that many passes, a dict = its arguments passes, lam, mu, boundary,
+        select_rings, normals and buckets_log2, or only_fills=R (with fill_holes only): only the vertices fill_holes appended and R rings around them move, which relaxes
+        the flat fans and leaves the rest of the mesh as it was. The dict gains `smooth_stats`; with error=True the distance is then measured to the smoothed mesh. With
+        None (the default) nothing of that runs and the calls made are exactly those made without it."""
+        if smooth is True:
+            smooth = {}
+        elif isinstance(smooth, (int, np.integer)) and smooth is not False:
+            smooth = dict(passes=int(smooth))
+        if smooth is not None and not isinstance(smooth, dict):
+            raise ValueError("smooth must be None, True, a number of passes or a dict of DeviceMesh.smooth's arguments")
+        if smooth is not None and set(smooth) - {"passes", "lam", "mu", "boundary", "select_rings", "normals", "buckets_log2", "only_fills"}:
+            raise ValueError("smooth takes passes, lam, mu, boundary, select_rings, normals, buckets_log2 and only_fills")
+        if smooth is not None:
+            smooth = dict(smooth)
+            only_fills = smooth.pop("only_fills", None)
+            if only_fills is not None and fill_holes is None:
+                raise ValueError("smooth['only_fills'] needs fill_holes")
+            if only_fills is not None and "select_rings" in smooth:
+                raise ValueError("smooth takes only_fills or select_rings, not both")
+            if only_fills is not None:
+                smooth["select_rings"] = int(only_fills)
+            self._smooth_options(**smooth)  # a bad argument fails before anything is extracted
         if self_intersections is True:
             self_intersections = dict(report=True)
         elif self_intersections == "drop":
@@ -692,6 +717,10 @@ class Context:
             if fill_holes is not None:
                 chain.append(chain[-1].fill_holes(stream=stream, **fill_holes))
                 filled = chain[-1]
+            if smooth is not None:
+                appended = None if only_fills is None else np.arange(filled.n_verts) >= filled.stats["n_verts_out"] - filled.stats["n_verts_added"]
+                chain.append(chain[-1].smooth(select=appended, stream=stream, **smooth))
+                smoothed = chain[-1]
             if si_report:
                 si_census = chain[-1].self_intersections(cells=si_cells, stream=stream)
             if grid is not None and error:
@@ -718,6 +747,8 @@ class Context:
                 out["repair_stats"] = repaired.stats
             if fill_holes is not None:
                 out["fill_stats"] = filled.stats
+            if smooth is not None:
+                out["smooth_stats"] = smoothed.stats
             if topology:
                 out["topology"] = census
             if si_drop is not None:
@@ -847,6 +878,54 @@ class Context:
             if loop_of_tri:
                 out["loop_of_tri"] = filled.loop_of_tri
         return out
+
+    def _smooth_options(self, passes=2, lam=0.5, mu=-0.53, boundary="pin", select_rings=0, normals="keep", buckets_log2=0):
+        bounds = {"pin": _abi.MESH_SMOOTH_BOUNDARY_PIN, "slide": _abi.MESH_SMOOTH_BOUNDARY_SLIDE, "free": _abi.MESH_SMOOTH_BOUNDARY_FREE}
+        norms = {"keep": _abi.MESH_SMOOTH_NORMALS_KEEP, "recompute": _abi.MESH_SMOOTH_NORMALS_RECOMPUTE}
+        if boundary not in bounds:
+            raise ValueError("boundary must be 'pin', 'slide' or 'free'")
+        if normals not in norms:
+            raise ValueError("normals must be 'keep' or 'recompute'")
+        if isinstance(passes, bool) or not 0 <= int(passes) <= _abi.MESH_SMOOTH_MAX_PASSES:
+            raise ValueError("passes must be 0 .. 10000")
+        if not 0 <= int(select_rings) <= _abi.MESH_SMOOTH_MAX_SELECT_RINGS:
+            raise ValueError("select_rings must be 0 .. 1024")
+        if not 0.0 < float(lam) <= 1.0:
+            raise ValueError("lam must be above 0 and at most 1")
+        if not -1.5 <= float(mu) <= 0.0:
+            raise ValueError("mu must be at least -1.5 and at most 0")
+        opt = _abi.MeshSmoothOptions()
+        self._check(self.f.mesh_smooth_default_options(C.byref(opt)))
+        opt.passes, opt.lambda_, opt.mu, opt.boundary, opt.select_rings, opt.normals, opt.buckets_log2 = int(passes), float(lam), float(mu), bounds[boundary], int(select_rings), norms[normals], int(buckets_log2)
+        return opt
+
+    def _vertex_normals_options(self, flip=False):
+        opt = _abi.MeshVertexNormalsOptions()
+        self._check(self.f.mesh_vertex_normals_default_options(C.byref(opt)))
+        opt.flip = int(bool(flip))
+        return opt
+
+    def smooth_mesh(self, verts, indices, colors=None, normals_in=None, passes=2, lam=0.5, mu=-0.53, boundary="pin", select=None, select_rings=0, normals="keep", displacement=False,
+                    census=False, buckets_log2=0, stream=None):
+        """rnb_mesh_smooth (include/rnb_mesh_smooth.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals_in; the
+        other arguments are those of DeviceMesh.smooth. Returns a dict of numpy arrays like clean_mesh, with `stats` = `smooth_stats` and, when asked for,
+        `displacement`, `valence` and `kind`. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, colors, normals_in) as m:
+            smoothed = m.smooth(passes, lam, mu, boundary, select, select_rings, normals, displacement, census, buckets_log2, stream)
+        with smoothed:
+            out = smoothed.download()
+            out["stats"] = out["smooth_stats"] = smoothed.stats
+            if displacement:
+                out["displacement"] = smoothed.displacement
+            if census:
+                out["valence"], out["kind"] = smoothed.valence, smoothed.kind
+        return out
+
+    def mesh_vertex_normals(self, verts, indices, flip=False, stream=None):
+        """rnb_mesh_vertex_normals (include/rnb_mesh_smooth.h) on a host mesh (verts float32[n,3], indices uint32[m] or [m/3,3]): the dict of DeviceMesh.vertex_normals.
+        Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices) as m:
+            return m.vertex_normals(flip, stream=stream)
 
     def _intersect_options(self, cells=0):
         if not 0 <= int(cells) <= _abi.MESH_INTERSECT_MAX_CELLS:
@@ -1308,6 +1387,7 @@ class DeviceMesh(_abi.Mesh):
         self._table, self._table_host = C.c_void_p(), None
         self.vertex_map = None  # set by repair(vertex_map=True) on the mesh it returns
         self.loop_of_tri = None  # set by fill_holes(loop_of_tri=True) on the mesh it returns
+        self.displacement = self.valence = self.kind = None  # set by smooth(displacement=True / census=True) on the mesh it returns
 
     n_verts = property(lambda self: _abi.Mesh.n_verts.__get__(self))
     n_triangles = property(lambda self: self.n_indices // 3)
@@ -1488,6 +1568,62 @@ class DeviceMesh(_abi.Mesh):
         finally:
             if lot:
                 c.device_free(lot)
+        return out
+
+    def smooth(self, passes=2, lam=0.5, mu=-0.53, boundary="pin", select=None, select_rings=0, normals="keep", displacement=False, census=False, buckets_log2=0, stream=None):
+        """rnb_mesh_smooth (include/rnb_mesh_smooth.h) -> a new DeviceMesh with the same vertices (none added, none removed), triangles and colours, the moving vertices
+        relaxed towards the centroids of their one-rings by `passes` passes with the factors lam (odd passes) and mu (even ones; mu=0: lam in every pass, plain Laplacian
+        smoothing, which shrinks); its `stats` are the smooth stats. Interior vertices move; boundary vertices stay (boundary="pin"), move along the rim ("slide") or like
+        interior ones ("free"); vertices on a non-manifold edge and unused ones never move. select: None (every vertex) or one value per vertex (non-zero = selected), grown
+        `select_rings` times over the edges; only selected vertices move. normals="recompute": the returned mesh has the normals of vertex_normals() on it, whether or not
+        this mesh has normals ("keep": this mesh's normals, if any, unchanged). displacement=True: `displacement` of the returned mesh is float32[n_verts], how far each
+        vertex moved; census=True: `valence` and `kind` (0 unused, 1 interior, 2 boundary, 3 non-manifold) are uint32[n_verts]."""
+        c = self._live()
+        opt, st = c._smooth_options(passes, lam, mu, boundary, select_rings, normals, buckets_log2), _abi.MeshSmoothStats()
+        n = self.n_verts
+        if select is not None:
+            select = np.ascontiguousarray(np.asarray(select).ravel() != 0, dtype=np.uint32)
+            if select.size != n:
+                raise ValueError("select must have one value per vertex")
+        bufs = {}
+        try:
+            if select is not None:
+                bufs["select"] = c.upload(select) if n else c.device_malloc(4)
+            for key in (("valence", "kind") if census else ()) + (("displacement",) if displacement else ()):
+                bufs[key] = c.device_malloc(max(n, 1) * 4)
+            out = _returned_mesh(c, st, lambda m: c.f.mesh_smooth(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), bufs.get("select"), m, bufs.get("valence"), bufs.get("kind"),
+                                                                 bufs.get("displacement"), C.byref(st)))
+            try:
+                for key, dt in (("valence", np.uint32), ("kind", np.uint32), ("displacement", np.float32)):
+                    if key in bufs:
+                        setattr(out, key, c.download(bufs[key], n, dt) if n else np.empty(0, dt))
+            except BaseException:
+                out.free()
+                raise
+        finally:
+            for p_ in bufs.values():
+                c.device_free(p_)
+        return out
+
+    def vertex_normals(self, flip=False, on_device=False, stream=None):
+        """rnb_mesh_vertex_normals (include/rnb_mesh_smooth.h): area-weighted vertex normals from the triangles around every vertex -> the dict of
+        rnb_mesh_vertex_normals_stats (n_zero, max_corners, peak_workspace, ms) with `normals`, float32[n_verts, 3]: unit length, counter-clockwise (on an extracted mesh
+        the direction of its SDF-gradient normals), 0 for a vertex no triangle with an area uses; flip=True negates them (the sign of the host's compute_normals).
+        on_device=True: `normals` is a device pointer instead; the caller releases it with Context.device_free. Nothing of the mesh changes."""
+        c = self._live()
+        opt, st = c._vertex_normals_options(flip), _abi.MeshVertexNormalsStats()
+        n = self.n_verts
+        buf = c.device_malloc(max(n, 1) * 12)
+        try:
+            c._check(c.f.mesh_vertex_normals(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), buf, C.byref(st)))
+            out = st.as_dict()
+            if on_device:
+                out["normals"], buf = buf, None
+            else:
+                out["normals"] = c.download(buf, n * 3, np.float32).reshape(-1, 3) if n else np.empty((0, 3), np.float32)
+        finally:
+            if buf:
+                c.device_free(buf)
         return out
 
     def self_intersections(self, pairs=False, cells=0, on_device=False, stream=None):

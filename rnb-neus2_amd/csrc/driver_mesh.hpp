@@ -2,7 +2,7 @@
 // rnb_mesh_draw_textured, rnb_mesh_visibility, rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views, rnb_mesh_topology, rnb_mesh_repair
 // (include/rnb_mesh_topology.h; their hash join is tp_join, beside them), rnb_mesh_boundary_loops, rnb_mesh_fill_holes (include/rnb_mesh_holes.h; hl_census is the
 // part they share), rnb_mesh_intersections, rnb_mesh_intersections_select (include/rnb_mesh_intersect.h; md_build_lists, beside rnb_mesh_distance, is the grid they
-// share with it). What they share:
+// share with it), rnb_mesh_smooth, rnb_mesh_vertex_normals (include/rnb_mesh_smooth.h; on tp_join too; vn_run is the part they share). What they share:
 //   scan_exclusive, count_and_scan                  the prefix sums behind every numbering, and the count half of a count / write kernel pair
 //   MeshWorkspace, alloc_mesh, hand_over            the device memory of one call and the mesh it returns
 //   check_mesh_input, check_reserved, free_device   the argument checks every stage makes; the *_free functions
@@ -2110,6 +2110,201 @@ int rnb_mesh_intersections_select(rnb_ctx* c, void* stream, const rnb_mesh* in, 
 	if (stats) {
 		stats->n_verts_in = nv; stats->n_verts_out = nvo; stats->n_tris_in = nt; stats->n_tris_out = nto;
 		stats->n_selected = hmi.n_selected; stats->n_tris_removed = nt - nto; stats->n_verts_removed = nv - nvo;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- smoothing: Taubin passes over the one-ring, ring normals (include/rnb_mesh_smooth.h) ----
+uint32_t rnb_mesh_smooth_abi_version(void) { return RNB_MESH_SMOOTH_ABI_VERSION; }
+
+int rnb_mesh_smooth_default_options(rnb_mesh_smooth_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_SMOOTH_ABI_VERSION;
+	opt->passes = 2; // one Taubin pair: the one row of profiles/mesh_smooth.md that lowers the mean normal angle on every mesh measured there
+	opt->lambda = 0.5;
+	opt->mu = -0.53;
+	opt->boundary = RNB_MESH_SMOOTH_BOUNDARY_PIN;
+	opt->normals = RNB_MESH_SMOOTH_NORMALS_KEEP;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_vertex_normals_default_options(rnb_mesh_vertex_normals_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_SMOOTH_ABI_VERSION;
+	return RNB_OK;
+} RNB_GUARD
+
+extern "C++" {
+namespace {
+// The normals of a mesh with at least one vertex into `normals` (both entry points of the header; steps in the order of its definitions). Synchronised on return.
+int vn_run(MeshCall& call, const rnb_mesh& m, uint32_t flip, float* normals, VnResult* hres) {
+	const hipStream_t s = call.s;
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	std::memset(hres, 0, sizeof(*hres));
+	if (!nt) { // no corner anywhere: every normal is 0
+		HIP_TRY(hipMemsetAsync(normals, 0, (size_t)nv * 12, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		hres->n_zero = nv;
+		return RNB_OK;
+	}
+	uint32_t* used = nullptr;
+	long long* sums = nullptr;
+	VnResult* dres = nullptr;
+	if (!call.ws.alloc(&used, nv) || !call.ws.alloc(&sums, 4 * (size_t)nv) || !call.ws.alloc(&dres, 1)) return call.nomem("hipMalloc failed for the sums of " + std::to_string(nv) + " vertices");
+	HIP_TRY(hipMemsetAsync(dres, 0, sizeof(VnResult), s));
+	HIP_TRY(hipMemsetAsync(sums, 0, 4 * (size_t)nv * 8, s));
+	if (int rc = call.check_indices(m, used, &dres->flags); rc != RNB_OK) return rc;
+	call.launch(groups(nt), k_vn_accumulate, (const uint32_t*)m.indices, (const float*)m.verts, nt, sums, dres);
+	call.launch(groups(nv), k_vn_finish, (const long long*)sums, nv, flip, normals, dres);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(hres, dres, sizeof(VnResult), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	call.ws.release(used, sums, dres);
+	if (hres->flags & SM_BAD_TERM) return call.invalid("a component of a triangle's cross product is not finite or not below 2^3 in magnitude");
+	if (hres->flags & SM_BAD_RING) return call.invalid("a vertex has more than RNB_MESH_SMOOTH_MAX_RING = 2^20 corners");
+	return RNB_OK;
+}
+} // namespace
+} // extern "C++"
+
+int rnb_mesh_vertex_normals(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_vertex_normals_options* opt, float* normals_dev, rnb_mesh_vertex_normals_stats* stats) try {
+	if (!c || !in || !opt) return fail(RNB_ERR_INVALID, "rnb_mesh_vertex_normals: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_vertex_normals", in); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (m.n_verts && !normals_dev) return fail(RNB_ERR_INVALID, "rnb_mesh_vertex_normals: normals_dev is null");
+	if (opt->abi_version != RNB_MESH_SMOOTH_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_vertex_normals: options abi_version mismatch (expected RNB_MESH_SMOOTH_ABI_VERSION)");
+	if (opt->flip > 1u) return fail(RNB_ERR_INVALID, "rnb_mesh_vertex_normals: flip must be 0 or 1");
+	if (int rc = check_reserved("rnb_mesh_vertex_normals", opt->reserved); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_vertex_normals", c, stream);
+	VnResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	if (m.n_verts)
+		if (int rc = vn_run(call, m, opt->flip, normals_dev, &hres); rc != RNB_OK) return rc;
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_zero = hres.n_zero; stats->max_corners = hres.max_corners;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_smooth(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_smooth_options* opt, const uint32_t* select_dev, rnb_mesh* out, uint32_t* valence_dev, uint32_t* kind_dev,
+                    float* displacement_dev, rnb_mesh_smooth_stats* stats) try {
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_smooth", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_SMOOTH_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: options abi_version mismatch (expected RNB_MESH_SMOOTH_ABI_VERSION)");
+	if (opt->passes > RNB_MESH_SMOOTH_MAX_PASSES) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: passes must be 0 .. 10000");
+	if (!(opt->lambda > 0.0 && opt->lambda <= 1.0)) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: lambda must be finite, above 0 and at most 1");
+	if (!(opt->mu >= -1.5 && opt->mu <= 0.0)) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: mu must be finite, at least -1.5 and at most 0");
+	if (opt->boundary > RNB_MESH_SMOOTH_BOUNDARY_FREE) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: boundary must be PIN, SLIDE or FREE");
+	if (opt->select_rings > RNB_MESH_SMOOTH_MAX_SELECT_RINGS) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: select_rings must be 0 .. 1024");
+	if (opt->normals > RNB_MESH_SMOOTH_NORMALS_RECOMPUTE) return fail(RNB_ERR_INVALID, "rnb_mesh_smooth: normals must be KEEP or RECOMPUTE");
+	if (int rc = tp_check_buckets("rnb_mesh_smooth", opt->buckets_log2); rc != RNB_OK) return rc;
+	if (int rc = check_reserved("rnb_mesh_smooth", opt->reserved); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_smooth", c, stream);
+	const hipStream_t s = call.s;
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u, nh = m.n_indices;
+	const bool recompute = opt->normals == RNB_MESH_SMOOTH_NORMALS_RECOMPUTE;
+	SmResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	float ms_passes = 0.0f;
+	rnb_mesh o;
+	if (!alloc_mesh(call.ws, &o, nv, nt, m.colors != nullptr, m.normals != nullptr || recompute)) return call.nomem("hipMalloc failed for the output mesh");
+	if (nv) {
+		const uint32_t g_v = groups(nv), g_h = groups(nh);
+		const TpEdgeKeys keys{TpTris{(const uint32_t*)m.indices, nullptr}};
+		uint32_t *vinfo = nullptr, *sel = nullptr, *mode = nullptr, *off = nullptr, *wide = nullptr, *eface = nullptr, *scan = nullptr;
+		SmResult* dres = nullptr;
+		if (!call.ws.alloc(&vinfo, 4 * (size_t)nv) || !call.ws.alloc(&sel, nv) || !call.ws.alloc(&mode, nv) || !call.ws.alloc(&off, (size_t)nv + 1) || !call.ws.alloc(&wide, nv) ||
+		    !call.ws.alloc(&eface, nh) || !call.ws.alloc(&scan, scan_scratch_elems((uint64_t)nv + 1)) || !call.ws.alloc(&dres, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices and " + std::to_string(nt) + " triangles");
+		HIP_TRY(hipMemsetAsync(dres, 0, sizeof(SmResult), s));
+		HIP_TRY(hipMemsetAsync(vinfo, 0, 4 * (size_t)nv * 4, s));
+		HIP_TRY(hipMemsetAsync(off + nv, 0, 4, s));
+		if (nt) {
+			// 1. every index is range-checked before any is used as an address (sel's memory takes the marks of the check)
+			if (int rc = call.check_indices(m, sel, &dres->flags); rc != RNB_OK) return rc;
+			// 2. the topology stage's edge join: the faces on every edge, at its lowest half-edge; valence, boundary and non-manifold edges per vertex
+			TpTable j;
+			TpResult* tres = nullptr;
+			if (!call.ws.alloc(&tres, 1)) return call.nomem("hipMalloc failed for the edge join");
+			HIP_TRY(hipMemsetAsync(tres, 0, sizeof(TpResult), s));
+			if (int rc = tp_join(call, keys, nh, opt->buckets_log2, tres, &j); rc != RNB_OK) return rc;
+			call.launch(g_h, k_sm_edges, keys, nh, j.join, eface, vinfo, dres);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			call.ws.release(j.offs, j.items, tres);
+		}
+		// 3. the selection: D_0, then one launch per ring
+		call.launch(g_v, k_sm_select_init, select_dev, nv, sel);
+		if (select_dev && nt)
+			for (uint32_t r = 0; r < opt->select_rings; ++r) call.launch(g_h, k_sm_grow, keys, (const uint32_t*)eface, nh, r, sel);
+		// 4. kinds, who moves, the lengths of the neighbour lists and their offsets
+		const uint32_t lists = opt->passes ? 1u : 0u;
+		call.launch(g_v, k_sm_kind, (const uint32_t*)vinfo, (const uint32_t*)sel, nv, opt->boundary, lists, mode, off, wide, valence_dev, kind_dev, dres);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		uint32_t n_entries = 0;
+		if (int rc = scan_exclusive(off, (uint64_t)nv + 1, s, &n_entries, scan); rc != RNB_OK) return rc;
+		call.ws.release(vinfo, sel, scan);
+		if (hres.n_edges >= (1u << 31)) return call.invalid("the mesh has 2^31 edges or more");
+		if (hres.flags & SM_BAD_RING) return call.invalid("a moving vertex has more than RNB_MESH_SMOOTH_MAX_RING = 2^20 neighbours");
+		if (n_entries) {
+			// 5. the neighbour lists; P_0 in both buffers; the passes, each a gather from one buffer into the other
+			uint32_t *cursor = nullptr, *adj = nullptr;
+			double *cur = nullptr, *nxt = nullptr;
+			if (!call.ws.alloc(&cursor, nv) || !call.ws.alloc(&adj, n_entries) || !call.ws.alloc(&cur, 3 * (size_t)nv) || !call.ws.alloc(&nxt, 3 * (size_t)nv))
+				return call.nomem("hipMalloc failed for the neighbour lists of " + std::to_string(n_entries) + " entries and the positions of " + std::to_string(nv) + " vertices");
+			HIP_TRY(hipMemcpyAsync(cursor, off, (size_t)nv * 4, hipMemcpyDeviceToDevice, s));
+			call.launch(g_h, k_sm_fill, keys, (const uint32_t*)eface, nh, (const uint32_t*)mode, cursor, adj);
+			call.launch(groups(3 * (uint64_t)nv), k_sm_widen, (const float*)m.verts, 3 * (uint64_t)nv, cur, nxt);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			const auto t_passes = std::chrono::steady_clock::now();
+			for (uint32_t k = 1; k <= opt->passes; ++k) {
+				const double f = ((k & 1u) || opt->mu == 0.0) ? opt->lambda : opt->mu;
+				call.launch(g_v, k_sm_pass, (const uint32_t*)off, (const uint32_t*)adj, (const double*)cur, nxt, nv, f, dres);
+				if (hres.n_wide) call.launch(hres.n_wide, k_sm_pass_wide, (const uint32_t*)wide, (const uint32_t*)off, (const uint32_t*)adj, (const double*)cur, nxt, f, dres);
+				std::swap(cur, nxt);
+			}
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipStreamSynchronize(s));
+			ms_passes = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_passes).count();
+			// 6. the output vertices and the displacement
+			call.launch(g_v, k_sm_finish, (const float*)m.verts, (const double*)cur, (const uint32_t*)mode, nv, o.verts, displacement_dev, dres);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
+			call.ws.release(cursor, adj, cur, nxt);
+			if (hres.flags & SM_BAD_TERM) return call.invalid("a difference between a moving vertex and a neighbour is not finite or not below 2^10 in magnitude");
+		} else { // nothing moves, or no pass is asked for: a copy
+			HIP_TRY(hipMemcpyAsync(o.verts, m.verts, (size_t)nv * 12, hipMemcpyDeviceToDevice, s));
+			if (displacement_dev) HIP_TRY(hipMemsetAsync(displacement_dev, 0, (size_t)nv * 4, s));
+		}
+		call.ws.release(mode, off, wide, eface, dres);
+		if (m.colors) HIP_TRY(hipMemcpyAsync(o.colors, m.colors, (size_t)nv * 12, hipMemcpyDeviceToDevice, s));
+		if (m.normals && !recompute) HIP_TRY(hipMemcpyAsync(o.normals, m.normals, (size_t)nv * 12, hipMemcpyDeviceToDevice, s));
+	}
+	if (nt) HIP_TRY(hipMemcpyAsync(o.indices, m.indices, (size_t)nt * 12, hipMemcpyDeviceToDevice, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if (recompute && nv) { // of the output, with the defaults of rnb_mesh_vertex_normals
+		VnResult vres;
+		if (int rc = vn_run(call, o, 0u, o.normals, &vres); rc != RNB_OK) return rc;
+	}
+	hand_over(call.ws, o, out);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_edges = hres.n_edges; stats->n_interior = hres.n_interior; stats->n_boundary = hres.n_boundary; stats->n_nonmanifold = hres.n_nonmanifold; stats->n_unused = hres.n_unused;
+		stats->n_selected = hres.n_selected; stats->n_moving = hres.n_moving; stats->max_valence = hres.max_valence; stats->passes = opt->passes; stats->n_wide = hres.n_wide;
+		float md;
+		std::memcpy(&md, &hres.max_displacement, 4);
+		stats->max_displacement = (double)md;
+		stats->ms_passes = ms_passes;
 		call.finish(stats);
 	}
 	return RNB_OK;

@@ -8,6 +8,7 @@
 //        [--keep-seen component|faces [--seen-min-views N] [--seen-rings R] [--seen-masks [--seen-max-off N]] [--seen-supersample K]]
 //        [--repair [--weld] [--duplicates keep|first|cancel] [--orient-consistent]] [--report-topology]
 //        [--drop-intersecting proper|all [--drop-rings R]] [--fill-holes [--fill-max-edges N] [--fill-skip-largest]] [--report-intersections]
+//        [--smooth N [--smooth-lambda L] [--smooth-mu M] [--smooth-boundary pin|slide|free] [--smooth-only-fills R] [--smooth-normals keep|recompute]]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -47,6 +48,11 @@
 // With --drop-intersecting the triangles that pass through other triangles of the mesh (proper), or also those that touch or overlap them (all), are removed by
 // rnb_mesh_intersections and rnb_mesh_intersections_select (include/rnb_mesh_intersect.h) after --simplify / --repair and before --fill-holes, which closes the rims;
 // with --report-intersections the census of the mesh as written is printed as one JSON line, {"intersections": {...}}.
+// With --smooth N the device mesh goes through N passes of rnb_mesh_smooth (include/rnb_mesh_smooth.h) right after --fill-holes (before --keep / --orient where they
+// run late) and before the reports and --texture: Taubin's pairs with --smooth-lambda and --smooth-mu (0.5 and -0.53; mu 0 is plain Laplacian smoothing), the boundary
+// pinned, sliding along itself or free; with --smooth-only-fills R only the vertices --fill-holes appended and R rings around them move, which relaxes the flat fans and
+// leaves the rest as extracted. With --normals ring the host's ring normals are those of the smoothed positions; with --normals gradient the SDF-gradient normals would
+// be stale, so --smooth-normals defaults to recompute there (the device's ring normals, the same direction) and to keep otherwise. One `smooth:` line is printed.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -61,6 +67,7 @@
 #include "../../include/rnb_mesh_topology.h"
 #include "../../include/rnb_mesh_holes.h"
 #include "../../include/rnb_mesh_intersect.h"
+#include "../../include/rnb_mesh_smooth.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -121,6 +128,12 @@ const Flag FLAGS[] = {
 	{"fill-skip-largest", nullptr, "--fill-holes only (takes no value). Leave the longest loop of every connected component open: the rim of a relief."},
 	{"drop-intersecting", "MODE", "Remove self-intersecting triangles on the device. proper: those an edge of another triangle of the mesh passes through; all: also those that touch or overlap others; after --simplify / --repair and before --fill-holes."},
 	{"drop-rings", "R", "--drop-intersecting only. Also remove R rings of triangles around them (0 .. 8, default 0)."},
+	{"smooth", "N", "Smooth the mesh on the device with N passes (0 .. 10000) over the one-ring, after --fill-holes and before the reports and --texture: Taubin's lambda / mu pairs."},
+	{"smooth-lambda", "L", "--smooth only. The factor of the odd passes (0 < L <= 1, default 0.5)."},
+	{"smooth-mu", "M", "--smooth only. The factor of the even passes (-1.5 <= M <= 0, default -0.53); 0: every pass uses lambda (plain Laplacian smoothing, which shrinks)."},
+	{"smooth-boundary", "MODE", "--smooth only. pin (default): boundary vertices stay; slide: they move along the boundary; free: they move like interior ones."},
+	{"smooth-only-fills", "R", "--smooth with --fill-holes only. Move only the vertices --fill-holes appended and R rings of neighbours around them (0 .. 1024)."},
+	{"smooth-normals", "MODE", "--smooth only. keep: the normals the mesh has; recompute: the device's ring normals of the smoothed mesh (default with --normals gradient)."},
 	{"report-intersections", nullptr, "(takes no value). Print the self-intersection census of the written mesh as one JSON line: candidates, proper and contact pairs and triangles."},
 	{"report-topology", nullptr, "(takes no value). Print the edge census of the written mesh as one JSON line: edges by kind, duplicates, patches, boundary loops, Euler characteristic."},
 };
@@ -165,6 +178,13 @@ uint32_t parse_u32(const std::string& k, const std::string& s) {
 	const unsigned long long v = std::strtoull(s.c_str(), &e, 10);
 	if (s.empty() || *e || s[0] == '-' || v > 0xffffffffull) throw ParseError("Argument '" + k + "' received invalid value type '" + s + "'");
 	return (uint32_t)v;
+}
+
+double parse_double(const std::string& k, const std::string& s) {
+	char* e = nullptr;
+	const double v = std::strtod(s.c_str(), &e);
+	if (s.empty() || *e || !std::isfinite(v)) throw ParseError("Argument '" + k + "' received invalid value type '" + s + "'");
+	return v;
 }
 
 float parse_float(const std::string& k, const std::string& s) {
@@ -398,6 +418,9 @@ int main(int argc, char** argv) {
 	uint32_t drop_classes = 0, drop_rings = 0; // 0: nothing is dropped
 	rnb_mesh_repair_options repair_opt;
 	std::memset(&repair_opt, 0, sizeof(repair_opt));
+	bool smooth = false, smooth_only_fills = false;
+	rnb_mesh_smooth_options smooth_opt;
+	(void)rnb_mesh_smooth_default_options(&smooth_opt); // (touches no device)
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -520,6 +543,38 @@ int main(int argc, char** argv) {
 			if (!drop_classes) throw ParseError("Argument 'drop-rings' is only used with --drop-intersecting");
 			drop_rings = parse_u32("drop-rings", a["drop-rings"]);
 			if (drop_rings > RNB_MESH_INTERSECT_MAX_RINGS) throw ParseError("Argument 'drop-rings' must be 0 .. 8");
+		}
+		if (a.count("smooth")) {
+			smooth = true;
+			smooth_opt.passes = parse_u32("smooth", a["smooth"]);
+			if (smooth_opt.passes > RNB_MESH_SMOOTH_MAX_PASSES) throw ParseError("Argument 'smooth' must be 0 .. 10000");
+		}
+		for (const char* sub : {"smooth-lambda", "smooth-mu", "smooth-boundary", "smooth-only-fills", "smooth-normals"})
+			if (a.count(sub) && !smooth) throw ParseError(std::string("Argument '") + sub + "' is only used with --smooth");
+		if (a.count("smooth-lambda")) {
+			smooth_opt.lambda = parse_double("smooth-lambda", a["smooth-lambda"]);
+			if (!(smooth_opt.lambda > 0.0 && smooth_opt.lambda <= 1.0)) throw ParseError("Argument 'smooth-lambda' must be above 0 and at most 1");
+		}
+		if (a.count("smooth-mu")) {
+			smooth_opt.mu = parse_double("smooth-mu", a["smooth-mu"]);
+			if (!(smooth_opt.mu >= -1.5 && smooth_opt.mu <= 0.0)) throw ParseError("Argument 'smooth-mu' must be at least -1.5 and at most 0");
+		}
+		if (a.count("smooth-boundary")) {
+			if (a["smooth-boundary"] == "slide") smooth_opt.boundary = RNB_MESH_SMOOTH_BOUNDARY_SLIDE;
+			else if (a["smooth-boundary"] == "free") smooth_opt.boundary = RNB_MESH_SMOOTH_BOUNDARY_FREE;
+			else if (a["smooth-boundary"] != "pin") throw ParseError("Argument 'smooth-boundary' must be pin, slide or free");
+		}
+		if (a.count("smooth-only-fills")) {
+			if (!fill_holes) throw ParseError("Argument 'smooth-only-fills' is only used with --fill-holes");
+			smooth_only_fills = true;
+			smooth_opt.select_rings = parse_u32("smooth-only-fills", a["smooth-only-fills"]);
+			if (smooth_opt.select_rings > RNB_MESH_SMOOTH_MAX_SELECT_RINGS) throw ParseError("Argument 'smooth-only-fills' must be 0 .. 1024");
+		}
+		if (smooth && gradient) smooth_opt.normals = RNB_MESH_SMOOTH_NORMALS_RECOMPUTE; // the SDF-gradient normals of the old positions would be stale
+		if (a.count("smooth-normals")) {
+			if (a["smooth-normals"] == "recompute") smooth_opt.normals = RNB_MESH_SMOOTH_NORMALS_RECOMPUTE;
+			else if (a["smooth-normals"] == "keep") smooth_opt.normals = RNB_MESH_SMOOTH_NORMALS_KEEP;
+			else throw ParseError("Argument 'smooth-normals' must be keep or recompute");
 		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
@@ -652,7 +707,24 @@ int main(int argc, char** argv) {
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		}
-		if (clean && late_clean) run_clean(); // on what the repair and the fill leave
+		rnb_mesh_smooth_stats ms;
+		if (smooth) { // device to device, right after the fill: its appended vertices are still the last ones
+			void* select = nullptr;
+			if (smooth_only_fills && dm.n_verts) {
+				std::vector<uint32_t> sel(dm.n_verts, 0u);
+				for (uint32_t v = fs.n_verts_out - fs.n_verts_added; v < dm.n_verts; ++v) sel[v] = 1u;
+				RNB_CHECK(rnb_device_malloc(ctx, (uint64_t)dm.n_verts * 4, &select));
+				int rc = rnb_memcpy(ctx, select, sel.data(), (uint64_t)dm.n_verts * 4, RNB_H2D);
+				if (rc != RNB_OK) { (void)rnb_device_free(ctx, select); RNB_CHECK(rc); }
+			}
+			const int rc = rnb_mesh_smooth(ctx, nullptr, &dm, &smooth_opt, (const uint32_t*)select, &cm, nullptr, nullptr, nullptr, &ms);
+			if (select) (void)rnb_device_free(ctx, select);
+			RNB_CHECK(rc);
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+		}
+		if (clean && late_clean) run_clean(); // on what the repair, the fill and the smoothing leave
 		rnb_mesh_topology_stats tp;
 		if (report_topology) { // of the mesh as it will be written
 			rnb_mesh_topology_options to;
@@ -728,6 +800,9 @@ int main(int argc, char** argv) {
 		if (fill_holes) std::printf("fill: %u loops, %u filled, %u not simple, %u over the limit, %u largest left open, %u vertices and %u triangles added, %u -> %u triangles, %.1f ms\n", fs.n_loops,
 		                            fs.n_filled, fs.n_skipped_not_simple, fs.n_skipped_over_max, fs.n_skipped_largest, fs.n_verts_added, fs.n_tris_added, fs.n_tris_out - fs.n_tris_added,
 		                            fs.n_tris_out, fs.ms);
+		if (smooth) std::printf("smooth: %u passes, %u of %u vertices moving (%u selected; %u interior, %u boundary, %u non-manifold, %u unused), %u edges, valence up to %u, %u on the wide path, "
+		                        "greatest displacement %.9g, %.1f ms of which %.1f in the passes\n", ms.passes, ms.n_moving, ms.n_interior + ms.n_boundary + ms.n_nonmanifold + ms.n_unused,
+		                        ms.n_selected, ms.n_interior, ms.n_boundary, ms.n_nonmanifold, ms.n_unused, ms.n_edges, ms.max_valence, ms.n_wide, ms.max_displacement, ms.ms, ms.ms_passes);
 		if (clean && late_clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
 		                                 cs.n_verts_in, cs.n_verts_out, cs.ms);
 		if (report_topology)

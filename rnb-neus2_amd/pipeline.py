@@ -169,7 +169,7 @@ def postprocess_mesh(data_dir, output_mesh_path, logger=None):
 
 
 def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None, texture_from=None,
-                            repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False):
+                            repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None):
     """The last stage on the device: one `build/mesh` process that extracts the mesh of the stage-2 snapshot (plan_two_stage passes --save-snapshot) at `resolution`,
     keeps the largest connected component and turns it outward (include/rnb_mesh_clean.h), and writes `output_mesh_path`. Pure; the snapshot named here is the first
     of snapshot_candidates, run_device_postprocess replaces it by the one that exists. simplify = N: the cleaned mesh is then simplified on N^3 cells over the
@@ -189,7 +189,10 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
     drop_intersecting = "proper" or "all", or a dict(classes=..., rings=R): the triangles that pass through (all: or touch) other triangles of the mesh are removed on
     the device after the simplification and the repair and before fill_holes, which closes the rims (include/rnb_mesh_intersect.h, build/mesh --drop-intersecting and
     --drop-rings); report_intersections: build/mesh --report-intersections prints the self-intersection census of the final mesh as one JSON line. None / False (the
-    defaults) plan the command without them."""
+    defaults) plan the command without them.
+    smooth = N or a dict(passes=N, lam=L, mu=M, boundary="pin" / "slide" / "free", only_fills=R, normals="keep" / "recompute") of which only `passes` is needed: the
+    mesh is smoothed on the device by N passes over the one-ring right after fill_holes (include/rnb_mesh_smooth.h, build/mesh --smooth N and its --smooth-* flags);
+    only_fills needs fill_holes. None (the default) plans the command without it."""
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if texture_from not in (None, "views"):
@@ -216,6 +219,36 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
         argv += drop_intersecting_flags(drop_intersecting)
     if report_intersections:
         argv += ["--report-intersections"]
+    if smooth is not None:
+        argv += smooth_flags(smooth, fill_holes=bool(fill_holes))
+    return argv
+
+
+def smooth_flags(smooth, fill_holes=True):
+    """The --smooth flags of build/mesh for plan_device_postprocess' smooth; fill_holes: whether the command also fills (only_fills needs it)."""
+    sm = dict(passes=smooth) if isinstance(smooth, int) and not isinstance(smooth, bool) else (dict(smooth) if isinstance(smooth, dict) else None)
+    if sm is None or set(sm) - {"passes", "lam", "mu", "boundary", "only_fills", "normals"} or sm.get("passes") is None or not 0 <= int(sm["passes"]) <= 10000:
+        raise ValueError("smooth must be a number of passes (0 .. 10000) or a dict of passes and any of lam, mu, boundary, only_fills, normals")
+    if sm.get("lam") is not None and not 0.0 < float(sm["lam"]) <= 1.0:
+        raise ValueError("smooth: lam must be above 0 and at most 1")
+    if sm.get("mu") is not None and not -1.5 <= float(sm["mu"]) <= 0.0:
+        raise ValueError("smooth: mu must be at least -1.5 and at most 0")
+    if sm.get("boundary") not in (None, "pin", "slide", "free"):
+        raise ValueError("smooth: boundary must be 'pin', 'slide' or 'free'")
+    if sm.get("normals") not in (None, "keep", "recompute"):
+        raise ValueError("smooth: normals must be 'keep' or 'recompute'")
+    if sm.get("only_fills") is not None and (not fill_holes or not 0 <= int(sm["only_fills"]) <= 1024):
+        raise ValueError("smooth: only_fills (0 .. 1024) needs fill_holes")
+    argv = ["--smooth", str(int(sm["passes"]))]
+    for key, flag in (("lam", "--smooth-lambda"), ("mu", "--smooth-mu")):
+        if sm.get(key) is not None:
+            argv += [flag, repr(float(sm[key]))]
+    if sm.get("boundary") is not None:
+        argv += ["--smooth-boundary", sm["boundary"]]
+    if sm.get("only_fills") is not None:
+        argv += ["--smooth-only-fills", str(int(sm["only_fills"]))]
+    if sm.get("normals") is not None:
+        argv += ["--smooth-normals", sm["normals"]]
     return argv
 
 
@@ -287,12 +320,12 @@ def default_mesh_exe(testbed_path):
 
 
 def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None, simplify=None, report_views=False, texture=None, keep_seen=None,
-                           texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False):
+                           texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None):
     """postprocess_mesh's job without the OBJ round trip: runs plan_device_postprocess' command, then drops the training output directory as postprocess_mesh does."""
     logger = logger or SimpleLogger()
     cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=simplify, report_views=report_views, texture=texture, keep_seen=keep_seen,
                                   texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes,
-                                  drop_intersecting=drop_intersecting, report_intersections=report_intersections)
+                                  drop_intersecting=drop_intersecting, report_intersections=report_intersections, smooth=smooth)
     found = [p for p in snapshot_candidates(data_dir, max_steps) if os.path.exists(p)]
     if not found:
         raise RuntimeError("Snapshot not found after {} iterations".format(max_steps))
@@ -314,7 +347,7 @@ def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, me
 def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mesh_resolution=1024, scaling_mode="auto", sphere_scale=1.0, margin_px=20,
                       warmup_ratio=0.1, mask_weight=1.0, super_normal=False, use_l1=False, use_rgb_plus=True, has_albedo=False,
                       albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None, device_postprocess=False, mesh_exe=None, simplify=None, report_views=False, texture=None,
-                      keep_seen=None, texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False):
+                      keep_seen=None, texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None):
     """load -> prepare (<output_dir>/prepared_data) -> train (two-stage, or warm-up + albedo scaling + two-stage when
     `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
     device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh;
@@ -328,7 +361,10 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     describes the values; build/mesh --repair, --report-topology);
     fill_holes (with device_postprocess only): that step also closes the boundary loops of the mesh (plan_device_postprocess describes the value; build/mesh --fill-holes).
     drop_intersecting, report_intersections (with device_postprocess only): that step also removes the self-intersecting triangles before it fills, and prints the
-    self-intersection census of the final mesh (plan_device_postprocess describes the values; build/mesh --drop-intersecting, --report-intersections)."""
+    self-intersection census of the final mesh (plan_device_postprocess describes the values; build/mesh --drop-intersecting, --report-intersections).
+    smooth (with device_postprocess only): that step also smooths the mesh after it fills (plan_device_postprocess describes the value; build/mesh --smooth)."""
+    if smooth is not None and not device_postprocess:
+        raise ValueError("smooth needs device_postprocess")
     if (repair or report_topology) and not device_postprocess:
         raise ValueError("repair and report_topology need device_postprocess")
     if fill_holes and not device_postprocess:
@@ -363,7 +399,7 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     if device_postprocess:
         run_device_postprocess(data_dir, max_steps, mesh_resolution, output_mesh, mesh_exe or default_mesh_exe(testbed_path), logger, simplify=simplify, report_views=report_views, texture=texture,
                                keep_seen=keep_seen, texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes,
-                               drop_intersecting=drop_intersecting, report_intersections=report_intersections)
+                               drop_intersecting=drop_intersecting, report_intersections=report_intersections, smooth=smooth)
     else:
         postprocess_mesh(data_dir, output_mesh, logger)
     logger.info("=== Pipeline complete ===")

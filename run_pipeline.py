@@ -57,6 +57,12 @@ _SPEC = """
 --drop-intersecting | str   |        | --device-postprocess only: remove the self-intersecting triangles of the final mesh on the GPU before --fill-holes, proper or all (build/mesh --drop-intersecting)
 --drop-rings        | int   |        | --drop-intersecting only: also remove R rings of triangles around them (0 .. 8)
 --report-intersections | flag |      | --device-postprocess only: print the self-intersection census of the final mesh as one JSON line (build/mesh --report-intersections)
+--smooth            | int   |        | --device-postprocess only: smooth the final mesh on the GPU by N passes over the one-ring after --fill-holes, Taubin's lambda / mu pairs (build/mesh --smooth N)
+--smooth-lambda     | float |        | --smooth only: the factor of the odd passes (0 < L <= 1, build/mesh's default 0.5)
+--smooth-mu         | float |        | --smooth only: the factor of the even passes (-1.5 <= M <= 0, build/mesh's default -0.53; 0 = plain Laplacian smoothing)
+--smooth-boundary   | str   |        | --smooth only: pin (build/mesh's default), slide or free
+--smooth-only-fills | int   |        | --smooth with --fill-holes only: move only the vertices --fill-holes appended and R rings around them
+--smooth-normals    | str   |        | --smooth only: keep or recompute
 """
 
 
@@ -88,7 +94,7 @@ def pipeline_kwargs(ns):
     kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "texture_from", "keep_seen", "seen_min_views",
                                                                                 "seen_rings", "seen_masks", "seen_max_off", "seen_supersample", "repair", "weld", "duplicates", "orient_consistent",
                                                                                 "report_topology", "fill_holes", "fill_max_edges", "fill_skip_largest", "drop_intersecting", "drop_rings",
-                                                                                "report_intersections")}
+                                                                                "report_intersections", "smooth", "smooth_lambda", "smooth_mu", "smooth_boundary", "smooth_only_fills", "smooth_normals")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
@@ -114,6 +120,9 @@ def pipeline_kwargs(ns):
             kw["drop_intersecting"] = dict(classes=ns.drop_intersecting, **({"rings": ns.drop_rings} if ns.drop_rings is not None else {}))
         if ns.report_intersections:
             kw["report_intersections"] = True
+        if ns.smooth is not None:
+            sm = dict(passes=ns.smooth, lam=ns.smooth_lambda, mu=ns.smooth_mu, boundary=ns.smooth_boundary or None, only_fills=ns.smooth_only_fills, normals=ns.smooth_normals or None)
+            kw["smooth"] = {k: v for k, v in sm.items() if v is not None}
     return kw
 
 
@@ -167,6 +176,23 @@ def main(argv=None):
         parser.error("--drop-rings is only used with --drop-intersecting")
     if ns.drop_rings is not None and not 0 <= ns.drop_rings <= 8:
         parser.error("--drop-rings must be 0 .. 8")
+    if ns.smooth is not None and not ns.device_postprocess:
+        parser.error("--smooth is only used with --device-postprocess")
+    for name in ("smooth_lambda", "smooth_mu", "smooth_boundary", "smooth_only_fills", "smooth_normals"):
+        if getattr(ns, name) not in (None, "") and ns.smooth is None:
+            parser.error("--%s is only used with --smooth" % name.replace("_", "-"))
+    if ns.smooth is not None and not 0 <= ns.smooth <= 10000:
+        parser.error("--smooth must be 0 .. 10000")
+    if ns.smooth_lambda is not None and not 0.0 < ns.smooth_lambda <= 1.0:
+        parser.error("--smooth-lambda must be above 0 and at most 1")
+    if ns.smooth_mu is not None and not -1.5 <= ns.smooth_mu <= 0.0:
+        parser.error("--smooth-mu must be at least -1.5 and at most 0")
+    if ns.smooth_boundary and ns.smooth_boundary not in ("pin", "slide", "free"):
+        parser.error("--smooth-boundary must be pin, slide or free")
+    if ns.smooth_normals and ns.smooth_normals not in ("keep", "recompute"):
+        parser.error("--smooth-normals must be keep or recompute")
+    if ns.smooth_only_fills is not None and (not ns.fill_holes or not 0 <= ns.smooth_only_fills <= 1024):
+        parser.error("--smooth-only-fills (0 .. 1024) is only used with --fill-holes")
     if ns.duplicates and ns.duplicates not in ("keep", "first", "cancel"):
         parser.error("--duplicates must be keep, first or cancel")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
