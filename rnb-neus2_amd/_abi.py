@@ -1112,6 +1112,66 @@ MESH_SMOOTH_PROTOTYPES = {
 }
 
 
+# ---- include/rnb_mesh_snap.h: guarded Newton steps of a device mesh onto the model's SDF, a header of its own with its own version (the HIP library only) ----
+MESH_SNAP_ABI_VERSION = 1
+MESH_SNAP_MAX_ITERATIONS, MESH_SNAP_MAX_IN_FLIGHT, MESH_SNAP_RESIDUAL_LOG2, MESH_SNAP_Q_SHIFT = 64, 1 << 22, 8, 24
+(MESH_SNAP_UNSELECTED, MESH_SNAP_CONVERGED, MESH_SNAP_UNFINISHED, MESH_SNAP_FLAT, MESH_SNAP_LEASHED, MESH_SNAP_OUTSIDE, MESH_SNAP_STALLED, MESH_SNAP_INVALID,
+ MESH_SNAP_REVERTED) = range(9)
+MESH_SNAP_STATE_NAMES = ("unselected", "converged", "unfinished", "flat", "leashed", "outside", "stalled", "invalid", "reverted")
+
+
+class MeshSnapOptions(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_uint32),
+        ("iterations", C.c_uint32),
+        ("level", C.c_float),
+        ("tolerance", C.c_float),
+        ("max_step", C.c_float),
+        ("max_displacement", C.c_float),
+        ("min_gradient", C.c_float),
+        ("attributes", C.c_uint32),
+        ("use_inference_params", C.c_uint32),
+        ("max_points_in_flight", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class MeshSnapStats(C.Structure):
+    _fields_ = [
+        ("n_selected", C.c_uint32),
+        ("n_unselected", C.c_uint32),
+        ("n_converged", C.c_uint32),
+        ("n_unfinished", C.c_uint32),
+        ("n_flat", C.c_uint32),
+        ("n_leashed", C.c_uint32),
+        ("n_outside", C.c_uint32),
+        ("n_stalled", C.c_uint32),
+        ("n_invalid", C.c_uint32),
+        ("n_reverted", C.c_uint32),
+        ("n_moved", C.c_uint32),
+        ("rounds", C.c_uint32),
+        ("max_displacement", C.c_double),
+        ("max_before", C.c_double),
+        ("max_after", C.c_double),
+        ("sum_before_q", C.c_uint64),
+        ("sum_after_q", C.c_uint64),
+        ("n_network_points", C.c_uint64),
+        ("peak_workspace", C.c_uint64),
+        ("ms", C.c_float),
+        ("ms_network", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+MESH_SNAP_PROTOTYPES = {
+    "mesh_snap_abi_version": (_u32, []),
+    "mesh_snap_default_options": (_i, [C.POINTER(MeshSnapOptions)]),
+    "mesh_snap": (_i, [_ctx, _stream, C.POINTER(Mesh), C.POINTER(MeshSnapOptions), C.c_void_p, C.POINTER(Mesh), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MeshSnapStats)]),
+}
+
+
 class Functions:
     """Bound, typed entry points of one library."""
 
@@ -1133,16 +1193,16 @@ class Functions:
 
 
 def declare(lib, prefix="rnb_", render=False, mesh=False, mesh_clean=False, mesh_simplify=False, mesh_distance=False, mesh_raster=False, mesh_texture=False,
-            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False, mesh_holes=False, mesh_intersect=False, mesh_smooth=False):
+            mesh_visibility=False, mesh_project=False, mesh_draw=False, mesh_topology=False, mesh_holes=False, mesh_intersect=False, mesh_smooth=False, mesh_snap=False):
     """render=True also binds RENDER_PROTOTYPES (include/rnb_render.h), mesh=True MESH_PROTOTYPES (include/rnb_mesh.h), mesh_clean=True MESH_CLEAN_PROTOTYPES
     (include/rnb_mesh_clean.h), mesh_simplify=True MESH_SIMPLIFY_PROTOTYPES (include/rnb_mesh_simplify.h), mesh_distance=True MESH_DISTANCE_PROTOTYPES (include/rnb_mesh_distance.h),
     mesh_raster=True MESH_RASTER_PROTOTYPES (include/rnb_mesh_raster.h), mesh_texture=True MESH_TEXTURE_PROTOTYPES (include/rnb_mesh_texture.h),
     mesh_visibility=True MESH_VISIBILITY_PROTOTYPES (include/rnb_mesh_visibility.h), mesh_project=True MESH_PROJECT_PROTOTYPES (include/rnb_mesh_project.h),
     mesh_draw=True MESH_DRAW_PROTOTYPES (include/rnb_mesh_draw.h), mesh_topology=True MESH_TOPOLOGY_PROTOTYPES (include/rnb_mesh_topology.h),
     mesh_holes=True MESH_HOLES_PROTOTYPES (include/rnb_mesh_holes.h), mesh_intersect=True MESH_INTERSECT_PROTOTYPES (include/rnb_mesh_intersect.h),
-    mesh_smooth=True MESH_SMOOTH_PROTOTYPES (include/rnb_mesh_smooth.h); only the HIP library exports those."""
+    mesh_smooth=True MESH_SMOOTH_PROTOTYPES (include/rnb_mesh_smooth.h), mesh_snap=True MESH_SNAP_PROTOTYPES (include/rnb_mesh_snap.h); only the HIP library exports those."""
     return Functions(lib, prefix, (PROTOTYPES,) + ((RENDER_PROTOTYPES,) if render else ()) + ((MESH_PROTOTYPES,) if mesh else ()) + ((MESH_CLEAN_PROTOTYPES,) if mesh_clean else ())
                      + ((MESH_SIMPLIFY_PROTOTYPES,) if mesh_simplify else ()) + ((MESH_DISTANCE_PROTOTYPES,) if mesh_distance else ()) + ((MESH_RASTER_PROTOTYPES,) if mesh_raster else ())
                      + ((MESH_TEXTURE_PROTOTYPES,) if mesh_texture else ()) + ((MESH_VISIBILITY_PROTOTYPES,) if mesh_visibility else ())
                      + ((MESH_PROJECT_PROTOTYPES,) if mesh_project else ()) + ((MESH_DRAW_PROTOTYPES,) if mesh_draw else ()) + ((MESH_TOPOLOGY_PROTOTYPES,) if mesh_topology else ()) + ((MESH_HOLES_PROTOTYPES,) if mesh_holes else ())
-                     + ((MESH_INTERSECT_PROTOTYPES,) if mesh_intersect else ()) + ((MESH_SMOOTH_PROTOTYPES,) if mesh_smooth else ()))
+                     + ((MESH_INTERSECT_PROTOTYPES,) if mesh_intersect else ()) + ((MESH_SMOOTH_PROTOTYPES,) if mesh_smooth else ()) + ((MESH_SNAP_PROTOTYPES,) if mesh_snap else ()))

@@ -47,7 +47,7 @@ def load_library():
                 "There is no CPU fallback for the hot path." % path)
         lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
         _FUNCS = _abi.declare(lib, "rnb_", render=True, mesh=True, mesh_clean=True, mesh_simplify=True, mesh_distance=True, mesh_raster=True, mesh_texture=True,
-                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True, mesh_holes=True, mesh_intersect=True, mesh_smooth=True)
+                              mesh_visibility=True, mesh_project=True, mesh_draw=True, mesh_topology=True, mesh_holes=True, mesh_intersect=True, mesh_smooth=True, mesh_snap=True)
         if _FUNCS.abi_version() != _abi.ABI_VERSION:
             raise RuntimeError("ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.render_abi_version() != _abi.RENDER_ABI_VERSION:
@@ -78,6 +78,8 @@ def load_library():
             raise RuntimeError("mesh-intersect ABI version mismatch between %s and the Python host side" % path)
         if _FUNCS.mesh_smooth_abi_version() != _abi.MESH_SMOOTH_ABI_VERSION:
             raise RuntimeError("mesh-smooth ABI version mismatch between %s and the Python host side" % path)
+        if _FUNCS.mesh_snap_abi_version() != _abi.MESH_SNAP_ABI_VERSION:
+            raise RuntimeError("mesh-snap ABI version mismatch between %s and the Python host side" % path)
     return _FUNCS
 
 
@@ -603,7 +605,7 @@ class Context:
     def extract_mesh(self, res=256, lattice_min=0.0, lattice_max=1.0, aabb_min=(0.0, 0.0, 0.0), aabb_max=(1.0, 1.0, 1.0), thresh=0.0, inference=True,
                      cull="occupancy", brick=0, colors=False, normals=False, max_points_in_flight=0, max_active_points=0, stream=None, keep=None, orient=None,
                      simplify=None, placement="quadric", error=False, texture=None, texture_maps=("albedo",), seen_by=None, seen_masks=None, texture_from=None, repair=None, topology=False, fill_holes=None,
-                     self_intersections=None, smooth=None):
+                     self_intersections=None, smooth=None, snap=None):
         """rnb_extract_mesh (include/rnb_mesh.h): the iso-surface on the lattice res (int or 3 ints) extracted brick by brick, the bricks the occupancy bitfield
         marks empty skipped (cull="occupancy", the default; "none" keeps every brick and gives the mesh of sdf_lattice + marching_cubes in brick-major order).
         Returns a dict of numpy arrays: verts float32[n,3], indices uint32[m], colors / normals float32[n,3] when asked for, and `stats`.
@@ -643,7 +645,27 @@ class Context:
         rnb_mesh_smooth (include/rnb_mesh_smooth.h): True = the defaults of DeviceMesh.smooth, N = that many passes, a dict = its arguments passes, lam, mu, boundary,
         select_rings, normals and buckets_log2, or only_fills=R (with fill_holes only): only the vertices fill_holes appended and R rings around them move, which relaxes
         the flat fans and leaves the rest of the mesh as it was. The dict gains `smooth_stats`; with error=True the distance is then measured to the smoothed mesh. With
-        None (the default) nothing of that runs and the calls made are exactly those made without it."""
+        None (the default) nothing of that runs and the calls made are exactly those made without it.
+        snap = True, N or dict(...): after smooth and before the self-intersection report, error, topology and texture, still on the device, the vertices are moved back
+        onto the model's surface by rnb_mesh_snap (include/rnb_mesh_snap.h) at level = thresh with the weights of `inference`: True = the defaults of DeviceMesh.snap,
+        N = that many iterations, a dict = its arguments iterations, tolerance, max_step, max_displacement, min_gradient, attributes and max_points_in_flight, or
+        only_fills=True (with fill_holes only): only the vertices fill_holes appended move, and those a smoothing moved. The dict gains `snap_stats`; with error=True
+        the distance is then measured to the snapped mesh. With None (the default) nothing of that runs and the calls made are exactly those made without it."""
+        if snap is True:
+            snap = {}
+        elif isinstance(snap, (int, np.integer)) and snap is not False:
+            snap = dict(iterations=int(snap))
+        if snap is not None and not isinstance(snap, dict):
+            raise ValueError("snap must be None, True, a number of iterations or a dict of DeviceMesh.snap's arguments")
+        if snap is not None and set(snap) - {"iterations", "tolerance", "max_step", "max_displacement", "min_gradient", "attributes", "max_points_in_flight", "only_fills"}:
+            raise ValueError("snap takes iterations, tolerance, max_step, max_displacement, min_gradient, attributes, max_points_in_flight and only_fills")
+        snap_only_fills = False
+        if snap is not None:
+            snap = dict(snap)
+            snap_only_fills = bool(snap.pop("only_fills", False))
+            if snap_only_fills and fill_holes is None:
+                raise ValueError("snap['only_fills'] needs fill_holes")
+            self._snap_options(level=thresh, inference=inference, **snap)  # a bad argument fails before anything is extracted
         if smooth is True:
             smooth = {}
         elif isinstance(smooth, (int, np.integer)) and smooth is not False:
@@ -719,8 +741,16 @@ class Context:
                 filled = chain[-1]
             if smooth is not None:
                 appended = None if only_fills is None else np.arange(filled.n_verts) >= filled.stats["n_verts_out"] - filled.stats["n_verts_added"]
-                chain.append(chain[-1].smooth(select=appended, stream=stream, **smooth))
+                chain.append(chain[-1].smooth(select=appended, stream=stream, **dict(smooth, displacement=True) if snap_only_fills else smooth))
                 smoothed = chain[-1]
+            if snap is not None:
+                chosen = None
+                if snap_only_fills:
+                    chosen = np.arange(filled.n_verts) >= filled.stats["n_verts_out"] - filled.stats["n_verts_added"]
+                    if smooth is not None:
+                        chosen = chosen | (smoothed.displacement > 0)
+                chain.append(chain[-1].snap(level=thresh, select=chosen, inference=inference, stream=stream, **snap))
+                snapped = chain[-1]
             if si_report:
                 si_census = chain[-1].self_intersections(cells=si_cells, stream=stream)
             if grid is not None and error:
@@ -749,6 +779,8 @@ class Context:
                 out["fill_stats"] = filled.stats
             if smooth is not None:
                 out["smooth_stats"] = smoothed.stats
+            if snap is not None:
+                out["snap_stats"] = snapped.stats
             if topology:
                 out["topology"] = census
             if si_drop is not None:
@@ -919,6 +951,49 @@ class Context:
                 out["displacement"] = smoothed.displacement
             if census:
                 out["valence"], out["kind"] = smoothed.valence, smoothed.kind
+        return out
+
+    def _snap_options(self, iterations=3, tolerance=None, max_step=None, max_displacement=None, min_gradient=None, level=0.0, attributes=(), inference=True, max_points_in_flight=0):
+        """The options of rnb_mesh_snap; None leaves the library's default. The ranges are the header's, checked here before any call."""
+        bits = {"colors": _abi.MESH_ATTR_COLORS, "normals": _abi.MESH_ATTR_NORMALS}
+        if isinstance(attributes, str):
+            attributes = (attributes,)
+        if set(attributes) - set(bits):
+            raise ValueError("attributes must be a set of 'colors' and 'normals'")
+        if isinstance(iterations, bool) or not 0 <= int(iterations) <= _abi.MESH_SNAP_MAX_ITERATIONS:
+            raise ValueError("iterations must be 0 .. 64")
+        opt = _abi.MeshSnapOptions()
+        self._check(self.f.mesh_snap_default_options(C.byref(opt)))
+        for name, value, low, strict in (("level", level, None, False), ("tolerance", tolerance, 0.0, False), ("max_step", max_step, 0.0, True),
+                                         ("max_displacement", max_displacement, 0.0, False), ("min_gradient", min_gradient, 0.0, True)):
+            if value is None:
+                continue
+            value = float(value)
+            if not np.isfinite(value) or (low is not None and (value <= low if strict else value < low)):
+                raise ValueError("%s must be finite%s" % (name, "" if low is None else (" and above 0" if strict else " and at least 0")))
+            setattr(opt, name, value)
+        if not 0 <= int(max_points_in_flight) < 1 << 32:
+            raise ValueError("max_points_in_flight must be 0 .. 2^32 - 1")
+        opt.iterations, opt.use_inference_params, opt.max_points_in_flight = int(iterations), int(bool(inference)), int(max_points_in_flight)
+        opt.attributes = sum(bits[a] for a in set(attributes))
+        return opt
+
+    def snap_mesh(self, verts, indices, colors=None, normals=None, iterations=3, tolerance=None, max_step=None, max_displacement=None, min_gradient=None, level=0.0, select=None,
+                  attributes=(), inference=True, max_points_in_flight=0, residuals=False, states=False, displacement=False, stream=None):
+        """rnb_mesh_snap (include/rnb_mesh_snap.h) on a host mesh: verts float32[n,3], indices uint32[m] (or [m/3,3]), optional per-vertex colors / normals; the other
+        arguments are those of DeviceMesh.snap. Returns a dict of numpy arrays like clean_mesh, with `stats` = `snap_stats` and, when asked for, `residual_before`,
+        `residual_after`, `state` and `displacement`. Leaves the training state as it was."""
+        with self.upload_mesh(verts, indices, colors, normals) as m:
+            snapped = m.snap(iterations, tolerance, max_step, max_displacement, min_gradient, level, select, attributes, inference, max_points_in_flight, residuals, states, displacement, stream)
+        with snapped:
+            out = snapped.download()
+            out["stats"] = out["snap_stats"] = snapped.stats
+            if residuals:
+                out["residual_before"], out["residual_after"] = snapped.residual_before, snapped.residual_after
+            if states:
+                out["state"] = snapped.state
+            if displacement:
+                out["displacement"] = snapped.displacement
         return out
 
     def mesh_vertex_normals(self, verts, indices, flip=False, stream=None):
@@ -1388,6 +1463,7 @@ class DeviceMesh(_abi.Mesh):
         self.vertex_map = None  # set by repair(vertex_map=True) on the mesh it returns
         self.loop_of_tri = None  # set by fill_holes(loop_of_tri=True) on the mesh it returns
         self.displacement = self.valence = self.kind = None  # set by smooth(displacement=True / census=True) on the mesh it returns
+        self.residual_before = self.residual_after = self.state = None  # set by snap(residuals=True / states=True) on the mesh it returns (displacement=True: `displacement`)
 
     n_verts = property(lambda self: _abi.Mesh.n_verts.__get__(self))
     n_triangles = property(lambda self: self.n_indices // 3)
@@ -1604,6 +1680,50 @@ class DeviceMesh(_abi.Mesh):
             for p_ in bufs.values():
                 c.device_free(p_)
         return out
+
+    def snap(self, iterations=3, tolerance=None, max_step=None, max_displacement=None, min_gradient=None, level=0.0, select=None, attributes=(), inference=True,
+             max_points_in_flight=0, residuals=False, states=False, displacement=False, stream=None):
+        """rnb_mesh_snap (include/rnb_mesh_snap.h) -> a new DeviceMesh with the same vertices (none added, none removed) and triangles, every selected vertex moved
+        along the model's SDF gradient towards sdf = level by up to `iterations` guarded Newton steps; its `stats` are the snap stats. A step is at most max_step long, a
+        vertex never ends further than max_displacement from where it was (both in world units), stops where the gradient is shorter than min_gradient, where
+        |sdf - level| <= tolerance, at the box, and goes back one step if a step made the residual larger (None: the library's default). select: None (every vertex) or
+        one value per vertex (non-zero = selected). attributes: "colors" and / or "normals" are resampled from the model at the new positions (for the selected
+        vertices; () carries this mesh's). inference: the EMA weights. residuals=True: `residual_before` and `residual_after` of the returned mesh are float32[n_verts],
+        sdf - level at the old and the new position; states=True: `state` is uint32[n_verts] (_abi.MESH_SNAP_*); displacement=True: `displacement` is float32[n_verts].
+        max_points_in_flight bounds the workspace and changes no bit of the result."""
+        c = self._live()
+        opt, st = c._snap_options(iterations, tolerance, max_step, max_displacement, min_gradient, level, attributes, inference, max_points_in_flight), _abi.MeshSnapStats()
+        n = self.n_verts
+        if select is not None:
+            select = np.ascontiguousarray(np.asarray(select).ravel() != 0, dtype=np.uint32)
+            if select.size != n:
+                raise ValueError("select must have one value per vertex")
+        wanted = (("residual_before", "residual_after") if residuals else ()) + (("state",) if states else ()) + (("displacement",) if displacement else ())
+        bufs = {}
+        try:
+            if select is not None:
+                bufs["select"] = c.upload(select) if n else c.device_malloc(4)
+            for key in wanted:
+                bufs[key] = c.device_malloc(max(n, 1) * 4)
+            out = _returned_mesh(c, st, lambda m: c.f.mesh_snap(c._h, _stream_handle(stream), C.byref(self), C.byref(opt), bufs.get("select"), m, bufs.get("residual_before"),
+                                                               bufs.get("residual_after"), bufs.get("state"), bufs.get("displacement"), C.byref(st)))
+            try:
+                for key in wanted:
+                    dt = np.uint32 if key == "state" else np.float32
+                    setattr(out, key, c.download(bufs[key], n, dt) if n else np.empty(0, dt))
+            except BaseException:
+                out.free()
+                raise
+        finally:
+            for p_ in bufs.values():
+                c.device_free(p_)
+        return out
+
+    def sdf_residual(self, level=0.0, inference=True, stream=None):
+        """The census of rnb_mesh_snap with iterations = 0: -> (residual float32[n_verts], the model's sdf - level at every vertex; the snap stats, whose max_before and
+        sum_before_q / 2^24 / n_selected are the largest and the mean |residual|). Nothing of the mesh changes."""
+        with self.snap(iterations=0, level=level, inference=inference, residuals=True, stream=stream) as census:
+            return census.residual_before, census.stats
 
     def vertex_normals(self, flip=False, on_device=False, stream=None):
         """rnb_mesh_vertex_normals (include/rnb_mesh_smooth.h): area-weighted vertex normals from the triangles around every vertex -> the dict of

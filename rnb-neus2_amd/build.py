@@ -110,7 +110,7 @@ MESH_SRC = os.path.join(PKG_DIR, "host", "mesh_main.cpp")
 MESH_OUT = os.path.join(ROOT, "build", "mesh")
 MESH_DEPS = [os.path.join(PKG_DIR, "host", f) for f in ("mesh_main.cpp", "dataset.hpp", "json_min.hpp", "png16.hpp", "msgpack_min.hpp", "snapshot.hpp", "mesh.hpp", "mc_table.hpp", "view_metrics.hpp")] + [
     os.path.join(ROOT, "include", f) for f in ("rnb_neus2.h", "rnb_mesh.h", "rnb_mesh_clean.h", "rnb_mesh_simplify.h", "rnb_mesh_distance.h", "rnb_mesh_raster.h", "rnb_mesh_texture.h",
-                                          "rnb_mesh_visibility.h", "rnb_mesh_project.h", "rnb_mesh_draw.h", "rnb_mesh_topology.h", "rnb_mesh_holes.h", "rnb_mesh_intersect.h", "rnb_mesh_smooth.h")]
+                                          "rnb_mesh_visibility.h", "rnb_mesh_project.h", "rnb_mesh_draw.h", "rnb_mesh_topology.h", "rnb_mesh_holes.h", "rnb_mesh_intersect.h", "rnb_mesh_smooth.h", "rnb_mesh_snap.h")]
 
 
 def build_mesh(force=False, verbose=False):

@@ -2,7 +2,8 @@
 // rnb_mesh_draw_textured, rnb_mesh_visibility, rnb_mesh_visibility_select, rnb_mesh_bake_texture, rnb_mesh_project_views, rnb_mesh_topology, rnb_mesh_repair
 // (include/rnb_mesh_topology.h; their hash join is tp_join, beside them), rnb_mesh_boundary_loops, rnb_mesh_fill_holes (include/rnb_mesh_holes.h; hl_census is the
 // part they share), rnb_mesh_intersections, rnb_mesh_intersections_select (include/rnb_mesh_intersect.h; md_build_lists, beside rnb_mesh_distance, is the grid they
-// share with it), rnb_mesh_smooth, rnb_mesh_vertex_normals (include/rnb_mesh_smooth.h; on tp_join too; vn_run is the part they share). What they share:
+// share with it), rnb_mesh_smooth, rnb_mesh_vertex_normals (include/rnb_mesh_smooth.h; on tp_join too; vn_run is the part they share), rnb_mesh_snap
+// (include/rnb_mesh_snap.h; launch_forward round by round). What they share:
 //   scan_exclusive, count_and_scan                  the prefix sums behind every numbering, and the count half of a count / write kernel pair
 //   MeshWorkspace, alloc_mesh, hand_over            the device memory of one call and the mesh it returns
 //   check_mesh_input, check_reserved, free_device   the argument checks every stage makes; the *_free functions
@@ -2305,6 +2306,151 @@ int rnb_mesh_smooth(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh
 		std::memcpy(&md, &hres.max_displacement, 4);
 		stats->max_displacement = (double)md;
 		stats->ms_passes = ms_passes;
+		call.finish(stats);
+	}
+	return RNB_OK;
+} RNB_GUARD
+
+// ---- snapping: guarded Newton steps onto the model's SDF (include/rnb_mesh_snap.h) ----
+uint32_t rnb_mesh_snap_abi_version(void) { return RNB_MESH_SNAP_ABI_VERSION; }
+
+int rnb_mesh_snap_default_options(rnb_mesh_snap_options* opt) try {
+	if (!opt) return fail(RNB_ERR_INVALID, "opt is null");
+	std::memset(opt, 0, sizeof(*opt));
+	opt->abi_version = RNB_MESH_SNAP_ABI_VERSION;
+	opt->iterations = 3;
+	opt->tolerance = 1.0f / 8192.0f;
+	opt->max_step = 1.0f / 128.0f;
+	opt->max_displacement = 1.0f / 64.0f;
+	opt->min_gradient = 0.25f;
+	opt->use_inference_params = 1;
+	return RNB_OK;
+} RNB_GUARD
+
+int rnb_mesh_snap(rnb_ctx* c, void* stream, const rnb_mesh* in, const rnb_mesh_snap_options* opt, const uint32_t* select_dev, rnb_mesh* out, float* residual_before_dev, float* residual_after_dev,
+                  uint32_t* state_dev, float* displacement_dev, rnb_mesh_snap_stats* stats) try {
+	if (!c || !in || !opt || !out) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: null argument");
+	if (int rc = check_mesh_input("rnb_mesh_snap", in, out); rc != RNB_OK) return rc;
+	const rnb_mesh m = *in;
+	if (opt->abi_version != RNB_MESH_SNAP_ABI_VERSION) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: options abi_version mismatch (expected RNB_MESH_SNAP_ABI_VERSION)");
+	if (opt->iterations > RNB_MESH_SNAP_MAX_ITERATIONS) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: iterations must be 0 .. 64");
+	if (!std::isfinite(opt->level)) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: level must be finite");
+	if (!(std::isfinite(opt->tolerance) && opt->tolerance >= 0.0f)) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: tolerance must be finite and at least 0");
+	if (!(std::isfinite(opt->max_step) && opt->max_step > 0.0f)) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: max_step must be finite and above 0");
+	if (!(std::isfinite(opt->max_displacement) && opt->max_displacement >= 0.0f)) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: max_displacement must be finite and at least 0");
+	if (!(std::isfinite(opt->min_gradient) && opt->min_gradient > 0.0f)) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: min_gradient must be finite and above 0");
+	if (opt->attributes & ~(RNB_MESH_ATTR_COLORS | RNB_MESH_ATTR_NORMALS)) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: attributes must be a set of RNB_MESH_ATTR_COLORS and RNB_MESH_ATTR_NORMALS");
+	if (opt->use_inference_params > 1u) return fail(RNB_ERR_INVALID, "rnb_mesh_snap: use_inference_params must be 0 or 1");
+	if (int rc = check_reserved("rnb_mesh_snap", opt->reserved); rc != RNB_OK) return rc;
+	MeshCall call("rnb_mesh_snap", c, stream);
+	const hipStream_t s = call.s;
+
+	const uint32_t nv = m.n_verts, nt = m.n_indices / 3u;
+	const bool new_colors = (opt->attributes & RNB_MESH_ATTR_COLORS) != 0, new_normals = (opt->attributes & RNB_MESH_ATTR_NORMALS) != 0;
+	SnResult hres;
+	std::memset(&hres, 0, sizeof(hres));
+	uint32_t rounds = 0;
+	uint64_t n_points = 0;
+	float ms_network = 0.0f;
+	rnb_mesh o;
+	if (!alloc_mesh(call.ws, &o, nv, nt, m.colors != nullptr || new_colors, m.normals != nullptr || new_normals)) return call.nomem("hipMalloc failed for the output mesh");
+	if (nv) {
+		const uint32_t g_v = groups(nv);
+		float* prev = nullptr;
+		double *a_prev = nullptr, *r_before = nullptr;
+		uint32_t *state = nullptr, *flag = nullptr, *pos = nullptr, *list = nullptr, *scan = nullptr;
+		SnResult* dres = nullptr;
+		if (!call.ws.alloc(&prev, 3 * (size_t)nv) || !call.ws.alloc(&a_prev, nv) || !call.ws.alloc(&r_before, nv) || !call.ws.alloc(&state, nv) || !call.ws.alloc(&flag, nv) ||
+		    !call.ws.alloc(&pos, nv) || !call.ws.alloc(&list, nv) || !call.ws.alloc(&scan, scan_scratch_elems(nv)) || !call.ws.alloc(&dres, 1))
+			return call.nomem("hipMalloc failed for the workspace of " + std::to_string(nv) + " vertices");
+		HIP_TRY(hipMemsetAsync(dres, 0, sizeof(SnResult), s));
+		// 1. the triangles are only carried, but an index out of range is refused before anything else (pos's memory takes the marks of the check)
+		if (nt)
+			if (int rc = call.check_indices(m, pos, &dres->flags); rc != RNB_OK) return rc;
+		const uint32_t per_launch = std::min<uint32_t>(opt->max_points_in_flight ? opt->max_points_in_flight : (1u << 20), RNB_MESH_SNAP_MAX_IN_FLIGHT);
+		const uint32_t batch = std::min(per_launch, nv);
+		float* coords = nullptr;
+		half_t* net = nullptr;
+		if (!call.ws.alloc(&coords, (size_t)batch * 7) || !call.ws.alloc(&net, (size_t)batch * 16)) return call.nomem("hipMalloc failed for a batch of " + std::to_string(batch) + " points");
+		SnParams P;
+		P.aabb_min = c->aabb.mn; P.aabb_diag = c->aabb.mx - c->aabb.mn;
+		P.level = (double)opt->level; P.tolerance = (double)opt->tolerance; P.max_step = (double)opt->max_step; P.max_displacement = (double)opt->max_displacement;
+		P.min_gradient2 = (double)opt->min_gradient * (double)opt->min_gradient; P.diag = (double)P.aabb_diag;
+		const bool inference = opt->use_inference_params != 0;
+		// 2. P = P_prev = P0; the unselected vertices' outputs; the attributes every vertex starts from
+		call.launch(g_v, k_sn_init, (const float*)m.verts, select_dev, nv, o.verts, prev, a_prev, r_before, state, flag, dres);
+		HIP_TRY(hipGetLastError());
+		for (float* per_vertex : {residual_before_dev, residual_after_dev, displacement_dev})
+			if (per_vertex) HIP_TRY(hipMemsetAsync(per_vertex, 0, (size_t)nv * 4, s));
+		if (o.colors) { if (m.colors) HIP_TRY(hipMemcpyAsync(o.colors, m.colors, (size_t)nv * 12, hipMemcpyDeviceToDevice, s)); else HIP_TRY(hipMemsetAsync(o.colors, 0, (size_t)nv * 12, s)); }
+		if (o.normals) { if (m.normals) HIP_TRY(hipMemcpyAsync(o.normals, m.normals, (size_t)nv * 12, hipMemcpyDeviceToDevice, s)); else HIP_TRY(hipMemsetAsync(o.normals, 0, (size_t)nv * 12, s)); }
+		// The vertices whose flag is set, packed into list; their number is the host read. Then, batch by batch: inputs, the network, and `after` on its outputs.
+		const auto evaluate = [&](uint32_t* n_out, auto&& after) -> int {
+			uint32_t n = 0;
+			*n_out = 0;
+			HIP_TRY(hipMemcpyAsync(pos, flag, (size_t)nv * 4, hipMemcpyDeviceToDevice, s));
+			if (int rc = scan_exclusive(pos, nv, s, &n, scan); rc != RNB_OK) return rc;
+			*n_out = n;
+			if (!n) return RNB_OK;
+			call.launch(g_v, k_sn_pack, (const uint32_t*)flag, (const uint32_t*)pos, nv, list);
+			for (uint32_t b0 = 0; b0 < n; b0 += batch) {
+				const uint32_t nb = std::min(batch, n - b0);
+				call.launch(groups(nb), k_sn_coords, (const uint32_t*)list + b0, nb, (const float*)o.verts, P.aabb_min, P.aabb_diag, coords);
+				HIP_TRY(hipGetLastError());
+				HIP_TRY(hipStreamSynchronize(s));
+				const auto t_net = std::chrono::steady_clock::now();
+				if (int rc = launch_forward(c, s, coords, nullptr, nb, net, inference); rc != RNB_OK) return rc;
+				HIP_TRY(hipStreamSynchronize(s));
+				ms_network += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_net).count();
+				after((const uint32_t*)list + b0, nb);
+				HIP_TRY(hipGetLastError());
+				n_points += nb;
+			}
+			return RNB_OK;
+		};
+		// 3. the rounds
+		for (uint32_t k = 1; k <= opt->iterations + 1u; ++k) {
+			uint32_t n_active = 0;
+			const int rc = evaluate(&n_active, [&](const uint32_t* l, uint32_t nb) {
+				call.launch(groups(nb), k_sn_step, l, nb, (const half_t*)net, (const float*)m.verts, P, k == 1u ? 1u : 0u, k == opt->iterations + 1u ? 1u : 0u, o.verts, prev, a_prev, r_before,
+				            residual_before_dev, state, flag);
+			});
+			if (rc != RNB_OK) return rc;
+			if (!n_active) break;
+			++rounds;
+		}
+		// 4. every selected vertex once more, at its final position
+		call.launch(g_v, k_sn_selected, (const uint32_t*)state, nv, flag);
+		uint32_t n_selected = 0;
+		const int rc = evaluate(&n_selected, [&](const uint32_t* l, uint32_t nb) {
+			call.launch(groups(nb), k_sn_final, l, nb, (const half_t*)net, (const float*)m.verts, (const float*)o.verts, P.level, (const double*)r_before, (const uint32_t*)state, residual_after_dev,
+			            displacement_dev, new_colors ? o.colors : nullptr, new_normals ? o.normals : nullptr, dres);
+		});
+		if (rc != RNB_OK) return rc;
+		if (state_dev) HIP_TRY(hipMemcpyAsync(state_dev, state, (size_t)nv * 4, hipMemcpyDeviceToDevice, s));
+		HIP_TRY(hipMemcpyAsync(&hres, dres, sizeof(hres), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		call.ws.release(prev, a_prev, r_before, state, flag, pos, list, scan);
+		call.ws.release(dres, coords, net);
+	}
+	if (nt) HIP_TRY(hipMemcpyAsync(o.indices, m.indices, (size_t)nt * 12, hipMemcpyDeviceToDevice, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	hand_over(call.ws, o, out);
+	if (stats) {
+		std::memset(stats, 0, sizeof(*stats));
+		stats->n_unselected = hres.n_state[RNB_MESH_SNAP_UNSELECTED]; stats->n_converged = hres.n_state[RNB_MESH_SNAP_CONVERGED]; stats->n_unfinished = hres.n_state[RNB_MESH_SNAP_UNFINISHED];
+		stats->n_flat = hres.n_state[RNB_MESH_SNAP_FLAT]; stats->n_leashed = hres.n_state[RNB_MESH_SNAP_LEASHED]; stats->n_outside = hres.n_state[RNB_MESH_SNAP_OUTSIDE];
+		stats->n_stalled = hres.n_state[RNB_MESH_SNAP_STALLED]; stats->n_invalid = hres.n_state[RNB_MESH_SNAP_INVALID]; stats->n_reverted = hres.n_state[RNB_MESH_SNAP_REVERTED];
+		stats->n_selected = nv - stats->n_unselected;
+		stats->n_moved = hres.n_moved; stats->rounds = rounds;
+		float md;
+		std::memcpy(&md, &hres.max_displacement, 4);
+		stats->max_displacement = (double)md;
+		std::memcpy(&stats->max_before, &hres.max_before, 8);
+		std::memcpy(&stats->max_after, &hres.max_after, 8);
+		stats->sum_before_q = hres.sum_before_q; stats->sum_after_q = hres.sum_after_q;
+		stats->n_network_points = n_points;
+		stats->ms_network = ms_network;
 		call.finish(stats);
 	}
 	return RNB_OK;

@@ -20,6 +20,7 @@
 #include "kernels_mesh_holes.cuh"
 #include "kernels_mesh_intersect.cuh"
 #include "kernels_mesh_smooth.cuh"
+#include "kernels_mesh_snap.cuh"
 #include "../host/mesh.hpp" // the marching-cubes case table generator (header only)
 
 #include <hip/hip_ext.h>

@@ -9,6 +9,7 @@
 //        [--repair [--weld] [--duplicates keep|first|cancel] [--orient-consistent]] [--report-topology]
 //        [--drop-intersecting proper|all [--drop-rings R]] [--fill-holes [--fill-max-edges N] [--fill-skip-largest]] [--report-intersections]
 //        [--smooth N [--smooth-lambda L] [--smooth-mu M] [--smooth-boundary pin|slide|free] [--smooth-only-fills R] [--smooth-normals keep|recompute]]
+//        [--snap N [--snap-tolerance T] [--snap-max-step S] [--snap-max-displacement D] [--snap-only-fills] [--snap-attributes keep|resample]] [--report-residual]
 //
 // The lattice is the testbed's: R rounded up to a multiple of 16, over the scene's bounding box, threshold 0. Vertex colours come from the device; the normals are the
 // ring normals of mesh::compute_normals (default, as the testbed) or the device's SDF-gradient normals. The OBJ is written by mesh::save_obj as the testbed writes it.
@@ -53,6 +54,11 @@
 // pinned, sliding along itself or free; with --smooth-only-fills R only the vertices --fill-holes appended and R rings around them move, which relaxes the flat fans and
 // leaves the rest as extracted. With --normals ring the host's ring normals are those of the smoothed positions; with --normals gradient the SDF-gradient normals would
 // be stale, so --smooth-normals defaults to recompute there (the device's ring normals, the same direction) and to keep otherwise. One `smooth:` line is printed.
+// With --snap N the vertices are then moved back onto the model's surface by up to N guarded Newton steps of rnb_mesh_snap (include/rnb_mesh_snap.h), right after
+// --smooth and before the late --keep / --orient, the reports and --texture: a step of at most --snap-max-step, no vertex further than --snap-max-displacement from where
+// it was (defaults: the box edge / 128 and / 64), done where |sdf| <= --snap-tolerance; with --snap-only-fills only the vertices --fill-holes appended and those --smooth
+// moved are snapped. --snap-attributes resample (the default) takes the colours, and with --normals gradient the normals, of the snapped vertices from the model at the
+// new positions; keep carries the old ones. One `snap:` line is printed. --report-residual prints {"residual": {...}}: mean and maximum |sdf| of the mesh as written.
 // Exit codes as the testbed's: 0, 255 on a command-line error, 1 on a missing path or a failure.
 #include "../../include/rnb_neus2.h"
 #include "../../include/rnb_mesh.h"
@@ -68,6 +74,7 @@
 #include "../../include/rnb_mesh_holes.h"
 #include "../../include/rnb_mesh_intersect.h"
 #include "../../include/rnb_mesh_smooth.h"
+#include "../../include/rnb_mesh_snap.h"
 #include "dataset.hpp"
 #include "json_min.hpp"
 #include "mesh.hpp"
@@ -135,6 +142,13 @@ const Flag FLAGS[] = {
 	{"smooth-only-fills", "R", "--smooth with --fill-holes only. Move only the vertices --fill-holes appended and R rings of neighbours around them (0 .. 1024)."},
 	{"smooth-normals", "MODE", "--smooth only. keep: the normals the mesh has; recompute: the device's ring normals of the smoothed mesh (default with --normals gradient)."},
 	{"report-intersections", nullptr, "(takes no value). Print the self-intersection census of the written mesh as one JSON line: candidates, proper and contact pairs and triangles."},
+	{"snap", "N", "Move the vertices back onto the model's surface with up to N guarded Newton steps (0 .. 64) along the SDF gradient, after --smooth and before the reports and --texture."},
+	{"snap-tolerance", "T", "--snap only. A vertex is done where |sdf| <= T (T >= 0, default 2^-13)."},
+	{"snap-max-step", "S", "--snap only. The longest single step, in world units (S > 0, default the box edge / 128)."},
+	{"snap-max-displacement", "D", "--snap only. No vertex ends further than D from where it was, in world units (D >= 0, default the box edge / 64)."},
+	{"snap-only-fills", nullptr, "(takes no value). --snap with --fill-holes only. Snap only the vertices --fill-holes appended and those --smooth moved."},
+	{"snap-attributes", "MODE", "--snap only. resample (default): colours (and gradient normals) of the snapped vertices from the model at the new positions; keep: the old ones."},
+	{"report-residual", nullptr, "(takes no value). Print mean and maximum |sdf| of the written mesh's vertices as one JSON line."},
 	{"report-topology", nullptr, "(takes no value). Print the edge census of the written mesh as one JSON line: edges by kind, duplicates, patches, boundary loops, Euler characteristic."},
 };
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -401,6 +415,9 @@ void project_views(rnb_ctx* ctx, const Dataset& ds, const rnb_mesh& dm, const rn
 
 } // namespace
 
+// The mean |sdf| behind a sum of trunc(|r| * 2^24) over n vertices (rnb_mesh_snap_stats).
+static double residual_mean(uint64_t sum_q, uint32_t n) { return n ? (double)sum_q / (double)(1u << RNB_MESH_SNAP_Q_SHIFT) / (double)n : 0.0; }
+
 int main(int argc, char** argv) {
 	std::map<std::string, std::string> a;
 	uint32_t resolution = 256, brick = 0, cull = RNB_MESH_CULL_OCCUPANCY;
@@ -421,6 +438,9 @@ int main(int argc, char** argv) {
 	bool smooth = false, smooth_only_fills = false;
 	rnb_mesh_smooth_options smooth_opt;
 	(void)rnb_mesh_smooth_default_options(&smooth_opt); // (touches no device)
+	bool snap = false, snap_only_fills = false, snap_resample = true, snap_step_given = false, snap_leash_given = false, report_residual = false;
+	rnb_mesh_snap_options snap_opt;
+	(void)rnb_mesh_snap_default_options(&snap_opt); // (touches no device)
 	try {
 		bool help = false;
 		a = parse_cli(argc, argv, help);
@@ -576,6 +596,36 @@ int main(int argc, char** argv) {
 			else if (a["smooth-normals"] == "keep") smooth_opt.normals = RNB_MESH_SMOOTH_NORMALS_KEEP;
 			else throw ParseError("Argument 'smooth-normals' must be keep or recompute");
 		}
+		if (a.count("report-residual")) report_residual = true;
+		if (a.count("snap")) {
+			snap = true;
+			snap_opt.iterations = parse_u32("snap", a["snap"]);
+			if (snap_opt.iterations > RNB_MESH_SNAP_MAX_ITERATIONS) throw ParseError("Argument 'snap' must be 0 .. 64");
+		}
+		for (const char* sub : {"snap-tolerance", "snap-max-step", "snap-max-displacement", "snap-only-fills", "snap-attributes"})
+			if (a.count(sub) && !snap) throw ParseError(std::string("Argument '") + sub + "' is only used with --snap");
+		if (a.count("snap-tolerance")) {
+			snap_opt.tolerance = (float)parse_double("snap-tolerance", a["snap-tolerance"]);
+			if (!(std::isfinite(snap_opt.tolerance) && snap_opt.tolerance >= 0.0f)) throw ParseError("Argument 'snap-tolerance' must be finite and at least 0");
+		}
+		if (a.count("snap-max-step")) {
+			snap_opt.max_step = (float)parse_double("snap-max-step", a["snap-max-step"]);
+			snap_step_given = true;
+			if (!(std::isfinite(snap_opt.max_step) && snap_opt.max_step > 0.0f)) throw ParseError("Argument 'snap-max-step' must be finite and above 0");
+		}
+		if (a.count("snap-max-displacement")) {
+			snap_opt.max_displacement = (float)parse_double("snap-max-displacement", a["snap-max-displacement"]);
+			snap_leash_given = true;
+			if (!(std::isfinite(snap_opt.max_displacement) && snap_opt.max_displacement >= 0.0f)) throw ParseError("Argument 'snap-max-displacement' must be finite and at least 0");
+		}
+		if (a.count("snap-only-fills")) {
+			if (!fill_holes) throw ParseError("Argument 'snap-only-fills' is only used with --fill-holes");
+			snap_only_fills = true;
+		}
+		if (a.count("snap-attributes")) {
+			if (a["snap-attributes"] == "keep") snap_resample = false;
+			else if (a["snap-attributes"] != "resample") throw ParseError("Argument 'snap-attributes' must be keep or resample");
+		}
 	} catch (const ParseError& e) {
 		std::cerr << e.what() << std::endl;
 		print_help(std::cerr, argv[0]);
@@ -708,6 +758,7 @@ int main(int argc, char** argv) {
 			std::memset(&cm, 0, sizeof(cm));
 		}
 		rnb_mesh_smooth_stats ms;
+		std::vector<float> smooth_moved;
 		if (smooth) { // device to device, right after the fill: its appended vertices are still the last ones
 			void* select = nullptr;
 			if (smooth_only_fills && dm.n_verts) {
@@ -717,14 +768,54 @@ int main(int argc, char** argv) {
 				int rc = rnb_memcpy(ctx, select, sel.data(), (uint64_t)dm.n_verts * 4, RNB_H2D);
 				if (rc != RNB_OK) { (void)rnb_device_free(ctx, select); RNB_CHECK(rc); }
 			}
-			const int rc = rnb_mesh_smooth(ctx, nullptr, &dm, &smooth_opt, (const uint32_t*)select, &cm, nullptr, nullptr, nullptr, &ms);
+			void* moved = nullptr; // --snap-only-fills: how far the smoothing moved every vertex
+			if (snap && snap_only_fills && dm.n_verts) {
+				const int rc = rnb_device_malloc(ctx, (uint64_t)dm.n_verts * 4, &moved);
+				if (rc != RNB_OK) { if (select) (void)rnb_device_free(ctx, select); RNB_CHECK(rc); }
+			}
+			int rc = rnb_mesh_smooth(ctx, nullptr, &dm, &smooth_opt, (const uint32_t*)select, &cm, nullptr, nullptr, (float*)moved, &ms);
+			if (select) (void)rnb_device_free(ctx, select);
+			if (moved) {
+				smooth_moved.resize(dm.n_verts);
+				if (rc == RNB_OK) rc = rnb_memcpy(ctx, smooth_moved.data(), moved, (uint64_t)dm.n_verts * 4, RNB_D2H);
+				(void)rnb_device_free(ctx, moved);
+			}
+			RNB_CHECK(rc);
+			RNB_CHECK(rnb_mesh_free(ctx, &dm));
+			dm = cm;
+			std::memset(&cm, 0, sizeof(cm));
+		}
+		rnb_mesh_snap_stats sn;
+		if (snap) { // device to device, right after the smoothing: the fill's appended vertices are still the last ones
+			if (!snap_step_given) snap_opt.max_step = (float)cfg.aabb_scale / 128.0f;
+			if (!snap_leash_given) snap_opt.max_displacement = (float)cfg.aabb_scale / 64.0f;
+			snap_opt.level = mo.thresh;
+			snap_opt.attributes = snap_resample ? mo.attributes : 0u;
+			void* select = nullptr;
+			if (snap_only_fills && dm.n_verts) {
+				std::vector<uint32_t> sel(dm.n_verts, 0u);
+				for (uint32_t v = fs.n_verts_out - fs.n_verts_added; v < dm.n_verts; ++v) sel[v] = 1u;
+				for (size_t v = 0; v < smooth_moved.size() && v < sel.size(); ++v) if (smooth_moved[v] > 0.0f) sel[v] = 1u;
+				RNB_CHECK(rnb_device_malloc(ctx, (uint64_t)dm.n_verts * 4, &select));
+				int rc = rnb_memcpy(ctx, select, sel.data(), (uint64_t)dm.n_verts * 4, RNB_H2D);
+				if (rc != RNB_OK) { (void)rnb_device_free(ctx, select); RNB_CHECK(rc); }
+			}
+			const int rc = rnb_mesh_snap(ctx, nullptr, &dm, &snap_opt, (const uint32_t*)select, &cm, nullptr, nullptr, nullptr, nullptr, &sn);
 			if (select) (void)rnb_device_free(ctx, select);
 			RNB_CHECK(rc);
 			RNB_CHECK(rnb_mesh_free(ctx, &dm));
 			dm = cm;
 			std::memset(&cm, 0, sizeof(cm));
 		}
-		if (clean && late_clean) run_clean(); // on what the repair, the fill and the smoothing leave
+		if (clean && late_clean) run_clean(); // on what the repair, the fill, the smoothing and the snap leave
+		rnb_mesh_snap_stats rr;
+		if (report_residual) { // of the mesh as it will be written: the census of a snap without a step
+			rnb_mesh_snap_options ro;
+			RNB_CHECK(rnb_mesh_snap_default_options(&ro));
+			ro.iterations = 0; ro.level = mo.thresh;
+			RNB_CHECK(rnb_mesh_snap(ctx, nullptr, &dm, &ro, nullptr, &cm, nullptr, nullptr, nullptr, nullptr, &rr));
+			RNB_CHECK(rnb_mesh_free(ctx, &cm));
+		}
 		rnb_mesh_topology_stats tp;
 		if (report_topology) { // of the mesh as it will be written
 			rnb_mesh_topology_options to;
@@ -803,6 +894,11 @@ int main(int argc, char** argv) {
 		if (smooth) std::printf("smooth: %u passes, %u of %u vertices moving (%u selected; %u interior, %u boundary, %u non-manifold, %u unused), %u edges, valence up to %u, %u on the wide path, "
 		                        "greatest displacement %.9g, %.1f ms of which %.1f in the passes\n", ms.passes, ms.n_moving, ms.n_interior + ms.n_boundary + ms.n_nonmanifold + ms.n_unused,
 		                        ms.n_selected, ms.n_interior, ms.n_boundary, ms.n_nonmanifold, ms.n_unused, ms.n_edges, ms.max_valence, ms.n_wide, ms.max_displacement, ms.ms, ms.ms_passes);
+		if (snap) std::printf("snap: %u iterations, %u of %u vertices selected, %u moved; %u converged, %u unfinished, %u flat, %u leashed, %u outside, %u stalled, %u invalid, %u reverted; "
+		                      "mean |sdf| %.9g -> %.9g, max %.9g -> %.9g, greatest displacement %.9g, %u rounds, %llu points through the network, %.1f ms of which %.1f in the network\n",
+		                      snap_opt.iterations, sn.n_selected, sn.n_selected + sn.n_unselected, sn.n_moved, sn.n_converged, sn.n_unfinished, sn.n_flat, sn.n_leashed, sn.n_outside, sn.n_stalled,
+		                      sn.n_invalid, sn.n_reverted, residual_mean(sn.sum_before_q, sn.n_selected - sn.n_invalid), residual_mean(sn.sum_after_q, sn.n_selected - sn.n_invalid), sn.max_before,
+		                      sn.max_after, sn.max_displacement, sn.rounds, (unsigned long long)sn.n_network_points, sn.ms, sn.ms_network);
 		if (clean && late_clean) std::printf("clean: %u components found, %u kept, %u -> %u triangles, %u -> %u vertices, %.1f ms\n", cs.n_components, cs.n_kept, cs.n_tris_in, cs.n_tris_out,
 		                                 cs.n_verts_in, cs.n_verts_out, cs.ms);
 		if (report_topology)
@@ -811,6 +907,9 @@ int main(int argc, char** argv) {
 			            "\"n_unorientable_patches\": %u, \"n_boundary_components\": %u, \"closed\": %u, \"oriented\": %u, \"euler\": %lld}}\n",
 			            tp.n_verts_used, tp.n_tris, tp.n_degenerate, tp.n_edges, tp.n_boundary_edges, tp.n_manifold_edges, tp.n_nonmanifold_edges, tp.n_inconsistent_edges, tp.max_faces_on_edge,
 			            tp.n_duplicate_tris, tp.n_folded_pairs, tp.n_components, tp.n_patches, tp.n_unorientable_patches, tp.n_boundary_components, tp.closed, tp.oriented, (long long)tp.euler);
+		if (report_residual)
+			std::printf("{\"residual\": {\"n_verts\": %u, \"n_invalid\": %u, \"mean\": %.9g, \"max\": %.9g, \"ms\": %.3f}}\n", rr.n_selected, rr.n_invalid,
+			            residual_mean(rr.sum_before_q, rr.n_selected - rr.n_invalid), rr.max_before, rr.ms);
 		if (report_intersections)
 			std::printf("{\"intersections\": {\"n_tris\": %u, \"n_degenerate\": %u, \"n_same_set\": %llu, \"n_candidates\": %llu, \"n_pairs_proper\": %llu, \"n_pairs_contact\": %llu, "
 			            "\"n_tris_proper\": %u, \"n_tris_contact\": %u, \"n_coplanar_pairs\": %llu, \"dims\": [%u, %u, %u], \"n_large\": %u, \"n_cell_entries\": %llu, \"n_visited\": %llu, "

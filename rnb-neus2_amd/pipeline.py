@@ -169,7 +169,7 @@ def postprocess_mesh(data_dir, output_mesh_path, logger=None):
 
 
 def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=None, report_views=False, texture=None, keep_seen=None, texture_from=None,
-                            repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None):
+                            repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None, snap=None, report_residual=False):
     """The last stage on the device: one `build/mesh` process that extracts the mesh of the stage-2 snapshot (plan_two_stage passes --save-snapshot) at `resolution`,
     keeps the largest connected component and turns it outward (include/rnb_mesh_clean.h), and writes `output_mesh_path`. Pure; the snapshot named here is the first
     of snapshot_candidates, run_device_postprocess replaces it by the one that exists. simplify = N: the cleaned mesh is then simplified on N^3 cells over the
@@ -192,7 +192,11 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
     defaults) plan the command without them.
     smooth = N or a dict(passes=N, lam=L, mu=M, boundary="pin" / "slide" / "free", only_fills=R, normals="keep" / "recompute") of which only `passes` is needed: the
     mesh is smoothed on the device by N passes over the one-ring right after fill_holes (include/rnb_mesh_smooth.h, build/mesh --smooth N and its --smooth-* flags);
-    only_fills needs fill_holes. None (the default) plans the command without it."""
+    only_fills needs fill_holes. None (the default) plans the command without it.
+    snap = N or a dict(iterations=N, tolerance=T, max_step=S, max_displacement=D, only_fills=bool, attributes="keep" / "resample") of which only `iterations` is needed:
+    the vertices are moved back onto the model's surface on the device by up to N guarded Newton steps right after smooth (include/rnb_mesh_snap.h, build/mesh --snap N
+    and its --snap-* flags); only_fills needs fill_holes. report_residual: build/mesh --report-residual prints mean and maximum |sdf| of the final mesh as one JSON
+    line. None / False (the defaults) plan the command without them."""
     if texture_from is not None and texture is None:
         raise ValueError("texture_from needs texture")
     if texture_from not in (None, "views"):
@@ -221,6 +225,10 @@ def plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, m
         argv += ["--report-intersections"]
     if smooth is not None:
         argv += smooth_flags(smooth, fill_holes=bool(fill_holes))
+    if snap is not None:
+        argv += snap_flags(snap, fill_holes=bool(fill_holes))
+    if report_residual:
+        argv += ["--report-residual"]
     return argv
 
 
@@ -249,6 +257,29 @@ def smooth_flags(smooth, fill_holes=True):
         argv += ["--smooth-only-fills", str(int(sm["only_fills"]))]
     if sm.get("normals") is not None:
         argv += ["--smooth-normals", sm["normals"]]
+    return argv
+
+
+def snap_flags(snap, fill_holes=True):
+    """The --snap flags of build/mesh for plan_device_postprocess' snap; fill_holes: whether the command also fills (only_fills needs it)."""
+    sn = dict(iterations=snap) if isinstance(snap, int) and not isinstance(snap, bool) else (dict(snap) if isinstance(snap, dict) else None)
+    if sn is None or set(sn) - {"iterations", "tolerance", "max_step", "max_displacement", "only_fills", "attributes"} or sn.get("iterations") is None or not 0 <= int(sn["iterations"]) <= 64:
+        raise ValueError("snap must be a number of iterations (0 .. 64) or a dict of iterations and any of tolerance, max_step, max_displacement, only_fills, attributes")
+    for key, strict in (("tolerance", False), ("max_step", True), ("max_displacement", False)):
+        if sn.get(key) is not None and not (0.0 < float(sn[key]) < float("inf") if strict else 0.0 <= float(sn[key]) < float("inf")):
+            raise ValueError("snap: %s must be finite and %s 0" % (key, "above" if strict else "at least"))
+    if sn.get("attributes") not in (None, "keep", "resample"):
+        raise ValueError("snap: attributes must be 'keep' or 'resample'")
+    if sn.get("only_fills") and not fill_holes:
+        raise ValueError("snap: only_fills needs fill_holes")
+    argv = ["--snap", str(int(sn["iterations"]))]
+    for key, flag in (("tolerance", "--snap-tolerance"), ("max_step", "--snap-max-step"), ("max_displacement", "--snap-max-displacement")):
+        if sn.get(key) is not None:
+            argv += [flag, repr(float(sn[key]))]
+    if sn.get("only_fills"):
+        argv += ["--snap-only-fills"]
+    if sn.get("attributes") is not None:
+        argv += ["--snap-attributes", sn["attributes"]]
     return argv
 
 
@@ -320,12 +351,13 @@ def default_mesh_exe(testbed_path):
 
 
 def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, logger=None, simplify=None, report_views=False, texture=None, keep_seen=None,
-                           texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None):
+                           texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None, snap=None,
+                           report_residual=False):
     """postprocess_mesh's job without the OBJ round trip: runs plan_device_postprocess' command, then drops the training output directory as postprocess_mesh does."""
     logger = logger or SimpleLogger()
     cmd = plan_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, mesh_exe, simplify=simplify, report_views=report_views, texture=texture, keep_seen=keep_seen,
                                   texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes,
-                                  drop_intersecting=drop_intersecting, report_intersections=report_intersections, smooth=smooth)
+                                  drop_intersecting=drop_intersecting, report_intersections=report_intersections, smooth=smooth, snap=snap, report_residual=report_residual)
     found = [p for p in snapshot_candidates(data_dir, max_steps) if os.path.exists(p)]
     if not found:
         raise RuntimeError("Snapshot not found after {} iterations".format(max_steps))
@@ -347,7 +379,8 @@ def run_device_postprocess(data_dir, max_steps, resolution, output_mesh_path, me
 def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mesh_resolution=1024, scaling_mode="auto", sphere_scale=1.0, margin_px=20,
                       warmup_ratio=0.1, mask_weight=1.0, super_normal=False, use_l1=False, use_rgb_plus=True, has_albedo=False,
                       albedo_sfm_path="", mask_sfm_path="", mask_folder_path="", n_samples=2000, logger=None, device_postprocess=False, mesh_exe=None, simplify=None, report_views=False, texture=None,
-                      keep_seen=None, texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None):
+                      keep_seen=None, texture_from=None, repair=None, report_topology=False, fill_holes=None, drop_intersecting=None, report_intersections=False, smooth=None, snap=None,
+                      report_residual=False):
     """load -> prepare (<output_dir>/prepared_data) -> train (two-stage, or warm-up + albedo scaling + two-stage when
     `has_albedo`) -> post-process to <output_dir>/mesh.obj, which is returned. (pipeline.py:222-305)
     device_postprocess: the last step runs on the GPU (run_device_postprocess; mesh_exe defaults to build/mesh beside the testbed) instead of postprocess_mesh;
@@ -362,7 +395,11 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     fill_holes (with device_postprocess only): that step also closes the boundary loops of the mesh (plan_device_postprocess describes the value; build/mesh --fill-holes).
     drop_intersecting, report_intersections (with device_postprocess only): that step also removes the self-intersecting triangles before it fills, and prints the
     self-intersection census of the final mesh (plan_device_postprocess describes the values; build/mesh --drop-intersecting, --report-intersections).
-    smooth (with device_postprocess only): that step also smooths the mesh after it fills (plan_device_postprocess describes the value; build/mesh --smooth)."""
+    smooth (with device_postprocess only): that step also smooths the mesh after it fills (plan_device_postprocess describes the value; build/mesh --smooth).
+    snap, report_residual (with device_postprocess only): that step also moves the vertices back onto the model's surface after it smooths, and prints mean and maximum
+    |sdf| of the final mesh (plan_device_postprocess describes the values; build/mesh --snap, --report-residual)."""
+    if (snap is not None or report_residual) and not device_postprocess:
+        raise ValueError("snap and report_residual need device_postprocess")
     if smooth is not None and not device_postprocess:
         raise ValueError("smooth needs device_postprocess")
     if (repair or report_topology) and not device_postprocess:
@@ -399,7 +436,7 @@ def run_full_pipeline(input_path, testbed_path, output_dir, max_steps=10000, mes
     if device_postprocess:
         run_device_postprocess(data_dir, max_steps, mesh_resolution, output_mesh, mesh_exe or default_mesh_exe(testbed_path), logger, simplify=simplify, report_views=report_views, texture=texture,
                                keep_seen=keep_seen, texture_from=texture_from, repair=repair, report_topology=report_topology, fill_holes=fill_holes,
-                               drop_intersecting=drop_intersecting, report_intersections=report_intersections, smooth=smooth)
+                               drop_intersecting=drop_intersecting, report_intersections=report_intersections, smooth=smooth, snap=snap, report_residual=report_residual)
     else:
         postprocess_mesh(data_dir, output_mesh, logger)
     logger.info("=== Pipeline complete ===")

@@ -63,6 +63,13 @@ _SPEC = """
 --smooth-boundary   | str   |        | --smooth only: pin (build/mesh's default), slide or free
 --smooth-only-fills | int   |        | --smooth with --fill-holes only: move only the vertices --fill-holes appended and R rings around them
 --smooth-normals    | str   |        | --smooth only: keep or recompute
+--snap              | int   |        | --device-postprocess only: move the vertices of the final mesh back onto the model's surface on the GPU by up to N guarded Newton steps after --smooth (build/mesh --snap N)
+--snap-tolerance    | float |        | --snap only: a vertex is done where the SDF's magnitude is at most T (build/mesh's default 2^-13)
+--snap-max-step     | float |        | --snap only: the longest single step in world units (build/mesh's default: the box edge / 128)
+--snap-max-displacement | float |    | --snap only: no vertex ends further than D from where it was (build/mesh's default: the box edge / 64)
+--snap-only-fills   | flag  |        | --snap with --fill-holes only: snap only the vertices --fill-holes appended and those --smooth moved
+--snap-attributes   | str   |        | --snap only: keep or resample (build/mesh's default)
+--report-residual   | flag  |        | --device-postprocess only: print mean and maximum SDF magnitude of the final mesh's vertices as one JSON line (build/mesh --report-residual)
 """
 
 
@@ -94,7 +101,8 @@ def pipeline_kwargs(ns):
     kw = {renamed.get(k, k): v for k, v in vars(ns).items() if k not in ("seed", "no_rgbplus", "device_postprocess", "mesh_exe", "simplify", "report_views", "texture", "texture_from", "keep_seen", "seen_min_views",
                                                                                 "seen_rings", "seen_masks", "seen_max_off", "seen_supersample", "repair", "weld", "duplicates", "orient_consistent",
                                                                                 "report_topology", "fill_holes", "fill_max_edges", "fill_skip_largest", "drop_intersecting", "drop_rings",
-                                                                                "report_intersections", "smooth", "smooth_lambda", "smooth_mu", "smooth_boundary", "smooth_only_fills", "smooth_normals")}
+                                                                                "report_intersections", "smooth", "smooth_lambda", "smooth_mu", "smooth_boundary", "smooth_only_fills", "smooth_normals", "snap", "snap_tolerance",
+                                                                                "snap_max_step", "snap_max_displacement", "snap_only_fills", "snap_attributes", "report_residual")}
     kw["use_rgb_plus"] = not ns.no_rgbplus
     if ns.device_postprocess:  # (absent otherwise: the default call is the reference's)
         kw["device_postprocess"] = True
@@ -123,6 +131,12 @@ def pipeline_kwargs(ns):
         if ns.smooth is not None:
             sm = dict(passes=ns.smooth, lam=ns.smooth_lambda, mu=ns.smooth_mu, boundary=ns.smooth_boundary or None, only_fills=ns.smooth_only_fills, normals=ns.smooth_normals or None)
             kw["smooth"] = {k: v for k, v in sm.items() if v is not None}
+        if ns.snap is not None:
+            sn = dict(iterations=ns.snap, tolerance=ns.snap_tolerance, max_step=ns.snap_max_step, max_displacement=ns.snap_max_displacement, only_fills=ns.snap_only_fills or None,
+                      attributes=ns.snap_attributes or None)
+            kw["snap"] = {k: v for k, v in sn.items() if v is not None}
+        if ns.report_residual:
+            kw["report_residual"] = True
     return kw
 
 
@@ -193,6 +207,23 @@ def main(argv=None):
         parser.error("--smooth-normals must be keep or recompute")
     if ns.smooth_only_fills is not None and (not ns.fill_holes or not 0 <= ns.smooth_only_fills <= 1024):
         parser.error("--smooth-only-fills (0 .. 1024) is only used with --fill-holes")
+    if (ns.snap is not None or ns.report_residual) and not ns.device_postprocess:
+        parser.error("--snap and --report-residual are only used with --device-postprocess")
+    for name in ("snap_tolerance", "snap_max_step", "snap_max_displacement", "snap_only_fills", "snap_attributes"):
+        if getattr(ns, name) not in (None, "", False) and ns.snap is None:
+            parser.error("--%s is only used with --snap" % name.replace("_", "-"))
+    if ns.snap is not None and not 0 <= ns.snap <= 64:
+        parser.error("--snap must be 0 .. 64")
+    if ns.snap_tolerance is not None and not 0.0 <= ns.snap_tolerance < float("inf"):
+        parser.error("--snap-tolerance must be finite and at least 0")
+    if ns.snap_max_step is not None and not 0.0 < ns.snap_max_step < float("inf"):
+        parser.error("--snap-max-step must be finite and above 0")
+    if ns.snap_max_displacement is not None and not 0.0 <= ns.snap_max_displacement < float("inf"):
+        parser.error("--snap-max-displacement must be finite and at least 0")
+    if ns.snap_only_fills and not ns.fill_holes:
+        parser.error("--snap-only-fills is only used with --fill-holes")
+    if ns.snap_attributes and ns.snap_attributes not in ("keep", "resample"):
+        parser.error("--snap-attributes must be keep or resample")
     if ns.duplicates and ns.duplicates not in ("keep", "first", "cancel"):
         parser.error("--duplicates must be keep, first or cancel")
     if ns.simplify is not None and not 1 <= ns.simplify <= 1024:
